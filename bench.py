@@ -8,6 +8,9 @@ xSlot, 10 classes, channel 2048, to_k_layer 3, power 2, T=3, 224x224, per-GPU ba
   python bench.py --config {1,2,3,4,5} [--precision fp32|bf16]   the other BASELINE configs at their per-GPU batch
          (1-based, SURVEY.md section 8 table: 1 = MNIST resnet18, 2 = the headline, 3 = negative xSlot, 4 = CUB200,
          5 = ImageNet-100 resnest50d 100x3 slots -- the config that names bf16, its default precision); same JSON schema
+  python bench.py ... --dump-outputs DIR    also write what the last timed step computed as DIR/<name>.npy (float32, see
+         dump_outputs; bench_outputs/ is ignored by git) -- the inputs are seeded, so two builds run with the same
+         arguments compare output for output
 
 A step = zero_grad -> forward -> loss -> backward (+ gradient all-reduce) -> AdamW, on a synthetic batch already
 resident in HBM.  Rank 0 prints ONE JSON line.  Extra objects on that line:
@@ -313,6 +316,35 @@ def hbm_step_roofline(files, ms_per_step):
             "note": "HBM-side counter bytes of all kernels of one step / this run's ms_per_step (kernels overlap on streams)"}
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a flattened parameter / gradient array (4 MB each in float32)
+
+
+def dump_outputs(path, model, logp):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy --
+      log_probs    [B, C] log-probabilities of the forward
+      stats        [5] loss, nll, area**power, top-1, area (SlotModel.last_stats)
+      params       the trainable parameters after the AdamW update, flattened in named_parameters() order
+      grads        their gradients, same order (zeros where the forward does not use a parameter: slot.to_q)
+      bn_running   every BatchNorm running_mean / running_var, flattened in named_buffers() order
+    params / grads longer than DUMP_SAMPLE are sampled at the same seeded, sorted positions in every run (and in both
+    files), so two builds run with the same arguments can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                        for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    bn = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.dtype.is_floating_point]
+    arrays = {"log_probs": logp, "stats": model.last_stats[:5], "params": flat_p, "grads": flat_g,
+              "bn_running": torch.cat(bn) if bn else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU, RCCL) the way the reference's README
     does with torch.distributed.launch (reference README.md:20-22, tools/prepare_things.py:9-31) and pass their single
@@ -348,7 +380,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel hipEvent pass (no roofline object)")
     ap.add_argument("--prof-steps", type=int, default=5, help="steps of the serial per-kernel timing pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (log-probabilities, loss statistics, sampled parameters "
+                         "and gradients, BatchNorm running statistics) to DIR/<name>.npy; rank 0 only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         spawn_ranks(a.gpus, sys.argv[1:])
@@ -409,12 +446,12 @@ def main():
     def step(eager=False):
         if graphed is not None and not eager:
             logp, stats = graphed(x, y)
-            return [stats[0]]
+            return logp, [stats[0]]
         opt.zero_grad()
         out, losses = net(x, y)
         losses[0].backward(model.loss_seed(losses[0]))      # (as engine.calculation: cached ones instead of autograd's fill)
         opt.step()
-        return losses
+        return out, losses
 
     def fence():
         torch.cuda.synchronize()
@@ -438,10 +475,13 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        losses = step()
+        logp, losses = step()
     t_host = time.perf_counter() - t0           # the host has ENQUEUED the K steps (diagnostic: close to dt = launch-bound)
     fence()
     dt = time.perf_counter() - t0
+    # what the last timed step left, taken before the passes below run further steps on the same model
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, logp)
     # Per-kernel timing pass (same process, model, batch): hipEvents around every launch, on its stream.  It runs with
     # the weight-gradient side stream DISABLED: in the timed region above wgrad kernels overlap BatchNorm-backward /
     # dgrad kernels on purpose, which inflates each kernel's elapsed time and would misstate the kernels' own quality.

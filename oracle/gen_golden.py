@@ -44,6 +44,7 @@ MODEL_CASES = {
 }
 LAMBDA = "1"
 ENGINE_BATCH, ENGINE_SIZE = 16, 128      # engine fixture: 2 AdamW steps of config 1 at reduced batch / resolution
+GEN_THREADS = 8                          # intra-op threads the head / model / engine fixtures were recorded with
 
 
 def head_inputs(case, seed=100):
@@ -287,7 +288,7 @@ def run_reference_engine():
 def main(heads_only=False):
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    torch.set_num_threads(8)
+    torch.set_num_threads(GEN_THREADS)
     for case in HEAD_CASES:
         f32 = run_reference_head(case, torch.float32)
         f64 = run_reference_head(case, torch.float64)

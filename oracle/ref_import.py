@@ -1,9 +1,9 @@
 """TEST INFRASTRUCTURE ONLY -- harness that imports the *reference* (wbw520/scouter) read-only.
 
 Runs ONLY in the build container (``/root/reference`` does not exist on the GPU box).  It is used by
-``oracle/gen_golden.py`` to produce the committed fixtures under ``tests/golden/`` and by
-``tests/test_oracle_vs_reference.py`` (skipped when the reference is absent) to pin the restatement in
-``oracle/torch_oracle.py`` against the real thing.  Nothing in ``scouter_amd/`` may import this module.
+``oracle/gen_golden.py``, ``oracle/gen_golden_resize.py`` and ``oracle/gen_golden_pins.py`` to produce the committed
+fixtures under ``tests/golden/`` that pin the restatement in ``oracle/torch_oracle.py`` against the real thing.
+Nothing in ``scouter_amd/`` may import this module.
 
 The reference needs three environment shims on torch 2.10; none modifies a reference file:
   1. stub ``torchvision`` (+ ``.transforms``, ``.transforms.functional``): ``timm/data/transforms.py:2`` imports it;

@@ -19,8 +19,8 @@ dict, spells out the GRU cell / split attention / AdamW maths explicitly instead
 timm / torch.optim, and works in fp32 or fp64.
 
 PINNING: the reference has no tests and no golden vectors.  The restatement is pinned by
-``tests/test_oracle_vs_reference.py`` (runs where /root/reference exists) and by the fixtures under
-``tests/golden/`` that ``oracle/gen_golden.py`` produced by importing the reference itself.
+the fixtures under ``tests/golden/`` that ``oracle/gen_golden*.py`` produced by importing the reference itself
+(``tests/test_oracle_vs_reference.py``, ``tests/test_oracle_golden.py``).
 """
 import math
 

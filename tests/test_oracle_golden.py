@@ -7,10 +7,21 @@ import pytest
 import torch
 
 from oracle import torch_oracle as O
-from oracle.gen_golden import (HEAD_CASES, MODEL_CASES, LAMBDA, ENGINE_BATCH, ENGINE_SIZE, head_inputs, model_inputs,
-                               grad_digest)
+from oracle.gen_golden import (HEAD_CASES, MODEL_CASES, LAMBDA, ENGINE_BATCH, ENGINE_SIZE, GEN_THREADS, head_inputs,
+                               model_inputs, grad_digest)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
+
+
+@pytest.fixture(autouse=True)
+def recording_threads():
+    """The fp32 fixtures were recorded with GEN_THREADS intra-op threads.  The CPU convolutions split their reductions by
+    thread count and the random-init networks amplify that rounding, so the restatement runs with the same count --
+    whatever the host's default, or what an earlier test in the session left set."""
+    keep = torch.get_num_threads()
+    torch.set_num_threads(GEN_THREADS)
+    yield
+    torch.set_num_threads(keep)
 
 
 def load(name):
