@@ -1353,6 +1353,10 @@ extern "C" int scouter_maxpool_bwd_f32(const float* dy, const unsigned char* arg
                                        int C, int k, int stride, int pad, void* stream) {
     const int ceil_mode = 0, count_include_pad = 0;
     POOL_SETUP("maxpool_bwd")
+    // (profile rows name the kernel: the grid-stride one serves what pool_bwd_rows_ok refuses)
+    const bool rows_ok = pool_bwd_rows_ok(g);
+    ScProfScope prof(rows_ok ? "maxpool_bwd<rows>" : "maxpool_bwd<grid>", st, 0,
+                     4.0 * (double)B * H * W * C + 5.0 * (double)B * g.Ho * g.Wo * C);
     if (pool_bwd_rows<true>(dy, argmax, dx, g, st)) return sc_check_launch("maxpool_bwd");
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_blocks((long)B * H * W * C / 4)), dim3(256), 0, st, dy, argmax, dx, g);
     return sc_check_launch("maxpool_bwd");
@@ -1374,6 +1378,9 @@ extern "C" int scouter_avgpool_fwd_f32(const float* x, float* y, int B, int H, i
 extern "C" int scouter_avgpool_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, int k, int stride,
                                        int pad, int ceil_mode, int count_include_pad, void* stream) {
     POOL_SETUP("avgpool_bwd")
+    const bool rows_ok = pool_bwd_rows_ok(g);
+    ScProfScope prof(rows_ok ? "avgpool_bwd<rows>" : "avgpool_bwd<grid>", st, 0,
+                     4.0 * (double)B * H * W * C + 4.0 * (double)B * g.Ho * g.Wo * C);
     if (pool_bwd_rows<false>(dy, nullptr, dx, g, st)) return sc_check_launch("avgpool_bwd");
     hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(ew_blocks((long)B * H * W * C / 4)), dim3(256), 0, st, dy, dx, g);
     return sc_check_launch("avgpool_bwd");

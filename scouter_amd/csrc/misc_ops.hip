@@ -448,7 +448,10 @@ extern "C" int scouter_im2col_nchw_f32(const float* x, float* col, int B, int Ci
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     const long n = (long)B * Ho * Wo * Kpad;
     const long xw = (long)Wo * (Kpad / 4), rows = (long)B * Ho;
-    if (Kpad <= 64 && Cin < 256 && k < 256 && xw < (1 << 20) && rows <= 65535) {
+    const bool rows_ok = Kpad <= 64 && Cin < 256 && k < 256 && xw < (1 << 20) && rows <= 65535;
+    ScProfScope prof(rows_ok ? "im2col<rows>" : "im2col<elem>", (hipStream_t)stream, 0,
+                     4.0 * (double)B * Cin * H * W + 4.0 * (double)n);
+    if (rows_ok) {
         hipLaunchKernelGGL(im2col_nchw_rows_kernel, dim3((unsigned)((xw + 255) / 256), (unsigned)rows), dim3(256), 0,
                            (hipStream_t)stream, x, col, Cin, H, W, Ho, Wo, k, stride, pad, Kpad, 1.0f / (float)(Kpad / 4));
         return sc_check_launch("im2col");

@@ -790,6 +790,13 @@ def x3_halo_eligible(cin, cout, kh, kw, stride, pad, groups, has_bias):
 X3_HALO_MAX_W = 126
 
 
+def x3_halo_fits(M, cin, cout, groups=1):
+    """The byte guards of tile 7 (csrc/conv_xhalo.hip sc_xhalo_ok), per call: its buffer descriptors cover the whole input and
+    output tensor (M pixels, fp32) and the weight planes in 31-bit byte counts.  Past them the layer keeps the route it had
+    before tile 7 (nn_hip.Conv2d.fwd / bwd); the entry points would refuse the call (SC_ERR_UNSUPPORTED)."""
+    return bool(4 * M * max(cin, cout) < (1 << 31) and 9 * cin * (cout // groups) * 2 * 3 < (1 << 31))
+
+
 def _x3_tile_ok(t, n):
     if t == 7:
         return n == 32
@@ -1266,6 +1273,14 @@ def bn_maxpool_fwd(x, saved, k=3, stride=2, pad=1, want_argmax=True):
     _native.check(_native.lib().scouter_bn_maxpool_fwd_f32(_p(x), _p(saved), _p(y), _p(arg), B, H, W, C, k, stride, pad,
                                                            _stream()), "bn_maxpool_fwd")
     return y, arg
+
+
+def bn_maxpool_fused_ok(B, H):
+    """The stem's bn1 + ReLU + maxpool run as the fused pair (bn_maxpool_fwd / bn_maxpool_bwd) for B images of H input rows:
+    the fused backward walks one workgroup row per input pixel row, grid.y = B * H <= 65535 (csrc/bn_elem.hip
+    pool_bwd_rows_ok; 585 images of 224 x 224).  Larger batches take the unfused chain, whose pool backward has a
+    grid-stride kernel."""
+    return B * H <= 65535
 
 
 def bn_maxpool_bwd(dy, arg, x, saved, training, dgamma=None, dbeta=None, k=3, stride=2, pad=1, dx_dtype=F32):

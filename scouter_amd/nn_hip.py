@@ -206,7 +206,8 @@ class Conv2d(nn.Module):
         # (the persistent bf16x3 forward has the plain epilogue only; a call with an addend / ReLU takes the other kernels)
         xpw = 5 if (self.fwd_on_xpw() and addend is None and not relu and x.dtype == K.F32 and out_dtype in (None, K.F32)) else None
         if (xm & 87) and x.dtype == K.F32 and out_dtype in (None, K.F32):
-            hf = bool(xm & 64) and self.halo_fwd() and addend is None and x.shape[2] <= K.X3_HALO_MAX_W
+            hf = (bool(xm & 64) and self.halo_fwd() and addend is None and x.shape[2] <= K.X3_HALO_MAX_W and
+                  K.x3_halo_fits(x.shape[0] * x.shape[1] * x.shape[2], self.in_channels, self.out_channels, self.groups))
             want_wd = bool(save and ((xm & 6) or ((xm & 64) and self.halo_dgrad())))
             want_wf = (bool(xm & 17) and xpw is None) or hf
             wf, wd = self._x3_weights(want_wf, want_wd) if (want_wf or want_wd) else (None, None)
@@ -274,8 +275,10 @@ class Conv2d(nn.Module):
         if not need_dx:
             return dx
         if (self.halo_dgrad() and wd is not None and dy is not None and dy.dtype == K.F32 and xshape[2] <= K.X3_HALO_MAX_W and
-                dx_dtype in (None, K.F32)):
-            # 3x3 layer with 32 input channels per group: resident rows, split once per element (csrc/conv_xhalo.hip)
+                dx_dtype in (None, K.F32) and
+                K.x3_halo_fits(xshape[0] * xshape[1] * xshape[2], self.in_channels, self.out_channels, self.groups)):
+            # 3x3 layer with 32 input channels per group: resident rows, split once per element (csrc/conv_xhalo.hip); past
+            # its byte guards (K.x3_halo_fits) the fp32 MFMA kernel below, as before tile 7
             return K.conv2d_dgrad_x3(dy, wd, xshape, addend, post=post, tile=7, kh=3, pad=1, groups=self.groups)
         if self.x3_mode() and wd is not None and dyp is None and dy is not None and dy.dtype == K.F32:
             # pointwise layer on the register-split bf16x3 GEMM (x3_mode): plain input gradient (bit 1), or with the
