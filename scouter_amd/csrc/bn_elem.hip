@@ -6,6 +6,9 @@
 // 404-412, 292-306; resnest.py:93,128-129) and their autograd backward.
 #include "common.h"
 
+#include <string>
+#include <vector>
+
 #define MAXB 1024   // max partial blocks of a column reduction
 
 struct ColGeom { long M; int C; int tpr; int rpb; int cslab; };
@@ -817,6 +820,37 @@ static inline int ew_blocks_hoist(long n, int cv) {
     }
     return 0;
 }
+// the route of a channel-parameter pass as ew_blocks_hoist sees it: 0 hoisted, 1 hoisted on a rounded grid (rows wider
+// than a workgroup), 2 un-hoisted
+static inline int hoist_kind(int cv) { return cv > 0 && 256 % cv == 0 ? 0 : (cv > 0 && cv % 256 == 0 ? 1 : 2); }
+
+// Profile labels name the route a call took, "<prefix><a,b,c>" (tests/test_bn_routes_gpu.py asserts them).  The profiler
+// keeps the pointer, so every combination is built once, at the first call of its entry point (thread-safe static init).
+namespace {     // (internal linkage: no symbol added to the library)
+struct RouteLabels {
+    std::vector<std::vector<const char*>> opt;       // opt[0]: prefixes; opt[1..]: the suffix fields ("" = field left out)
+    std::vector<std::string> s;
+    RouteLabels(std::vector<std::vector<const char*>> o) : opt(o) { add(0, ""); }
+    void add(size_t f, std::string t) {
+        if (f == opt.size()) { s.push_back(t + ">"); return; }
+        for (const char* p : opt[f])
+            add(f + 1, f == 0 ? std::string(p) + "<" : (*p ? t + (t.back() == '<' ? "" : ",") + p : t));
+    }
+    const char* operator()(std::initializer_list<int> idx) const {
+        size_t k = 0, f = 0;
+        for (int i : idx) k = k * opt[f++].size() + i;
+        return s[k].c_str();
+    }
+};
+}
+// the suffix fields of the column reductions and of the channel-parameter passes
+#define GEOM_ROUTES {"row", "row-cap", "slab", "slab-cap", ""}   // col_geom: whole-row / 1024-channel slab; col_blocks capped
+static inline int geom_kind(const ColGeom& g) {
+    return (g.cslab == g.C ? 0 : 2) + ((g.M + (long)g.rpb * 8 - 1) / ((long)g.rpb * 8) > MAXB ? 1 : 0);
+}
+#define APPLY_ROUTES {"hoist", "hoist-wide", "stride", "bf16x8h", "bf16x8", "none"}   // hoist_kind, bf16x8<true / false>, no pass
+#define LOOP_ROUTES {"", "loop"}          // a thread of the pass walks more than one vector (n > grid * 256)
+enum { AR_BF16X8H = 3, AR_BF16X8 = 4, AR_NONE = 5 };
 
 extern "C" size_t scouter_colreduce_workspace_bytes(long M, int C) { (void)M; return (size_t)MAXB * C * 2 * sizeof(double); }
 
@@ -851,12 +885,24 @@ extern "C" int scouter_bn_fwd_io(const void* x, void* y, const void* residual, l
     SC_REQUIRE(training || (running_mean && running_var), "bn_fwd: eval mode needs running statistics");
     COL_CHECKS("bn_fwd")
     hipStream_t st = (hipStream_t)stream;
-    ScProfScope prof("bn_fwd(stats+finalize+apply)", st, 0,
-                     ((ext_partial ? 0.0 : 4.0) + ((io & SC_IO_X_BF16) ? 2.0 : 4.0) + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0)) * M * C);
     const double* part = (const double*)ws;
     int nparts = nb;
     if (training && ext_partial) { part = ext_partial; nparts = ext_rows; }     // statistics came from the conv epilogue
-    else if (training)
+    const bool all_bf16 = (io & SC_IO_X_BF16) && (io & SC_IO_Y_BF16) && y && (!residual || (io & SC_IO_R_BF16)) &&
+                          !planes_out && C % 8 == 0;
+    static const RouteLabels labels({{"bn_fwd(stats+finalize+apply)"}, {"partial", "ext", "eval"}, GEOM_ROUTES, {"fin4", "fin1"},
+                                     APPLY_ROUTES, LOOP_ROUTES});
+    const long n4 = M * C / 4;
+    const int hb = ew_blocks_hoist(n4, C / 4);
+    const int apply_route = !(y || planes_out) ? AR_NONE
+                            : all_bf16 ? (256 % (C / 8) == 0 ? AR_BF16X8H : AR_BF16X8) : hoist_kind(C / 4);
+    const long nvec = all_bf16 ? n4 / 2 : n4;
+    const long grid = all_bf16 ? ew_blocks(nvec) : (hb ? hb : ew_blocks(n4));
+    const int src = !training ? 2 : (ext_partial ? 1 : 0);
+    ScProfScope prof(labels({0, src, src == 0 ? geom_kind(g) : 4, fin_narrow(C, nparts) ? 1 : 0, apply_route,
+                             apply_route != AR_NONE && nvec > grid * 256 ? 1 : 0}), st, 0,
+                     ((ext_partial ? 0.0 : 4.0) + ((io & SC_IO_X_BF16) ? 2.0 : 4.0) + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0)) * M * C);
+    if (training && !ext_partial)
         hipLaunchKernelGGL(colsum_partial_kernel<0>, pgrid, dim3(256), 0, st, (const float*)x, nullptr, nullptr, nullptr,
                            nullptr, nullptr, (double*)ws, g);
     if (fin_narrow(C, nparts))
@@ -865,14 +911,11 @@ extern "C" int scouter_bn_fwd_io(const void* x, void* y, const void* residual, l
     else
         hipLaunchKernelGGL(bn_stats_finalize_kernel<4>, dim3(sc_cdiv(C, 4)), dim3(256), 0, st, part, nparts, M, C, gamma, beta,
                            running_mean, running_var, momentum, eps, training, mean_out, rstd_out, scale_out, shift_out);
-    const long n4 = M * C / 4;
     if (y || planes_out) {     // neither: the consumer applies (x - mean) * scale + shift itself (fused split attention)
 #define SSA(XB_, YB_, RB_)                                                                                            \
         hipLaunchKernelGGL((scale_shift_act_kernel<XB_, YB_, RB_>), dim3(ew_blocks(n4)), dim3(256), 0, st, x, mean_out, \
                            scale_out, shift_out, residual, y, relu_mask_out, n4, C, relu, (unsigned short*)planes_out, \
                            nplanes, residual_bn_saved)
-        const bool all_bf16 = (io & SC_IO_X_BF16) && (io & SC_IO_Y_BF16) && y && (!residual || (io & SC_IO_R_BF16)) &&
-                              !planes_out && C % 8 == 0;
         if (all_bf16) {
             const long n8 = n4 / 2;
             if (256 % (C / 8) == 0)         // (the grid stride, a multiple of 256, is then a multiple of C / 8: see HOIST)
@@ -883,7 +926,6 @@ extern "C" int scouter_bn_fwd_io(const void* x, void* y, const void* residual, l
                                    scale_out, shift_out, residual, y, relu_mask_out, n8, C, relu, residual_bn_saved);
         } else
         {
-        const int hb = ew_blocks_hoist(n4, C / 4);
 #define SSH(XB_, YB_, RB_)                                                                                            \
         do {                                                                                                          \
             if (hb) hipLaunchKernelGGL((scale_shift_act_kernel<XB_, YB_, RB_, true>), dim3(hb), dim3(256), 0, st, x,    \
@@ -952,26 +994,41 @@ extern "C" int scouter_bn_bwd_io(const void* dy, const float* ymask, const void*
     float* c1 = (float*)((char*)ws + coef_off);
     float* c2 = c1 + C;
     hipStream_t st = (hipStream_t)stream;
-    ScProfScope prof(ext_partial ? "bn_bwd(finalize+apply)" : "bn_bwd(reduce+finalize+apply)", st, 0,
+    const bool small = !ext_partial && M <= (long)g.rpb * 24 && !xb && !yb && !db;
+    const bool slab16 = C % 16 == 0 && C >= 32;
+    const int nparts = ext_partial ? ext_rows : nb;
+    const bool bf16x8 = xb && yb && db && !ymask && !relu_mask && !gout && C % 8 == 0;
+    static const RouteLabels labels({{"bn_bwd(reduce+finalize+apply)", "bn_bwd(finalize+apply)"}, {"small", "partial", "ext"},
+                                     {"row", "row-cap", "slab", "slab-cap", "", "slab16"}, {"fin4", "fin1", ""},
+                                     {"hoist", "hoist-wide", "stride", "bf16x8h", "bf16x8", ""}, LOOP_ROUTES});
+    const long n4 = M * C / 4;
+    const int hb4 = ew_blocks_hoist(n4, C / 4);
+    const long nvec = bf16x8 ? n4 / 2 : n4;
+    const long grid = bf16x8 ? ew_blocks(nvec) : (hb4 ? hb4 : ew_blocks(n4));
+    ScProfScope prof(small ? labels({0, 0, slab16 ? 5 : (g.cslab == C ? 0 : 2), 2, 5, 0})
+                           : labels({ext_partial ? 1 : 0, ext_partial ? 2 : 1, ext_partial ? 4 : geom_kind(g),
+                                     fin_narrow(C, nparts) ? 1 : 0,
+                                     bf16x8 ? (256 % (C / 8) == 0 ? AR_BF16X8H : AR_BF16X8) : hoist_kind(C / 4),
+                                     nvec > grid * 256 ? 1 : 0}),
+                     st, 0,
                      ((ext_partial ? 12.0 : (ymask && !relu_mask ? 28.0 : 20.0)) + (gout ? 4.0 : 0.0) +
                       (relu_mask ? 0.25 : 0.0) - (xb ? (ext_partial ? 2.0 : 4.0) : 0.0) - (yb ? 2.0 : 0.0) -
                       (db ? (ext_partial ? 2.0 : 4.0) : 0.0)) * M * C);
-    if (!ext_partial && M <= (long)g.rpb * 24 && !xb && !yb && !db) {   // few row passes: everything in one launch
+    if (small) {   // few row passes: everything in one launch
         // 16-channel slabs (4 threads per row, 64 rows per pass) when the channel count allows: C / 16 workgroups with one or
         // two passes each instead of ONE workgroup walking up to 24 dependent passes (14 us on every block's critical path)
         ColGeom gs = g;
         int slabs = pgrid.y;
-        if (C % 16 == 0 && C >= 32) { gs.cslab = 16; gs.tpr = 4; gs.rpb = 64; slabs = C / 16; }
+        if (slab16) { gs.cslab = 16; gs.tpr = 4; gs.rpb = 64; slabs = C / 16; }
         hipLaunchKernelGGL(bn_bwd_small_kernel, dim3(1, slabs), dim3(256), 0, st, (const float*)dy, ymask, (const float*)x, mean,
                            rstd, scale, relu_mask, training, dgamma, dbeta, (float*)dx, gout, gs);
         return sc_check_launch("bn_bwd");
     }
-    const double* part = (const double*)ws;
-    int nparts = nb;
-    if (ext_partial) { part = ext_partial; nparts = ext_rows; }   // reduced by the epilogue of the kernel that produced dy
+    const double* part = ext_partial ? ext_partial : (const double*)ws;   // ext: reduced by the epilogue that produced dy
 #define CSP(XB_, DB_)                                                                                                 \
         hipLaunchKernelGGL((colsum_partial_kernel<1, XB_, DB_>), pgrid, dim3(256), 0, st, (const float*)dy, ymask,          \
                            (const float*)x, mean, rstd, relu_mask, (double*)ws, g)
+    if (ext_partial) {}                    // (the statistics rows are given)
     else if (xb && db) CSP(true, true);
     else if (xb) CSP(true, false);
     else if (db) CSP(false, true);
@@ -982,8 +1039,6 @@ extern "C" int scouter_bn_bwd_io(const void* dy, const float* ymask, const void*
     else
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<4>, dim3(sc_cdiv(C, 4)), dim3(256), 0, st, part, nparts, M, C, training, dgamma,
                            dbeta, c1, c2);
-    const long n4 = M * C / 4;
-    const int hb4 = ew_blocks_hoist(n4, C / 4);
 #define BBA(XB_, YB_, DB_)                                                                                            \
     do {                                                                                                              \
         if (hb4) hipLaunchKernelGGL((bn_bwd_apply_kernel<XB_, YB_, DB_, true>), dim3(hb4), dim3(256), 0, st, dy, ymask, x,  \
@@ -991,10 +1046,10 @@ extern "C" int scouter_bn_bwd_io(const void* dy, const float* ymask, const void*
         else hipLaunchKernelGGL((bn_bwd_apply_kernel<XB_, YB_, DB_>), dim3(ew_blocks(n4)), dim3(256), 0, st, dy, ymask, x,  \
                                 mean, rstd, scale, c1, c2, relu_mask, dx, gout, n4, C);                               \
     } while (0)
-    if (xb && yb && db && !ymask && !relu_mask && !gout && C % 8 == 0 && 256 % (C / 8) == 0)
+    if (bf16x8 && 256 % (C / 8) == 0)
         hipLaunchKernelGGL(bn_bwd_apply_bf16x8_kernel<true>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, st, dy, x, mean, rstd, scale,
                            c1, c2, dx, n4 / 2, C);
-    else if (xb && yb && db && !ymask && !relu_mask && !gout && C % 8 == 0)
+    else if (bf16x8)
         hipLaunchKernelGGL(bn_bwd_apply_bf16x8_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, st, dy, x, mean, rstd, scale,
                            c1, c2, dx, n4 / 2, C);
     else
@@ -1200,7 +1255,16 @@ extern "C" int scouter_sa_bn_bwd_io(const float* dout, const float* a, const flo
     float* c1 = (float*)((char*)ws + coef_off);
     float* c2 = c1 + C;
     hipStream_t st = (hipStream_t)stream;
-    ScProfScope prof(bn_sums ? "sa_bn_bwd(finalize+apply)" : "sa_bn_bwd(reduce+finalize+apply)", st, 0,
+    const bool bf16x8 = xb && !dx && dx_planes && nplanes == 1 && Cp % 8 == 0;
+    static const RouteLabels labels({{"sa_bn_bwd(reduce+finalize+apply)", "sa_bn_bwd(finalize+apply)"}, {"partial", "sums"},
+                                     GEOM_ROUTES, {"fin4", ""}, APPLY_ROUTES, LOOP_ROUTES});
+    const long n4 = M * C / 4;
+    const int hb = ew_blocks_hoist(n4, C / 4);
+    const long nvec = bf16x8 ? n4 / 2 : n4;
+    const long grid = bf16x8 ? ew_blocks(nvec) : (hb ? hb : ew_blocks(n4));
+    ScProfScope prof(labels({bn_sums ? 1 : 0, bn_sums ? 1 : 0, bn_sums ? 4 : geom_kind(g), bn_sums ? 1 : 0,
+                             bf16x8 ? (256 % (C / 8) == 0 ? AR_BF16X8H : AR_BF16X8) : hoist_kind(C / 4),
+                             nvec > grid * 256 ? 1 : 0}), st, 0,
                      ((bn_sums ? 8.0 : 12.0) * C + (bn_sums ? 4.0 : 8.0) * Cp - (xb ? (bn_sums ? 2.0 : 4.0) * C : 0.0)) * M);
     if (bn_sums) {
         hipLaunchKernelGGL(sa_bn_bwd_sums_kernel, dim3(sc_cdiv((long)C * SBS_L, 256)), dim3(256), 0, st, bn_sums, a, dgap, B, C, Cp,
@@ -1213,15 +1277,13 @@ extern "C" int scouter_sa_bn_bwd_io(const float* dout, const float* a, const flo
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<4>, dim3(sc_cdiv(C, 4)), dim3(256), 0, st, (const double*)ws, nb, M, C,
                            training, dgamma, dbeta, c1, c2);
     }
-    const long n4 = M * C / 4;
-    if (xb && !dx && dx_planes && nplanes == 1 && Cp % 8 == 0 && 256 % (C / 8) == 0)
+    if (bf16x8 && 256 % (C / 8) == 0)
         hipLaunchKernelGGL(sa_bn_bwd_apply_bf16x8_kernel<true>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, st, dout, a, dgap, x0,
                            bn_saved, c1, c2, n4 / 2, C, HW, Cp, 1.f / HW, (unsigned short*)dx_planes);
-    else if (xb && !dx && dx_planes && nplanes == 1 && Cp % 8 == 0)
+    else if (bf16x8)
         hipLaunchKernelGGL(sa_bn_bwd_apply_bf16x8_kernel<false>, dim3(ew_blocks(n4 / 2)), dim3(256), 0, st, dout, a, dgap, x0,
                            bn_saved, c1, c2, n4 / 2, C, HW, Cp, 1.f / HW, (unsigned short*)dx_planes);
     else {
-        const int hb = ew_blocks_hoist(n4, C / 4);
 #define SBA(XB_, H_, G_)                                                                                              \
         hipLaunchKernelGGL((sa_bn_bwd_apply_kernel<XB_, H_>), dim3(G_), dim3(256), 0, st, dout, a, dgap, x0, bn_saved, c1, c2, \
                            dx, n4, C, HW, Cp, 1.f / HW, (unsigned short*)dx_planes, nplanes)
@@ -1250,7 +1312,11 @@ extern "C" int scouter_colsum_f32(const float* a, const float* b, float* out, lo
     // few rows (bias gradients of the pooled-vector layers: M = batch): ONE launch, one row block per channel slab -- also
     // for the wide layers (C >= 256: 1-4 rows per pass), where a second 5-us launch costs more than the 70 sequential,
     // independent row loads of a thread
-    if (M <= (long)g.rpb * 12 || M <= 256) {
+    const bool direct = M <= (long)g.rpb * 12 || M <= 256;
+    static const RouteLabels labels({{"colsum"}, {"direct", "partial"}, GEOM_ROUTES, {"", "fin4"}});
+    ScProfScope prof(labels({0, direct ? 0 : 1, direct ? g.cslab == C ? 0 : 2 : geom_kind(g), direct ? 0 : 1}), st, 0,
+                     (b ? 8.0 : 4.0) * M * C);
+    if (direct) {
         dim3 sgrid(1, pgrid.y);
         if (b) hipLaunchKernelGGL(colsum_partial_kernel<3>, sgrid, dim3(256), 0, st, a, b, nullptr, nullptr, nullptr, nullptr, (double*)ws, g, out, alpha);
         else hipLaunchKernelGGL(colsum_partial_kernel<2>, sgrid, dim3(256), 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, (double*)ws, g, out, alpha);
