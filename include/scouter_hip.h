@@ -7,8 +7,9 @@
  *
  * Conventions
  *   - plain C types only: device pointers, sizes, a `void* stream` (hipStream_t); no torch types;
- *   - every function is asynchronous on `stream`, re-entrant, keeps no global mutable state, never allocates
- *     device memory (callers pass workspaces sized by the *_workspace_bytes helpers), never throws or exits;
+ *   - every function is asynchronous on `stream`, re-entrant, keeps no global mutable state besides the routing
+ *     switches below, never allocates device memory (callers pass workspaces sized by the *_workspace_bytes
+ *     helpers), never throws or exits;
  *   - return 0 on success, <0 on error (SC_ERR_* below); the message is in scouter_last_error() (thread-local);
  *   - tensors are caller-owned, dense, 16-byte aligned fp32 unless stated;
  *   - activations are NHWC ("[M = B*H*W][C]"), convolution weights are HWIO ([kh][kw][Cin/groups][Cout]).
@@ -28,6 +29,16 @@ extern "C" {
 
 int scouter_abi_version(void);
 const char* scouter_last_error(void);
+
+/* routing switches: each is read from its environment variable once, when the library first needs one, and changed
+ * afterwards only here.  Names (variable, default): "xwt" (SCOUTER_XWT, 1), "bwt" (SCOUTER_BWT, 1), "bhalo"
+ * (SCOUTER_BHALO, 1), "xslot_small" (SCOUTER_XSLOT_SMALL, 1), "xslot_bwd_halves" (SCOUTER_XSLOT_BWD_HALVES, 1),
+ * "xslot_bwd_scratch" (SCOUTER_XSLOT_BWD_SCRATCH, 0), "pwp_bn" / "pwp_resident" (SCOUTER_PWP_PLAN_DEV="bn,resident",
+ * 0 = the library's own plan).  Values are >= 0.  scouter_set_switch returns SC_ERR_ARG for an unknown name or a negative
+ * value; scouter_get_switch returns the value, or SC_ERR_ARG for an unknown name.  A launch already enqueued keeps the
+ * route it took. */
+int scouter_set_switch(const char* name, int value);
+int scouter_get_switch(const char* name);
 
 /* ---- input pipeline on the GPU: the reference's make_transform
  * (dataset/transform_func.py:101-124) = Resize((S,S)) [:19-31, torchvision F.resize -> PIL Image.resize BILINEAR with

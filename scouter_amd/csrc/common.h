@@ -18,6 +18,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 void sc_set_error(const char* fmt, ...);
 int sc_check_launch(const char* what);
 
+// routing switches (include/scouter_hip.h scouter_set_switch): read from the environment once, at first use; a launch path
+// reads each one once per call and routes on that one value
+enum ScSwitch { SC_SW_XWT, SC_SW_BWT, SC_SW_BHALO, SC_SW_XSLOT_SMALL, SC_SW_XSLOT_BWD_HALVES, SC_SW_XSLOT_BWD_SCRATCH,
+                SC_SW_PWP_BN, SC_SW_PWP_RESIDENT, SC_SW_COUNT };
+int sc_switch(ScSwitch s);
+
+// raises the dynamic-LDS limit of `kern` on the current device when a launch needs more than it was given before; a
+// failure is reported by the caller's next sc_check_launch
+void sc_dyn_lds(const void* kern, size_t bytes);
+
 #define SC_REQUIRE(cond, ...)                 \
     do {                                      \
         if (!(cond)) {                        \

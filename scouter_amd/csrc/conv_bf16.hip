@@ -264,7 +264,7 @@ static void launch_bf16(const void* src, const void* w, const float* bias, const
         const int one = ktiles <= 1 || (DGRAD && ktiles <= ONE_STAGE_MAX);
         size_t lds = (size_t)(one ? 1 : 2) * (BM + BN) * (kt + 8) * 2;
         if (lds < epi) lds = epi;
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        sc_dyn_lds((const void*)kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, src, w, bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, fz,
                            (io & SC_IO_Y_BF16) ? 1 : 0, one);
     };
@@ -276,36 +276,29 @@ static void launch_bf16(const void* src, const void* w, const float* bias, const
     if (g.Cg % 64 == 0) go(igemm_bf16_kernel<BM, BN, WM, WN, 64, DGRAD>, 64);
     else go(igemm_bf16_kernel<BM, BN, WM, WN, 32, DGRAD>, 32);
 }
-static bool bhalo_dgrad_on(const ConvGeom& g, int io) {        // SCOUTER_BHALO=0: the tile kernel
-    const char* e = getenv("SCOUTER_BHALO");
-    return !(e && e[0] == '0') && bhalo_dgrad_ok(g, io);
-}
-static bool bhalo_fwd_on(const ConvGeom& g, int io, int tile) {  // tiles 1 (128 x 64) / 3 (128 x 32): the same 128-pixel partial rows
-    const char* e = getenv("SCOUTER_BHALO");
-    return !(e && e[0] == '0') && bhalo_fwd_ok(g, io) && tile == (g.Ng == 64 ? 1 : 3);
+// persistent resident-rows workgroups: `wgs` (three / two per CU) at most, one group per workgroup (weights resident)
+static unsigned bhalo_grid(long wgs, int mtiles, int groups) {
+    if (wgs > (long)mtiles * groups) wgs = (long)mtiles * groups;
+    wgs -= wgs % groups;
+    return (unsigned)(wgs < groups ? groups : wgs);
 }
 template <int NB>
 static void launch_bhalo_fwd(const void* src, const void* w, const float* bias, const float* addend, float* dst, double* bn_part,
                              const ConvGeom& g, int relu, hipStream_t st, int io) {
     const int mtiles = sc_cdiv(g.M, 128);
     const size_t blds = bhalo_fwd_lds_bytes(NB);
-    const char* we = getenv("SCOUTER_BHALO_WGS");
-    long wgs = we ? atoi(we) : (NB == 1 ? 768 : 512);            // three / two workgroups per CU
-    if (wgs > (long)mtiles * g.groups) wgs = (long)mtiles * g.groups;
-    wgs -= wgs % g.groups;                                       // one group per workgroup (weights resident)
-    if (wgs < g.groups) wgs = g.groups;
     auto kern = bhalo_fwd_kernel<NB>;
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), blds, st, (const unsigned short*)src, (const unsigned short*)w, bias,
-                       addend, dst, bn_part, g, relu, mtiles, (io & SC_IO_Y_BF16) ? 1 : 0);
+    sc_dyn_lds((const void*)kern, blds);
+    hipLaunchKernelGGL(kern, dim3(bhalo_grid(NB == 1 ? 768 : 512, mtiles, g.groups)), dim3(256), blds, st, (const unsigned short*)src,
+                       (const unsigned short*)w, bias, addend, dst, bn_part, g, relu, mtiles, (io & SC_IO_Y_BF16) ? 1 : 0);
 }
 template <bool DGRAD>
 static int dispatch_bf16(const void* src, const void* w, const float* bias, const float* addend, float* dst,
                          double* bn_part, const ConvGeom& g, int relu, int tile, hipStream_t st,
-                         const BnBwdFuse& fz = BnBwdFuse{}, int io = 0) {
+                         const BnBwdFuse& fz, int io, bool bhalo) {   // bhalo: the caller's resident-rows decision
     SC_UNSUPPORTED(g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28),
                    "conv2d_bf16: more than 2^31 output pixels or an image above 2^28 elements is not supported");
-    if (!DGRAD && bhalo_fwd_on(g, io, tile)) {
+    if (!DGRAD && bhalo) {
         // resident x rows for all nine taps (conv_halo_dgrad_bf16.h): bit-identical to tiles 1 / 3, same partial rows
         if (g.Ng == 64) launch_bhalo_fwd<2>(src, w, bias, addend, dst, bn_part, g, relu, st, io);
         else launch_bhalo_fwd<1>(src, w, bias, addend, dst, bn_part, g, relu, st, io);
@@ -316,18 +309,14 @@ static int dispatch_bf16(const void* src, const void* w, const float* bias, cons
         case 1: launch_bf16<128, 64, 64, 32, DGRAD>(src, w, bias, addend, dst, bn_part, g, relu, st, fz, io); break;
         case 2: launch_bf16<64, 64, 32, 32, DGRAD>(src, w, bias, addend, dst, bn_part, g, relu, st, fz, io); break;
         default:
-            if (DGRAD && bhalo_dgrad_on(g, io) && !fz.part2 && !bias && !bn_part && !relu) {
+            if (DGRAD && bhalo) {
                 // resident dy rows for all nine taps (conv_halo_dgrad_bf16.h): same tiles, partial rows and epilogue as <128, 32>
                 const int mtiles = sc_cdiv(g.M, 128), halves = g.Cg / 32;
                 const size_t blds = bhalo_lds_bytes(halves);
-                const char* we = getenv("SCOUTER_BHALO_WGS");
-                long wgs = we ? atoi(we) : (halves == 1 ? 768 : 512);          // three / two workgroups per CU
-                if (wgs > (long)mtiles * g.groups) wgs = (long)mtiles * g.groups;
-                wgs -= wgs % g.groups;                                         // one group per workgroup (weights resident)
-                if (wgs < g.groups) wgs = g.groups;
-                hipFuncSetAttribute((const void*)bhalo_dgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-                hipLaunchKernelGGL(bhalo_dgrad_kernel, dim3((unsigned)wgs), dim3(256), blds, st, (const unsigned short*)src,
-                                   (const float*)w, addend, dst, g, mtiles, fz, (io & SC_IO_Y_BF16) ? 1 : 0);
+                sc_dyn_lds((const void*)bhalo_dgrad_kernel, blds);
+                hipLaunchKernelGGL(bhalo_dgrad_kernel, dim3(bhalo_grid(halves == 1 ? 768 : 512, mtiles, g.groups)), dim3(256), blds,
+                                   st, (const unsigned short*)src, (const float*)w, addend, dst, g, mtiles, fz,
+                                   (io & SC_IO_Y_BF16) ? 1 : 0);
                 break;
             }
             launch_bf16<128, 32, 32, 32, DGRAD>(src, w, bias, addend, dst, bn_part, g, relu, st, fz, io);
@@ -373,20 +362,17 @@ static void launch_pwb_fused(const void* src, const float* w, const void* addend
     const int mtiles = sc_cdiv(g.M, 64), grid = p.wg_per_col * (g.Ng / 128);
     const size_t lds = (size_t)128 * g.Cg * 2 + 4 * 8192;
     const long mask_words = ((g.M * g.Ng / 4 + 63) / 64) * 4;
-#define PWB(KS_, TWO_)                                                                                             \
+#define PWB(KS_)                                                                                                   \
     do {                                                                                                           \
-        auto kern = pwb_fused_kernel<KS_, TWO_>;                                                                   \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 64 * KS_ * 2 + 4 * 8192); attr_set = true; } \
+        auto kern = fz.part2 ? pwb_fused_kernel<KS_, true> : pwb_fused_kernel<KS_, false>;                         \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, g.M, g.Ng, mtiles, p.wg_per_col, fz, \
                            mask_words);                                                                            \
     } while (0)
-#define PWB2(KS_) do { if (fz.part2) PWB(KS_, true); else PWB(KS_, false); } while (0)
-    if (p.ks == 1) PWB2(1);
-    else if (p.ks == 2) PWB2(2);
-    else if (p.ks == 4) PWB2(4);
-    else PWB2(8);
-#undef PWB2
+    if (p.ks == 1) PWB(1);
+    else if (p.ks == 2) PWB(2);
+    else if (p.ks == 4) PWB(4);
+    else PWB(8);
 #undef PWB
 }
 
@@ -404,22 +390,19 @@ static void launch_pwb_dgrad(const void* src, const float* w, const void* addend
     if (wg < 8) wg = 8;
     const int mtiles = sc_cdiv(g.M, 64), grid = wg * (g.Ng / 64);
     const size_t lds = (size_t)64 * g.Cg * 2 + 4 * 8192;
-#define PWD(KS_, ADD_)                                                                                             \
+#define PWD(KS_)                                                                                                   \
     do {                                                                                                           \
-        auto kern = pwb_dgrad_kernel<KS_, ADD_>;                                                                   \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 64 * KS_ * 2 + 4 * 8192); attr_set = true; } \
+        auto kern = addend ? pwb_dgrad_kernel<KS_, true> : pwb_dgrad_kernel<KS_, false>;                           \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, g.M, g.Ng, mtiles, wg, add_bf16); \
     } while (0)
-#define PWD2(KS_) do { if (addend) PWD(KS_, true); else PWD(KS_, false); } while (0)
     switch (ks) {
-        case 1: PWD2(1); break;
-        case 2: PWD2(2); break;
-        case 4: PWD2(4); break;
-        case 8: PWD2(8); break;
-        default: PWD2(16); break;
+        case 1: PWD(1); break;
+        case 2: PWD(2); break;
+        case 4: PWD(4); break;
+        case 8: PWD(8); break;
+        default: PWD(16); break;
     }
-#undef PWD2
 #undef PWD
 }
 
@@ -438,25 +421,20 @@ static int pwb_fwd_wg_per_col(const ConvGeom& g) {
 static void launch_pwb_fwd(const void* src, const void* wt, void* dst, double* bn_part, const ConvGeom& g, hipStream_t st, int io) {
     const int wg = pwb_fwd_wg_per_col(g), mtiles = sc_cdiv(g.M, 64), grid = wg * (g.Ng / 128);
     const size_t lds = (size_t)128 * g.Cg * 2 + 4 * 8192;
-#define PWF(KS_, YB_, ST_)                                                                                         \
+#define PWF(KS_, YB_)                                                                                              \
     do {                                                                                                           \
-        auto kern = pwb_fwd_kernel<KS_, YB_, ST_>;                                                                 \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 64 * KS_ * 2 + 4 * 8192); attr_set = true; } \
+        auto kern = bn_part ? pwb_fwd_kernel<KS_, YB_, true> : pwb_fwd_kernel<KS_, YB_, false>;                    \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, wt, dst, bn_part, g.M, g.Ng, mtiles, wg);    \
     } while (0)
-#define PWF3(KS_)                                                                                                  \
-    do {                                                                                                           \
-        if (io & SC_IO_Y_BF16) { if (bn_part) PWF(KS_, true, true); else PWF(KS_, true, false); }                  \
-        else { if (bn_part) PWF(KS_, false, true); else PWF(KS_, false, false); }                                  \
-    } while (0)
+#define PWF2(KS_) do { if (io & SC_IO_Y_BF16) PWF(KS_, true); else PWF(KS_, false); } while (0)
     switch (g.Cg / 64) {
-        case 1: PWF3(1); break;
-        case 2: PWF3(2); break;
-        case 4: PWF3(4); break;
-        default: PWF3(8); break;
+        case 1: PWF2(1); break;
+        case 2: PWF2(2); break;
+        case 4: PWF2(4); break;
+        default: PWF2(8); break;
     }
-#undef PWF3
+#undef PWF2
 #undef PWF
 }
 
@@ -491,14 +469,16 @@ extern "C" int scouter_conv2d_fwd_bf16_io(const void* x, const void* wt_bf16, co
                    "conv2d_fwd_bf16: tile 4 (persistent) covers 1x1 / stride 1 / groups 1 layers with 64 / 128 / 256 / 512 input "
                    "channels stored as bf16, 128-multiples of output channels, no bias / addend / ReLU");
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
-    ScProfScope prof(bhalo_fwd_on(g, io, tile) ? "bhalo_fwd<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cout * g.Cg * kh * kw,
+    // tiles 1 (128 x 64) / 3 (128 x 32): the same 128-pixel partial rows (SCOUTER_BHALO=0: the tile kernel)
+    const bool bhalo = tile == (g.Ng == 64 ? 1 : 3) && sc_switch(SC_SW_BHALO) && bhalo_fwd_ok(g, io);
+    ScProfScope prof(bhalo ? "bhalo_fwd<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cout * g.Cg * kh * kw,
                      ((io & SC_IO_X_BF16) ? 2.0 : 4.0) * B * H * W * Cin + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0) * g.M * Cout);
     if (tile == 4) {
         launch_pwb_fwd(x, wt_bf16, y, bn_partial, g, (hipStream_t)stream, io);
         return sc_check_launch("conv2d_fwd_bf16(persistent)");
     }
     return dispatch_bf16<false>(x, wt_bf16, bias, addend, (float*)y, bn_partial, g, relu, tile, (hipStream_t)stream,
-                                BnBwdFuse{}, io);
+                                BnBwdFuse{}, io, bhalo);
 }
 // rows of bn_partial the typed forward writes: tiles 0-3 one per M tile, tile 4 one per workgroup row
 extern "C" int scouter_conv2d_fwd_bn_partial_rows_bf16(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
@@ -550,7 +530,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
     // algorithmic bytes: dy, dx and -- the fused launch -- the shortcut gradient, the BatchNorm input(s) and the ReLU bits
     const double out_elems = (double)g.M * Cin;
-    const bool bhalo = tile == 3 && !part2 && bhalo_dgrad_on(g, io_xy);
+    const bool bhalo = tile == 3 && !part2 && sc_switch(SC_SW_BHALO) && bhalo_dgrad_ok(g, io_xy);   // (SCOUTER_BHALO=0: the tile kernel)
     ScProfScope prof(bhalo ? "bhalo_dgrad<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cin * Cog * kh * kw,
                      ((io & 8) ? 2.0 : 4.0) * B * Ho * Wo * Cout + ((io & 16) ? 2.0 : 4.0) * out_elems +
                          (addend ? ((io & 4) ? 2.0 : 4.0) * out_elems : 0.0) +
@@ -563,7 +543,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
         return sc_check_launch("conv2d_dgrad_bf16(persistent)");
     }
     return dispatch_bf16<true>(dy, w, nullptr, (const float*)addend, (float*)dx, nullptr, g, 0, tile, (hipStream_t)stream,
-                               fz, io_xy);
+                               fz, io_xy, bhalo);
 }
 // partial rows ([rows][Cin][2] fp64) the fused launch writes: tiles 0-3 one per M tile, tile 4 one per workgroup row
 extern "C" int scouter_conv2d_dgrad_bn_partial_rows_bf16(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,

@@ -684,13 +684,11 @@ static PwpPlan pwp_plan(const ConvGeom& g) {
     //  per M range share the XCD's L2 copy of A; tools_dev/pwp_plan_bench.py.  256 stays reachable through the development override)
     p.bn = (cap >= 128 && g.Ng % 128 == 0) ? 128 : 64;
     int resident = 1;
-    // development override (tools_dev/pwp_plan_bench.py): "bn,resident"
-    if (const char* e = getenv("SCOUTER_PWP_PLAN_DEV")) {
-        int bn = 0, r = 0;
-        if (sscanf(e, "%d,%d", &bn, &r) == 2 && (bn == 64 || bn == 128 || bn == 256) && bn * p.ks <= 256 && g.Ng % bn == 0 && r >= 1 && r <= 4) {
-            p.bn = bn;
-            resident = r;
-        }
+    // development override (tools_dev/pwp_plan_bench.py): switches pwp_bn / pwp_resident, where legal for the shape
+    const int bn = sc_switch(SC_SW_PWP_BN), r = sc_switch(SC_SW_PWP_RESIDENT);
+    if ((bn == 64 || bn == 128 || bn == 256) && bn * p.ks <= 256 && g.Ng % bn == 0 && r >= 1 && r <= 4) {
+        p.bn = bn;
+        resident = r;
     }
     const int colgroups = g.Ng / p.bn;
     int w = ((256 * resident) / colgroups) & ~7;
@@ -706,19 +704,11 @@ static void launch_pwp(const float* src, const float* w, const float* addend, fl
     const size_t lds = (size_t)g.Cg * p.bn * 4 + 4 * 16384;
 #define PWP(KS_, BN_)                                                                                              \
     do {                                                                                                           \
-        if (DGRAD ? addend != nullptr : bn_part != nullptr) {                                                      \
-            auto kern = pwp_kernel<KS_, BN_, DGRAD, true>;                                                         \
-            static bool attr_set = false;                                                                          \
-            if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4 * 16384); attr_set = true; } \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, bn_part, g.M, g.Ng, mtiles, \
-                               p.wg_per_col);                                                                      \
-        } else {                                                                                                   \
-            auto kern = pwp_kernel<KS_, BN_, DGRAD, false>;                                                        \
-            static bool attr_set = false;                                                                          \
-            if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4 * 16384); attr_set = true; } \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, bn_part, g.M, g.Ng, mtiles, \
-                               p.wg_per_col);                                                                      \
-        }                                                                                                          \
+        auto kern = (DGRAD ? addend != nullptr : bn_part != nullptr) ? pwp_kernel<KS_, BN_, DGRAD, true>           \
+                                                                     : pwp_kernel<KS_, BN_, DGRAD, false>;         \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, bn_part, g.M, g.Ng, mtiles,  \
+                           p.wg_per_col);                                                                          \
     } while (0)
     if (p.ks == 1 && p.bn == 256) PWP(1, 256);
     else if (p.ks == 1 && p.bn == 128) PWP(1, 128);
@@ -747,21 +737,18 @@ static void launch_pwp_fused(const float* src, const float* w, const float* adde
     const int mtiles = sc_cdiv(g.M, 64), grid = p.wg_per_col * (g.Ng / p.bn);
     const size_t lds = (size_t)g.Cg * p.bn * 4 + 4 * 16384;
     const long mask_words = ((g.M * g.Ng / 4 + 63) / 64) * 4;
-#define PWF(KS_, BN_, TWO_)                                                                                        \
+#define PWF(KS_, BN_)                                                                                              \
     do {                                                                                                           \
-        auto kern = pwp_fused_kernel<KS_, BN_, TWO_>;                                                              \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4 * 16384); attr_set = true; } \
+        auto kern = fz.part2 ? pwp_fused_kernel<KS_, BN_, true> : pwp_fused_kernel<KS_, BN_, false>;               \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, g.M, g.Ng, mtiles, p.wg_per_col, fz, \
                            mask_words);                                                                            \
     } while (0)
-#define PWF2(KS_, BN_) do { if (fz.part2) PWF(KS_, BN_, true); else PWF(KS_, BN_, false); } while (0)
-    if (p.ks == 1 && p.bn == 128) PWF2(1, 128);
-    else if (p.ks == 1) PWF2(1, 64);
-    else if (p.ks == 2 && p.bn == 128) PWF2(2, 128);
-    else if (p.ks == 2) PWF2(2, 64);
-    else PWF2(4, 64);
-#undef PWF2
+    if (p.ks == 1 && p.bn == 128) PWF(1, 128);
+    else if (p.ks == 1) PWF(1, 64);
+    else if (p.ks == 2 && p.bn == 128) PWF(2, 128);
+    else if (p.ks == 2) PWF(2, 64);
+    else PWF(4, 64);
 #undef PWF
 }
 
@@ -788,19 +775,16 @@ static void launch_xpw_fused(const float* src, const float* w, const float* adde
     const int mtiles = sc_cdiv(g.M, 64), grid = p.wg_per_col * (g.Ng / 64);
     const size_t lds = (size_t)3 * 64 * g.Cg * 2 + 4 * 8192;
     const long mask_words = ((g.M * g.Ng / 4 + 63) / 64) * 4;
-#define XPW(KS_, TWO_)                                                                                             \
+#define XPW(KS_)                                                                                                   \
     do {                                                                                                           \
-        auto kern = xpw_fused_kernel<KS_, TWO_>;                                                                   \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 64 * 64 * KS_ * 2 + 4 * 8192); attr_set = true; } \
+        auto kern = fz.part2 ? xpw_fused_kernel<KS_, true> : xpw_fused_kernel<KS_, false>;                         \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, addend, dst, g.M, g.Ng, mtiles, p.wg_per_col, fz, \
                            mask_words);                                                                            \
     } while (0)
-#define XPW2(KS_) do { if (fz.part2) XPW(KS_, true); else XPW(KS_, false); } while (0)
-    if (p.ks == 1) XPW2(1);
-    else if (p.ks == 2) XPW2(2);
-    else XPW2(4);
-#undef XPW2
+    if (p.ks == 1) XPW(1);
+    else if (p.ks == 2) XPW(2);
+    else XPW(4);
 #undef XPW
 }
 
@@ -808,18 +792,15 @@ static void launch_xpw_fwd(const float* src, const float* w, float* dst, double*
     const XpwPlan p = xpw_plan(g);
     const int mtiles = sc_cdiv(g.M, 64), grid = p.wg_per_col * (g.Ng / 64);
     const size_t lds = (size_t)3 * 64 * g.Cg * 2 + 4 * 8192;
-#define XPF(KS_, ST_)                                                                                              \
+#define XPF(KS_)                                                                                                   \
     do {                                                                                                           \
-        auto kern = xpw_fwd_kernel<KS_, ST_>;                                                                      \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 64 * 64 * KS_ * 2 + 4 * 8192); attr_set = true; } \
+        auto kern = bn_part ? xpw_fwd_kernel<KS_, true> : xpw_fwd_kernel<KS_, false>;                              \
+        sc_dyn_lds((const void*)kern, lds);                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, src, w, dst, bn_part, g.M, g.Ng, mtiles, p.wg_per_col); \
     } while (0)
-#define XPF2(KS_) do { if (bn_part) XPF(KS_, true); else XPF(KS_, false); } while (0)
-    if (p.ks == 1) XPF2(1);
-    else if (p.ks == 2) XPF2(2);
-    else XPF2(4);
-#undef XPF2
+    if (p.ks == 1) XPF(1);
+    else if (p.ks == 2) XPF(2);
+    else XPF(4);
 #undef XPF
 }
 
@@ -1058,10 +1039,8 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
         const long tiles = (long)co_tiles * groups;
         // default (SCOUTER_XWT=0: off): the register-split bf16x3 kernel (64-pixel chunks, rows up to 112 pixels wide).  One workgroup per CU
         // (147 KB of LDS) and a five-unit prologue per workgroup: ONE round of long pixel ranges, not four of short ones
-        const char* xe = getenv("SCOUTER_XWT");
-        const bool xwt = !(xe && xe[0] == '0') && g.W <= 112 && g.H >= 2 && BK == 32;
-        const char* xw = getenv("SCOUTER_XWT_WGS");
-        long want = (xwt ? (xw ? atoi(xw) : 256) : 1024) / tiles;
+        const bool xwt = sc_switch(SC_SW_XWT) && g.W <= 112 && g.H >= 2 && BK == 32;
+        long want = (xwt ? 256 : 1024) / tiles;
         if (want < 1) want = 1;
         long chunks = (g.M + BK - 1) / BK, cps = (chunks + want - 1) / want;
         if (cps < 8) cps = 8;
@@ -1080,31 +1059,17 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
                 const size_t xlds = xwgrad_taps_lds_bytes(bn);
                 ScProfScope prof("xwgrad_taps<bf16x3>", st, 2.0 * g.M * Cout * g.Cg * 9,
                                  4.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
-                if (bn == 64) {
-                    auto kern = xwgrad_taps_kernel<64>;
-                    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), xlds, st, x, dy, out, g,
-                                       co_tiles, pps, slab_t, dw, arr);
-                } else {
-                    auto kern = xwgrad_taps_kernel<32>;
-                    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), xlds, st, x, dy, out, g,
-                                       co_tiles, pps, slab_t, dw, arr);
-                }
+                auto kern = bn == 64 ? xwgrad_taps_kernel<64> : xwgrad_taps_kernel<32>;
+                sc_dyn_lds((const void*)kern, xlds);
+                hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), xlds, st, x, dy, out, g, co_tiles,
+                                   pps, slab_t, dw, arr);
             } else {
                 ScProfScope prof("wgrad_taps", st, 2.0 * g.M * Cout * g.Cg * 9,
                                  4.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
-                if (bn == 64) {
-                    auto kern = wgrad_taps_kernel<64>;
-                    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), lds, st, x, dy, out, g,
-                                       co_tiles, pps, slab_t, dw, arr);
-                } else {
-                    auto kern = wgrad_taps_kernel<32>;
-                    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), lds, st, x, dy, out, g,
-                                       co_tiles, pps, slab_t, dw, arr);
-                }
+                auto kern = bn == 64 ? wgrad_taps_kernel<64> : wgrad_taps_kernel<32>;
+                sc_dyn_lds((const void*)kern, lds);
+                hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), lds, st, x, dy, out, g, co_tiles,
+                                   pps, slab_t, dw, arr);
             }
             int rc = sc_check_launch("conv2d_wgrad_taps");
             if (rc) return rc;
@@ -1200,12 +1165,10 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     // the library's own plan, SCOUTER_BWT=0: off) -- every X row fetched once per workgroup instead of once per tap
     if (plan_hint < 0 && xb && db && kh == 3 && kw == 3 && stride == 1 && pad == 1 && g.Cg == 32 && g.W <= 112 && g.H >= 2 &&
         BWT_CH / g.Wo + 1 < g.Ho && (g.M + 512) * (long)(g.C > g.N ? g.C : g.N) * 2 < (1L << 31)) {
-        const char* be = getenv("SCOUTER_BWT");
         const int bn = g.Ng % 64 == 0 ? 64 : 32;
         const int co_tiles = g.Ng / bn;
         const long tiles = (long)co_tiles * groups;
-        const char* bw = getenv("SCOUTER_BWT_WGS");
-        long want = (bw ? atoi(bw) : 512) / tiles;                 // two workgroups per CU
+        long want = 512 / tiles;                                   // two workgroups per CU
         if (want < 1) want = 1;
         long chunks = (g.M + BWT_CH - 1) / BWT_CH, cps = (chunks + want - 1) / want;
         if (cps < 4) cps = 4;
@@ -1213,24 +1176,17 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
         const int splits = (int)((g.M + pps - 1) / pps);
         const long slab_t = (long)9 * g.Cg * Cout;
         const size_t need_t = splits > 1 ? (size_t)splits * slab_t * sizeof(float) : 0;
-        if (!(be && be[0] == '0') && need_t <= ws_bytes && (!need_t || ws)) {
+        if (sc_switch(SC_SW_BWT) && need_t <= ws_bytes && (!need_t || ws)) {
             hipStream_t st = (hipStream_t)stream;
             float* out = splits > 1 ? (float*)ws : dw;
             unsigned* arr = splits > 1 && arrival && tiles <= arrival_slots ? (unsigned*)arrival : nullptr;
             const size_t blds = bwgrad_taps_lds_bytes(bn);
             {
             ScProfScope prof("bwgrad_taps<bf16>", st, 2.0 * g.M * Cout * g.Cg * 9, 2.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
-            if (bn == 64) {
-                auto kern = bwgrad_taps_kernel<64>;
-                hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-                hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), blds, st, (const unsigned short*)x,
-                                   (const unsigned short*)dy, out, g, co_tiles, pps, slab_t, dw, arr);
-            } else {
-                auto kern = bwgrad_taps_kernel<32>;
-                hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-                hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), blds, st, (const unsigned short*)x,
-                                   (const unsigned short*)dy, out, g, co_tiles, pps, slab_t, dw, arr);
-            }
+            auto kern = bn == 64 ? bwgrad_taps_kernel<64> : bwgrad_taps_kernel<32>;
+            sc_dyn_lds((const void*)kern, blds);
+            hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), blds, st, (const unsigned short*)x,
+                               (const unsigned short*)dy, out, g, co_tiles, pps, slab_t, dw, arr);
             }
             int rc = sc_check_launch("conv2d_wgrad_taps_bf16");
             if (rc) return rc;
@@ -1262,7 +1218,7 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
 #define WGK(KERN)                                                                                                   \
     do {                                                                                                            \
         auto kern = KERN;                                                                                           \
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
+        sc_dyn_lds((const void*)kern, lds);                                                                         \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, x, dy, out, g, p.ci_tiles, p.co_tiles, p.pix_per_split,  \
                            slab, dw, arr);                                                                          \
     } while (0)

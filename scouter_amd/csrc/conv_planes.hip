@@ -728,11 +728,7 @@ static void launch_pconv(const void* a, long a_pe, const void* w, long w_pe, con
     constexpr int EPI_BYTES = 2 * NWM * (BM / NWM) * (BN / 2 + 4) * 4;
     const size_t lds = (size_t)(NSTAGE * STAGE_BYTES > EPI_BYTES ? NSTAGE * STAGE_BYTES : EPI_BYTES);
     auto kern = pconv_kernel<BM, BN, NP, NSTAGE, DGRAD, NWM>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    sc_dyn_lds((const void*)kern, lds);
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles * g.groups), dim3(NWM * 128), lds, st, (const unsigned short*)a, a_pe,
                        (const unsigned short*)w, w_pe, bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, fz);
 }
@@ -759,11 +755,7 @@ static void launch_ppersist(const void* a, long a_pe, const void* w, long w_pe, 
     gg.inv_ho = 1.0f / (float)g.Ho;
     constexpr int LDS = 2 * NP * (BM + BN) * 64 + 1024;
     auto kern = ppersist_kernel<BN, NP, DGRAD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
+    sc_dyn_lds((const void*)kern, LDS);
     const int ntot = mtiles * ntiles * g.groups, cus = sc_persistent_grid();
     hipLaunchKernelGGL(kern, dim3(ntot <= cus ? ntot : cus), dim3(512), LDS, st, (const unsigned short*)a, a_pe,
                        (const unsigned short*)w, w_pe, bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, fz);
@@ -781,11 +773,7 @@ static void launch_phalo(const void* a, long a_pe, const void* w, long w_pe, con
     constexpr int IMG = 2 * NP * 13 * 1024, WST = 2 * 3 * NP * BN * 32, EPI = 8 * 64 * (BN / 2 + 4) * 4;
     constexpr int LDS = IMG + WST > EPI ? IMG + WST : EPI;
     auto kern = phalo_kernel<BN, NP, DGRAD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
+    sc_dyn_lds((const void*)kern, LDS);
     const int agroups = (BM + 2 * g.W + 2 + 31) / 32;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles * g.groups), dim3(512), LDS, st, (const unsigned short*)a, a_pe,
                        (const unsigned short*)w, w_pe, bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, agroups, fz);
@@ -1253,19 +1241,10 @@ extern "C" int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_
         ScProfScope prof(nplanes == 3 ? "pwgrad<bf16x3>" : "pwgrad<bf16>", st, 2.0 * g.M * Cout * Cg * kh * kw,
                          2.0 * nplanes * ((double)x_pe + (double)dy_pe));
         const size_t lds = (size_t)nplanes * (256 * 128 + 128) + (size_t)3 * nplanes * 32 * 64 * 2;
-        if (nplanes == 3) {
-            auto kern = pwgrad_taps_kernel<3, 1>;
-            static bool attr_set = false;
-            if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned short*)x_planes, x_pe,
-                               (const unsigned short*)dy_planes, dy_pe, out, g, ci_tiles, co_tiles, pps, slab, dw, arr);
-        } else {
-            auto kern = pwgrad_taps_kernel<1, 1>;
-            static bool attr_set = false;
-            if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned short*)x_planes, x_pe,
-                               (const unsigned short*)dy_planes, dy_pe, out, g, ci_tiles, co_tiles, pps, slab, dw, arr);
-        }
+        auto kern = nplanes == 3 ? pwgrad_taps_kernel<3, 1> : pwgrad_taps_kernel<1, 1>;
+        sc_dyn_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned short*)x_planes, x_pe,
+                           (const unsigned short*)dy_planes, dy_pe, out, g, ci_tiles, co_tiles, pps, slab, dw, arr);
     } else {
         ScProfScope prof(nplanes == 3 ? "pwgrad<bf16x3>" : "pwgrad<bf16>", st, 2.0 * g.M * Cout * Cg * kh * kw,
                          2.0 * nplanes * ((double)x_pe + (double)dy_pe));
@@ -1274,8 +1253,7 @@ extern "C" int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_
         constexpr int NST = 3;                                                                                      \
         const size_t lds = (size_t)NST * NP_ * 32 * (BM_ + BN_) * 2;                                                \
         auto kern = pwgrad_kernel<BM_, BN_, NP_, NST>;                                                              \
-        static bool attr_set = false;                                                                               \
-        if (!attr_set) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; } \
+        sc_dyn_lds((const void*)kern, lds);                                                                         \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const unsigned short*)x_planes, x_pe,                   \
                            (const unsigned short*)dy_planes, dy_pe, out, g, ci_tiles, co_tiles, pps, slab, dw, arr);         \
     } while (0)

@@ -351,11 +351,7 @@ static void launch_x3(const float* a, const void* w, long w_pe, const float* bia
     constexpr int EPI_BYTES = NWM * NWN * (BM / NWM) * (BN / NWN + 4) * 4;
     const size_t lds = (size_t)(2 * STAGE_BYTES > EPI_BYTES ? 2 * STAGE_BYTES : EPI_BYTES);
     auto kern = xgemm_kernel<BM, BN, NWM, NWN, MINB, DGRAD, CONV>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    sc_dyn_lds((const void*)kern, lds);
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles * g.groups), dim3(NWM * NWN * 64), lds, st, a, (const unsigned short*)w, w_pe,
                        bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, fz);
 }
@@ -706,11 +702,7 @@ extern "C" int scouter_conv2d_wgrad_x3(const float* x, const float* dy, float* d
         ScProfScope prof("xwgrad<bf16x3>", st, 2.0 * g.M * Cout * Cin, 4.0 * g.M * (Cin + Cout));
         constexpr int LDS = 2 * 3 * (128 + 128) * 40 * 2;
         auto kern = xwgrad_kernel<0>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            attr_set = true;
-        }
+        sc_dyn_lds((const void*)kern, LDS);
         hipLaunchKernelGGL(kern, dim3((unsigned)p.tiles, (unsigned)p.splits), dim3(256), LDS, st, x, dy, out, g, p.ci_tiles,
                            p.co_tiles, p.pix_per_split, slab);
         rc = sc_check_launch("conv2d_wgrad_x3");

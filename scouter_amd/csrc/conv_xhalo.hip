@@ -405,11 +405,7 @@ static void launch_xhalo_ag(const float* a, const void* w, long w_pe, const floa
     gg.inv_ho = 1.0f / (float)g.Ho;
     constexpr int LDS = 2 * 3 * (AG + 1) * 1024 + 2 * 27 * 1024 + (AG < 16 ? 3 * 1024 : 0);
     auto kern = xhalo_kernel<AG, DGRAD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
+    sc_dyn_lds((const void*)kern, LDS);
     hipLaunchKernelGGL(kern, dim3(xh_grid(g.groups)), dim3(512), LDS, st, a, (const unsigned short*)w, w_pe, addend, dst, bn_part,
                        gg, sc_cdiv(g.M, 256), relu, fz);
 }

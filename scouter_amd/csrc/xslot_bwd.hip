@@ -1287,17 +1287,9 @@ __global__ __launch_bounds__(256) void xslot_bwd_kernel(XsBwdArgs a) {
 
 #include "xslot_small_bwd.h"
 
-static bool xs_small_bwd_enabled() {       // SCOUTER_XSLOT_SMALL=0: heads with <= 16 slots stay on the 32-slot-tile kernels (A/B, tests)
-    const char* e = getenv("SCOUTER_XSLOT_SMALL");
-    return !(e && e[0] == '0');
-}
-static bool xs_bwd_scratch_variant() {       // SCOUTER_XSLOT_BWD_SCRATCH=1: the first-generation kernel for 64 < N <= 96 (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SCOUTER_XSLOT_BWD_SCRATCH"); v = e && e[0] == '1'; }
-    return v != 0;
-}
-static size_t xs_bwd_lds_bytes(int NJT) {
-    if (NJT > 2 && xs_bwd_scratch_variant())
+// scratch: SCOUTER_XSLOT_BWD_SCRATCH=1, the first-generation kernel for 64 < N <= 96 (A/B)
+static size_t xs_bwd_lds_bytes(int NJT, bool scratch) {
+    if (NJT > 2 && scratch)
         return (size_t)(2 * 32 * NJT * XS_LD + 384 * XS_LD + 256 + 2 * (64 + 16) + 32 + 1024) * sizeof(float);
     // (three token tiles: W_ih stays in global memory -- one 192-row matrix less)
     return (size_t)(256 + 2 * 64 + 2 * 32 + 32 + 64 + 512 + 64 + 2 * 32 * NJT * XS_LD + (NJT > 2 ? 192 : 384) * XS_LD +
@@ -1332,43 +1324,34 @@ extern "C" int scouter_xslot_bwd_f32(const float* X, const float* PE, const floa
     }
     SC_UNSUPPORTED(L <= 8, "xslot_bwd: at most 8 to_k layers (got %d)", L);
     XsBwdArgs a{X, PE, {}, slots0, w_ih, w_hh, b_ih, b_hh, Ksave, Hsave, states, dlogits, g_area_sum,
-                dX, dgi, dgh, Usave, ds0, dZ, (float*)ws, B, N, S, S / spc, spc, T, L, loss_status, 1};
-    { const char* e = getenv("SCOUTER_XSLOT_BWD_HALVES"); if (e && e[0] == '0') a.halves = 0; }
+                dX, dgi, dgh, Usave, ds0, dZ, (float*)ws, B, N, S, S / spc, spc, T, L, loss_status,
+                sc_switch(SC_SW_XSLOT_BWD_HALVES) != 0};
     for (int l = 0; l < L; ++l) {
         SC_REQUIRE(tok_w[l], "xslot_bwd: null to_k layer %d", l);
         a.tok_w[l] = tok_w[l];
     }
     const int NJT = (N + 31) / 32;
-    const size_t lds = xs_bwd_lds_bytes(NJT);
+    const bool scratch = NJT > 2 && sc_switch(SC_SW_XSLOT_BWD_SCRATCH);
+    const size_t lds = xs_bwd_lds_bytes(NJT, scratch);
     hipStream_t st = (hipStream_t)stream;
     const double flops = 2.0 * (double)B * (2.0 * L * N * d * d + (double)T * 4.0 * S * N * d + (T - 1) * 12.0 * S * d * d);
     ScProfScope prof("xslot_bwd", st, flops, 4.0 * B * (3.0 * N * d + (double)S * d));
-    if (S <= 16 && xs_small_bwd_enabled()) {        // the metric's own head: xslot_small_bwd.h
+    // (SCOUTER_XSLOT_SMALL=0: heads with <= 16 slots stay on the 32-slot-tile kernels: A/B, tests)
+    if (S <= 16 && sc_switch(SC_SW_XSLOT_SMALL)) {        // the metric's own head: xslot_small_bwd.h
         const int NTW = N <= 64 ? 1 : 2;
         const int slds = (int)xs_small_bwd_lds_bytes(NTW);
         if (ws_bytes < xs_small_bwd_park_bytes(B, NTW)) {
             sc_set_error("xslot_bwd: workspace too small");
             return SC_ERR_WORKSPACE;
         }
-        if (NTW == 1) {
-            hipFuncSetAttribute((const void*)xslot_small_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, slds);
-            hipLaunchKernelGGL(xslot_small_bwd_kernel<1>, dim3(B), dim3(256), slds, st, a);
-        } else {
-            hipFuncSetAttribute((const void*)xslot_small_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, slds);
-            hipLaunchKernelGGL(xslot_small_bwd_kernel<2>, dim3(B), dim3(256), slds, st, a);
-        }
+        auto kern = NTW == 1 ? xslot_small_bwd_kernel<1> : xslot_small_bwd_kernel<2>;
+        sc_dyn_lds((const void*)kern, slds);
+        hipLaunchKernelGGL(kern, dim3(B), dim3(256), slds, st, a);
         return sc_check_launch("xslot_small_bwd");
     }
-#define XSB_LAUNCH(KERN)                                                                                   \
-    do {                                                                                                   \
-        auto kern = KERN;                                                                                  \
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, st, a);                                          \
-    } while (0)
-    if (NJT == 1) XSB_LAUNCH(xslot_bwd_kernel<1>);
-    else if (NJT == 2) XSB_LAUNCH(xslot_bwd_kernel<2>);
-    else if (xs_bwd_scratch_variant()) XSB_LAUNCH(xslot_bwd_scratch_kernel<3>);
-    else XSB_LAUNCH((xslot_bwd_kernel<3, true>));
-#undef XSB_LAUNCH
+    auto kern = NJT == 1 ? xslot_bwd_kernel<1> : NJT == 2 ? xslot_bwd_kernel<2>
+              : scratch ? xslot_bwd_scratch_kernel<3> : xslot_bwd_kernel<3, true>;
+    sc_dyn_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, st, a);
     return sc_check_launch("xslot_bwd");
 }

@@ -4,7 +4,10 @@ hand-written HIP kernel of libscouter_hip.so, and there is no CPU / ATen fallbac
 
 Layouts: activations NHWC (torch tensors of shape [B, H, W, C], contiguous); convolution weights are
 nn.Parameters of LOGICAL shape (Cout, Cin/g, kh, kw) whose PHYSICAL storage is HWIO ([kh][kw][Cin/g][Cout])."""
+import contextlib
 import os
+import sys
+import types
 
 import torch
 
@@ -27,6 +30,51 @@ def _stream():
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+# the library's routing switches (include/scouter_hip.h scouter_set_switch: "xwt", "bwt", "bhalo", ...): the library reads
+# them from the environment once; the wrappers that route on one keep a copy taken from the library at first use
+_switches = {}
+
+
+def get_switch(name):
+    if name not in _switches:
+        v = _native.lib().scouter_get_switch(name.encode())
+        _native.check(min(v, 0), "get_switch")          # (negative: an unknown name)
+        _switches[name] = v
+    return _switches[name]
+
+
+def set_switch(name, value):
+    """Sets a routing switch in the library, then the wrappers' copy of it."""
+    _native.check(_native.lib().scouter_set_switch(name.encode(), int(value)), "set_switch")
+    _switches[name] = int(value)
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """Sets routing switches for the duration of a with-block and restores their previous values after it."""
+    old = {k: get_switch(k) for k in values}
+    try:
+        for k, v in values.items():
+            set_switch(k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            set_switch(k, v)
+
+
+def _switch_alias(name):
+    return property(lambda m: bool(get_switch(name)), lambda m, v: set_switch(name, bool(v)))
+
+
+class _Module(types.ModuleType):
+    """kernels.XWT / BHALO / BWT read and write the library switches xwt / bhalo / bwt (no copy of their own), so callers
+    that assign them keep the library and the wrappers in step"""
+    XWT, BHALO, BWT = _switch_alias("xwt"), _switch_alias("bhalo"), _switch_alias("bwt")
+
+
+sys.modules[__name__].__class__ = _Module
 
 
 def _chk(t, name, dtype=F32):
@@ -392,8 +440,8 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
         # tiles (1: 64 columns per group, 3: 32), behind which the library runs the persistent resident-rows kernel when x is STORED
         # as bf16 (csrc/conv_halo_dgrad_bf16.h bhalo_fwd_kernel) -- bit-identical to the tile kernels, output and statistics rows,
         # so the rule names the tile by the SHAPE (behind the table's lookup, whose entry it overrides) and storage stays bit-neutral.
-        if (bf16 and BHALO and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and
-                Cout // groups in (32, 64) and W <= 112 and H >= 2):
+        if (bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and
+                Cout // groups in (32, 64) and W <= 112 and H >= 2 and get_switch("bhalo")):
             tile = 1 if Cout // groups == 64 else 3
     part, rows = None, 0
     if bn_stats:
@@ -423,8 +471,8 @@ def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, pr
     # (BatchNorm inputs stored as bf16: only the bf16-input kernel's epilogue reads them; otherwise that BatchNorm's own
     #  backward -- typed -- does the reduction)
     fuse = _fuse_wanted(post, kh) and (bf16 or post.x_io() == 0)
-    if (BHALO and bf16 and dy.dtype == F32 and kh == 3 and kw == 3 and pad == 1 and Cin // groups == 32 and
-            Cout // groups in (32, 64) and W <= 112 and H >= 2 and B * H * W * Cout * 2 < (1 << 31) - (1 << 20)):
+    if (bf16 and dy.dtype == F32 and kh == 3 and kw == 3 and pad == 1 and Cin // groups == 32 and
+            Cout // groups in (32, 64) and W <= 112 and H >= 2 and get_switch("bhalo") and B * H * W * Cout * 2 < (1 << 31) - (1 << 20)):
         # 3x3 layers with 32 input channels per group: the library's resident-rows input gradient (csrc/conv_halo_dgrad_bf16.h)
         # reads a bf16-STORED dy.  The rule is a function of the shape only -- an fp32-stored dy (SCOUTER_BF16_GRADS=0) is rounded
         # to bf16 (RNE: the value the tile kernel's loader rounds it to) by one extra pass first: storage stays bit-neutral
@@ -995,12 +1043,6 @@ def join_side_stream(device, which="wgrad"):
 # process (the cache), not across processes; SCOUTER_WGRAD_TUNE=0 or SCOUTER_AUTOTUNE=0 pin the static plan.
 # Measured on the benchmark step: +0.7 % images/sec (3 x 120 steps, interleaved, one box).
 _WGRAD_PLANS = (-1,)
-# SCOUTER_XWT=0: the 32-channel-group 3x3 weight gradients stay on the exact-fp32 MFMA kernels (read by the library too)
-XWT = os.environ.get("SCOUTER_XWT", "1") != "0"
-# SCOUTER_BHALO=0: the input gradients of those layers in bf16 mode stay on the 128 x 32 tile kernel (read by the library too)
-BHALO = os.environ.get("SCOUTER_BHALO", "1") != "0"
-# SCOUTER_BWT=0: the bf16-stored twins of those layers stay on the per-tap bf16 kernel (read by the library too)
-BWT = os.environ.get("SCOUTER_BWT", "1") != "0"
 if os.environ.get("SCOUTER_WGRAD_TUNE", "1") == "1":
     _WGRAD_PLANS += tuple(t | b for t in (0, 16, 32, 48) for b in (0, 1, 2, 3))
 
@@ -1044,13 +1086,13 @@ def conv2d_wgrad(x, dy, dw_hwio, stride=1, pad=0, groups=1, precision="fp32"):
         return True
 
     plan = _pick_tile(("wgrad", bf16, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, _WGRAD_PLANS)
-    if XWT and not bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2:
+    if not bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2 and get_switch("xwt"):
         # the 32-channel-group 3x3 layers (deep stem, layer1's radix convolutions): the library's own plan, which is the tap-fused
         # register-split bf16x3 kernel (csrc/conv_wgrad_taps_x3.h) -- a static rule of the shape that overrides the table's
         # (tile, split-K) entry for the exact-fp32 kernels, like SCOUTER_X3 does for the layers it moves
         plan = -1
-    if (BWT and bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2 and
-            B * H * W * max(Cin, Cout) * 2 < (1 << 31) - (1 << 20)):
+    if (bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2 and
+            B * H * W * max(Cin, Cout) * 2 < (1 << 31) - (1 << 20) and get_switch("bwt")):
         # the same layers in bf16 mode (BASELINE configs[4]): the library's own plan for bf16-STORED operands is the tap-fused
         # one-plane kernel (csrc/conv_wgrad_taps_bf16.h) instead of one workgroup per tap.  The rule is a function of the SHAPE
         # only: an operand stored as fp32 (SCOUTER_BF16_STORAGE=0 / SCOUTER_BF16_GRADS=0) is rounded to bf16 (RNE: the value

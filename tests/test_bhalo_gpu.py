@@ -23,11 +23,10 @@ def _ref64(dy, w_hwio, x_shape, groups):
     return x.grad.permute(0, 2, 3, 1).contiguous()
 
 
-def _dgrad(monkeypatch, flag, dy, w, x_shape, groups, addend=None, post=None):
+def _dgrad(flag, dy, w, x_shape, groups, addend=None, post=None):
     from scouter_amd import kernels as K
-    monkeypatch.setenv("SCOUTER_BHALO", "1" if flag else "0")
-    monkeypatch.setattr(K, "BHALO", bool(flag))
-    dx = K.conv2d_dgrad(dy, w, x_shape, addend, 1, 1, groups, precision="bf16", post=post)
+    with K.switches(bhalo=int(flag)):
+        dx = K.conv2d_dgrad(dy, w, x_shape, addend, 1, 1, groups, precision="bf16", post=post)
     torch.cuda.synchronize()
     return dx
 
@@ -41,40 +40,40 @@ SHAPES = [(2, 24, 24, 64, 128, 2),       # layer1's radix convolution: two group
 
 
 @pytest.mark.parametrize("cfg", SHAPES)
-def test_input_gradient_is_as_close_to_fp64_as_the_tile_kernel(cfg, monkeypatch):
+def test_input_gradient_is_as_close_to_fp64_as_the_tile_kernel(cfg):
     B, H, W, Cin, Cout, groups = cfg
     gen = torch.Generator(device="cuda"); gen.manual_seed(sum(cfg))
     dy = (torch.randn(B, H, W, Cout, device="cuda", generator=gen)).to(BF16)
     w = torch.randn(3, 3, Cin // groups, Cout, device="cuda", generator=gen) * 0.1
     ref = _ref64(dy, w, (B, H, W, Cin), groups)
-    dh = _dgrad(monkeypatch, True, dy, w, (B, H, W, Cin), groups)
-    dt = _dgrad(monkeypatch, False, dy, w, (B, H, W, Cin), groups)
+    dh = _dgrad(True, dy, w, (B, H, W, Cin), groups)
+    dt = _dgrad(False, dy, w, (B, H, W, Cin), groups)
     assert dh.dtype == torch.float32 and torch.isfinite(dh).all()
     eh = float((dh.cpu().double() - ref).abs().max())
     et = float((dt.cpu().double() - ref).abs().max())
     scale = float(ref.abs().max())
     assert eh <= max(1.5 * et, 2e-6 * scale), (eh, et, scale)
-    assert torch.equal(dh, _dgrad(monkeypatch, True, dy, w, (B, H, W, Cin), groups))
+    assert torch.equal(dh, _dgrad(True, dy, w, (B, H, W, Cin), groups))
 
 
-def test_addend_and_storage_neutrality(monkeypatch):
+def test_addend_and_storage_neutrality():
     B, H, W, Cin, Cout, groups = 3, 20, 19, 64, 128, 2
     gen = torch.Generator(device="cuda"); gen.manual_seed(3)
     dy32 = torch.randn(B, H, W, Cout, device="cuda", generator=gen)
     w = torch.randn(3, 3, Cin // groups, Cout, device="cuda", generator=gen) * 0.1
     add = torch.randn(B, H, W, Cin, device="cuda", generator=gen)
-    a = _dgrad(monkeypatch, True, dy32.to(BF16), w, (B, H, W, Cin), groups, addend=add)
-    b = _dgrad(monkeypatch, True, dy32, w, (B, H, W, Cin), groups, addend=add)          # fp32-stored dy: rounded, same kernel
-    c = _dgrad(monkeypatch, True, dy32.to(BF16).float(), w, (B, H, W, Cin), groups, addend=add)
+    a = _dgrad(True, dy32.to(BF16), w, (B, H, W, Cin), groups, addend=add)
+    b = _dgrad(True, dy32, w, (B, H, W, Cin), groups, addend=add)          # fp32-stored dy: rounded, same kernel
+    c = _dgrad(True, dy32.to(BF16).float(), w, (B, H, W, Cin), groups, addend=add)
     assert torch.equal(a, b) and torch.equal(a, c)
-    plain = _dgrad(monkeypatch, True, dy32.to(BF16), w, (B, H, W, Cin), groups)
+    plain = _dgrad(True, dy32.to(BF16), w, (B, H, W, Cin), groups)
     assert float((a - (plain + add)).abs().max()) <= 1e-5 * float(a.abs().max())
-    t = _dgrad(monkeypatch, False, dy32.to(BF16), w, (B, H, W, Cin), groups, addend=add)
+    t = _dgrad(False, dy32.to(BF16), w, (B, H, W, Cin), groups, addend=add)
     assert float((a - t).abs().max()) <= 2e-6 * float(t.abs().max()) * np.sqrt(9 * 64 / 16.0)
 
 
 @pytest.mark.parametrize("x_bf16", [False, True])
-def test_fused_batchnorm_backward_epilogue_matches_the_tile_kernel(x_bf16, monkeypatch):
+def test_fused_batchnorm_backward_epilogue_matches_the_tile_kernel(x_bf16):
     """The epilogue is shared (igemm_epilogue_typed): masked gradient and partial sums agree with the tile kernel's to the
     rounding of the different K order."""
     from scouter_amd import kernels as K
@@ -90,7 +89,7 @@ def test_fused_batchnorm_backward_epilogue_matches_the_tile_kernel(x_bf16, monke
     res = []
     for flag in (True, False):
         post = K.BnBwdFuse(mask, [(xs, saved)])
-        g = _dgrad(monkeypatch, flag, dy, w, (B, H, W, Cin), groups, post=post)
+        g = _dgrad(flag, dy, w, (B, H, W, Cin), groups, post=post)
         assert post.applied
         res.append((g, post.parts[0].sum(0)))
     (gh, ph), (gt, pt) = res
@@ -105,7 +104,7 @@ FWD_SHAPES = [(2, 24, 24, 64, 128, 2), (3, 20, 19, 32, 32, 1), (1, 12, 112, 32, 
 
 
 @pytest.mark.parametrize("cfg", FWD_SHAPES)
-def test_forward_is_bit_identical_to_the_tile_kernel(cfg, monkeypatch):
+def test_forward_is_bit_identical_to_the_tile_kernel(cfg):
     """bhalo_fwd_kernel keeps the tile kernel's MFMA sequence per accumulator (tap outer, k-step inner): output, fused BatchNorm
     statistics rows and the bf16-stored output agree bit for bit; an fp32-stored x (the tile kernel) gives the same bits too."""
     from scouter_amd import kernels as K
@@ -115,28 +114,27 @@ def test_forward_is_bit_identical_to_the_tile_kernel(cfg, monkeypatch):
     w = torch.randn(3, 3, Cin // groups, Cout, device="cuda", generator=gen) * 0.1
     res = {}
     for flag in (True, False):
-        monkeypatch.setenv("SCOUTER_BHALO", "1" if flag else "0")
-        monkeypatch.setattr(K, "BHALO", flag)
         if not flag:                     # the same 128-pixel tile, so that the statistics rows line up
             K._tile_cache[("fwd", True, B, H, W, Cin, Cout, 3, 3, 1, 1, groups)] = 1 if Cout // groups == 64 else 3
-        y, (p, rows) = K.conv2d_fwd(x, w, None, None, 1, 1, groups, False, bn_stats=True, precision="bf16")
-        yb = K.conv2d_fwd(x, w, None, None, 1, 1, groups, False, precision="bf16", out_dtype=BF16)
-        yr = K.conv2d_fwd(x, w, None, None, 1, 1, groups, True, precision="bf16")
+        with K.switches(bhalo=int(flag)):
+            y, (p, rows) = K.conv2d_fwd(x, w, None, None, 1, 1, groups, False, bn_stats=True, precision="bf16")
+            yb = K.conv2d_fwd(x, w, None, None, 1, 1, groups, False, precision="bf16", out_dtype=BF16)
+            yr = K.conv2d_fwd(x, w, None, None, 1, 1, groups, True, precision="bf16")
         torch.cuda.synchronize()
         res[flag] = (y, p[:rows].clone(), yb, yr)
     K._tile_cache.clear()
     for a, b in zip(res[True], res[False]):
         assert torch.equal(a, b)
     assert torch.equal(res[True][2], res[True][0].to(BF16)) and torch.equal(res[True][3], res[True][0].clamp_min(0))
-    monkeypatch.setenv("SCOUTER_BHALO", "1"); monkeypatch.setattr(K, "BHALO", True)
-    y32, (p32, rows) = K.conv2d_fwd(x.float(), w, None, None, 1, 1, groups, False, bn_stats=True, precision="bf16")
+    with K.switches(bhalo=1):
+        y32, (p32, rows) = K.conv2d_fwd(x.float(), w, None, None, 1, 1, groups, False, bn_stats=True, precision="bf16")
     assert torch.equal(y32, res[True][0]) and torch.equal(p32[:rows], res[True][1])
     ref = torch.nn.functional.conv2d(x.double().cpu().permute(0, 3, 1, 2), w.to(BF16).double().cpu().permute(3, 2, 0, 1),
                                      padding=1, groups=groups).permute(0, 2, 3, 1)
     assert float((res[True][0].cpu().double() - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
 
 
-def test_library_profile_names_the_kernel(monkeypatch):
+def test_library_profile_names_the_kernel():
     import ctypes
     from scouter_amd import _native
     L = _native.lib()
@@ -147,8 +145,9 @@ def test_library_profile_names_the_kernel(monkeypatch):
     from scouter_amd import kernels as K
     for flag, name, fname in ((True, "bhalo_dgrad<bf16>", "bhalo_fwd<bf16>"), (False, "igemm_dgrad_bf16<128x32>", "igemm_fwd_bf16<")):
         L.scouter_prof_collect(buf, len(buf)); L.scouter_prof_enable(1)
-        _dgrad(monkeypatch, flag, dy, w, (8, 16, 16, 32), 1)
-        K.conv2d_fwd(dy[..., :32].contiguous(), w, None, None, 1, 1, 1, precision="bf16")
+        with K.switches(bhalo=int(flag)):
+            _dgrad(flag, dy, w, (8, 16, 16, 32), 1)
+            K.conv2d_fwd(dy[..., :32].contiguous(), w, None, None, 1, 1, 1, precision="bf16")
         torch.cuda.synchronize()
         L.scouter_prof_enable(0); L.scouter_prof_collect(buf, len(buf))
         names = [row.split("\t")[0] for row in buf.value.decode().splitlines()]

@@ -21,12 +21,11 @@ def _ref64(x, dy, groups):
     return w.grad.permute(2, 3, 1, 0).contiguous()          # HWIO
 
 
-def _wgrad(monkeypatch, flag, x, dy, groups):
+def _wgrad(flag, x, dy, groups):
     from scouter_amd import kernels as K
-    monkeypatch.setenv("SCOUTER_BWT", "1" if flag else "0")
-    monkeypatch.setattr(K, "BWT", bool(flag))
     dw = torch.full((3, 3, x.shape[-1] // groups, dy.shape[-1]), float("nan"), device="cuda")
-    K.conv2d_wgrad(x, dy, dw, 1, 1, groups, precision="bf16")
+    with K.switches(bwt=int(flag)):
+        K.conv2d_wgrad(x, dy, dw, 1, 1, groups, precision="bf16")
     torch.cuda.synchronize()
     return dw
 
@@ -43,36 +42,36 @@ SHAPES = [(8, 12, 12, 32, 32, 1),        # few pixel ranges
 
 
 @pytest.mark.parametrize("cfg", SHAPES)
-def test_weight_gradient_is_as_close_to_fp64_as_the_per_tap_kernel(cfg, monkeypatch):
+def test_weight_gradient_is_as_close_to_fp64_as_the_per_tap_kernel(cfg):
     B, H, W, Cin, Cout, groups = cfg
     gen = torch.Generator(device="cuda"); gen.manual_seed(sum(cfg))
     x = torch.randn(B, H, W, Cin, device="cuda", generator=gen).to(torch.bfloat16)
     dy = (torch.randn(B, H, W, Cout, device="cuda", generator=gen) * 0.1).to(torch.bfloat16)
     ref = _ref64(x, dy, groups)                                      # of the bf16 values: the products are exact in fp32
-    dt = _wgrad(monkeypatch, True, x, dy, groups)
-    dp = _wgrad(monkeypatch, False, x, dy, groups)
+    dt = _wgrad(True, x, dy, groups)
+    dp = _wgrad(False, x, dy, groups)
     assert torch.isfinite(dt).all()
     et = float((dt.cpu().double() - ref).abs().max())
     ep = float((dp.cpu().double() - ref).abs().max())
     scale = float(ref.abs().max())
     assert et <= max(1.5 * ep, 3e-7 * scale * np.sqrt(B * H * W / 64.0)), (et, ep, scale)
-    again = _wgrad(monkeypatch, True, x, dy, groups)
+    again = _wgrad(True, x, dy, groups)
     assert torch.equal(dt, again)                                   # deterministic split-K
 
 
-def test_storage_is_bit_neutral(monkeypatch):
+def test_storage_is_bit_neutral():
     """The rule is a function of the shape only: an fp32-stored operand is rounded to bf16 (RNE) by one extra pass and meets the
     same kernel -- bit for bit the gradient of the bf16-stored operands (the contract of tests/test_storage_gpu.py)."""
     gen = torch.Generator(device="cuda"); gen.manual_seed(11)
     x = torch.randn(8, 16, 16, 32, device="cuda", generator=gen)
     dy = torch.randn(8, 16, 16, 64, device="cuda", generator=gen) * 0.1
     xb, dyb = x.to(torch.bfloat16), dy.to(torch.bfloat16)
-    ref = _wgrad(monkeypatch, True, xb, dyb, 1)
+    ref = _wgrad(True, xb, dyb, 1)
     for a, b in ((x, dyb), (xb, dy), (x, dy), (xb.float(), dyb.float())):
-        assert torch.equal(_wgrad(monkeypatch, True, a, b, 1), ref)
+        assert torch.equal(_wgrad(True, a, b, 1), ref)
 
 
-def test_library_profile_names_the_kernel(monkeypatch):
+def test_library_profile_names_the_kernel():
     """The static rule routes the shape to the tap-fused kernel (and SCOUTER_BWT=0 away from it): what ran is read from the
     library's own per-kernel profile."""
     import ctypes
@@ -84,7 +83,7 @@ def test_library_profile_names_the_kernel(monkeypatch):
     dy = torch.randn(8, 16, 16, 64, device="cuda", generator=gen).to(torch.bfloat16)
     for flag, name in ((True, "bwgrad_taps<bf16>"), (False, "wgrad_bf16")):
         L.scouter_prof_collect(buf, len(buf)); L.scouter_prof_enable(1)
-        _wgrad(monkeypatch, flag, x, dy, 1)
+        _wgrad(flag, x, dy, 1)
         L.scouter_prof_enable(0); L.scouter_prof_collect(buf, len(buf))
         names = [row.split("\t")[0] for row in buf.value.decode().splitlines()]
         assert name in names, (flag, names)

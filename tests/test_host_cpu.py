@@ -237,3 +237,64 @@ def test_device_batches_plain_iteration_on_cpu():
     for i, (x, y) in enumerate(out):
         assert x.dtype == torch.float32 and float(x[0, 0, 0, 0]) == i and y.dtype == torch.int64 and y.tolist() == [i, i + 1]
     assert list(engine.device_batches([], torch.device("cpu"))) == []
+
+
+SWITCHES = {"xwt": 1, "bwt": 1, "bhalo": 1, "xslot_small": 1, "xslot_bwd_halves": 1, "xslot_bwd_scratch": 0, "pwp_bn": 0,
+            "pwp_resident": 0}          # the documented defaults (include/scouter_hip.h)
+SWITCH_VARS = ("SCOUTER_XWT", "SCOUTER_BWT", "SCOUTER_BHALO", "SCOUTER_XSLOT_SMALL", "SCOUTER_XSLOT_BWD_HALVES",
+               "SCOUTER_XSLOT_BWD_SCRATCH", "SCOUTER_PWP_PLAN_DEV")
+
+
+def _switches_in_fresh_process(env_extra):
+    """{name: (library value, wrappers' copy)} in a new process whose environment holds only env_extra of the switch variables"""
+    import json
+    import subprocess
+    import sys
+    import __graft_entry__ as G
+    G.build()
+    env = {k: v for k, v in os.environ.items() if k not in SWITCH_VARS}
+    env.update(env_extra)
+    script = ("import json, sys; sys.path.insert(0, %r)\n"
+              "from scouter_amd import _native, kernels as K\n"
+              "print(json.dumps({n: (_native.lib().scouter_get_switch(n.encode()), K.get_switch(n)) for n in %r}))"
+              % (ROOT, sorted(SWITCHES)))
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return {k: tuple(v) for k, v in json.loads(r.stdout.splitlines()[-1]).items()}
+
+
+def test_switches_read_the_documented_defaults():
+    assert _switches_in_fresh_process({}) == {k: (v, v) for k, v in SWITCHES.items()}
+
+
+def test_switches_read_the_environment_at_process_start():
+    got = _switches_in_fresh_process({"SCOUTER_BHALO": "0", "SCOUTER_XWT": "0", "SCOUTER_XSLOT_SMALL": "0",
+                                      "SCOUTER_PWP_PLAN_DEV": "256,2"})
+    assert got == {k: (v, v) for k, v in dict(SWITCHES, bhalo=0, xwt=0, xslot_small=0, pwp_bn=256, pwp_resident=2).items()}
+
+
+def test_set_switch_round_trips_and_restores():
+    import __graft_entry__ as G
+    G.build()
+    from scouter_amd import _native, kernels as K
+    L = _native.lib()
+    before = {n: K.get_switch(n) for n in SWITCHES}
+    with K.switches(bwt=0, pwp_bn=128):
+        assert K.get_switch("bwt") == 0 and L.scouter_get_switch(b"bwt") == 0
+        assert K.get_switch("pwp_bn") == 128 and L.scouter_get_switch(b"pwp_bn") == 128
+        K.set_switch("xslot_bwd_scratch", 1)
+        assert K.get_switch("xslot_bwd_scratch") == 1 and L.scouter_get_switch(b"xslot_bwd_scratch") == 1
+        K.set_switch("xslot_bwd_scratch", before["xslot_bwd_scratch"])
+    assert {n: K.get_switch(n) for n in SWITCHES} == before
+    assert {n: L.scouter_get_switch(n.encode()) for n in SWITCHES} == before
+    K.BHALO = False                     # the module attributes are the library's switches, not copies
+    assert K.get_switch("bhalo") == 0 and L.scouter_get_switch(b"bhalo") == 0 and K.BHALO is False
+    K.BHALO = before["bhalo"]
+    assert L.scouter_get_switch(b"bhalo") == before["bhalo"]
+    with pytest.raises(RuntimeError, match="unknown switch 'nope'"):
+        K.set_switch("nope", 1)
+    with pytest.raises(RuntimeError, match="unknown switch 'nope'"):
+        K.get_switch("nope")
+    with pytest.raises(RuntimeError, match="negative"):
+        K.set_switch("xwt", -1)
+    assert K.get_switch("xwt") == before["xwt"]

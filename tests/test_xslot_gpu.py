@@ -199,7 +199,7 @@ def test_xslot_kernels_at_their_limits_match_the_oracle(B, S, N, T, L, spc):
 
 
 @pytest.mark.parametrize("B,S,N,T", [(2, 300, 49, 3), (2, 289, 64, 2), (2, 160, 25, 3), (2, 40, 33, 3), (2, 21, 9, 3)])
-def test_xslot_backward_half_tiles_agree_with_whole_tiles(B, S, N, T, monkeypatch):
+def test_xslot_backward_half_tiles_agree_with_whole_tiles(B, S, N, T):
     """ntiles % 4 = 1, 2: the leftover 32-slot tiles are walked as 16-slot half tiles, one per wave, on 16x16x4 MFMAs
     (xslot_bwd.hip, `halves`); SCOUTER_XSLOT_BWD_HALVES=0 walks them as whole tiles.  Same maths, different summation order:
     the two launches agree to rounding on every output."""
@@ -216,8 +216,8 @@ def test_xslot_backward_half_tiles_agree_with_whole_tiles(B, S, N, T, monkeypatc
     dl, ga = r(B, S // spc), torch.full((1,), 0.01, device=dev)
     outs = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("SCOUTER_XSLOT_BWD_HALVES", flag)
-        o = Kk.xslot_bwd(X, PE, tw, s0, *gru, fwd, dl, ga, spc, T, 1)
+        with Kk.switches(xslot_bwd_halves=int(flag)):
+            o = Kk.xslot_bwd(X, PE, tw, s0, *gru, fwd, dl, ga, spc, T, 1)
         torch.cuda.synchronize()
         outs[flag] = {k: v.clone() for k, v in o.items()}
     for k in outs["1"]:

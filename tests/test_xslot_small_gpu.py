@@ -5,7 +5,6 @@ sloter/utils/slot_attention.py:44-96; scouter_amd/csrc/xslot_small_fwd.h / xslot
  (c) bit-reproducible, batch entries independent, stale output buffers ignored.
 Shapes: the headline head (70 x 10 slots x 49 tokens, three to_k layers), ragged slot / token counts, one token, one
 iteration (no GRU), two token tiles per wave (the reference's 9 x 9 grid), slots_per_class > 1."""
-import os
 
 import numpy as np
 import pytest
@@ -42,8 +41,7 @@ def _inputs(B, S, N, T, L, spc, seed=0):
 
 def _run(P, X, PE, wl, ga, S, T, L, spc, small):
     from scouter_amd import kernels as Kk
-    os.environ["SCOUTER_XSLOT_SMALL"] = "1" if small else "0"
-    try:
+    with Kk.switches(xslot_small=int(small)):
         dev = torch.device("cuda")
         cu = lambda t: t.float().contiguous().to(dev)
         tw = [cu(P["slot.to_k.%d.weight" % (2 * l)]) for l in range(L)]
@@ -54,8 +52,6 @@ def _run(P, X, PE, wl, ga, S, T, L, spc, small):
         bwd = Kk.xslot_bwd(cu(X), cu(PE), tw, s0, *gru, fwd, cu(wl), torch.full((1,), ga, device=dev), spc, T, 1)
         torch.cuda.synchronize()
         return fwd, bwd
-    finally:
-        os.environ.pop("SCOUTER_XSLOT_SMALL", None)
 
 
 @pytest.mark.parametrize("B,S,N,T,L,spc", SHAPES)

@@ -20,12 +20,11 @@ def _ref64(x, dy, groups):
     return w.grad.permute(2, 3, 1, 0).contiguous()          # HWIO
 
 
-def _wgrad(monkeypatch, flag, x, dy, groups):
+def _wgrad(flag, x, dy, groups):
     from scouter_amd import kernels as K
-    monkeypatch.setenv("SCOUTER_XWT", "1" if flag else "0")
-    monkeypatch.setattr(K, "XWT", bool(flag))
     dw = torch.full((3, 3, x.shape[-1] // groups, dy.shape[-1]), float("nan"), device="cuda")
-    K.conv2d_wgrad(x, dy, dw, 1, 1, groups)
+    with K.switches(xwt=int(flag)):
+        K.conv2d_wgrad(x, dy, dw, 1, 1, groups)
     torch.cuda.synchronize()
     return dw
 
@@ -42,25 +41,25 @@ SHAPES = [(2, 12, 12, 32, 32, 1),        # one pixel range
 
 
 @pytest.mark.parametrize("cfg", SHAPES)
-def test_weight_gradient_is_as_close_to_fp64_as_the_fp32_kernel(cfg, monkeypatch):
+def test_weight_gradient_is_as_close_to_fp64_as_the_fp32_kernel(cfg):
     B, H, W, Cin, Cout, groups = cfg
     gen = torch.Generator(device="cuda"); gen.manual_seed(sum(cfg))
     x = torch.randn(B, H, W, Cin, device="cuda", generator=gen)
     dy = torch.randn(B, H, W, Cout, device="cuda", generator=gen) * 0.1
     ref = _ref64(x, dy, groups)
-    d3 = _wgrad(monkeypatch, True, x, dy, groups)
-    d32 = _wgrad(monkeypatch, False, x, dy, groups)
+    d3 = _wgrad(True, x, dy, groups)
+    d32 = _wgrad(False, x, dy, groups)
     assert torch.isfinite(d3).all()
     e3 = float((d3.cpu().double() - ref).abs().max())
     e32 = float((d32.cpu().double() - ref).abs().max())
     scale = float(ref.abs().max())
     # fp32-grade: the six-product split is exact, what is left is fp32 accumulation in a different order
     assert e3 <= max(1.5 * e32, 3e-7 * scale * np.sqrt(B * H * W / 64.0)), (e3, e32, scale)
-    again = _wgrad(monkeypatch, True, x, dy, groups)
+    again = _wgrad(True, x, dy, groups)
     assert torch.equal(d3, again)                                   # deterministic split-K
 
 
-def test_library_profile_names_the_kernel(monkeypatch):
+def test_library_profile_names_the_kernel():
     """The static rule routes the shape to the register-split kernel (and SCOUTER_XWT=0 away from it): what ran is read from the
     library's own per-kernel profile."""
     import ctypes
@@ -72,7 +71,7 @@ def test_library_profile_names_the_kernel(monkeypatch):
     dy = torch.randn(2, 16, 16, 64, device="cuda", generator=gen)
     for flag, name in ((True, "xwgrad_taps<bf16x3>"), (False, "wgrad_taps")):
         L.scouter_prof_collect(buf, len(buf)); L.scouter_prof_enable(1)
-        _wgrad(monkeypatch, flag, x, dy, 1)
+        _wgrad(flag, x, dy, 1)
         L.scouter_prof_enable(0); L.scouter_prof_collect(buf, len(buf))
         names = [row.split("\t")[0] for row in buf.value.decode().splitlines()]
         assert name in names, (flag, names)

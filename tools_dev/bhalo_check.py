@@ -1,7 +1,7 @@
 """The resident-rows bf16 input gradient (csrc/conv_halo_dgrad_bf16.h, SCOUTER_BHALO=1) against the 128 x 32 tile kernel on the
 32-input-channel-group 3x3 layers (config 5's shapes at batch B): relative difference, run-to-run identity, microseconds
 (library hipEvents).  usage: python tools_dev/bhalo_check.py [B=256]"""
-import ctypes, os, sys
+import ctypes, sys
 import torch
 sys.path.insert(0, '.')
 from scouter_amd import kernels as K, _native
@@ -36,8 +36,7 @@ for (b, H, W, Cin, Cout, groups) in shapes:
                               want_mask=True)
     res, tm = {}, {}
     for flag in ("0", "1"):
-        os.environ["SCOUTER_BHALO"] = flag
-        K.BHALO = flag == "1"
+        K.set_switch("bhalo", int(flag))
         def fn():
             post = K.BnBwdFuse(mask, [(x1, saved)])
             return K.conv2d_dgrad(dy, w, (b, H, W, Cin), None, 1, 1, groups, precision="bf16", post=post)
@@ -48,4 +47,3 @@ for (b, H, W, Cin, Cout, groups) in shapes:
     d = float((res["0"] - res["1"]).abs().max()) / float(res["0"].abs().max())
     print("B=%d %dx%d %d<-%d g%d (fused BatchNorm backward, bf16-stored x): rel diff %.2e | us: " % (b, H, W, Cin, Cout, groups, d)
           + " vs ".join(", ".join("%s %.1f" % kv for kv in tm[f].items()) for f in ("0", "1")), flush=True)
-os.environ.pop("SCOUTER_BHALO", None)

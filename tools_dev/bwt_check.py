@@ -1,7 +1,7 @@
 """The bf16 tap-fused weight gradient (csrc/conv_wgrad_taps_bf16.h, SCOUTER_BWT=1) against the per-tap bf16 kernel and an fp64
 reference of the same bf16 values on the 32-channel-group 3x3 layers: error, run-to-run identity, microseconds (library hipEvents).
 usage: python tools_dev/bwt_check.py [B=256]"""
-import ctypes, os, sys
+import ctypes, sys
 import torch
 sys.path.insert(0, '.')
 from scouter_amd import kernels as K, _native
@@ -40,8 +40,7 @@ for (b, H, W, Cin, Cout, groups) in shapes:
     x, dy = r(b, H, W, Cin).to(torch.bfloat16), (r(b, H, W, Cout) * 0.1).to(torch.bfloat16)
     res, tm = {}, {}
     for flag in ("0", "1"):
-        os.environ["SCOUTER_BWT"] = flag
-        K.BWT = flag == "1"
+        K.set_switch("bwt", int(flag))
         dw = torch.empty(3, 3, Cin // groups, Cout, device=dev)
         fn = lambda: K.conv2d_wgrad(x, dy, dw, 1, 1, groups, precision="bf16")
         tm[flag] = timed(fn)
@@ -56,4 +55,3 @@ for (b, H, W, Cin, Cout, groups) in shapes:
     d = float((res["0"] - res["1"]).abs().max()) / float(res["0"].abs().max())
     line += "rel diff %.2e | us: " % d + " vs ".join(", ".join("%s %.1f" % kv for kv in tm[f].items()) for f in ("0", "1"))
     print(line, flush=True)
-os.environ.pop("SCOUTER_BWT", None)

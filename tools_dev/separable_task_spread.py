@@ -1,16 +1,17 @@
 """Spread of tests/test_engine_gpu.py::test_training_learns_a_separable_task over model seeds, with the small-S xSlot kernels
 on and off (SCOUTER_XSLOT_SMALL): is a low final accuracy a property of the trajectory (chaotic first hundred steps) or of a kernel?
 usage: python tools_dev/separable_task_spread.py [nseeds]"""
-import os, sys
+import sys
 import numpy as np
 import torch
 sys.path.insert(0, '.')
+from scouter_amd import kernels as K
 from scouter_amd.optim import FusedAdamW
 from scouter_amd.sloter.slot_model import SlotModel
 from scouter_amd.train import get_args_parser
 
 def run(seed, small, precision="fp32", steps=160):
-    os.environ["SCOUTER_XSLOT_SMALL"] = "1" if small else "0"
+    K.set_switch("xslot_small", int(small))
     args = get_args_parser().parse_args(["--dataset", "MNIST", "--model", "resnet18", "--channel", "512", "--img_size", "64",
                                          "--num_classes", "4", "--slots_per_class", "1", "--pre_trained", "false",
                                          "--lambda_value", "0.1", "--precision", precision])

@@ -6,10 +6,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <vector>
-void sc_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
-int sc_check_launch(const char*) { return hipGetLastError() == hipSuccess ? 0 : -2; }
-ScProfScope::ScProfScope(const char*, hipStream_t st, double, double) : stream(st), slot(-1) {}
-ScProfScope::~ScProfScope() {}
+#include "../scouter_amd/csrc/abi_core.hip"          // error text, switches, dynamic-LDS limits, profiling
 
 static float* dev_rand(size_t n, float scale, bool positive) {
     std::vector<float> h(n);
@@ -37,7 +34,7 @@ int main(int argc, char** argv) {
     a.B = B; a.N = N; a.S = S; a.C = S / spc; a.spc = spc; a.T = T; a.L = L; a.loss_status = 1.f; a.halves = getenv("HALVES") ? atoi(getenv("HALVES")) : 1;
     hipMalloc(&a.stamps, (size_t)B * 64 * 8); hipMemset(a.stamps, 0, (size_t)B * 64 * 8);
     const int NJT = (N + 31) / 32;
-    const size_t lds = xs_bwd_lds_bytes(NJT);
+    const size_t lds = xs_bwd_lds_bytes(NJT, false);
     if (NJT != 2) { printf("harness is specialised for NJT=2\n"); return 1; }
     auto kern = xslot_bwd_kernel<2>;
     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

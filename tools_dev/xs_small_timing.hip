@@ -5,10 +5,7 @@
 #include "../scouter_amd/csrc/xslot_bwd.hip"
 #include <stdarg.h>
 #include <vector>
-void sc_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
-int sc_check_launch(const char*) { return hipGetLastError() == hipSuccess ? 0 : -2; }
-ScProfScope::ScProfScope(const char*, hipStream_t st, double, double) : stream(st), slot(-1) {}
-ScProfScope::~ScProfScope() {}
+#include "../scouter_amd/csrc/abi_core.hip"          // error text, switches, dynamic-LDS limits, profiling
 
 static float* dev_rand(size_t n, float scale, bool positive) {
     std::vector<float> h(n);
