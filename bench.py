@@ -11,13 +11,18 @@ xSlot, 10 classes, channel 2048, to_k_layer 3, power 2, T=3, 224x224, per-GPU ba
   python bench.py ... --dump-outputs DIR    also write what the last timed step computed as DIR/<name>.npy (float32, see
          dump_outputs; bench_outputs/ is ignored by git) -- the inputs are seeded, so two builds run with the same
          arguments compare output for output
+  python bench.py ... --full    also measure what the headline figure does not need (below)
 
 A step = zero_grad -> forward -> loss -> backward (+ gradient all-reduce) -> AdamW, on a synthetic batch already
-resident in HBM.  Rank 0 prints ONE JSON line.  Extra objects on that line:
-  roofline      the dominant kernel class (fp32-MFMA implicit-GEMM convolution): algorithmic FLOPs / hipEvent time
-                measured over the timed region on the launch stream, vs the 157.3 TFLOP/s fp32 matrix peak
-  cpu_baseline  the CPU oracle (oracle/torch_oracle.py, a port of the reference's PyTorch path) timed on this box's
-                host cores on a bounded sample of the same workload (rank 0, N=1 only)."""
+resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs and prints that line.  --full adds, after the timed steps (--no-prof / --no-cpu-baseline drop parts):
+  roofline, kernels   per-kernel hipEvent times of a few serial steps on the launch stream, grouped into kernel classes
+                      (algorithmic FLOPs / time vs each class's matrix peak), plus hbm_roofline_step from the committed
+                      PMC passes
+  xslot_roofline*     the fused xSlot kernels alone against the fp32 MFMA roofline (N=1 only)
+  cpu_baseline        the CPU oracle (oracle/torch_oracle.py, a port of the reference's PyTorch path) timed on the
+                      host cores on a bounded sample of the same workload (N=1 only)
+  data_parallel       N > 1: RCCL group size, per-rank times and the exposed all-reduce time of a few extra steps"""
 import argparse
 import ctypes
 import json
@@ -135,7 +140,7 @@ def cpu_baseline(cfg, budget_s=20.0, steps=3):
     timed(sample_b, 1)                                   # the warm-up step at the sample batch
     dt = timed(sample_b, steps)
     why = "the config's own batch" if sample_b == full else \
-        "batch %d instead of the config's %d to keep the default run within ~%d s of CPU work" % (sample_b, full, budget_s)
+        "batch %d instead of the config's %d to keep the --full run within ~%d s of CPU work" % (sample_b, full, budget_s)
     return {"value": round(sample_b / dt, 3), "unit": "images/sec", "cores": cores, "kind": "port",
             "cpu_model": cpu_model_name(), "host_logical_cpus": ncpu, "seconds_per_step": round(dt, 3),
             "sample": "%d timed train steps (+1 warm-up) of the torch-CPU oracle (oracle/torch_oracle.py, fp32), batch %d "
@@ -377,9 +382,13 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step from a captured hipGraph (scouter_amd/graph.py) instead of issuing it kernel by "
                          "kernel; measured SLOWER on ROCm 7.0 / MI355X for this GPU-bound step, hence opt-in")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel hipEvent pass (no roofline object)")
-    ap.add_argument("--prof-steps", type=int, default=5, help="steps of the serial per-kernel timing pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the per-kernel pass, the xSlot rooflines, the CPU baseline and "
+                         "(N > 1) the data-parallel measurements; a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true",
+                    help="--full without the per-kernel hipEvent pass and the xSlot rooflines (no roofline object)")
+    ap.add_argument("--prof-steps", type=int, default=5, help="steps of the serial per-kernel timing pass (--full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (log-probabilities, loss statistics, sampled parameters "
                          "and gradients, BatchNorm running statistics) to DIR/<name>.npy; rank 0 only")
@@ -486,7 +495,7 @@ def main():
     # the weight-gradient side stream DISABLED: in the timed region above wgrad kernels overlap BatchNorm-backward /
     # dgrad kernels on purpose, which inflates each kernel's elapsed time and would misstate the kernels' own quality.
     prof_buf = ctypes.create_string_buffer(1 << 16)
-    prof_steps = 0 if a.no_prof else max(1, a.prof_steps)
+    prof_steps = max(1, a.prof_steps) if a.full and not a.no_prof else 0
     if prof_steps:
         model.set_side_stream(False)
         step(eager=True)
@@ -501,7 +510,7 @@ def main():
     loss_val = float(losses[0].detach())
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     dp_info = None
-    if dist.is_initialized():
+    if dist.is_initialized() and a.full:
         # what explains a scaling curve: the group size RCCL actually ran with, every rank's own time, and
         # the time the compute stream spent WAITING for the gradient all-reduces (hipEvents around the waits, a few extra steps)
         net.measure_exposed = True
@@ -526,6 +535,7 @@ def main():
                    "allreduce_exposed_measured": "hipEvents around the compute stream's wait for the gradient collectives on 5 "
                                                  "extra EAGER steps after the timed region (also under --graph)",
                    "buffer_broadcast": "asynchronous in every forward, consumed in front of the first BatchNorm"}
+    if dist.is_initialized():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
 
@@ -627,19 +637,19 @@ def main():
                            # ms_per_step: the GPU is the limiter; close to it: the eager launch chain is (slow / shared host)
                            "host_enqueue_ms_per_step": round(1e3 * t_host / a.steps, 3)},
                 "roofline": roofline, "kernels": kern}
-        if pmc_files and world == 1:
+        if pmc_files and world == 1 and a.full:
             hb = hbm_step_roofline(pmc_files, 1e3 * dt / a.steps)
             if hb is not None:
                 line["hbm_roofline_step"] = hb
         if dp_info is not None:
             line["data_parallel"] = dp_info
-        if world == 1 and not a.no_prof:
+        if world == 1 and prof_steps:
             line["xslot_roofline"] = xslot_roofline(device)
             # the reference's default geometry (--img_size 260 -> 9 x 9 = 81 tokens, reference train.py:39)
             line["xslot_roofline_n81"] = xslot_roofline(device, tokens=81)
             # the head of the configuration the metric is quoted on: 70 images x 10 slots
             line["xslot_metric_head"] = xslot_roofline(device, batch=70, slots=10, spc=1)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

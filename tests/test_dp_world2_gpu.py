@@ -197,8 +197,8 @@ def test_world2_over_rccl_on_two_devices(tmp_path):
         assert float((a - b).abs().max()) <= 2e-5 * scale, (name, float((a - b).abs().max()), scale)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "1", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True,
+                       timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["data_parallel"]["rccl_ranks"] == 2 and line["data_parallel"]["backend"] == "nccl"

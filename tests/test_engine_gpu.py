@@ -251,6 +251,30 @@ def test_bench_self_launches_ranks_and_reports_the_group_size():
     assert line["n_gpus"] == 1 and line["config"]["parallelism"] == "dp1" and line["value"] > 0
 
 
+def test_bench_plain_run_reports_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """A plain `python bench.py` sets up, warms up, times its steps, writes --dump-outputs and prints the headline line;
+    the per-kernel pass (roofline, kernels), the xSlot rooflines and the CPU baseline run only under --full."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "1", "--batch", "8"]
+
+    def run(*extra):
+        r = subprocess.run(base + list(extra), cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    extras = {"hbm_roofline_step", "xslot_roofline", "xslot_roofline_n81", "xslot_metric_head", "cpu_baseline",
+              "data_parallel"}
+    plain = run("--dump-outputs", str(tmp_path))
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "images/sec"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "f32" and plain["steps"] == 2
+    assert plain["roofline"] is None and plain["kernels"] == {} and not extras & set(plain)
+    assert np.load(tmp_path / "log_probs.npy").shape == (8, 10) and np.load(tmp_path / "stats.npy").shape == (5,)
+    full = run("--full")
+    assert full["metric"] == plain["metric"] and full["value"] > 0
+    assert full["roofline"] is not None and full["kernels"]
+    assert {"xslot_roofline", "xslot_roofline_n81", "xslot_metric_head", "cpu_baseline"} <= set(full)
+
+
 def test_vis_inference_path_writes_reference_style_maps(tmp_path):
     """scouter_amd.test.run: eval forward of one image, per-class uint8 maps == the oracle's vis_maps (<= 1 level)."""
     from scouter_amd import test as vis_cli

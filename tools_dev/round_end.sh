@@ -21,11 +21,11 @@ cp "$O/prof/pmc_traffic_config5.json" profiles/${R}_pmc_hbm_traffic_config5.json
 cp "$O/prof/pmc_mfma_util_config5.json" profiles/${R}_pmc_mfma_util_config5.json 2>/dev/null
 CONFIGS=${CONFIGS:-1 2 3 4 5}
 if [[ " $CONFIGS " == *" 2 "* ]]; then
-python bench.py --steps 40 2>/dev/null | tail -1 > "$O/bench_line_1gpu.json"
-python bench.py --no-cpu-baseline --steps 40 --img-size 260 2>/dev/null | tail -1 > "$O/bench_config2_260.json"
+python bench.py --full --steps 40 2>/dev/null | tail -1 > "$O/bench_line_1gpu.json"
+python bench.py --full --no-cpu-baseline --steps 40 --img-size 260 2>/dev/null | tail -1 > "$O/bench_config2_260.json"
 cp "$O/bench_line_1gpu.json" "$O/bench_config2.json"
 fi
-for c in $CONFIGS; do [ $c = 2 ] || python bench.py --config $c --steps 20 2>/dev/null | tail -1 > "$O/bench_config$c.json"; done
+for c in $CONFIGS; do [ $c = 2 ] || python bench.py --full --config $c --steps 20 2>/dev/null | tail -1 > "$O/bench_config$c.json"; done
 python - "$O" <<'PY'
 import json, glob, sys
 for f in sorted(glob.glob(sys.argv[1] + '/bench_*.json')):
