@@ -371,6 +371,13 @@ def xpw_fwd_eligible(cin, cout, kh, kw, stride, pad, groups, has_bias):
                 cin in (64, 128, 256) and cout % 64 == 0)
 
 
+def _rows32_3x3(kh, kw, stride, pad, cg, H, W):
+    """3x3 / stride 1 / pad 1 with 32 input channels per group on an H x W map at most 112 pixels wide (the deep stem, layer1's
+    radix convolutions): the shape rule of the library's resident-rows bf16 forward / input gradient (bhalo) and of its tap-fused
+    weight gradients (xwt, bwt).  Each caller adds its own byte guard and switch."""
+    return kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2
+
+
 def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, relu=False, bn_stats=False,
                precision="fp32", out_dtype=F32, tile=None):
     """bn_stats=True: the epilogue also produces the per-tile fp64 channel sums BatchNorm needs; returns
@@ -440,8 +447,7 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
         # tiles (1: 64 columns per group, 3: 32), behind which the library runs the persistent resident-rows kernel when x is STORED
         # as bf16 (csrc/conv_halo_dgrad_bf16.h bhalo_fwd_kernel) -- bit-identical to the tile kernels, output and statistics rows,
         # so the rule names the tile by the SHAPE (behind the table's lookup, whose entry it overrides) and storage stays bit-neutral.
-        if (bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and
-                Cout // groups in (32, 64) and W <= 112 and H >= 2 and get_switch("bhalo")):
+        if bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and Cout // groups in (32, 64) and get_switch("bhalo"):
             tile = 1 if Cout // groups == 64 else 3
     part, rows = None, 0
     if bn_stats:
@@ -471,8 +477,8 @@ def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, pr
     # (BatchNorm inputs stored as bf16: only the bf16-input kernel's epilogue reads them; otherwise that BatchNorm's own
     #  backward -- typed -- does the reduction)
     fuse = _fuse_wanted(post, kh) and (bf16 or post.x_io() == 0)
-    if (bf16 and dy.dtype == F32 and kh == 3 and kw == 3 and pad == 1 and Cin // groups == 32 and
-            Cout // groups in (32, 64) and W <= 112 and H >= 2 and get_switch("bhalo") and B * H * W * Cout * 2 < (1 << 31) - (1 << 20)):
+    if (bf16 and dy.dtype == F32 and _rows32_3x3(kh, kw, stride, pad, Cin // groups, H, W) and Cout // groups in (32, 64) and
+            get_switch("bhalo") and B * H * W * Cout * 2 < (1 << 31) - (1 << 20)):
         # 3x3 layers with 32 input channels per group: the library's resident-rows input gradient (csrc/conv_halo_dgrad_bf16.h)
         # reads a bf16-STORED dy.  The rule is a function of the shape only -- an fp32-stored dy (SCOUTER_BF16_GRADS=0) is rounded
         # to bf16 (RNE: the value the tile kernel's loader rounds it to) by one extra pass first: storage stays bit-neutral
@@ -1086,13 +1092,13 @@ def conv2d_wgrad(x, dy, dw_hwio, stride=1, pad=0, groups=1, precision="fp32"):
         return True
 
     plan = _pick_tile(("wgrad", bf16, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, _WGRAD_PLANS)
-    if not bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2 and get_switch("xwt"):
+    if not bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and get_switch("xwt"):
         # the 32-channel-group 3x3 layers (deep stem, layer1's radix convolutions): the library's own plan, which is the tap-fused
         # register-split bf16x3 kernel (csrc/conv_wgrad_taps_x3.h) -- a static rule of the shape that overrides the table's
         # (tile, split-K) entry for the exact-fp32 kernels, like SCOUTER_X3 does for the layers it moves
         plan = -1
-    if (bf16 and kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2 and
-            B * H * W * max(Cin, Cout) * 2 < (1 << 31) - (1 << 20) and get_switch("bwt")):
+    if (bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and B * H * W * max(Cin, Cout) * 2 < (1 << 31) - (1 << 20) and
+            get_switch("bwt")):
         # the same layers in bf16 mode (BASELINE configs[4]): the library's own plan for bf16-STORED operands is the tap-fused
         # one-plane kernel (csrc/conv_wgrad_taps_bf16.h) instead of one workgroup per tap.  The rule is a function of the SHAPE
         # only: an operand stored as fp32 (SCOUTER_BF16_STORAGE=0 / SCOUTER_BF16_GRADS=0) is rounded to bf16 (RNE: the value

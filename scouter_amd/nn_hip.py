@@ -9,6 +9,7 @@ interchangeable; conv weights have the reference's logi
 over an HWIO physical layout."""
 import math
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -25,6 +26,49 @@ class Act(nn.Module):
 
 # bf16 storage of the gradients that only bf16-input convolution kernels read (Conv2d.grad_storage); SCOUTER_BF16_GRADS=0: fp32
 GRAD_STORAGE_BF16 = os.environ.get("SCOUTER_BF16_GRADS", "1") != "0"
+
+# The kernels of one convolution layer (Conv2d.route): a function of its shape and its (x3, precision, planes).
+# fwd / dgrad: the kernel families of that pass in order of preference -- a call runs on the first one it fits
+# (Conv2d._fwd_fits / _dgrad_fits), on the igemm kernels (kernels.conv2d_fwd / conv2d_dgrad) if it fits none; wgrad: the
+# family of the weight gradient.  Families: "planes" (bf16x3 operand planes, csrc/conv_planes.hip), "xpw" (the persistent
+# bf16x3 pointwise forward, csrc/conv_pw_persist_x3.h; SCOUTER_X3 bit 5), "xhalo" (the persistent resident-rows kernel,
+# csrc/conv_xhalo.hip; bits 7 / 6), "x3" (the register-split bf16x3 GEMM, csrc/conv_x3.hip; bits 0 / 1 / 3 / 4) and
+# "x3_fused" (the same GEMM with the fused BatchNorm-backward epilogue; bit 2).  split_fwd / split_dgrad: the layer takes
+# forward / input-gradient weight planes from the model's one-launch split (SlotModel._split_items).  planes_in /
+# planes_dy: number of operand planes the layer wants its input / output gradient in (0: a plain tensor).
+ConvRoute = namedtuple("ConvRoute", "fwd dgrad wgrad split_fwd split_dgrad planes_in planes_dy")
+# What Conv2d.fwd saves for bwd: the input (its shape only when the producer wrote planes only), the input-gradient weight
+# planes, the operand planes of the input.
+ConvCtx = namedtuple("ConvCtx", "x wd xp")
+# What StemConv2d.fwd saves: the NCHW image (image=True: the direct forward) or its patch rows.
+StemCtx = namedtuple("StemCtx", "x image")
+
+
+def _conv_route(c):
+    k, g = c.kernel_size, c.groups
+    cg, ng = c.in_channels // g, c.out_channels // g
+    shape = (c.in_channels, c.out_channels, k, k, c.stride, c.padding, g, c.bias is not None)
+    n = c._nplanes()
+    planes_in = n if n and c.stride == 1 and cg % 32 == 0 and ng % 64 == 0 else 0
+    planes_dy = n if n and c.stride == 1 and ng % 32 == 0 and cg % 64 == 0 else 0
+    bits = c.x3 if c.precision == "fp32" else 0              # (the register-split kernels: fp32 precision only)
+    halo_fwd, halo_dgrad = K.x3_halo_eligible(*shape)
+    # (the resident-rows input gradient also serves plane layers: their gradient planes need 64 input channels per group)
+    dgrad = ("xhalo",) if bits & 64 and halo_dgrad else ()
+    if c.planes:
+        wgrad = "planes" if planes_in and planes_dy and cg % 64 == 0 and ng % 64 == 0 and 2 * c.padding == k - 1 else "igemm"
+        return ConvRoute(("planes",) if planes_in else (), ("planes",) if planes_dy else dgrad, wgrad, True,
+                         bool(planes_dy or dgrad), planes_in, planes_dy)
+    x3 = K.x3_eligible(*shape)
+    # (the persistent forward serves 64 / 128 input channels always, 256 where the register-split GEMM does not: it wins from
+    #  512 output channels on, tools_dev/xpw_fwd_bench.py)
+    xpw = bits & 32 and K.xpw_fwd_eligible(*shape) and (c.in_channels <= 128 or not x3)
+    fwd = ((("xpw",) if xpw else ()) + (("xhalo",) if bits & 128 and halo_fwd else ()) +
+           (("x3",) if (bits & 1 and x3) or (bits & 16 and K.x3_conv_eligible(*shape)) else ()))
+    dgrad += (("x3",) if bits & 2 and x3 else ()) + (("x3_fused",) if bits & 4 and x3 else ())
+    wgrad = "x3" if bits & 8 and x3 and K.x3_wgrad_ok(c.in_channels, c.out_channels) else "igemm"
+    # (the persistent forward splits its weight tile itself)
+    return ConvRoute(fwd, dgrad, wgrad, fwd[:1] in (("xhalo",), ("x3",)), bool(dgrad), 0, 0)
 
 
 class Conv2d(nn.Module):
@@ -44,69 +88,25 @@ class Conv2d(nn.Module):
         self.planes = 0                                             # 3: bf16x3 plane kernels (SlotModel.set_planes)
         self._wsplit = None                                         # (wf, wd) of this step, from the model's one-launch split
         self.x3 = 0                                                 # bits of kernels.X3_DEFAULT (SlotModel.set_x3): register-split bf16x3 GEMM
+        self._routes = {}                                           # (x3, precision, planes) -> ConvRoute
         self._capture = None                                        # test instrumentation, see BatchNorm2d
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")   # timm resnet.py:447-448
         if bias:
             bound = 1.0 / math.sqrt(in_channels // groups * k * k)
             nn.init.uniform_(self.bias, -bound, bound)
 
-    # ---- pointwise layers on the register-split bf16x3 GEMM (csrc/conv_x3.hip): fp32 tensors in, weight planes from the
-    # model's one split launch
-    def x3_static(self):
-        """Shape rule alone (kernels.x3_eligible): 1x1 / stride 1 / no bias / deep enough."""
-        k = self.kernel_size
-        return K.x3_eligible(self.in_channels, self.out_channels, k, k, self.stride, self.padding, self.groups,
-                             self.bias is not None)
-
-    def x3_conv_static(self):
-        """Shape rule alone (kernels.x3_conv_eligible): 3x3 / stride 1 / pad 1 with 32 channels per group."""
-        k = self.kernel_size
-        return K.x3_conv_eligible(self.in_channels, self.out_channels, k, k, self.stride, self.padding, self.groups,
-                                  self.bias is not None)
-
-    def xpw_static(self):
-        """Shape rule alone: the FORWARD of this pointwise layer runs on the persistent bf16x3 kernel (kernels.xpw_fwd_eligible;
-        csrc/conv_pw_persist_x3.h) -- 64 / 128 input channels always, 256 where the register-split GEMM does not serve the
-        layer (it wins from 512 output channels on: tools_dev/xpw_fwd_bench.py)."""
-        k = self.kernel_size
-        return (K.xpw_fwd_eligible(self.in_channels, self.out_channels, k, k, self.stride, self.padding, self.groups,
-                                   self.bias is not None) and (self.in_channels <= 128 or not self.x3_static()))
-
-    def x3_halo_static(self):
-        """(forward, input gradient) on the persistent resident-rows kernel -- shape rule alone (kernels.x3_halo_eligible)."""
-        k = self.kernel_size
-        return K.x3_halo_eligible(self.in_channels, self.out_channels, k, k, self.stride, self.padding, self.groups,
-                                  self.bias is not None)
-
-    def halo_fwd(self):
-        """x3 bit 7 (opt-in), fp32 precision, no plane operands: the FORWARD of this 3x3 layer has 32 output channels per group
-        and runs on csrc/conv_xhalo.hip (tile 7 of the register-split entry points)."""
-        return bool(self.x3 & 128) and self.precision == "fp32" and not self.planes and self.x3_halo_static()[0]
-
-    def halo_dgrad(self):
-        """x3 bit 6, fp32 precision: the INPUT GRADIENT of this 3x3 layer has 32 input channels per group and runs on
-        csrc/conv_xhalo.hip from the fp32 output gradient (plane layers included: their gradient planes need 64)."""
-        return bool(self.x3 & 64) and self.precision == "fp32" and self.x3_halo_static()[1]
-
-    def fwd_on_xpw(self):
-        """x3 bit 5, fp32 precision, no plane operands, the shape rule."""
-        return bool(self.x3 & 32) and self.precision == "fp32" and not self.planes and self.xpw_static()
+    def route(self):
+        """This layer's ConvRoute for its current (x3, precision, planes)."""
+        key = (self.x3, self.precision, self.planes)
+        r = self._routes.get(key)
+        if r is None:
+            r = self._routes[key] = _conv_route(self)
+        return r
 
     def x3_mode(self):
-        """Bits of `x3` this layer uses now (fp32 precision only): bits 0-3 for a pointwise layer under the static shape
-        rule (and no plane operands), 16 for a 3x3 layer with 32-channel groups and no plane operands (forward only:
-        kernels.x3_conv_eligible); 0 otherwise."""
-        if not self.x3 or self.precision != "fp32":
-            return 0
-        if not self.planes and self.x3_static():
-            return self.x3 & 15
-        bits = 0
-        if (self.x3 & 16) and not self.planes and self.x3_conv_static():
-            bits |= 16
-        if not self.planes and (self.halo_fwd() or self.halo_dgrad()):
-            bits |= 64                    # (3x3 layers with 32 GEMM columns per group: csrc/conv_xhalo.hip; forward x3 bit 7,
-            #                               input gradient x3 bit 6)
-        return bits
+        """True if a pass of this layer runs on a register-split kernel (SlotModel._x3_convs)."""
+        r = self.route()
+        return not self.planes and any(f in ("xhalo", "x3", "x3_fused") for f in r.fwd + r.dgrad + (r.wgrad,))
 
     def _x3_weights(self, want_fwd, want_dgrad):
         ws, self._wsplit = self._wsplit, None
@@ -114,83 +114,90 @@ class Conv2d(nn.Module):
             return ws
         return K.planes_split_weight(K.hwio(self.weight), self.groups, 3, fwd=want_fwd, dgrad=want_dgrad)
 
+    def _halo_fits(self, shape):
+        """The resident-rows kernel takes a B x H x W map: width and byte guards (K.x3_halo_fits); past them the layer keeps
+        the fp32 MFMA kernels it had before tile 7."""
+        B, H, W = shape[:3]
+        return W <= K.X3_HALO_MAX_W and K.x3_halo_fits(B * H * W, self.in_channels, self.out_channels, self.groups)
+
+    def _fwd_fits(self, fam, x, relu, addend, out_dtype):
+        """This forward call fits family `fam` of the route: fp32 tensors in and out; the persistent pointwise kernel has the
+        plain epilogue only, the resident-rows kernel no addend."""
+        if x.dtype != K.F32 or out_dtype not in (None, K.F32):
+            return False
+        if fam == "xpw":
+            return addend is None and not relu
+        if fam == "xhalo":
+            return addend is None and self._halo_fits(x.shape)
+        return fam == "x3"
+
+    def _dgrad_fits(self, fam, dy, dyp, wd, post, dx_dtype, xshape):
+        """This input-gradient call fits family `fam` of the route: the weight planes were saved; the plane kernel reads the
+        gradient's planes, the register-split kernels an fp32 gradient -- with the fused BatchNorm-backward epilogue only
+        where the GEMM is deep enough (K.X3_FUSED_MIN_K)."""
+        if wd is None:
+            return False
+        if fam == "planes":
+            return dyp is not None
+        if dy is None or dy.dtype != K.F32:
+            return False
+        if fam == "xhalo":
+            return dx_dtype in (None, K.F32) and self._halo_fits(xshape)
+        fused = post is not None and K._fuse_wanted(post, self.kernel_size) and post.x_io() == 0
+        return dyp is None and (fused and self.out_channels >= K.X3_FUSED_MIN_K if fam == "x3_fused" else not fused)
+
     # ---- bf16x3 operand planes (csrc/conv_planes.hip): the producer of this layer's input hands over a K.PlaneTensor
     def _nplanes(self):
         """3 exact bf16 planes per operand in fp32 mode (fp32-grade products), 1 (the RNE-rounded value: what the
         bf16-input kernels compute, without their in-flight conversion and with half the operand bytes) in bf16 mode."""
         return 0 if not self.planes else (self.planes if self.precision == "fp32" else 1)
 
-    def planes_in(self):
-        """Number of operand planes this layer wants its INPUT in (0: plain fp32 tensor)."""
-        cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
-        n = self._nplanes()
-        return n if n and self.stride == 1 and cg % 32 == 0 and ng % 64 == 0 else 0
-
-    def planes_dy(self):
-        """Number of planes this layer wants its OUTPUT GRADIENT in (input-gradient kernel on planes)."""
-        cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
-        n = self._nplanes()
-        return n if n and self.stride == 1 and ng % 32 == 0 and cg % 64 == 0 else 0
-
     def planes_only(self, H, W, B=None):
         """True if forward, input gradient AND weight gradient of this layer all run on planes for an H x W map: its
         producers then need not write the fp32 copy of the tensor at all.  In bf16 mode (ONE plane = the bf16-stored
         tensor) that also holds when the gradients run on the bf16-input igemm kernels, which read that plane as a
         bf16-stored activation (32-channel groups: the first grouped layer; needs the batch size for their pixel rule)."""
-        if not (self.bias is None and self.planes_in()):
+        r = self.route()
+        if not (self.bias is None and r.planes_in):
             return False
-        if self.planes_dy() and self.planes_wgrad() and 32 // W + 1 < H:
+        # (the plane kernel's branch-free pixel walk needs maps that are not tiny: 32 // W + 1 < H)
+        if r.wgrad == "planes" and 32 // W + 1 < H:
             return True
-        return bool(B is not None and self._nplanes() == 1 and self._igemm_bf16_grads(B, H, W))
+        return bool(B is not None and self._nplanes() == 1 and self._bf16_igemm(B, H, W))
 
-    def _igemm_bf16_grads(self, B, H, W):
-        """input- and weight-gradient both on the bf16-input igemm kernels for a B x H x W map (kernels.conv2d_dgrad /
-        conv2d_wgrad rules): they read bf16-stored operands and round fp32 ones to the same values"""
+    def _bf16_igemm(self, B, H, W):
+        """The bf16-input igemm kernels run this layer for a B x H x W map (kernels.conv2d_fwd / conv2d_dgrad / conv2d_wgrad
+        rules): they read bf16-stored operands and round fp32 ones to the same values."""
         cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
         k = self.kernel_size
-        return bool(GRAD_STORAGE_BF16 and self.precision == "bf16" and self.bias is None and self.stride == 1 and
-                    2 * self.padding == k - 1 and B * H * W >= K.BF16_MIN_PIXELS and cg % 32 == 0 and ng % 32 == 0 and
-                    (k == 1 or 64 // W + 1 < H))
+        return bool(GRAD_STORAGE_BF16 and self.precision == "bf16" and self.stride == 1 and 2 * self.padding == k - 1 and
+                    B * H * W >= K.BF16_MIN_PIXELS and cg % 32 == 0 and ng % 32 == 0 and (k == 1 or 64 // W + 1 < H))
 
     def dy_plane_only(self, B, H, W):
         """bf16 mode, a plane layer whose input gradient does NOT run on planes (32-channel groups): its output gradient
         can still be handed over as ONE bf16 plane only -- the igemm kernels read it as a bf16-stored tensor."""
-        return bool(self.planes and self._nplanes() == 1 and not self.planes_dy() and self._igemm_bf16_grads(B, H, W))
-
-    def planes_wgrad(self):
-        """Weight gradient on planes too (same-size convolution, 64-multiples of channels per group)."""
-        cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
-        return bool(self.planes_in() and self.planes_dy() and cg % 64 == 0 and ng % 64 == 0
-                    and 2 * self.padding == self.kernel_size - 1)
+        return bool(self.planes and self._nplanes() == 1 and not self.route().planes_dy and self.bias is None and
+                    self._bf16_igemm(B, H, W))
 
     def grad_storage(self, B, H, W):
         """Storage type for this layer's OUTPUT gradient (B x H x W output pixels): bf16 when both of its readers -- the
         input-gradient and the weight-gradient kernel -- are the bf16-input ones, which round an fp32 gradient to exactly
         the stored values (so this storage changes no result); None (fp32) otherwise."""
-        cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
-        k = self.kernel_size
-        ok = (GRAD_STORAGE_BF16 and self.precision == "bf16" and not self.planes and self.bias is None and
-              self.stride == 1 and 2 * self.padding == k - 1 and B * H * W >= K.BF16_MIN_PIXELS and
-              cg % 32 == 0 and ng % 32 == 0 and (k == 1 or 64 // W + 1 < H))
-        return K.BF16 if ok else None
+        return K.BF16 if not self.planes and self.bias is None and self._bf16_igemm(B, H, W) else None
 
     def act_storage(self, B, H, W):
         """Storage type for this layer's INPUT activation (B x H x W pixels) when nothing else reads it: bf16 when the
         forward and the weight-gradient kernel are the bf16-input ones (which round an fp32 input to exactly the stored
         values: no result changes); None (fp32) otherwise."""
-        cg, ng = self.in_channels // self.groups, self.out_channels // self.groups
-        k = self.kernel_size
-        ok = (GRAD_STORAGE_BF16 and self.precision == "bf16" and not self.planes and self.stride == 1 and
-              2 * self.padding == k - 1 and B * H * W >= K.BF16_MIN_PIXELS and cg % 32 == 0 and ng % 32 == 0 and
-              (k == 1 or 64 // W + 1 < H))
-        return K.BF16 if ok else None
+        return K.BF16 if not self.planes and self._bf16_igemm(B, H, W) else None
 
     def fwd(self, x, save, relu=False, addend=None, bn_stats=False, out_dtype=None):
         """bn_stats=True (a train-mode BatchNorm follows): returns ((y, stats), ctx) -- see kernels.conv2d_fwd.
         out_dtype=torch.bfloat16: the output is STORED as bf16 (activation storage of the bf16 mode, kernels.conv2d_fwd)."""
+        r = self.route()
+        k = self.kernel_size
+        want_wd = save and r.split_dgrad
         if isinstance(x, K.PlaneTensor):
-            k = self.kernel_size
-            want_wd = save and (self.planes_dy() > 0 or self.halo_dgrad())
             ws, self._wsplit = self._wsplit, None
             if ws is not None and ws[0] is not None and ws[0].shape[0] == x.planes.shape[0] and (ws[1] is not None or not want_wd):
                 wf, wd = ws[0], (ws[1] if want_wd else None)        # split by SlotModel for the whole model in one launch
@@ -198,72 +205,55 @@ class Conv2d(nn.Module):
                 wf, wd = K.planes_split_weight(K.hwio(self.weight), self.groups, x.planes.shape[0], fwd=True, dgrad=want_wd)
             y = K.conv2d_fwd_planes(x.planes, wf, k, k, self.stride, self.padding, self.groups, self.bias, addend, relu,
                                     bn_stats, out_dtype=out_dtype or K.F32)
-            if self._capture is not None and relu:
-                self._capture[0][self._capture[1]] = y
-            return y, ((x.f32 if x.f32 is not None else tuple(x.shape), wd,
-                        x.planes if self.planes_wgrad() or x.f32 is None else None) if save else None)
-        xm = self.x3_mode()
-        # (the persistent bf16x3 forward has the plain epilogue only; a call with an addend / ReLU takes the other kernels)
-        xpw = 5 if (self.fwd_on_xpw() and addend is None and not relu and x.dtype == K.F32 and out_dtype in (None, K.F32)) else None
-        if (xm & 87) and x.dtype == K.F32 and out_dtype in (None, K.F32):
-            hf = (bool(xm & 64) and self.halo_fwd() and addend is None and x.shape[2] <= K.X3_HALO_MAX_W and
-                  K.x3_halo_fits(x.shape[0] * x.shape[1] * x.shape[2], self.in_channels, self.out_channels, self.groups))
-            want_wd = bool(save and ((xm & 6) or ((xm & 64) and self.halo_dgrad())))
-            want_wf = (bool(xm & 17) and xpw is None) or hf
-            wf, wd = self._x3_weights(want_wf, want_wd) if (want_wf or want_wd) else (None, None)
-            if xpw is not None:
-                y = K.conv2d_fwd(x, K.hwio(self.weight), None, None, 1, 0, 1, False, bn_stats, tile=5)
-            elif hf:
-                y = K.conv2d_fwd_x3(x, wf, None, relu, bn_stats, tile=7, kh=3, pad=1, groups=self.groups)
-            elif xm & 17:
-                k = self.kernel_size
-                y = K.conv2d_fwd_x3(x, wf, addend, relu, bn_stats, kh=k, pad=self.padding, groups=self.groups)
+            ctx = ConvCtx(x.f32 if x.f32 is not None else tuple(x.shape), wd,
+                          x.planes if r.wgrad == "planes" or x.f32 is None else None)
+        else:
+            fam = next((f for f in r.fwd if self._fwd_fits(f, x, relu, addend, out_dtype)), "igemm")
+            split = fam in ("xhalo", "x3")
+            want_wd = want_wd and not self.planes           # (a plane layer fed a plain tensor: the igemm kernels)
+            wf, wd = self._x3_weights(split, want_wd) if split or want_wd else (None, None)
+            if split:
+                y = K.conv2d_fwd_x3(x, wf, addend, relu, bn_stats, tile=7 if fam == "xhalo" else None, kh=k, pad=self.padding,
+                                    groups=self.groups)
             else:
                 y = K.conv2d_fwd(x, K.hwio(self.weight), self.bias, addend, self.stride, self.padding, self.groups, relu,
-                                 bn_stats, precision=self.precision)
-            if self._capture is not None and relu:
-                self._capture[0][self._capture[1]] = y
-            return y, ((x, wd, None) if save else None)
-        y = K.conv2d_fwd(x, K.hwio(self.weight), self.bias, addend, self.stride, self.padding, self.groups, relu,
-                         bn_stats, precision=self.precision, out_dtype=out_dtype or K.F32, tile=xpw)
+                                 bn_stats, precision=self.precision, out_dtype=out_dtype or K.F32,
+                                 tile=5 if fam == "xpw" else None)
+            ctx = ConvCtx(x, wd, None)
         if self._capture is not None and relu:
             self._capture[0][self._capture[1]] = y
-        return y, (x if save else None)
+        return y, (ctx if save else None)
 
     def bwd(self, dy, ctx, need_dx=True, addend=None, post=None, dx_dtype=None):
         """post (K.BnBwdFuse): the input gradient is the gradient of a BatchNorm(+ReLU) output -- its producer finishes
         that BatchNorm's backward reductions in the epilogue (only when dx is computed at all).  dx_dtype=torch.bfloat16:
         that masked gradient is stored as bf16 when the bf16-input kernel fuses (kernels.conv2d_dgrad; check dx.dtype)."""
-        wd = xp = None
-        if isinstance(ctx, tuple):
-            x, wd, xp = ctx
-        else:
-            x = ctx
+        r = self.route()
+        k = self.kernel_size
+        x, wd, xp = ctx
         dyp = None
         if isinstance(dy, K.PlaneTensor):
             dy, dyp = dy.f32, dy.planes
         xshape = x if isinstance(x, tuple) else tuple(x.shape)       # (a shape only: the producer wrote planes only)
         xt = None if isinstance(x, tuple) else x
-        if xt is None and xp is not None and xp.shape[0] == 1 and not self.planes_wgrad():
+        if xt is None and xp is not None and xp.shape[0] == 1 and r.wgrad != "planes":
             xt = xp[0]                    # (bf16 mode: the one plane IS the bf16-stored activation of the igemm kernels)
         if dy is None and dyp is not None and dyp.shape[0] == 1 and wd is None:
             dy, dyp = dyp[0], None        # (likewise the output gradient, Conv2d.dy_plane_only)
         dev = dy.device if dy is not None else dyp.device
-        if need_dx and dyp is not None and wd is not None and self.planes_dy():
-            k = self.kernel_size
+        fam = next((f for f in r.dgrad if self._dgrad_fits(f, dy, dyp, wd, post, dx_dtype, xshape)), "igemm") if need_dx else None
+        dx = None
+        if fam == "planes":               # (ahead of the weight gradient, like every input gradient that feeds the next layer)
             dx = K.conv2d_dgrad_planes(dyp, wd, xshape, k, k, self.stride, self.padding, self.groups, addend, post=post)
-            need_dx = False
-        else:
-            dx = None
         if self._dw is not None or self._db is not None:
             # weight / bias gradients: off the critical path
             with K.side_stream(dev, xt, dy, xp, dyp, enabled=self.use_side_stream):
                 # (the plane kernel's branch-free pixel walk needs maps that are not tiny: 32 // W + 1 < H)
-                if (self._dw is not None and xp is not None and dyp is not None and self.planes_wgrad() and
+                if (self._dw is not None and r.wgrad == "planes" and xp is not None and dyp is not None and
                         32 // xshape[2] + 1 < xshape[1]):
                     K.conv2d_wgrad_planes(xp, dyp, self._dw, self.padding, self.groups)
-                elif (self._dw is not None and (self.x3_mode() & 8) and xt is not None and dy is not None and
-                      xt.dtype == K.F32 and dy.dtype == K.F32 and K.x3_wgrad_ok(self.in_channels, self.out_channels)):
+                elif (self._dw is not None and r.wgrad == "x3" and xt is not None and dy is not None and
+                      xt.dtype == K.F32 and dy.dtype == K.F32):
                     K.conv2d_wgrad_x3(xt, dy, self._dw)      # (pointwise layer: register-split bf16x3 GEMM, csrc/conv_x3.hip)
                 elif self._dw is not None:
                     if xt is None or dy is None:
@@ -272,21 +262,12 @@ class Conv2d(nn.Module):
                     K.conv2d_wgrad(xt, dy, self._dw, self.stride, self.padding, self.groups, precision=self.precision)
                 if self._db is not None:
                     K.colsum(dy, self._db)
-        if not need_dx:
+        if fam in (None, "planes"):
             return dx
-        if (self.halo_dgrad() and wd is not None and dy is not None and dy.dtype == K.F32 and xshape[2] <= K.X3_HALO_MAX_W and
-                dx_dtype in (None, K.F32) and
-                K.x3_halo_fits(xshape[0] * xshape[1] * xshape[2], self.in_channels, self.out_channels, self.groups)):
-            # 3x3 layer with 32 input channels per group: resident rows, split once per element (csrc/conv_xhalo.hip); past
-            # its byte guards (K.x3_halo_fits) the fp32 MFMA kernel below, as before tile 7
-            return K.conv2d_dgrad_x3(dy, wd, xshape, addend, post=post, tile=7, kh=3, pad=1, groups=self.groups)
-        if self.x3_mode() and wd is not None and dyp is None and dy is not None and dy.dtype == K.F32:
-            # pointwise layer on the register-split bf16x3 GEMM (x3_mode): plain input gradient (bit 1), or with the
-            # fused BatchNorm-backward epilogue (bit 2)
-            xm, k = self.x3_mode(), self.kernel_size
-            fused = post is not None and K._fuse_wanted(post, k) and post.x_io() == 0
-            if ((xm & 4) and self.out_channels >= K.X3_FUSED_MIN_K) if fused else (xm & 2):
-                return K.conv2d_dgrad_x3(dy, wd, xshape, addend, post=post, kh=k, pad=self.padding, groups=self.groups)
+        if fam != "igemm":
+            # resident rows (tile 7), or the pointwise register-split GEMM, plain or with the fused BatchNorm-backward epilogue
+            return K.conv2d_dgrad_x3(dy, wd, xshape, addend, post=post, tile=7 if fam == "xhalo" else None, kh=k,
+                                     pad=self.padding, groups=self.groups)
         return K.conv2d_dgrad(dy, K.hwio(self.weight), xshape, addend, self.stride, self.padding, self.groups,
                               precision=self.precision, post=post, out_dtype=dx_dtype or K.F32)
 
@@ -310,7 +291,7 @@ class StemConv2d(Conv2d):
         self.use_side_stream = K.SIDE_STREAM_DEFAULT
         self.planes = 0
         self.x3 = 0
-        self._saved_image = False
+        self._routes = {}
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
 
     def fwd(self, x_nchw, save, relu=False, addend=None, bn_stats=False):
@@ -323,24 +304,21 @@ class StemConv2d(Conv2d):
             # deep stem (3 -> 32, 3x3 / 2), SCOUTER_STEM_DIRECT=1: one direct pass over the image, no patch rows; the weight
             # gradient builds its patch rows itself, on its side stream (bwd)
             y = K.stem_direct_fwd(x_nchw, K.hwio(self.weight), bn_stats)
-            self._saved_image = True
-            return y, (x_nchw if save else None)
-        self._saved_image = False
+            return y, (StemCtx(x_nchw, True) if save else None)
         col = K.im2col_nchw(x_nchw, self.kernel_size, self.stride, self.padding, self.kpad)
         wflat = K.hwio(self.weight).reshape(-1)
         wpad = K.pad_rows(wflat, wflat.numel(), self.kpad * self.out_channels).view(1, 1, self.kpad, self.out_channels)
         y = K.conv2d_fwd(col, wpad, None, addend, 1, 0, 1, relu, bn_stats, precision=self.precision)
-        return y, (col if save else None)
+        return y, (StemCtx(col, False) if save else None)
 
     def bwd(self, dy, ctx, need_dx=False, addend=None):
         if need_dx:
             raise NotImplementedError("gradient w.r.t. the input image is not part of the training hot path")
         if self._dw is not None:
-            with K.side_stream(dy.device, ctx, dy, enabled=self.use_side_stream):
-                if self._saved_image:             # (the direct forward saved the image, not patch rows)
-                    ctx = K.im2col_nchw(ctx, self.kernel_size, self.stride, self.padding, self.kpad)
+            with K.side_stream(dy.device, ctx.x, dy, enabled=self.use_side_stream):
+                rows = K.im2col_nchw(ctx.x, self.kernel_size, self.stride, self.padding, self.kpad) if ctx.image else ctx.x
                 dwpad = torch.empty((1, 1, self.kpad, self.out_channels), dtype=torch.float32, device=dy.device)
-                K.conv2d_wgrad(ctx, dy, dwpad, precision=self.precision)
+                K.conv2d_wgrad(rows, dy, dwpad, precision=self.precision)
                 n = self.kdim * self.out_channels
                 K.axpby(dwpad.view(-1)[:n], None, 1.0, 0.0, out=self._dw.reshape(-1))
         return None

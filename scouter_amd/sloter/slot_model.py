@@ -137,7 +137,7 @@ class SlotModel(nn.Module):
         """3 (default): the grouped 3x3 convolutions of the split-attention blocks run on the bf16 matrix cores over
         exact three-way bf16 splits of their fp32 operands (csrc/conv_planes.hip: six products per fp32 product, fp32
         accumulation -- the accuracy of the exact-fp32 MFMA kernel at 1.6x its speed); 0: every convolution on the fp32
-        MFMA kernels.  Only layers whose shapes qualify switch (Conv2d.planes_in / planes_dy).  With precision="bf16" the
+        MFMA kernels.  Only layers whose shapes qualify switch (Conv2d.route: planes_in / planes_dy).  With precision="bf16" the
         same layers take ONE plane -- the RNE-rounded bf16 value the bf16-input kernels would form in flight -- from their
         producers: half the operand bytes, LDS-DMA instead of a conversion pass through registers."""
         if nplanes not in (0, 3):
@@ -148,31 +148,36 @@ class SlotModel(nn.Module):
                 mod.conv.planes = nplanes
         self._plane_convs = [m for m in self.backbone.modules() if isinstance(m, Conv2d) and m.planes]
         self._wsplitter = K.PlaneWeightSplitter()
-        self._refresh_x3()
 
     def set_x3(self, bits):
         """Deep pointwise (1x1) convolutions of the backbone on the register-split bf16x3 GEMM (csrc/conv_x3.hip: fp32
         tensors in and out, fp32-grade products on the bf16 matrix cores): bit 0 forward, bit 1 plain input gradient, bit 2
         input gradient with the fused BatchNorm-backward epilogue, bit 3 weight gradient, bit 4 the forward of the 3x3
         layers with 32 input channels per group (kernels.x3_conv_eligible: the stem's 32 -> 64 convolution), bit 5 the forward of
-        the short-K pointwise layers on the persistent bf16x3 kernel (nn_hip.Conv2d.xpw_static, csrc/conv_pw_persist_x3.h), bit 6
+        the short-K pointwise layers on the persistent bf16x3 kernel (nn_hip.Conv2d.route, csrc/conv_pw_persist_x3.h), bit 6
         the INPUT GRADIENT of the 3x3 layers with 32 input channels per group on the persistent resident-rows kernel
-        (nn_hip.Conv2d.halo_dgrad, csrc/conv_xhalo.hip: both deep-stem convolutions and layer1's radix convolutions, plane
+        (csrc/conv_xhalo.hip: both deep-stem convolutions and layer1's radix convolutions, plane
         layers whose gradient planes would need 64), bit 7 (opt-in) the FORWARD of the 3x3 layers with 32 output channels per
         group on the same kernel (the stem's 32 -> 32); 0: the exact-fp32 MFMA kernels.  Which layers qualify is a static function of their channels (kernels.x3_eligible,
         kernels.xpw_fwd_eligible), so the forward does not depend on batch or timing."""
         if bits & ~255:
             raise ValueError("x3 bits must be within 0..255")
-        for mod in self.backbone.modules():
-            if isinstance(mod, Conv2d) and not isinstance(mod, StemConv2d):
-                mod.x3 = int(bits)
-        self._refresh_x3()
+        self._convs = [m for m in self.backbone.modules() if isinstance(m, Conv2d) and not isinstance(m, StemConv2d)]
+        for mod in self._convs:
+            mod.x3 = int(bits)
 
-    def _refresh_x3(self):
-        self._x3_convs = [m for m in self.backbone.modules() if isinstance(m, Conv2d) and not isinstance(m, StemConv2d) and
-                          not m.planes and ((getattr(m, "x3", 0) & 15 and m.x3_static()) or
-                                            (getattr(m, "x3", 0) & 16 and m.x3_conv_static()) or
-                                            (getattr(m, "x3", 0) & 192 and any(m.x3_halo_static())))]
+    @property
+    def _x3_convs(self):
+        """The backbone layers with a pass on a register-split kernel (Conv2d.x3_mode)."""
+        return [m for m in self._convs if m.x3_mode()]
+
+    def _split_items(self, save):
+        """[(layer, forward planes, input-gradient planes)] of this step's one-launch weight split (Conv2d.route): every plane
+        layer, then the layers on the register-split kernels -- whose three-way planes are split in fp32 mode only."""
+        convs = [c for c in self._plane_convs if c._nplanes()]
+        xconvs = self._x3_convs if not convs or convs[0]._nplanes() == 3 else []
+        items = [(c, c.route().split_fwd, bool(save and c.route().split_dgrad)) for c in convs + xconvs]
+        return [(c, f, d) for c, f, d in items if f or d]
 
     def set_side_stream(self, enabled):
         """Weight gradients on the side stream (default) or serially on the compute stream (per-kernel timing)."""
@@ -254,17 +259,7 @@ class SlotModel(nn.Module):
         if x.dtype != torch.float32:
             x = x.float()
         tracked = []
-        convs = [c for c in getattr(self, "_plane_convs", ()) if c._nplanes()]
-        # (input-gradient planes also where that gradient runs on the resident-rows register-split kernel: Conv2d.halo_dgrad)
-        items = [(K.hwio(c.weight), c.groups, True, bool(save and (c.planes_dy() or c.halo_dgrad()))) for c in convs]
-        # (the pointwise layers on the register-split GEMM take three WEIGHT planes too -- same launch; fp32 mode only)
-        xconvs = [c for c in getattr(self, "_x3_convs", ()) if c.x3_mode()] if (not convs or convs[0]._nplanes() == 3) else []
-        # (forward planes only where the forward runs on the register-split GEMM: the persistent bf16x3 forward -- bit 5 -- splits
-        #  its weight tile itself)
-        xitems = [(c, (bool(c.x3_mode() & 17) and not c.fwd_on_xpw()) or (bool(c.x3_mode() & 64) and c.halo_fwd()),
-                   bool(save and ((c.x3_mode() & 6) or ((c.x3_mode() & 64) and c.halo_dgrad())))) for c in xconvs]
-        xconvs = [c for c, f, d in xitems if f or d]
-        items += [(K.hwio(c.weight), c.groups, f, d) for c, f, d in xitems if f or d]
+        items = self._split_items(save)
         if items:      # this step's weight planes of every plane convolution: one launch into persistent buffers ...
             # ... on its own stream NEXT TO the stem's kernels (the stem reads no planes; MFMA-bound next to a byte-moving
             # pass): the backbone joins it after the max-pool (`_post_stem_hooks`).  SCOUTER_SPLIT_ASYNC=0: on the compute stream
@@ -274,8 +269,10 @@ class SlotModel(nn.Module):
                 hooks.append(lambda: K.join_side_stream(self._split_device, "wsplit") if self._split_device is not None else None)
             self._split_device = x.device if use_async else None
             with K.side_stream(x.device, enabled=use_async, which="wsplit"):
-                outs = self._wsplitter.run(items, convs[0]._nplanes() if convs else 3)
-            for c, o in zip(convs + xconvs, outs):
+                # (plane layers come first: their number of planes; the register-split layers take three)
+                outs = self._wsplitter.run([(K.hwio(c.weight), c.groups, f, d) for c, f, d in items],
+                                           items[0][0]._nplanes() or 3)
+            for (c, f, d), o in zip(items, outs):
                 c._wsplit = o
         feat, bctx = self.backbone.features_fwd(x, save, tracked)             # NHWC [B, h, w, channel]
         logp, stats, hstate = self._head_forward(feat, target, save)

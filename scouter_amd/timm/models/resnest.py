@@ -65,7 +65,7 @@ class ResNestBottleneck(nn.Module):
         c1, k1 = self.conv1.fwd(x, save, bn_stats=self.bn1.training)
         t1 = c1[0] if isinstance(c1, tuple) else c1
         conv = self.conv2.conv                   # (all three of its kernels on planes: no fp32 copy of h1 is written)
-        h1, b1 = self.bn1.fwd(c1, save, relu=True, tracked=tracked, planes=conv.planes_in(),
+        h1, b1 = self.bn1.fwd(c1, save, relu=True, tracked=tracked, planes=conv.route().planes_in,
                               keep_f32=not conv.planes_only(t1.shape[1], t1.shape[2], t1.shape[0]))
         # (stored blocks: the radix convolution's output -- the tensor the split attention reads four times -- as bf16; the
         #  attention-weighted sum too where conv3 alone reads it: the bf16-input kernels round it the same way)
@@ -108,8 +108,8 @@ class ResNestBottleneck(nn.Module):
             dxres = self.downsample.bwd_join(dxres, dres.device, hnd)
         # the block-INPUT gradient this produces is the previous block's masked output gradient (post): stored as bf16 where
         # that block stores its activations as bf16 (same rule: ResNestBottleneck._storage of the previous block)
-        gdt = K.BF16 if (post is not None and need_dx and self.grad_stream_bf16 and isinstance(k1, torch.Tensor) and
-                         k1.dtype == K.BF16) else None
+        gdt = K.BF16 if (post is not None and need_dx and self.grad_stream_bf16 and isinstance(k1.x, torch.Tensor) and
+                         k1.x.dtype == K.BF16) else None
         return self.conv1.bwd(dc1, k1, need_dx, addend=dxres, post=post if need_dx else None, dx_dtype=gdt)
 
 

@@ -67,7 +67,7 @@ class Downsample(nn.Sequential):
             return self.fwd(x, save, tracked, out_dtype) + (None,)
         with K.side_stream(x.device, x, enabled=True, which="branch"):
             craw, saved, ctx = self.fwd(x, save, tracked, out_dtype)
-        made = [craw, saved] + ([ctx[0][0] if isinstance(ctx[0], tuple) else ctx[0]] if ctx is not None else [])
+        made = [craw, saved] + ([ctx[0].x] if ctx is not None else [])
         return craw, saved, ctx, [t for t in made if torch.is_tensor(t) and t is not x]
 
     @staticmethod
@@ -209,10 +209,11 @@ class ResNet(nn.Module):
         ctx = []
         joined = [False]
 
-        def join_weight_planes():
+        def join_weight_planes(conv=None):
             # the stream that splits this step's weight planes is joined ONCE per forward, in front of the first kernel that
-            # reads planes: layer1 by default, a stem convolution when it runs on the register-split kernel (SCOUTER_X3 bit 4)
-            if not joined[0]:
+            # reads planes: layer1 by default, a stem convolution that takes planes from the split (Conv2d.route; SCOUTER_X3
+            # bits 4, 6, 7)
+            if not joined[0] and (conv is None or conv.route().split_fwd or conv.route().split_dgrad):
                 joined[0] = True
                 for hook in self._post_stem_hooks:
                     hook()
@@ -223,12 +224,10 @@ class ResNet(nn.Module):
             for hook in self._pre_bn_hooks:
                 hook()
             h, b0 = s[1].fwd(c, save, relu=True, tracked=tracked, out_dtype=s[3].act_storage(*_map_of(c)))
-            if s[3].x3_mode():
-                join_weight_planes()
+            join_weight_planes(s[3])
             c, k1 = s[3].fwd(h, save, bn_stats=s[4].training)
             h, b1 = s[4].fwd(c, save, relu=True, tracked=tracked, out_dtype=s[6].act_storage(*_map_of(c)))
-            if s[6].x3_mode():
-                join_weight_planes()
+            join_weight_planes(s[6])
             c, k2 = s[6].fwd(h, save, bn_stats=self.bn1.training)
             ctx.append((k0, b0, k1, b1, k2))
         else:

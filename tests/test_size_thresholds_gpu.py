@@ -485,7 +485,7 @@ def test_xhalo_both_sides_of_its_byte_guards(row):
     _run_layer(m, B, HW, HW, B + cin + cout, fwd_names, dgrad_names, fused_names=fused)
 
 
-def test_deep_stem_32_to_64_layer_past_the_xhalo_guard_with_default_switches():
+def test_deep_stem_32_to_64_layer_routed_to_xhalo_past_its_guard_with_default_switches():
     """The deep stem's 32 -> 64 3x3 convolution at 680 images of 112 x 112 with the default switches (SCOUTER_X3 as the model
     sets it): its input gradient is past tile 7's byte guard (4*M*64 >= 2^31 from 669 images on) and takes the fp32 MFMA
     kernel instead of raising from inside backward.  Peak 12.3 GB measured."""
@@ -493,7 +493,7 @@ def test_deep_stem_32_to_64_layer_past_the_xhalo_guard_with_default_switches():
     B, H = 680, 112
     assert not kk.x3_halo_fits(B * H * H, 32, 64) and kk.x3_halo_fits(668 * H * H, 32, 64)
     m = _conv_layer(32, 64, kk.X3_DEFAULT)
-    assert m.halo_dgrad()
+    assert m.route().dgrad == ("xhalo",)
     _run_layer(m, B, H, H, 680, ("xconv3_fwd<bf16x3>",), ("igemm_dgrad<",), fused_names=("igemm_dgrad+bn_bwd<",))
 
 

@@ -65,7 +65,7 @@ def test_unsupported_shapes_are_refused_loudly():
 
 
 @pytest.mark.parametrize("shape", [(4, 64, 64), (3, 45, 51)])
-def test_layer_forward_backward_against_the_im2col_route(shape, monkeypatch):
+def test_layer_forward_backward_against_the_im2col_route_with_the_ctx_naming_the_image(shape, monkeypatch):
     """nn_hip.StemConv2d: the direct forward saves the IMAGE; the weight gradient makes its patch rows on its own stream --
     the same rows, the same kernel, the same bits as the im2col route."""
     from scouter_amd import nn_hip
@@ -83,7 +83,7 @@ def test_layer_forward_backward_against_the_im2col_route(shape, monkeypatch):
             m.use_side_stream = side
             m._dw = torch.zeros(3, 3, 3, 32, device="cuda")
             (y, stats), ctx = m.fwd(x, True, bn_stats=True)
-            assert m._saved_image is direct and (ctx is x) is direct
+            assert ctx.image is direct and (ctx.x is x) is direct
             m.bwd(dy, ctx)
             kk.join_side_stream(x.device)
             torch.cuda.synchronize()

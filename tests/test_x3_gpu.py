@@ -190,7 +190,7 @@ def test_persistent_fused_input_gradient_on_the_bf16_matrix_cores(case, monkeypa
     assert rc != 0 and "tile 5" in L.scouter_last_error().decode()
 
 
-def test_model_routes_the_deep_pointwise_layers_and_the_switch_turns_them_off():
+def test_model_route_puts_the_deep_pointwise_layers_on_x3_and_the_switch_turns_them_off():
     """SlotModel.set_x3: the 14 deep 1x1 convolutions of resnest26d (Cin * Cout >= 2^16) run on the register-split
     GEMM -- a static rule of the layer shapes -- and with the switch off every one is back on the fp32 MFMA kernels;
     the two forwards agree to fp32 rounding (both are fp32-grade products), neither depends on the batch."""
@@ -202,7 +202,7 @@ def test_model_routes_the_deep_pointwise_layers_and_the_switch_turns_them_off():
         m.set_x3(bits)
         assert len(m._x3_convs) == ((15 if bits & 16 else 14) if bits else 0)       # 14 deep 1x1 layers + the stem's 32 -> 64 3x3
         # bit 5: the forward of the eight short-K pointwise layers (layer1's five, layer2's 256 -> 128 and its two 128 -> 512)
-        assert sum(c.fwd_on_xpw() for c in m.backbone.modules() if hasattr(c, "fwd_on_xpw")) == (8 if bits & 32 else 0)
+        assert sum("xpw" in c.route().fwd for c in m.backbone.modules() if hasattr(c, "route")) == (8 if bits & 32 else 0)
         L = _native.lib()
         L.scouter_prof_enable(1)
         out, (loss, nll, area) = m(images.cuda(), labels.cuda())

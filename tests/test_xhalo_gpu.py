@@ -148,7 +148,7 @@ def test_tile_7_names_what_it_does_not_cover():
     assert rc != 0 and "tile 7" in L.scouter_last_error().decode()
 
 
-def test_model_routes_the_32_column_passes_and_the_switch_turns_them_off():
+def test_model_route_puts_the_32_column_passes_on_xhalo_and_the_switch_turns_them_off():
     """SlotModel.set_x3 bits 6 / 7: which passes of resnest26d run on the resident-rows kernel is a static function of the layer
     shapes -- input gradients of stem convolutions 2 and 3 and of layer1's two radix convolutions (bit 6, default), the forward of
     stem convolution 2 (bit 7, opt-in).  Bit 6 does not touch the forward (bit-identical log-probabilities); every gradient
@@ -159,9 +159,9 @@ def test_model_routes_the_32_column_passes_and_the_switch_turns_them_off():
     for bits in (63, 127, 255):
         m, P, images, labels = T.build("resnest26d_96")
         m.set_x3(bits)
-        convs = [c for c in m.backbone.modules() if hasattr(c, "halo_dgrad")]
-        assert sum(c.halo_dgrad() for c in convs) == (4 if bits & 64 else 0)
-        assert sum(c.halo_fwd() for c in convs) == (1 if bits & 128 else 0)
+        routes = [c.route() for c in m.backbone.modules() if hasattr(c, "route")]
+        assert sum("xhalo" in r.dgrad for r in routes) == (4 if bits & 64 else 0)
+        assert sum("xhalo" in r.fwd for r in routes) == (1 if bits & 128 else 0)
         m.train()
         L = _native.lib()
         L.scouter_prof_enable(1)
