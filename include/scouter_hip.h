@@ -436,6 +436,29 @@ size_t scouter_conv2d_wgrad_x3_workspace_bytes(int B, int H, int W, int Cin, int
 int scouter_conv2d_wgrad_x3(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                             int plan_hint, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- BatchNorm-folded inference (eval mode: nn.BatchNorm2d is the fixed per-channel map y = (x - running_mean) * gamma /
+ * sqrt(running_var + eps) + beta, timm/models/resnet.py:383; SlotModel.set_inference_fold).
+ * scouter_bn_fold_multi folds EVERY (convolution, BatchNorm) pair of a model in one launch: with s[co] = gamma[co] /
+ * sqrt(running_var[co] + eps), w_out[r][co] = w[r][co] * s[co] and bias_out[co] = beta[co] - running_mean[co] * s[co]
+ * (+ conv_bias[co] * s[co]); every product is formed in fp64 and rounded once to fp32.  `table` = nrows device-resident rows
+ * of scouter_bn_fold_row_bytes() bytes each, laid out as { const float* w, *conv_bias (may be NULL), *gamma, *beta,
+ * *running_mean, *running_var; double eps; float* w_out, *bias_out; int rows, cout; long first; } with the HWIO weight seen as
+ * [rows = taps * Cin / groups][cout], cout a multiple of 4, `first` the running element count and total = sum of rows * cout.
+ * The kernel moves four output channels per access: w, w_out and bias_out must be 16-byte aligned and EVERY row's cout a
+ * multiple of 4 (the table lives on the device, so the entry point can only check the total: the caller checks each row).
+ * w_out / bias_out are caller-owned persistent buffers; the convolution entry points above then run on
+ * them unchanged (scouter_conv2d_weight_bf16t / scouter_planes_split_weights_multi for the bf16 and bf16x3 kernels). */
+size_t scouter_bn_fold_row_bytes(void);
+int scouter_bn_fold_multi(const void* table, int nrows, long total, void* stream);
+/* The split-attention gate of one block in one launch (timm/models/layers/split_attn.py:68-75 with bn1 folded into fc1):
+ * a[B][2Cp] = radix_softmax(fc2(relu(gap . w1 + b1)) + b2), gap [B][Cp] (scouter_sa_reduce_f32 mode 0), w1 HWIO [Cp][A] and
+ * b1 [A] the folded fc1, w2 HWIO [A][2Cp] and b2 [2Cp] fc2's own.  fp32 FMA; one workgroup per image and one fixed summation
+ * order per output element, no atomics: an image's row of `a` does not depend on B.  Covers A = 32 / 64 / 128 / 256 with
+ * Cp <= 512 a multiple of 8 * (256 / A) -- resnest26d / 50d: (Cp, A) = (64, 32), (128, 64), (256, 128), (512, 256); anything
+ * else is SC_ERR_UNSUPPORTED (callers keep the convolution / softmax entry points). */
+int scouter_sa_gate_fwd_f32(const float* gap, const float* w1, const float* b1, const float* w2, const float* b2, float* a,
+                            int B, int Cp, int A, void* stream);
+
 /* p[i] += v for n 64-bit counters (the num_batches_tracked buffers of a model as views of one flat buffer: one launch per
  * training forward instead of one ATen launch; torch.nn.BatchNorm2d increments them one by one) */
 int scouter_iadd_i64(long* p, long n, long v, void* stream);

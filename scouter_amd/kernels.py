@@ -379,13 +379,14 @@ def _rows32_3x3(kh, kw, stride, pad, cg, H, W):
 
 
 def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, relu=False, bn_stats=False,
-               precision="fp32", out_dtype=F32, tile=None):
+               precision="fp32", out_dtype=F32, tile=None, wt=None):
     """bn_stats=True: the epilogue also produces the per-tile fp64 channel sums BatchNorm needs; returns
     (y, (partial, rows)) and `bn_fwd(..., stats=(partial, rows))` then skips its own statistics pass.
     tile=5: the persistent bf16x3 kernel (xpw_fwd_eligible layers, plain epilogue; other calls fall back to the table).
     Activation storage (precision "bf16" only, layers the bf16 kernel runs): x may be a bfloat16 tensor -- the values the
     kernel rounds an fp32 input to, so the product is the same bits -- and out_dtype=torch.bfloat16 stores y rounded (the
-    statistics still come from the fp32 accumulators)."""
+    statistics still come from the fp32 accumulators).  wt: the weight_bf16t of w_hwio, if the caller keeps one (weights that
+    do not change between calls: the folded inference path); None: rebuilt per call."""
     _chk(x, "x", (F32, BF16)); _chk(w_hwio, "weight"); _chk(bias, "bias"); _chk(addend, "addend")
     B, H, W, Cin = x.shape
     kh, kw, cg, Cout = w_hwio.shape
@@ -400,10 +401,8 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
                            "'bf16', >= %d output pixels); got precision %r, %d pixels" % (BF16_MIN_PIXELS, precision, B * Ho * Wo))
     y = torch.empty((B, Ho, Wo, Cout), dtype=out_dtype, device=x.device)
     io = (IO_X_BF16 if x.dtype == BF16 else 0) | (IO_Y_BF16 if out_dtype == BF16 else 0)
-    wt = None
-    if bf16:                      # W^T as bf16 [taps][Cout][Cin/groups], rebuilt per call (weights change every step)
-        wt = torch.empty((kh * kw, Cout, cg), dtype=torch.bfloat16, device=x.device)
-        _native.check(L.scouter_conv2d_weight_bf16t(_p(w_hwio), _p(wt), kh, kw, Cin, Cout, groups, st), "weight_bf16t")
+    if bf16 and wt is None:       # W^T as bf16 [taps][Cout][Cin/groups], rebuilt per call (weights change every step)
+        wt = weight_bf16t(w_hwio, groups)
 
     plain = bias is None and addend is None and not relu
     picking = [AUTOTUNE != "1"]       # the table lookup asks whether the SHAPE admits tile 4; this call's epilogue is checked below
@@ -456,6 +455,16 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
         part = torch.empty((rows, Cout, 2), dtype=torch.float64, device=x.device)
     launch(tile, part=part)
     return (y, (part, rows)) if bn_stats else y
+
+
+def weight_bf16t(w_hwio, groups=1):
+    """HWIO fp32 weight -> W^T as bf16 [taps][Cout][Cin/groups], the operand of the bf16-input forward."""
+    _chk(w_hwio, "weight")
+    kh, kw, cg, Cout = w_hwio.shape
+    wt = torch.empty((kh * kw, Cout, cg), dtype=BF16, device=w_hwio.device)
+    _native.check(_native.lib().scouter_conv2d_weight_bf16t(_p(w_hwio), _p(wt), kh, kw, cg * groups, Cout, groups, _stream()),
+                  "weight_bf16t")
+    return wt
 
 
 def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, precision="fp32", post=None,
@@ -857,10 +866,28 @@ def _x3_tile_ok(t, n):
     return n % 128 == 0 if t in (0, 1) else (n % 64 == 0 if t in (2, 3, 4) else (n % 32 == 0 and t in (5, 6)))
 
 
-def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=1, pad=0, groups=1):
+def x3_fwd_abi_ok(cin, cout, k, stride, pad, groups):
+    """What scouter_conv2d_fwd_x3 takes at all (wider than the training routes' x3_eligible / x3_conv_eligible, which also
+    weigh speed against the plain-epilogue kernels): 1x1 or odd same-size filters up to 5x5, stride 1, 32-multiples of
+    channels per group, two 32-channel K-tiles."""
+    if stride != 1 or not (k & 1) or k > 5 or 2 * pad != k - 1 or cin % groups or cout % groups:
+        return False
+    cg, ng = cin // groups, cout // groups
+    return cg % 32 == 0 and ng % 32 == 0 and k * k * (cg // 32) >= 2
+
+
+def x3_fwd_fits(B, H, W, cin, cout, k, groups):
+    """The per-call size guards of scouter_conv2d_fwd_x3 (csrc/conv_x3.hip: 32-bit offsets): past them a caller keeps the
+    igemm kernels instead of running into SC_ERR_UNSUPPORTED."""
+    return bool(B * H * W < (1 << 31) and k * k * (cin // groups) * cout * 6 < (1 << 31) and H * W * cin < (1 << 28) and
+                1024 * cin < (1 << 31))
+
+
+def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=1, pad=0, groups=1, bias=None):
     """x: fp32 NHWC [B, H, W, Cin]; wf: forward weight planes [3, kh*kh, Cout, Cin/groups] (planes_split_weight).  Returns
-    y or (y, (partial, rows)) like conv2d_fwd.  Every tile gives the same bits; the choice comes from the static table."""
-    _chk(x, "x"); _chk(addend, "addend")
+    y or (y, (partial, rows)) like conv2d_fwd.  Every tile gives the same bits; the choice comes from the static table.
+    bias (per output channel; not with tile 7): added in the epilogue in front of addend and ReLU."""
+    _chk(x, "x"); _chk(addend, "addend"); _chk(bias, "bias")
     B, H, W, Cin = x.shape
     Cout = wf.shape[2]
     assert wf.dtype == BF16 and wf.shape[0] == 3 and wf.shape[1] == kh * kh and wf.shape[3] * groups == Cin, \
@@ -877,7 +904,7 @@ def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=
             if scratch[0] is None:
                 scratch[0] = torch.empty((max((M + 63) // 64, 512), Cout, 2), dtype=torch.float64, device=x.device)
             part = scratch[0]
-        _native.check(L.scouter_conv2d_fwd_x3(_p(x), _p(wf), None, _p(addend), _p(y), _p(part), B, H, W, Cin, Cout, kh, kh,
+        _native.check(L.scouter_conv2d_fwd_x3(_p(x), _p(wf), _p(bias), _p(addend), _p(y), _p(part), B, H, W, Cin, Cout, kh, kh,
                                               pad, groups, int(relu), t, _stream()), "conv2d_fwd_x3")
         return True
     if tile is None:
@@ -1442,6 +1469,81 @@ def radix_softmax_bwd(a, da):
     _native.check(_native.lib().scouter_radix_softmax_bwd_f32(_p(a), _p(da), _p(dz), a.shape[0], a.shape[1] // 2,
                                                               _stream()), "radix_softmax_bwd")
     return dz
+
+
+SA_GATE_THREADS = 256
+
+
+def sa_gate_eligible(Cp, A):
+    """The shapes scouter_sa_gate_fwd_f32 covers (csrc/fold.hip): every (C', attention width) of resnest26d / 50d."""
+    return A in (32, 64, 128, 256) and Cp <= 512 and Cp % (8 * (SA_GATE_THREADS // A)) == 0
+
+
+def sa_gate_fwd(gap, w1, b1, w2, b2):
+    """a [B, 2C'] = radix_softmax(fc2(relu(gap . w1 + b1)) + b2) in one launch: gap [B, C'], w1 HWIO [1, 1, C', A] / b1 [A]
+    (fc1 with its BatchNorm folded in), w2 HWIO [1, 1, A, 2C'] / b2 [2C'].  One workgroup per image, one summation order:
+    a row does not depend on the batch it is computed in."""
+    for n, t in (("gap", gap), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+        _chk(t, n)
+    B, Cp = gap.shape
+    A = w1.shape[-1]
+    assert tuple(w1.shape[-2:]) == (Cp, A) and tuple(w2.shape[-2:]) == (A, 2 * Cp) and b1.numel() == A and b2.numel() == 2 * Cp
+    a = torch.empty((B, 2 * Cp), dtype=F32, device=gap.device)
+    _native.check(_native.lib().scouter_sa_gate_fwd_f32(_p(gap), _p(w1), _p(b1), _p(w2), _p(b2), _p(a), B, Cp, A, _stream()),
+                  "sa_gate_fwd")
+    return a
+
+
+class BnFolder:
+    """Folds every (convolution, BatchNorm) pair of a model in ONE launch (scouter_bn_fold_multi) into one flat persistent
+    fp32 buffer: w' = w * s, b' = beta - mean * s (+ conv_bias * s), s = gamma / sqrt(var + eps), products in fp64.  Pointers,
+    table and buffer are set up once; `run()` folds the CURRENT values of the parameters / running statistics again."""
+
+    def __init__(self, items):
+        """items: [(w_hwio, conv_bias | None, gamma, beta, running_mean, running_var, eps, rows_pad)] -- rows_pad: the folded
+        weight is [1, 1, rows_pad, cout] with zero rows behind the taps * Cin / groups valid ones (the stem's patch rows,
+        padded to the GEMM's K multiple), 0: the shape of w_hwio."""
+        import struct
+        L = _native.lib()
+        dev = items[0][0].device
+        self.key = self.pointers(items)
+        if any(it[0].data_ptr() % 16 for it in items):
+            raise RuntimeError("scouter_amd: the one-launch fold reads the weights as 16-byte vectors: unaligned weight storage")
+        al = lambda n: (n + 63) // 64 * 64                       # (every tensor starts on a 256-byte boundary)
+        offs, off = [], 0
+        for w, cb, g, be, mu, var, eps, rows_pad in items:
+            cout = w.shape[-1]
+            rows = w.numel() // cout
+            if cout % 4 or rows_pad and rows_pad < rows:
+                raise RuntimeError("scouter_amd: the one-launch fold takes 4-multiples of output channels, got %s" % (tuple(w.shape),))
+            offs.append((off, off + al(max(rows, rows_pad) * cout)))
+            off = offs[-1][1] + al(cout)
+        self.flat = torch.zeros(off, dtype=F32, device=dev)
+        rows_blob, self.outs, first = [], [], 0
+        for (w, cb, g, be, mu, var, eps, rows_pad), (ow, ob) in zip(items, offs):
+            for n, t in (("weight", w), ("conv bias", cb), ("gamma", g), ("beta", be), ("running_mean", mu), ("running_var", var)):
+                _chk(t, n)
+            cout = w.shape[-1]
+            rows = w.numel() // cout
+            shape = (1, 1, rows_pad, cout) if rows_pad else tuple(w.shape)
+            wo = self.flat[ow:ow + max(rows, rows_pad) * cout].view(shape)
+            bo = self.flat[ob:ob + cout]
+            rows_blob.append(struct.pack("<6Qd2Qiiq", w.data_ptr(), _p(cb) or 0, g.data_ptr(), be.data_ptr(), mu.data_ptr(),
+                                         var.data_ptr(), float(eps), wo.data_ptr(), bo.data_ptr(), rows, cout, first))
+            self.outs.append((wo, bo))
+            first += rows * cout
+        blob = b"".join(rows_blob)
+        assert len(blob) == len(items) * L.scouter_bn_fold_row_bytes()
+        self.table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
+        self.total = first
+
+    @staticmethod
+    def pointers(items):
+        return tuple(t.data_ptr() if t is not None else 0 for it in items for t in it[:6])
+
+    def run(self):
+        _native.check(_native.lib().scouter_bn_fold_multi(_p(self.table), len(self.outs), self.total, _stream()), "bn_fold_multi")
+        return self.outs
 
 
 def sa_apply_fwd(x, a, bn=None, out_dtype=F32):

@@ -44,6 +44,42 @@ ConvCtx = namedtuple("ConvCtx", "x wd xp")
 StemCtx = namedtuple("StemCtx", "x image")
 
 
+# The INFERENCE variant (SlotModel.set_inference_fold: every BatchNorm folded into the convolution in front of it, so each
+# layer is conv + bias [+ residual addend] [+ ReLU] in one kernel): fwd is the one forward family of the layer -- one with
+# the bias + addend + ReLU epilogue.  The persistent pointwise forward ("xpw") has the plain epilogue only and the
+# resident-rows kernel ("xhalo") takes no bias / addend, so in fp32 mode a layer whose training forward runs on a bf16x3
+# family keeps fp32-grade bf16x3 arithmetic on the register-split GEMM ("x3", which takes all three); the plane layers (the
+# 3x3 radix convolutions), whose producer is now a convolution epilogue that writes no planes, run on it as well, fed the
+# fp32 tensor directly.  The other candidate, a K.planes_split pass in front of the plane kernel (FOLD_RADIX = "planes", kept
+# for tools_dev/eval_fold_bench.py --radix), measured at BASELINE config 2's shapes (batch 70, 224^2; conv + bias + ReLU, us,
+# x3 / split + planes): 64 -> 128 at 56^2 118 / 133, 128 -> 256 at 56^2 359 / 407 and at 28^2 106 / 105, 256 -> 512 at 28^2
+# 387 / 360 and at 14^2 108 / 90, 512 -> 1024 at 14^2 384 / 345 and at 7^2 105 / 102 -- the plane kernel wins from 256
+# channels on, the split pass costs more than that on the large maps: the whole folded forward 4.80 ms on x3, 4.88 ms on
+# split + planes (3 windows each, spread 0.1 %).  So: x3.  Everything else -- strided
+# layers, resnet18, the stem's 32 -> 32 convolution, the attention FCs, and every layer under precision "bf16" -- runs on
+# "igemm" with the folded weights.  split: the layer wants three-way forward planes of its FOLDED weight.
+InferRoute = namedtuple("InferRoute", "fwd split")
+# What the model's fold leaves on a layer (Conv2d._fold): folded HWIO weight and bias (views of the model's flat buffer),
+# the three-way forward planes / the bf16 transposed weight of the folded weight where the route / precision wants them.
+FoldedConv = namedtuple("FoldedConv", "w b wf wt")
+FOLD_RADIX = "x3"
+
+
+def _infer_route(c):
+    k = c.kernel_size
+    if c.precision != "fp32" or isinstance(c, StemConv2d):
+        return InferRoute("igemm", False)
+    abi = K.x3_fwd_abi_ok(c.in_channels, c.out_channels, k, c.stride, c.padding, c.groups)
+    r = c.route()
+    if c.planes:
+        if r.planes_in and FOLD_RADIX == "planes":
+            return InferRoute("planes", True)
+        return InferRoute("x3", True) if r.planes_in and abi else InferRoute("igemm", False)
+    if abi and ("x3" in r.fwd or "xpw" in r.fwd):
+        return InferRoute("x3", True)
+    return InferRoute("igemm", False)
+
+
 def _conv_route(c):
     k, g = c.kernel_size, c.groups
     cg, ng = c.in_channels // g, c.out_channels // g
@@ -89,6 +125,8 @@ class Conv2d(nn.Module):
         self._wsplit = None                                         # (wf, wd) of this step, from the model's one-launch split
         self.x3 = 0                                                 # bits of kernels.X3_DEFAULT (SlotModel.set_x3): register-split bf16x3 GEMM
         self._routes = {}                                           # (x3, precision, planes) -> ConvRoute
+        self._iroutes = {}                                          # (x3, precision, planes, FOLD_RADIX) -> InferRoute
+        self._fold = None                                           # FoldedConv of the model's last fold (SlotModel._refold)
         self._capture = None                                        # test instrumentation, see BatchNorm2d
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")   # timm resnet.py:447-448
         if bias:
@@ -102,6 +140,32 @@ class Conv2d(nn.Module):
         if r is None:
             r = self._routes[key] = _conv_route(self)
         return r
+
+    def infer_route(self):
+        """This layer's InferRoute (the folded inference forward) for its current (x3, precision, planes)."""
+        key = (self.x3, self.precision, self.planes, FOLD_RADIX)
+        r = self._iroutes.get(key)
+        if r is None:
+            r = self._iroutes[key] = _infer_route(self)
+        return r
+
+    def fwd_folded(self, x, relu=False, addend=None):
+        """[relu](conv'(x) + b' [+ addend]) with the BatchNorm behind this layer folded into (w', b') by the model's fold:
+        one kernel, fp32 tensors in and out, nothing saved."""
+        f = self._fold
+        if f is None:
+            raise RuntimeError("Conv2d.fwd_folded: the model has not folded this layer (SlotModel.set_inference_fold)")
+        fam = self.infer_route().fwd
+        k = self.kernel_size
+        if fam != "igemm" and not K.x3_fwd_fits(*x.shape[:3], self.in_channels, self.out_channels, k, self.groups):
+            fam = "igemm"                 # (past the 32-bit offset guards of the bf16x3 kernels, like Conv2d._fwd_fits in training)
+        if fam == "x3":
+            return K.conv2d_fwd_x3(x, f.wf, addend, relu, kh=k, pad=self.padding, groups=self.groups, bias=f.b)
+        if fam == "planes":
+            return K.conv2d_fwd_planes(K.planes_split(x, 3), f.wf, k, k, self.stride, self.padding, self.groups, f.b, addend,
+                                       relu)
+        return K.conv2d_fwd(x, f.w, f.b, addend, self.stride, self.padding, self.groups, relu, precision=self.precision,
+                            wt=f.wt)
 
     def x3_mode(self):
         """True if a pass of this layer runs on a register-split kernel (SlotModel._x3_convs)."""
@@ -292,7 +356,20 @@ class StemConv2d(Conv2d):
         self.planes = 0
         self.x3 = 0
         self._routes = {}
+        self._iroutes = {}
+        self._fold = None
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
+
+    def fwd_folded(self, x_nchw, relu=False, addend=None):
+        """Conv2d.fwd_folded for the stem: patch rows x the folded weight, which the fold keeps padded to `kpad` rows."""
+        f = self._fold
+        if f is None:
+            raise RuntimeError("StemConv2d.fwd_folded: the model has not folded this layer (SlotModel.set_inference_fold)")
+        if x_nchw.dim() != 4 or x_nchw.shape[1] != self.in_channels:
+            raise RuntimeError("expected an NCHW image batch with %d channel(s), got shape %s"
+                               % (self.in_channels, tuple(x_nchw.shape)))
+        col = K.im2col_nchw(x_nchw, self.kernel_size, self.stride, self.padding, self.kpad)
+        return K.conv2d_fwd(col, f.w, f.b, addend, 1, 0, 1, relu, precision=self.precision, wt=f.wt)
 
     def fwd(self, x_nchw, save, relu=False, addend=None, bn_stats=False):
         if x_nchw.dim() != 4 or x_nchw.shape[1] != self.in_channels:

@@ -60,6 +60,7 @@ def main():
         setattr(args, name, typ(getattr(args, name)))
     args.vis, args.vis_id = False, 0                  # maps are taken from model.slot.last_attn, image index 0
     model = SlotModel(args).to(args.device)
+    model.set_inference_fold(bool(args.eval_fold))
     ckpt = args.checkpoint or os.path.join(args.output_dir, checkpoint_name(args))
     if os.path.exists(ckpt):
         model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=False)["model"], strict=True)

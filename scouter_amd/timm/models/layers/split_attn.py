@@ -47,6 +47,22 @@ class SplitAttnConv2d(nn.Module):
         out = K.sa_apply_fwd(x0, a, saved0, out_dtype=out_dtype or K.F32)        # split_attn.py:76-79
         return out, ((c_conv, x0, saved0, self.bn0.training, c_fc1, c_bn1, c_fc2, a) if save else None)
 
+    def fwd_folded(self, x):
+        """The eval forward with bn0 folded into the radix convolution and bn1 into fc1 (SlotModel.set_inference_fold): the
+        radix convolution applies bias + ReLU itself, GAP and the weighted sum read its output as it is, and the gate
+        fc1 -> ReLU -> fc2 -> radix softmax is one launch where the library covers the shape (K.sa_gate_eligible)."""
+        x0 = self.conv.fwd_folded(x, relu=True)
+        B = x0.shape[0]
+        gap = K.sa_gap(x0, None)
+        if K.sa_gate_eligible(gap.shape[1], self.fc1.out_channels):
+            f = self.fc1._fold
+            a = K.sa_gate_fwd(gap, f.w, f.b, K.hwio(self.fc2.weight), self.fc2.bias)
+        else:
+            g1 = self.fc1.fwd_folded(gap.view(B, 1, 1, -1), relu=True)
+            z2, _ = self.fc2.fwd(g1, False)
+            a = K.radix_softmax_fwd(z2.view(B, -1))
+        return K.sa_apply_fwd(x0, a, None)
+
     def bwd(self, dout, ctx, post=None):
         """post: K.BnBwdFuse of the BatchNorm in front of this layer (finished in the input-gradient epilogue)."""
         c_conv, x0, saved0, training0, c_fc1, c_bn1, c_fc2, a = ctx

@@ -80,6 +80,21 @@ class ResNestBottleneck(nn.Module):
         out, b3 = self.bn3.fwd(c3, save, relu=True, residual=res, tracked=tracked, residual_bn=rbn, out_dtype=odt)
         return out, ((k1, b1, ksa, tuple(sa.shape), k3, b3, kd) if save else None)
 
+    def fold_pairs(self):
+        """[(convolution, BatchNorm)] an eval forward folds (SlotModel.set_inference_fold)"""
+        sa = self.conv2
+        pairs = [(self.conv1, self.bn1), (sa.conv, sa.bn0), (sa.fc1, sa.bn1), (self.conv3, self.bn3)]
+        return pairs + (self.downsample.fold_pairs() if self.downsample is not None else [])
+
+    def fwd_folded(self, x):
+        """relu(conv3'(avd(split_attention(relu(conv1'(x))))) + residual): every BatchNorm folded, the residual -- x or the
+        folded downsample convolution -- added in conv3's epilogue.  fp32 activation storage, also under precision "bf16"."""
+        res = self.downsample.fwd_folded(x) if self.downsample is not None else x
+        h1 = self.conv1.fwd_folded(x, relu=True)
+        sa = self.conv2.fwd_folded(h1)
+        p = self.avd_last.fwd(sa) if self.avd_last is not None else sa
+        return self.conv3.fwd_folded(p, relu=True, addend=res)
+
     def out_fuse(self, ctx):
         """What the kernel producing this block's OUTPUT gradient needs to finish the backward reductions of bn3 (and
         of the downsample BatchNorm, fed by the same masked gradient) in its epilogue."""

@@ -58,6 +58,16 @@ class Downsample(nn.Sequential):
         c_bn = (craw, None, saved, mods[1].training)
         return craw, saved, ((c_conv, c_bn, pool, tuple(x.shape)) if save else None)
 
+    def fold_pairs(self):
+        mods = list(self)[-2:]
+        return [(mods[0], mods[1])]
+
+    def fwd_folded(self, x):
+        """[pool ->] conv'(x) + b': the normalised shortcut, for the addend of the block's last convolution"""
+        mods = list(self)
+        pool = mods[0] if len(mods) == 3 and isinstance(mods[0], AvgPool2dSpec) else None
+        return mods[-2].fwd_folded(pool.fwd(x) if pool is not None else x)
+
     # ---- the branch on its own stream ("branch": never behind the backlog of weight gradients), next to the block's
     # main branch whose many small launches leave the GPU idle in between.  Measured on the benchmark step (3 x 120 steps,
     # interleaved, one box): forward +0.5 % (3 970 -> 3 991), backward +1.6 % (3 947 -> 4 011).
@@ -131,6 +141,14 @@ class BasicBlock(nn.Module):
             self.downsample.fwd_join(x.device, hnd)
         out, b2 = self.bn2.fwd(c2, save, relu=True, residual=res, tracked=tracked, residual_bn=rbn)
         return out, ((k1, b1, k2, b2, kd) if save else None)
+
+    def fold_pairs(self):
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)]
+        return pairs + (self.downsample.fold_pairs() if self.downsample is not None else [])
+
+    def fwd_folded(self, x):
+        res = self.downsample.fwd_folded(x) if self.downsample is not None else x
+        return self.conv2.fwd_folded(self.conv1.fwd_folded(x, relu=True), relu=True, addend=res)
 
     def out_fuse(self, ctx):
         """see ResNestBottleneck.out_fuse: bn2 (+ the downsample BatchNorm)"""
@@ -257,6 +275,33 @@ class ResNet(nn.Module):
                 x, c_blk = blk.fwd(x, save, tracked)
                 ctx.append(c_blk)
         return x, (ctx if save else None)
+
+    def fold_pairs(self):
+        """[(convolution, BatchNorm)] of the whole trunk, in forward order: every BatchNorm of the backbone is in one."""
+        if isinstance(self.conv1, nn.Sequential):
+            s = self.conv1
+            pairs = [(s[0], s[1]), (s[3], s[4]), (s[6], self.bn1)]
+        else:
+            pairs = [(self.conv1, self.bn1)]
+        for li in range(1, 5):
+            for blk in getattr(self, "layer%d" % li):
+                pairs += blk.fold_pairs()
+        return pairs
+
+    def features_fwd_folded(self, x_nchw):
+        """features_fwd in eval mode with every BatchNorm folded (SlotModel.set_inference_fold): convolutions with fused
+        bias / ReLU / residual, the plain max-pool, no BatchNorm kernel, no statistics workspace, nothing saved."""
+        if isinstance(self.conv1, nn.Sequential):
+            h = x_nchw
+            for i in (0, 3, 6):
+                h = self.conv1[i].fwd_folded(h, relu=True)
+        else:
+            h = self.conv1.fwd_folded(x_nchw, relu=True)
+        x, _ = K.maxpool_fwd(h, 3, 2, 1, want_argmax=False)
+        for li in range(1, 5):
+            for blk in getattr(self, "layer%d" % li):
+                x = blk.fwd_folded(x)
+        return x
 
     def _first_trainable_stage(self):
         """Index of the earliest stage (0 = stem, 1..4 = layer1..4) holding a trainable parameter; 5 if none."""

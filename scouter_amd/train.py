@@ -67,6 +67,7 @@ _CLI = [
     ("precision", "fp32", str, "fp32 | bf16 (backbone convolutions on bf16 matrix inputs, fp32 accumulate; wide bottleneck tensors stored as bf16)"),
     ("synthetic_data", True, _flag, "seeded synthetic batches (the benchmark input)"),
     ("synthetic_len", 256, int, "images per synthetic epoch"),
+    ("eval_fold", False, _flag, "eval-mode forwards run with every BatchNorm folded into its convolution (SlotModel.set_inference_fold)"),
 ]
 
 
@@ -136,6 +137,7 @@ def main(args):
         raise NotImplementedError("--thop (CPU FLOP counting with thop / tensorly) is outside the xSlot hot path")
     device = torch.device(args.device)
     net = SlotModel(args).to(device)
+    net.set_inference_fold(bool(getattr(args, "eval_fold", False)))       # (on the module itself, also under data parallelism)
     kind = ("use slot " if args.use_slot else "without slot ") + \
         ("negetive loss" if args.use_slot and args.loss_status != 1 else "positive loss")
     print("train model: " + kind)
