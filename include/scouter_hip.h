@@ -191,6 +191,14 @@ int scouter_pad_rows_f32(const float* w, float* wpad, long nvalid, long ntotal, 
 int scouter_stem_direct_partial_rows(int B, int H);
 int scouter_stem_direct_fwd_f32(const float* x, const float* w, float* y, double* bn_partial, int B, int H, int W, int Cout,
                                 void* stream);
+/* stem input gradient, d output / d image (train.py --grad / --grad_min_level, captum_vis.py: `image.requires_grad_()` and the
+ * attribution methods that read the gradient of the image; sloter/slot_model.py:23-24, timm/models/resnet.py stems):
+ * dx NCHW [B][Cin][H][W] = conv_transpose(dy NHWC [B][Ho][Wo][Cout], w HWIO [k][k][Cin][Cout]).  Gather form, no atomics:
+ * bit-identical run to run.  Cin < 32, stride 1 or 2, k <= 11, pad < k; the three stems of the project (7x7 / 2 / 3 with
+ * Cin 3, 3x3 / 2 / 1 with Cin 1 or 3; Cout a multiple of 16) run on the tiled kernel, the rest on a generic one.  Anything
+ * else, or a tensor past the 32-bit offset guards: SC_ERR_UNSUPPORTED, nothing is launched. */
+int scouter_stem_dgrad_f32(const float* dy, const float* w, float* dx, int B, int Cin, int H, int W, int Cout, int k, int stride,
+                           int pad, void* stream);
 
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats

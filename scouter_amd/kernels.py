@@ -1189,6 +1189,24 @@ def stem_direct_fwd(x, w_hwio, bn_stats=False):
     return (y, (part, rows)) if bn_stats else y
 
 
+def stem_dgrad(dy, w_hwio, x_shape, k, stride, pad):
+    """dx[B][Cin][H][W] (NCHW fp32, the image layout) = conv_transpose(dy[B][Ho][Wo][Cout] (NHWC), w (HWIO)): the input
+    gradient of the stem convolution (csrc/conv_stem_dgrad.hip; Cin < 32, stride 1 or 2).  One fixed-order sum per element:
+    bit-identical run to run.  A shape the library does not cover raises (nothing is launched)."""
+    _chk(dy, "dy"); _chk(w_hwio, "weight")
+    B, Cin, H, W = (int(v) for v in x_shape)
+    Cout = w_hwio.shape[-1]
+    if tuple(w_hwio.shape) != (k, k, Cin, Cout):
+        raise RuntimeError("stem_dgrad: weight %s is not HWIO (%d, %d, %d, Cout)" % (tuple(w_hwio.shape), k, k, Cin))
+    if stride < 1 or tuple(dy.shape) != (B, conv_out(H, k, stride, pad), conv_out(W, k, stride, pad), Cout):
+        raise RuntimeError("stem_dgrad: dy %s does not belong to an image batch %s (k %d, stride %d, pad %d)"
+                           % (tuple(dy.shape), (B, Cin, H, W), k, stride, pad))
+    dx = torch.empty((B, Cin, H, W), dtype=F32, device=dy.device)
+    _native.check(_native.lib().scouter_stem_dgrad_f32(_p(dy), _p(w_hwio), _p(dx), B, Cin, H, W, Cout, k, stride, pad, _stream()),
+                  "stem_dgrad")
+    return dx
+
+
 def pad_rows(w_flat, nvalid, ntotal):
     out = torch.empty(ntotal, dtype=F32, device=w_flat.device)
     _native.check(_native.lib().scouter_pad_rows_f32(_p(w_flat), _p(out), nvalid, ntotal, _stream()), "pad_rows")

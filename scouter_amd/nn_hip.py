@@ -40,8 +40,9 @@ ConvRoute = namedtuple("ConvRoute", "fwd dgrad wgrad split_fwd split_dgrad plane
 # What Conv2d.fwd saves for bwd: the input (its shape only when the producer wrote planes only), the input-gradient weight
 # planes, the operand planes of the input.
 ConvCtx = namedtuple("ConvCtx", "x wd xp")
-# What StemConv2d.fwd saves: the NCHW image (image=True: the direct forward) or its patch rows.
-StemCtx = namedtuple("StemCtx", "x image")
+# What StemConv2d.fwd saves: the NCHW image (image=True: the direct forward) or its patch rows, and the image's shape (the
+# input gradient's; the patch rows no longer have it).
+StemCtx = namedtuple("StemCtx", "x image shape")
 
 
 # The INFERENCE variant (SlotModel.set_inference_fold: every BatchNorm folded into the convolution in front of it, so each
@@ -338,7 +339,9 @@ class Conv2d(nn.Module):
 
 class StemConv2d(Conv2d):
     """First convolution of the network (Cin = 1 or 3, NCHW image in): im2col into [M][Kpad] rows (zero padded to a
-    multiple of 32) + the generic MFMA GEMM, for the forward and the weight gradient.  No input gradient.
+    multiple of 32) + the generic MFMA GEMM, for the forward and the weight gradient.  The input gradient (bwd(need_dx=True):
+    d output / d image, NCHW fp32 -- what attribution maps read) is one direct fp32 kernel, kernels.stem_dgrad, whatever the
+    precision and the forward route.
     SCOUTER_STEM_DIRECT=1 (opt-in, kernels.STEM_DIRECT): the deep stem's 3 -> 32 layer runs its forward as one direct pass."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding):
@@ -381,16 +384,21 @@ class StemConv2d(Conv2d):
             # deep stem (3 -> 32, 3x3 / 2), SCOUTER_STEM_DIRECT=1: one direct pass over the image, no patch rows; the weight
             # gradient builds its patch rows itself, on its side stream (bwd)
             y = K.stem_direct_fwd(x_nchw, K.hwio(self.weight), bn_stats)
-            return y, (StemCtx(x_nchw, True) if save else None)
+            return y, (StemCtx(x_nchw, True, tuple(x_nchw.shape)) if save else None)
         col = K.im2col_nchw(x_nchw, self.kernel_size, self.stride, self.padding, self.kpad)
         wflat = K.hwio(self.weight).reshape(-1)
         wpad = K.pad_rows(wflat, wflat.numel(), self.kpad * self.out_channels).view(1, 1, self.kpad, self.out_channels)
         y = K.conv2d_fwd(col, wpad, None, addend, 1, 0, 1, relu, bn_stats, precision=self.precision)
-        return y, (StemCtx(col, False) if save else None)
+        return y, (StemCtx(col, False, tuple(x_nchw.shape)) if save else None)
 
     def bwd(self, dy, ctx, need_dx=False, addend=None):
+        """need_dx: returns the gradient of the image (NCHW fp32), computed on the compute stream ahead of the weight
+        gradient on its side stream, like Conv2d.bwd."""
+        dx = None
         if need_dx:
-            raise NotImplementedError("gradient w.r.t. the input image is not part of the training hot path")
+            if addend is not None:
+                raise RuntimeError("StemConv2d.bwd: the image gradient takes no addend")
+            dx = K.stem_dgrad(dy, K.hwio(self.weight), ctx.shape, self.kernel_size, self.stride, self.padding)
         if self._dw is not None:
             with K.side_stream(dy.device, ctx.x, dy, enabled=self.use_side_stream):
                 rows = K.im2col_nchw(ctx.x, self.kernel_size, self.stride, self.padding, self.kpad) if ctx.image else ctx.x
@@ -398,7 +406,7 @@ class StemConv2d(Conv2d):
                 K.conv2d_wgrad(rows, dy, dwpad, precision=self.precision)
                 n = self.kdim * self.out_channels
                 K.axpby(dwpad.view(-1)[:n], None, 1.0, 0.0, out=self._dw.reshape(-1))
-        return None
+        return dx
 
 
 class BatchNorm2d(nn.Module):
@@ -503,7 +511,8 @@ class GradArena:
             self.entries.append((name, p, off, p.numel()))
             off += (p.numel() + 3) // 4 * 4
         self.numel = off
-        dev = self.entries[0][1].device if self.entries else torch.device("cpu")
+        # (no trainable parameter -- a frozen model whose INPUT requires grad: an empty arena on the model's device)
+        dev = self.entries[0][1].device if self.entries else self._model_device(model)
         self.flat = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
         self.views = {}
         for name, p, o, n in self.entries:
@@ -517,8 +526,20 @@ class GradArena:
                 self.views[name] = seg.view(p.shape)
         self._bind(model)
 
+    @staticmethod
+    def _model_device(model):
+        p = next(model.parameters(), None)
+        return p.device if p is not None else torch.device("cpu")
+
     def _bind(self, model):
         mods = dict(model.named_modules())
+        for m in mods.values():      # (bindings of an earlier arena: a parameter frozen since then gets no gradient)
+            if isinstance(m, Conv2d):
+                m._dw = m._db = None
+            elif isinstance(m, BatchNorm2d):
+                m._dg = m._db = None
+            elif isinstance(getattr(m, "_g", None), dict):
+                m._g.clear()
         for name, p, o, n in self.entries:
             mod_name, _, leaf = name.rpartition(".")
             m = mods[mod_name]
@@ -554,5 +575,7 @@ class GradArena:
 
     def matches(self, model):
         cur = [(n, p) for n, p in model.named_parameters() if p.requires_grad and "to_q" not in n]
+        if not cur and not self.entries:
+            return self._model_device(model) == self.flat.device
         return len(cur) == len(self.entries) and all(a[1] is b[1] and b[1].device == self.flat.device
                                                      for a, b in zip(cur, self.entries))

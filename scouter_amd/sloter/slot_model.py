@@ -64,9 +64,11 @@ class _FusedStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_logp, g_loss, g_nll, g_term):
-        ctx.model._backward_impl(ctx.state, g_logp, g_loss, g_nll, g_term)
+        # (an input that requires grad: the walk goes on to the image and its gradient -- NCHW fp32, the input's shape -- is
+        #  returned on x's edge; autograd casts it for an input of another floating type)
+        dx = ctx.model._backward_impl(ctx.state, g_logp, g_loss, g_nll, g_term, need_input_grad=ctx.needs_input_grad[2])
         ctx.state = None
-        return None, None, None, None
+        return None, None, dx, None
 
 
 class SlotModel(nn.Module):
@@ -112,7 +114,7 @@ class SlotModel(nn.Module):
     # ---- BatchNorm-folded inference
     def set_inference_fold(self, enabled):
         """enabled: an eval-mode forward that builds no training graph (model.eval() + torch.no_grad(), or no trainable
-        parameter) runs with every BatchNorm of the backbone folded into the convolution in front of it -- w' = w * s,
+        parameter and an input that does not require grad) runs with every BatchNorm of the backbone folded into the convolution in front of it -- w' = w * s,
         b' = beta - running_mean * s (+ conv_bias * s), s = gamma / sqrt(running_var + eps), formed in fp64 by ONE launch
         (K.BnFolder) -- so a block is three convolutions with bias / ReLU / residual in their epilogues, the split-attention
         gate one launch, and no BatchNorm kernel runs (nn_hip.InferRoute, ResNet.features_fwd_folded).  Off (the default) and
@@ -124,7 +126,9 @@ class SlotModel(nn.Module):
         version counters do not see them).  Activations of the folded path are stored as fp32, also under precision "bf16"
         (whose convolutions still round their matrix inputs to bf16).  Measured: +1.3 % at batch 70 and
         1.8 x on single images in fp32; under precision "bf16" at batch 256 it is 17 % SLOWER than the unfolded path with its
-        bf16 storage -- leave it off there."""
+        bf16 storage -- leave it off there.
+        The folded path has no backward: an input that requires grad (d output / d image, tools/attribution.py) runs the
+        unfolded eval forward, fold or no fold, and gets the same gradient."""
         self.inference_fold = bool(enabled)
         self._fold_stale = True
 
@@ -413,11 +417,14 @@ class SlotModel(nn.Module):
         for lo, hi, c in runs:
             K.iadd_i64(self._nbt_flat[lo:hi], c)
 
-    def _backward_impl(self, state, g_logp, g_loss, g_nll, g_term):
+    def _backward_impl(self, state, g_logp, g_loss, g_nll, g_term, need_input_grad=False):
+        """need_input_grad: the backbone backward runs whatever trains and goes on to the image (ResNet.features_bwd);
+        returns its gradient (None otherwise).  The parameter gradients are the same bits either way: the extra launches
+        come after their producers."""
         bctx, hstate = state
         arena = self.grad_arena()
-        need = self.backbone._first_trainable_stage() < 5
-        last = self.backbone.last_fuse(bctx) if need and self.use_slot else None
+        need = need_input_grad or self.backbone._first_trainable_stage() < 5
+        last = self.backbone.last_fuse(bctx, need_input_grad) if need and self.use_slot else None
         dfeat = self._head_backward(hstate, g_logp, g_loss, g_nll, g_term, need_dfeat=need, post=last)
         # gradient ranges become final from the END of the arena (head, layer4) towards its start (stem)
         done_hi = [arena.numel]
@@ -429,8 +436,10 @@ class SlotModel(nn.Module):
                 for hook in self._grad_ready_hooks:
                     hook(arena, lo, done_hi[0])
                 done_hi[0] = lo
+        dx = None
         if need:
-            self.backbone.features_bwd(dfeat, bctx, stage_done if self._grad_ready_hooks else None, own=last)
+            dx = self.backbone.features_bwd(dfeat, bctx, stage_done if self._grad_ready_hooks else None, own=last,
+                                            need_input_grad=need_input_grad)
         K.join_side_stream(arena.flat.device)               # all weight gradients are in the arena from here on
         if self._grad_ready_hooks and done_hi[0] > 0:
             for hook in self._grad_ready_hooks:
@@ -438,9 +447,12 @@ class SlotModel(nn.Module):
         arena.attach()
         for hook in self._post_backward_hooks:
             hook(arena)
+        return dx
 
     def forward(self, x, target=None):
-        train_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # (an input that requires grad takes the autograd route too -- in eval mode and with nothing trainable as well: the
+        #  node's backward returns d output / d image)
+        train_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if train_graph:
             if self._anchor is None or self._anchor.device != x.device:
                 self._anchor = torch.zeros(1, device=x.device, requires_grad=True)

@@ -1,12 +1,15 @@
 """Single-image inference + slot attention maps -- the `--vis` path of the reference (test.py:18-122 together with
 sloter/utils/slot_attention.py:68-85): eval-mode forward of ONE image on the HIP path, per-class uint8 attention
 maps written as `<out>/slot_{c}.png`, the input as `<out>/image.png`, and (optionally) the attention-area ratio the
-reference prints with --cal_area_size (test.py:40-44).  The jet-colormap overlay of test.py:33-38 is matplotlib
+reference prints with --cal_area_size (test.py:40-44).  `--grad true` adds the per-class gradient attribution maps
+`<out>/grad_{c}.png` (d log-probability / d image through tools/attribution.py, floored at --grad_min_level; also for the
+`--use_slot false` baseline, the model the reference attributes).  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
-        [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224"""
+        [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
+        [--grad true --grad_min_level 0.1]"""
 import argparse
 import os
 
@@ -38,14 +41,28 @@ def run(args, model, image, out_dir, label=None):
     model.eval()
     output = model(image.unsqueeze(0).to(args.device, dtype=torch.float32))
     pred = int(output.argmax(dim=1))
-    maps = model.slot.vis_maps()                      # [C, h, w] uint8, min-max scaled over the whole map (:74)
+    # [C, h, w] uint8, min-max scaled over the whole map (:74); the FC baseline (--use_slot false) has no slot maps
+    maps = model.slot.vis_maps() if model.use_slot else np.zeros((0, 0, 0), dtype=np.uint8)
     for c, m in enumerate(maps):
         Image.fromarray(m, mode="L").save(os.path.join(out_dir, "slot_%d.png" % c))
     ratio = None
-    if label is not None:
+    if label is not None and len(maps):
         idx = label if args.loss_status > 0 else min(label + 1, len(maps) - 1)
         ratio = float(maps[idx].astype(np.float64).sum()) / float(maps[idx].size * 255)
     return output[0].cpu(), pred, maps, ratio
+
+
+def run_grad(args, model, image, out_dir):
+    """--grad true: the gradient attribution of every class for the one image (reference train.py --grad /
+    --grad_min_level, captum_vis.py) -> `<out>/grad_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import attribution_maps, input_gradients
+    os.makedirs(out_dir, exist_ok=True)
+    grads = input_gradients(model, image.unsqueeze(0).to(args.device, dtype=torch.float32))
+    maps = attribution_maps(grads, min_level=float(args.grad_min_level))[0]
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "grad_%d.png" % c))
+    return maps
 
 
 def main():
@@ -59,6 +76,8 @@ def main():
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
     args.vis, args.vis_id = False, 0                  # maps are taken from model.slot.last_attn, image index 0
+    # (--grad asks THIS tool for gradient maps; the model is built as for training, so that its checkpoints load)
+    want_grad, args.grad = bool(args.grad), False
     model = SlotModel(args).to(args.device)
     model.set_inference_fold(bool(args.eval_fold))
     ckpt = args.checkpoint or os.path.join(args.output_dir, checkpoint_name(args))
@@ -75,6 +94,8 @@ def main():
     else:
         image = torch.from_numpy(np.random.default_rng(0).standard_normal((channels, size, size), dtype=np.float32))
     out, pred, maps, ratio = run(args, model, image, args.vis_dir, args.label)
+    if want_grad:
+        run_grad(args, model, image, args.vis_dir)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:

@@ -311,26 +311,29 @@ class ResNet(nn.Module):
                 return i
         return 5
 
-    def last_fuse(self, ctx):
+    def last_fuse(self, ctx, need_input_grad=False):
         """BnBwdFuse of the LAST block's output BatchNorm(s), for whatever kernel produces d(features) (the head's
         conv1x1 input gradient); None when the backbone gets no gradient."""
-        if self._first_trainable_stage() > 4:
+        if self._first_trainable_stage() > 4 and not need_input_grad:
             return None
         return self.layer4[-1].out_fuse(ctx[-1])
 
-    def features_bwd(self, dfeat, ctx, on_stage_done=None, own=None):
+    def features_bwd(self, dfeat, ctx, on_stage_done=None, own=None, need_input_grad=False):
         """`on_stage_done(name)` is called when every gradient of layer4 / layer3 / layer2 / layer1 has been
         written (used to launch that stage's gradient all-reduce while earlier layers are still in backward).
         BatchNorm-backward reductions ride in the epilogue of the input-gradient kernel that produces each gradient
         (K.BnBwdFuse): block i's conv1 finishes block i-1's bn3 / downsample sums, `own` is the last block's object if
-        the producer of `dfeat` applied it."""
-        first = self._first_trainable_stage()
+        the producer of `dfeat` applied it.
+        need_input_grad: the walk does not stop at the first trainable stage -- it goes on through frozen blocks (whose
+        parameter-gradient slices are None: only their input gradients run), the max-pool, bn1 and the stem, and returns
+        the gradient of the image (NCHW fp32).  Off: returns None, and the walk is what it was, launch for launch."""
+        first = 0 if need_input_grad else self._first_trainable_stage()
         blocks = [(li, blk) for li in range(1, 5) for blk in getattr(self, "layer%d" % li)]
         d = dfeat
         for idx in range(len(blocks) - 1, -1, -1):
             li, blk = blocks[idx]
             if li < first:
-                return
+                return None
             is_first_trainable = li == first and (idx == 0 or blocks[idx - 1][0] < first)
             post = blocks[idx - 1][1].out_fuse(ctx[2 + idx - 1]) if idx > 0 and not is_first_trainable else None
             d = blk.bwd(d, ctx[2 + idx], need_dx=not is_first_trainable, own=own, post=post)
@@ -338,7 +341,7 @@ class ResNet(nn.Module):
             if on_stage_done is not None and (idx == 0 or blocks[idx - 1][0] != li):
                 on_stage_done("layer%d" % li)
         if first > 0:
-            return
+            return None
         if len(ctx[1]) == 4:
             craw, saved, training1, arg = ctx[1]
             last = self.conv1[6] if isinstance(self.conv1, nn.Sequential) else None
@@ -357,9 +360,8 @@ class ResNet(nn.Module):
             f = BatchNorm2d.fuse(b0)
             dh = s[3].bwd(dc, k1, True, post=f)
             dc, _ = s[1].bwd(dh, b0, fused=f.ext(0) if f.applied else None)
-            s[0].bwd(dc, k0, False)
-        else:
-            self.conv1.bwd(dc, ctx[0][0], False)
+            return s[0].bwd(dc, k0, need_input_grad)
+        return self.conv1.bwd(dc, ctx[0][0], need_input_grad)
 
     @torch.no_grad()
     def forward_features(self, x):

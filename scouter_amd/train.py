@@ -49,7 +49,9 @@ _CLI = [
     ("pre_trained", True, _flag, "freeze `freeze_layers` stages (weights must be loaded from a checkpoint)"),
     ("use_slot", True, _flag, "xSlot head (false: global-pool + fc baseline)"),
     ("use_pre", False, _flag, "initialise the backbone from the FC-baseline checkpoint"),
-    ("aug", False, _flag, None), ("grad", False, _flag, None), ("grad_min_level", 0.0, float, None),
+    ("aug", False, _flag, None),
+    ("grad", False, _flag, "test.py: also write per-class gradient attribution maps grad_{c}.png (training ignores it)"),
+    ("grad_min_level", 0.0, float, "test.py --grad: floor of the scaled attribution map, in [0, 1) (training ignores it)"),
     ("iterated_evaluation_num", 1, int, "repetitions per sweep value"),
     ("cal_area_size", False, _flag, "tag checkpoints with lambda / slots_per_class"),
     ("thop", False, _flag, "refused (CPU FLOP counting)"),
