@@ -158,39 +158,26 @@ int scouter_conv2d_dgrad_bn_partial_rows_bf16(int B, int H, int W, int Cin, int 
                                               int groups, int tile_hint, int two_batchnorms);
 int scouter_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int kh,
                               int kw, int stride, int pad, int groups, int plan_hint, void* ws, size_t ws_bytes,
-                              void* arrival, int arrival_slots, void* stream);
+                              void* stream);
 /* io: SCOUTER_IO_X_BF16 -- x is stored as bf16, SCOUTER_IO_R_BF16 -- dy is.  plan_hint < 0 (the library's own plan) with BOTH
  * operands stored as bf16 on a 3x3 / stride 1 / pad 1 layer with 32 input channels per group and rows of at most 112 pixels: the
  * tap-fused kernel (every x row fetched once per workgroup, not once per tap; csrc/conv_wgrad_taps_bf16.h; SCOUTER_BWT=0: off).
  * Same workspace bound (scouter_conv2d_wgrad_workspace_bytes with the same plan_hint) and deterministic slab sum. */
 int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                  int kh, int kw, int stride, int pad, int groups, int plan_hint, void* ws,
-                                 size_t ws_bytes, void* arrival, int arrival_slots, int io, void* stream);
+                                 size_t ws_bytes, int io, void* stream);
 /* plan_hint: -1 = built-in plan; otherwise bits 0-1 = block budget {512,1024,2048,4096} (sets the split-K count),
  * bit 4 / bit 5 = halve the ci / co tile edge.  Every plan is deterministic; different plans sum the pixels in a
- * different order (results differ in the last bits), so a caller that autotunes keeps its choice for the whole run.
- * arrival (may be NULL), arrival_slots: caller-owned device buffer of arrival_slots 32-bit counters, ZERO on entry and left
- * zero on exit, private to the stream (two launches that overlap in time must not share it).  With it the split-K slabs
- * are summed INSIDE the kernel -- the last workgroup of an output tile to arrive adds the tile's partials in slab order
- * (deterministic) and writes dw; without it (or when the plan has more output tiles than slots) a separate slab-sum
- * kernel is launched.  The two paths add the slabs in different association orders: results agree to fp32 rounding. */
+ * different order (results differ in the last bits), so a caller that autotunes keeps its choice for the whole run. */
 size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
                                             int groups, int plan_hint);
 int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int kh,
                              int kw, int stride, int pad, int groups, int plan_hint, void* ws, size_t ws_bytes,
-                             void* arrival, int arrival_slots, void* stream);
+                             void* stream);
 /* stem (Cin < 32): im2col of the NCHW image into [M][Kpad] rows so the stem runs as a 1x1 conv on the same path */
 int scouter_im2col_nchw_f32(const float* x, float* col, int B, int Cin, int H, int W, int k, int stride, int pad,
                             int Kpad, void* stream);
 int scouter_pad_rows_f32(const float* w, float* wpad, long nvalid, long ntotal, void* stream);
-/* deep stem's first convolution (timm/models/resnet.py deep stem conv1[0], the 3 -> 32 channel 3x3 / stride 2 / pad 1 layer of
- * resnest26d / resnest50d), direct: x NCHW [B][3][H][W], w HWIO [3][3][3][32], y NHWC [B][Ho][Wo][32]; no patch rows are
- * written.  bn_partial (optional): [scouter_stem_direct_partial_rows(B, H)][32][2] fp64 (sum, sum of squares) of y, the layout
- * scouter_bn_fwd_f32 takes from scouter_conv2d_fwd_f32.  Cout != 32 or an image too wide for the LDS row stage: SC_ERR_UNSUPPORTED
- * (the caller keeps the im2col route). */
-int scouter_stem_direct_partial_rows(int B, int H);
-int scouter_stem_direct_fwd_f32(const float* x, const float* w, float* y, double* bn_partial, int B, int H, int W, int Cout,
-                                void* stream);
 /* stem input gradient, d output / d image (train.py --grad / --grad_min_level, captum_vis.py: `image.requires_grad_()` and the
  * attribution methods that read the gradient of the image; sloter/slot_model.py:23-24, timm/models/resnet.py stems):
  * dx NCHW [B][Cin][H][W] = conv_transpose(dy NHWC [B][Ho][Wo][Cout], w HWIO [k][k][Cin][Cout]).  Gather form, no atomics:
@@ -399,12 +386,12 @@ int scouter_conv2d_dgrad_planes_bnbwd(const void* dy_planes, const void* w_plane
  * instead of 128 input / output channels per tile; bit 6 (3x3, pad 1, maps up to 63 wide) = the TAP-FUSED kernel
  * (csrc/conv_planes_wgrad_taps.h: one workgroup accumulates all nine taps of a 64 x 64 tile from an LDS-resident ring of X
  * rows), bits 0-1 then = budget {256, 512, 1024, 2048} workgroups (callers autotune it; every plan is deterministic,
- * different plans sum the pixels in a different order).  arrival / arrival_slots: as for scouter_conv2d_wgrad_f32. */
+ * different plans sum the pixels in a different order). */
 size_t scouter_conv2d_wgrad_planes_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw, int groups,
                                                    int plan_hint);
 int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_planes, float* dw, int B, int H, int W, int Cin,
                                 int Cout, int kh, int kw, int pad, int groups, int nplanes, int plan_hint,
-                                void* ws, size_t ws_bytes, void* arrival, int arrival_slots, void* stream);
+                                void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Convolutions at fp32 accuracy on the bf16 matrix cores with the three-way operand split done in registers
  * (csrc/conv_x3.hip, round 5): the deep 1x1 layers of the bottlenecks -- conv1 / conv3 (timm/models/resnest.py:111-143),

@@ -358,8 +358,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const float* __restrict__
 template <int BM, int BN, int WM, int WN, int MODE>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__ act, const float* __restrict__ dy,
                                                        float* __restrict__ out, ConvGeom g, int ci_tiles,
-                                                       int co_tiles, long pix_per_split, long slab,
-                                                       float* __restrict__ dw, unsigned* __restrict__ arrival) {
+                                                       int co_tiles, long pix_per_split, long slab) {
     constexpr int MT = WM / 32, NT = WN / 32, WAVES_N = BN / WN, WAVES_MN = (BM / WM) * (BN / WN);
     constexpr int WK = 4 / WAVES_MN;           // small tiles: the spare waves split the 16 k-steps of a chunk
     constexpr int SPW = 16 / WK;
@@ -372,7 +371,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
     const int wm = wmn / WAVES_N, wn = wmn % WAVES_N;
     int bid, split_id;
     wgrad_block_coords(bid, split_id);
-    const int tile_id = bid;
     const int co_t = bid % co_tiles; bid /= co_tiles;
     const int ci_t = bid % ci_tiles; bid /= ci_tiles;
     const int grp = bid % g.groups;
@@ -564,7 +562,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
 #undef SB
     IG_STAMP(2)
     float* o = out + (long)split_id * slab + (long)tap * g.Cg * g.N;
-    const bool coh = arrival != nullptr;               // partial tiles leave write-through: another workgroup sums them
     if (WK == 1) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -574,7 +571,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     const int co = grp * g.Ng + co0 + wn * WN + j * 32 + l31;
-                    slab_store(o + (long)ci * g.N + co, acc[i][j][e], coh);
+                    o[(long)ci * g.N + co] = acc[i][j][e];
                 }
             }
     } else {   // cross-wave (k-split) reduction through LDS, fixed order
@@ -591,12 +588,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
             float v = lds[e];
 #pragma unroll
             for (int k = 1; k < WK; ++k) v += lds[k * BM * BN + e];
-            slab_store(o + (long)(ci0 + e / BN) * g.N + grp * g.Ng + co0 + e % BN, v, coh);
+            o[(long)(ci0 + e / BN) * g.N + grp * g.Ng + co0 + e % BN] = v;
         }
     }
-    if (coh)
-        slab_tile_finish(out + (long)tap * g.Cg * g.N, dw + (long)tap * g.Cg * g.N, slab, gridDim.y, arrival + tile_id, 1, 0,
-                         (long)ci0 * g.N, BM, g.N, grp * g.Ng + co0, BN);
 #ifdef IGEMM_STAMPS
     if (g_igemm_stamps && threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1026,7 +1020,7 @@ extern "C" size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int 
 
 extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin,
                                         int Cout, int kh, int kw, int stride, int pad, int groups, int plan_hint,
-                                        void* ws, size_t ws_bytes, void* arrival, int arrival_slots, void* stream) {
+                                        void* ws, size_t ws_bytes, void* stream) {
     SC_REQUIRE(x && dy && dw && B > 0, "conv2d_wgrad: null pointer or empty shape");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad: channels not divisible by groups");
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
@@ -1052,7 +1046,6 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
         if (need_t <= ws_bytes && (!need_t || ws)) {
             hipStream_t st = (hipStream_t)stream;
             float* out = splits > 1 ? (float*)ws : dw;
-            unsigned* arr = splits > 1 && arrival && tiles <= arrival_slots ? (unsigned*)arrival : nullptr;
             const size_t lds = (size_t)(9 * 32 * 32 + 32 * bn) * sizeof(float);
             if (xwt && pps % XWT_CH == 0) {
                 // the same tile on the bf16 matrix cores, operands split in registers (conv_wgrad_taps_x3.h)
@@ -1062,18 +1055,18 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
                 auto kern = bn == 64 ? xwgrad_taps_kernel<64> : xwgrad_taps_kernel<32>;
                 sc_dyn_lds((const void*)kern, xlds);
                 hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), xlds, st, x, dy, out, g, co_tiles,
-                                   pps, slab_t, dw, arr);
+                                   pps, slab_t);
             } else {
                 ScProfScope prof("wgrad_taps", st, 2.0 * g.M * Cout * g.Cg * 9,
                                  4.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
                 auto kern = bn == 64 ? wgrad_taps_kernel<64> : wgrad_taps_kernel<32>;
                 sc_dyn_lds((const void*)kern, lds);
                 hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), lds, st, x, dy, out, g, co_tiles,
-                                   pps, slab_t, dw, arr);
+                                   pps, slab_t);
             }
             int rc = sc_check_launch("conv2d_wgrad_taps");
             if (rc) return rc;
-            if (splits > 1 && !arr) {
+            if (splits > 1) {
                 ScProfScope prof2("slab_reduce", st, 0, 4.0 * (double)slab_t * (splits + 1));
                 hipLaunchKernelGGL(slab_reduce_kernel, dim3(sc_cdiv(slab_t / 4, 8)), dim3(256), 0, st, (const float*)ws,
                                    dw, slab_t, splits, slab_t);
@@ -1091,7 +1084,6 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     }
     hipStream_t st = (hipStream_t)stream;
     float* out = p.splits > 1 ? (float*)ws : dw;
-    unsigned* arr = p.splits > 1 && arrival && p.tiles <= arrival_slots ? (unsigned*)arrival : nullptr;
     dim3 grid((unsigned)p.tiles, (unsigned)p.splits);
     static char wname[9][24];
     static const int wb[9][2] = {{128, 128}, {128, 64}, {128, 32}, {64, 128}, {64, 64}, {64, 32}, {32, 128}, {32, 64}, {32, 32}};
@@ -1110,13 +1102,13 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     do {                                                                                                            \
         if (mode == 2)                                                                                              \
             hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, WM_, WN_, 2>), grid, dim3(256), 0, st, x, dy, out, g,       \
-                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab, dw, arr);                            \
+                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab);                                     \
         else if (mode == 1)                                                                                         \
             hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, WM_, WN_, 1>), grid, dim3(256), 0, st, x, dy, out, g,       \
-                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab, dw, arr);                            \
+                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab);                                     \
         else                                                                                                        \
             hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, WM_, WN_, 0>), grid, dim3(256), 0, st, x, dy, out, g,       \
-                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab, dw, arr);                            \
+                               p.ci_tiles, p.co_tiles, p.pix_per_split, slab);                                     \
     } while (0)
     if (p.bm == 128 && p.bn == 128) WG(128, 128, 64, 64);
     else if (p.bm == 128 && p.bn == 64) WG(128, 64, 64, 32);
@@ -1131,7 +1123,7 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     }
     rc = sc_check_launch("conv2d_wgrad");
     if (rc) return rc;
-    if (p.splits > 1 && !arr) {
+    if (p.splits > 1) {
         const long n = slab;
         ScProfScope prof2("slab_reduce", st, 0, 4.0 * (double)slab * (p.splits + 1));
         hipLaunchKernelGGL(slab_reduce_kernel, dim3(sc_cdiv(n / 4, 8)), dim3(256), 0, st, (const float*)ws, dw, n,
@@ -1150,8 +1142,7 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
 // `io`: SC_IO_X_BF16 -- the activation x is stored as bf16, SC_IO_R_BF16 -- dy is
 extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin,
                                             int Cout, int kh, int kw, int stride, int pad, int groups, int plan_hint,
-                                            void* ws, size_t ws_bytes, void* arrival, int arrival_slots, int io,
-                                            void* stream) {
+                                            void* ws, size_t ws_bytes, int io, void* stream) {
     SC_REQUIRE(x && dy && dw && B > 0, "conv2d_wgrad_bf16: null pointer or empty shape");
     SC_REQUIRE((io & ~(SC_IO_X_BF16 | SC_IO_R_BF16)) == 0, "conv2d_wgrad_bf16: unsupported io bits %d (x and dy may be bf16)", io);
     const bool xb = (io & SC_IO_X_BF16) != 0, db = (io & SC_IO_R_BF16) != 0;
@@ -1179,18 +1170,17 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
         if (sc_switch(SC_SW_BWT) && need_t <= ws_bytes && (!need_t || ws)) {
             hipStream_t st = (hipStream_t)stream;
             float* out = splits > 1 ? (float*)ws : dw;
-            unsigned* arr = splits > 1 && arrival && tiles <= arrival_slots ? (unsigned*)arrival : nullptr;
             const size_t blds = bwgrad_taps_lds_bytes(bn);
             {
             ScProfScope prof("bwgrad_taps<bf16>", st, 2.0 * g.M * Cout * g.Cg * 9, 2.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
             auto kern = bn == 64 ? bwgrad_taps_kernel<64> : bwgrad_taps_kernel<32>;
             sc_dyn_lds((const void*)kern, blds);
             hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(256), blds, st, (const unsigned short*)x,
-                               (const unsigned short*)dy, out, g, co_tiles, pps, slab_t, dw, arr);
+                               (const unsigned short*)dy, out, g, co_tiles, pps, slab_t);
             }
             int rc = sc_check_launch("conv2d_wgrad_taps_bf16");
             if (rc) return rc;
-            if (splits > 1 && !arr) {
+            if (splits > 1) {
                 ScProfScope prof2("slab_reduce", st, 0, 4.0 * (double)slab_t * (splits + 1));
                 hipLaunchKernelGGL(slab_reduce_kernel, dim3(sc_cdiv(slab_t / 4, 8)), dim3(256), 0, st, (const float*)ws,
                                    dw, slab_t, splits, slab_t);
@@ -1199,7 +1189,6 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
             return rc;
         }
     }
-    const bool ragged = g.Cg % 64 != 0 || g.Ng % 64 != 0;
     WgradPlan p = wgrad_plan(g, plan_hint, true, 64);                        // the bf16 kernel has no 32-wide tiles
     const long slab = (long)kh * kw * g.Cg * Cout;
     const size_t need = p.splits > 1 ? (size_t)p.splits * slab * sizeof(float) : 0;
@@ -1209,7 +1198,6 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     }
     hipStream_t st = (hipStream_t)stream;
     float* out = p.splits > 1 ? (float*)ws : dw;
-    unsigned* arr = p.splits > 1 && arrival && p.tiles <= arrival_slots && !ragged ? (unsigned*)arrival : nullptr;
     dim3 grid((unsigned)p.tiles, (unsigned)p.splits);
     int rc;
     {
@@ -1220,7 +1208,7 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
         auto kern = KERN;                                                                                           \
         sc_dyn_lds((const void*)kern, lds);                                                                         \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, x, dy, out, g, p.ci_tiles, p.co_tiles, p.pix_per_split,  \
-                           slab, dw, arr);                                                                          \
+                           slab);                                                                                   \
     } while (0)
 #define WGH(BM_, BN_, WM_, WN_)                                                                                     \
     do {                                                                                                            \
@@ -1243,7 +1231,7 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     }
     rc = sc_check_launch("conv2d_wgrad_bf16");
     if (rc) return rc;
-    if (p.splits > 1 && !arr) {
+    if (p.splits > 1) {
         ScProfScope prof2("slab_reduce", st, 0, 4.0 * (double)slab * (p.splits + 1));
         hipLaunchKernelGGL(slab_reduce_kernel, dim3(sc_cdiv(slab / 4, 8)), dim3(256), 0, st, (const float*)ws, dw, slab,
                            p.splits, slab);
@@ -1253,7 +1241,7 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
 }
 extern "C" int scouter_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin,
                                          int Cout, int kh, int kw, int stride, int pad, int groups, int plan_hint,
-                                         void* ws, size_t ws_bytes, void* arrival, int arrival_slots, void* stream) {
+                                         void* ws, size_t ws_bytes, void* stream) {
     return scouter_conv2d_wgrad_bf16_io(x, dy, dw, B, H, W, Cin, Cout, kh, kw, stride, pad, groups, plan_hint, ws, ws_bytes,
-                                        arrival, arrival_slots, 0, stream);
+                                        0, stream);
 }

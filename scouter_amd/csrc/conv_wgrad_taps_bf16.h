@@ -17,7 +17,7 @@
 //     the end (fixed order);
 //   * 65 KB of LDS and 256 registers: TWO workgroups per CU (the second one's MFMAs cover the first one's fragment reads and
 //     barrier), 512 pixel ranges.
-// Same slab / split-K output format as wgrad_taps_kernel (deterministic; slab_reduce_kernel or the arrival counters).
+// Same slab / split-K output format as wgrad_taps_kernel (deterministic; slab_reduce_kernel).
 #pragma once
 #include "conv_common.h"
 #include "conv_wgrad_taps_x3.h"
@@ -51,8 +51,7 @@ __device__ __forceinline__ void bwt_wait(xw_bf16x8& f) { asm volatile("s_waitcnt
 template <int BN>       // output-channel tile (32 | 64); the input-channel tile is the whole group (32)
 __global__ __launch_bounds__(256, 2) void bwgrad_taps_kernel(const unsigned short* __restrict__ act,
                                                              const unsigned short* __restrict__ dy, float* __restrict__ out,
-                                                             ConvGeom g, int co_tiles, long pix_per_split, long slab,
-                                                             float* __restrict__ dw, unsigned* __restrict__ arrival) {
+                                                             ConvGeom g, int co_tiles, long pix_per_split, long slab) {
     constexpr int CH = BWT_CH, RING = BWT_RING, HALO = BWT_HALO, XROW = BWT_XROW, XPL = BWT_XPL;
     constexpr int DYROW = BN * 2, DYST = CH * DYROW;
     constexpr int NWN = BN / 32, WK = 4 / NWN, KSW = 4 / WK;      // waves along co / along k; k-steps per wave and chunk
@@ -66,7 +65,6 @@ __global__ __launch_bounds__(256, 2) void bwgrad_taps_kernel(const unsigned shor
     const int wn = wave % NWN, wk = wave / NWN;
     int bid, split_id;
     wgrad_block_coords(bid, split_id);
-    const int tile_id = bid;
     const int co_t = bid % co_tiles, grp = bid / co_tiles;
     const int co0 = co_t * BN;
     const long mbeg = (long)split_id * pix_per_split;            // multiple of 64
@@ -213,10 +211,8 @@ __global__ __launch_bounds__(256, 2) void bwgrad_taps_kernel(const unsigned shor
             float v = red[e];
 #pragma unroll
             for (int k = 1; k < WK; ++k) v += red[k * 32 * BN + e];
-            slab_store(o + ((long)t * g.Cg + e / BN) * g.N + grp * g.Ng + co0 + e % BN, v, arrival != nullptr);
+            o[((long)t * g.Cg + e / BN) * g.N + grp * g.Ng + co0 + e % BN] = v;
         }
         __syncthreads();
     }
-    if (arrival)        // the last workgroup of this tile sums the slabs itself (conv_common.h slab_tile_finish)
-        slab_tile_finish(out, dw, slab, gridDim.y, arrival + tile_id, 9, (long)g.Cg * g.N, 0, 32, g.N, grp * g.Ng + co0, BN);
 }

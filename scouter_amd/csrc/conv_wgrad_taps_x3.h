@@ -26,7 +26,7 @@
 //     scheduling region); ONE round of 256 long pixel ranges (147 KB of LDS = one workgroup per CU, five-unit prologue each).
 // Measured (tools_dev/xwt_check.py, batch 70): stem 32 -> 32 191 -> 118 us, 32 -> 64 300 -> 194, layer1's radix convolution
 // 174 -> 100 (137 / 167 / 162 TFLOP/s; first version, reads in front of their MFMAs and 1 024 short ranges: 163 / 283).
-// Same slab / split-K output format as wgrad_taps_kernel (deterministic; slab_reduce_kernel or the arrival counters).
+// Same slab / split-K output format as wgrad_taps_kernel (deterministic; slab_reduce_kernel).
 #pragma once
 #include "conv_common.h"
 
@@ -67,8 +67,7 @@ static size_t xwgrad_taps_lds_bytes(int bn) { return (size_t)3 * XWT_XPL + (size
 template <int BN>       // output-channel tile (32 | 64); the input-channel tile is the whole group (32)
 __global__ __launch_bounds__(256, 1) void xwgrad_taps_kernel(const float* __restrict__ act, const float* __restrict__ dy,
                                                              float* __restrict__ out, ConvGeom g, int co_tiles,
-                                                             long pix_per_split, long slab, float* __restrict__ dw,
-                                                             unsigned* __restrict__ arrival) {
+                                                             long pix_per_split, long slab) {
     constexpr int CH = XWT_CH, RING = XWT_RING, HALO = XWT_HALO, XROW = XWT_XROW, XPL = XWT_XPL;
     constexpr int DYROW = BN * 2, DYPL = CH * DYROW, DYST = 3 * DYPL;
     constexpr int NWN = BN / 32, WK = 4 / NWN, KSW = 4 / WK;      // waves along co / along k; k-steps per wave and chunk
@@ -82,7 +81,6 @@ __global__ __launch_bounds__(256, 1) void xwgrad_taps_kernel(const float* __rest
     const int wn = wave % NWN, wk = wave / NWN;
     int bid, split_id;
     wgrad_block_coords(bid, split_id);
-    const int tile_id = bid;
     const int co_t = bid % co_tiles, grp = bid / co_tiles;
     const int co0 = co_t * BN;
     const long mbeg = (long)split_id * pix_per_split;            // multiple of 64
@@ -276,10 +274,8 @@ __global__ __launch_bounds__(256, 1) void xwgrad_taps_kernel(const float* __rest
             float v = red[e];
 #pragma unroll
             for (int k = 1; k < WK; ++k) v += red[k * 32 * BN + e];
-            slab_store(o + ((long)t * g.Cg + e / BN) * g.N + grp * g.Ng + co0 + e % BN, v, arrival != nullptr);
+            o[((long)t * g.Cg + e / BN) * g.N + grp * g.Ng + co0 + e % BN] = v;
         }
         __syncthreads();
     }
-    if (arrival)        // the last workgroup of this tile sums the slabs itself (conv_common.h slab_tile_finish)
-        slab_tile_finish(out, dw, slab, gridDim.y, arrival + tile_id, 9, (long)g.Cg * g.N, 0, 32, g.N, grp * g.Ng + co0, BN);
 }

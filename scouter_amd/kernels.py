@@ -105,32 +105,6 @@ def workspace(nbytes, device):
     return w
 
 
-_arrival = {}
-ARRIVAL_SLOTS = 1 << 16
-# SCOUTER_SLAB_FUSE=1: the split-K slabs are summed INSIDE the weight-gradient kernels by the last workgroup of a tile to
-# arrive (csrc/conv_common.h slab_tile_finish) instead of a slab-sum launch per layer.  Built, bit-
-# reproducible and green under the poisoned-workspace tests -- and measured 17-25 % SLOWER on the step (interleaved A/B on one
-# box, 2 x 60 steps each: 4 113 / 4 128 img/s with the separate launches; 3 432 / 3 461 with write-through stores + sc1 loads,
-# 3 121 / 3 122 with plain stores + agent-scope release / acquire fences): a layer has 4-64 output tiles, so 4-64 workgroups
-# walk `splits` x 16 KB of uncached partials each (~100 us tails) while the 10-us slab_reduce launch it replaces spreads the
-# same bytes over every CU.  Off by default; kept as a documented option.
-SLAB_FUSE = os.environ.get("SCOUTER_SLAB_FUSE", "0") == "1"
-
-
-def arrival_counters(device):
-    """Per-(device, stream) buffer of zeroed 32-bit arrival counters for the split-K weight-gradient kernels: with it the
-    LAST workgroup of an output tile sums the tile's slabs inside the kernel (include/scouter_hip.h `arrival`) -- no
-    slab-sum launch.  The kernels leave it zero; it is never part of the shared scratch (which tests poison and other
-    kernels overwrite)."""
-    if not SLAB_FUSE:
-        return None
-    key = (device.type, device.index, _stream())
-    a = _arrival.get(key)
-    if a is None:
-        a = _arrival[key] = torch.zeros(ARRIVAL_SLOTS, dtype=torch.int32, device=device)
-    return a
-
-
 def hwio(weight):
     """Physical HWIO view [kh, kw, Cin/g, Cout] of a logical-OIHW conv weight; relayouts (once) if needed."""
     v = weight.permute(2, 3, 1, 0)
@@ -1000,10 +974,8 @@ def conv2d_wgrad_planes(xp, dyp, dw_hwio, pad, groups=1):
             return plan < 64 or (kh == 3 and kw == 3 and pad == 1 and W <= 63 and
                                  2 * B * H * W * max(Cin, Cout) < (1 << 31))
         ws = workspace(L.scouter_conv2d_wgrad_planes_workspace_bytes(B, H, W, Cin, Cout, kh, kw, groups, plan), xp.device)
-        arr = arrival_counters(xp.device)
         _native.check(L.scouter_conv2d_wgrad_planes(_p(xp), _p(dyp), _p(dw_hwio), B, H, W, Cin, Cout, kh, kw, pad, groups,
-                                                    nplanes, plan, _p(ws), ws.numel(), _p(arr), ARRIVAL_SLOTS if arr is not None else 0,
-                                                    _stream()), "conv2d_wgrad_planes")
+                                                    nplanes, plan, _p(ws), ws.numel(), _stream()), "conv2d_wgrad_planes")
         return True
 
     launch(_pick_tile(("pwgrad", nplanes, B, H, W, Cin, Cout, kh, kw, pad, groups), launch, _PWGRAD_PLANS))
@@ -1108,9 +1080,7 @@ def conv2d_wgrad(x, dy, dw_hwio, stride=1, pad=0, groups=1, precision="fp32"):
             return True
         need = L.scouter_conv2d_wgrad_workspace_bytes(B, H, W, Cin, Cout, kh, kw, stride, pad, groups, plan)
         ws = workspace(need, x.device)
-        arr = arrival_counters(x.device)
-        args = (_p(x), _p(dy), _p(dw_hwio), B, H, W, Cin, Cout, kh, kw, stride, pad, groups, plan, _p(ws), ws.numel(),
-                _p(arr), ARRIVAL_SLOTS if arr is not None else 0)
+        args = (_p(x), _p(dy), _p(dw_hwio), B, H, W, Cin, Cout, kh, kw, stride, pad, groups, plan, _p(ws), ws.numel())
         if bf16:
             _native.check(L.scouter_conv2d_wgrad_bf16_io(
                 *args, (IO_X_BF16 if x.dtype == BF16 else 0) | (IO_R_BF16 if dy.dtype == BF16 else 0), st), "conv2d_wgrad")
@@ -1155,38 +1125,6 @@ def im2col_nchw(x, k, stride, pad, kpad):
     _native.check(_native.lib().scouter_im2col_nchw_f32(_p(x), _p(col), B, Cin, H, W, k, stride, pad, kpad, _stream()),
                   "im2col")
     return col
-
-
-# SCOUTER_STEM_DIRECT=1: the deep stem's 3 -> 32 convolution (fp32 mode) as ONE direct pass over the NCHW image instead of im2col +
-# GEMM (csrc/misc_ops.hip stem_direct_kernel: 88 -> 55 us at 70 x 224^2, no 112 MB of patch rows kept for the backward).  A
-# forward-changing option -- three nine-term fmaf chains instead of the MFMA's K order: half the GEMM route's error against
-# fp64, other bits -- and like every such option it is one more draw of rounding noise for the single-draw gradient bounds of
-# tests/test_model_gpu.py (resnest26d_96: one squeeze-path tensor at 1.06e-3 of its scale against the 1e-3 bound); the step
-# does not notice the 34 us (4 927 vs 4 929 img/s, 3 x 60 steps interleaved).  Off by default.
-STEM_DIRECT = os.environ.get("SCOUTER_STEM_DIRECT", "0") == "1"
-
-
-def stem_direct_eligible(Cin, Cout, k, stride, pad, W):
-    """The direct kernel of the deep stem's first convolution (csrc/misc_ops.hip stem_direct_kernel): 3 -> 32 channels,
-    3x3 / stride 2 / pad 1, rows narrow enough for its LDS stage.  A static rule of the layer shape."""
-    return Cin == 3 and Cout == 32 and k == 3 and stride == 2 and pad == 1 and W <= 1000
-
-
-def stem_direct_fwd(x, w_hwio, bn_stats=False):
-    """y[B][Ho][Wo][32] = conv3x3 / 2 of the NCHW image x with w (HWIO); bn_stats: also the (partials, rows) pair conv2d_fwd
-    returns for the BatchNorm behind it."""
-    _chk(x, "image"); _chk(w_hwio, "weight")
-    B, Cin, H, W = x.shape
-    Cout = w_hwio.shape[-1]
-    Ho, Wo = conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1)
-    L = _native.lib()
-    y = torch.empty((B, Ho, Wo, Cout), dtype=F32, device=x.device)
-    part, rows = None, 0
-    if bn_stats:
-        rows = L.scouter_stem_direct_partial_rows(B, H)
-        part = torch.empty((rows, Cout, 2), dtype=torch.float64, device=x.device)
-    _native.check(L.scouter_stem_direct_fwd_f32(_p(x), _p(w_hwio), _p(y), _p(part), B, H, W, Cout, _stream()), "stem_direct_fwd")
-    return (y, (part, rows)) if bn_stats else y
 
 
 def stem_dgrad(dy, w_hwio, x_shape, k, stride, pad):

@@ -40,9 +40,9 @@ ConvRoute = namedtuple("ConvRoute", "fwd dgrad wgrad split_fwd split_dgrad plane
 # What Conv2d.fwd saves for bwd: the input (its shape only when the producer wrote planes only), the input-gradient weight
 # planes, the operand planes of the input.
 ConvCtx = namedtuple("ConvCtx", "x wd xp")
-# What StemConv2d.fwd saves: the NCHW image (image=True: the direct forward) or its patch rows, and the image's shape (the
-# input gradient's; the patch rows no longer have it).
-StemCtx = namedtuple("StemCtx", "x image shape")
+# What StemConv2d.fwd saves: the image's patch rows, and the image's shape (the input gradient's; the patch rows no longer
+# have it).
+StemCtx = namedtuple("StemCtx", "x shape")
 
 
 # The INFERENCE variant (SlotModel.set_inference_fold: every BatchNorm folded into the convolution in front of it, so each
@@ -341,8 +341,7 @@ class StemConv2d(Conv2d):
     """First convolution of the network (Cin = 1 or 3, NCHW image in): im2col into [M][Kpad] rows (zero padded to a
     multiple of 32) + the generic MFMA GEMM, for the forward and the weight gradient.  The input gradient (bwd(need_dx=True):
     d output / d image, NCHW fp32 -- what attribution maps read) is one direct fp32 kernel, kernels.stem_dgrad, whatever the
-    precision and the forward route.
-    SCOUTER_STEM_DIRECT=1 (opt-in, kernels.STEM_DIRECT): the deep stem's 3 -> 32 layer runs its forward as one direct pass."""
+    precision."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding):
         nn.Module.__init__(self)
@@ -378,18 +377,11 @@ class StemConv2d(Conv2d):
         if x_nchw.dim() != 4 or x_nchw.shape[1] != self.in_channels:
             raise RuntimeError("expected an NCHW image batch with %d channel(s), got shape %s"
                                % (self.in_channels, tuple(x_nchw.shape)))
-        if (K.STEM_DIRECT and self.precision == "fp32" and not relu and addend is None and x_nchw.dtype == torch.float32 and
-                K.stem_direct_eligible(self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
-                                       x_nchw.shape[3])):
-            # deep stem (3 -> 32, 3x3 / 2), SCOUTER_STEM_DIRECT=1: one direct pass over the image, no patch rows; the weight
-            # gradient builds its patch rows itself, on its side stream (bwd)
-            y = K.stem_direct_fwd(x_nchw, K.hwio(self.weight), bn_stats)
-            return y, (StemCtx(x_nchw, True, tuple(x_nchw.shape)) if save else None)
         col = K.im2col_nchw(x_nchw, self.kernel_size, self.stride, self.padding, self.kpad)
         wflat = K.hwio(self.weight).reshape(-1)
         wpad = K.pad_rows(wflat, wflat.numel(), self.kpad * self.out_channels).view(1, 1, self.kpad, self.out_channels)
         y = K.conv2d_fwd(col, wpad, None, addend, 1, 0, 1, relu, bn_stats, precision=self.precision)
-        return y, (StemCtx(col, False, tuple(x_nchw.shape)) if save else None)
+        return y, (StemCtx(col, tuple(x_nchw.shape)) if save else None)
 
     def bwd(self, dy, ctx, need_dx=False, addend=None):
         """need_dx: returns the gradient of the image (NCHW fp32), computed on the compute stream ahead of the weight
@@ -401,9 +393,8 @@ class StemConv2d(Conv2d):
             dx = K.stem_dgrad(dy, K.hwio(self.weight), ctx.shape, self.kernel_size, self.stride, self.padding)
         if self._dw is not None:
             with K.side_stream(dy.device, ctx.x, dy, enabled=self.use_side_stream):
-                rows = K.im2col_nchw(ctx.x, self.kernel_size, self.stride, self.padding, self.kpad) if ctx.image else ctx.x
                 dwpad = torch.empty((1, 1, self.kpad, self.out_channels), dtype=torch.float32, device=dy.device)
-                K.conv2d_wgrad(rows, dy, dwpad, precision=self.precision)
+                K.conv2d_wgrad(ctx.x, dy, dwpad, precision=self.precision)
                 n = self.kdim * self.out_channels
                 K.axpby(dwpad.view(-1)[:n], None, 1.0, 0.0, out=self._dw.reshape(-1))
         return dx

@@ -1,6 +1,6 @@
-"""Gradient with respect to the input image (-m gpu): the stem input-gradient kernel against fp64, `x.grad` of the whole
-model against the CPU oracle with `images` as a leaf (train mode, frozen stages, eval mode with nothing trainable, the FC
-baseline), and the attribution tools on top of it (tools/attribution.py, test.py --grad true).
+"""Gradient with respect to the input image (-m gpu): the stem input-gradient kernel (and the stem layer's weight gradient)
+against fp64, `x.grad` of the whole model against the CPU oracle with `images` as a leaf (train mode, frozen stages, eval mode
+with nothing trainable, the FC baseline), and the attribution tools on top of it (tools/attribution.py, test.py --grad true).
 
 Model gradients are held to the project's per-tensor rule (tests/test_model_gpu.py pinned_gradient_check), with x.grad as
 one more tensor: the oracle's fp64 and fp32 autograd run under the sign pattern and max-pool windows the HIP forward
@@ -169,6 +169,38 @@ def test_stem_dgrad_rejects_unsupported_shapes(bad):
                        (2, 1, 28, 28), 3, 2, 1)
     ref = torch.nn.grad.conv2d_input((2, 1, 28, 28), w.double(), dy.double(), stride=2, padding=1)
     assert float((out.cpu().double() - ref).abs().max()) <= 2e-5 * math.sqrt(64 * 9) + 1e-5 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("shape", [(4, 64, 64), (3, 45, 51)])
+def test_stem_layer_weight_gradient_against_fp64(shape):
+    """nn_hip.StemConv2d (the deep stem's 3 -> 32 layer; the second shape has an odd height and width): the weight gradient
+    -- the saved patch rows through the generic weight-gradient kernel -- against fp64 autograd, 2e-5 x max(1, max|g|), and bit
+    for bit the same on its side stream and on the compute stream."""
+    from scouter_amd import kernels as K
+    from scouter_amd import nn_hip
+    B, H, W = shape
+    torch.manual_seed(11)
+    m = nn_hip.StemConv2d(3, 32, 3, 2, 1).cuda()
+    x = torch.randn(B, 3, H, W, device="cuda")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    dy = torch.randn(B, Ho, Wo, 32, device="cuda")
+    dw = {}
+    for side in (True, False):
+        m.use_side_stream = side
+        m._dw = torch.zeros(3, 3, 3, 32, device="cuda")
+        _, ctx = m.fwd(x, True, bn_stats=True)
+        assert tuple(ctx.shape) == (B, 3, H, W) and tuple(ctx.x.shape) == (B, Ho, Wo, m.kpad)
+        m.bwd(dy, ctx)
+        K.join_side_stream(x.device)
+        torch.cuda.synchronize()
+        dw[side] = m._dw.clone()
+    assert torch.equal(dw[True], dw[False])
+    wd = m.weight.detach().double().requires_grad_()
+    g, = torch.autograd.grad(torch.nn.functional.conv2d(x.double(), wd, None, 2, 1), wd, dy.double().permute(0, 3, 1, 2))
+    got = dw[True].double().permute(3, 2, 0, 1)                                           # HWIO -> OIHW
+    err = float((got - g).abs().max())
+    print("stem layer dW", shape, "max err %.3e (max|g| %.3e)" % (err, float(g.abs().max())))
+    assert err <= 2e-5 * max(1.0, float(g.abs().max()))
 
 
 # ------------------------------------------------------------------------------------------------------ 2: train mode
