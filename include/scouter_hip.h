@@ -187,6 +187,24 @@ int scouter_pad_rows_f32(const float* w, float* wpad, long nvalid, long ntotal, 
 int scouter_stem_dgrad_f32(const float* dy, const float* w, float* dx, int B, int Cin, int H, int W, int Cout, int k, int stride,
                            int pad, void* stream);
 
+/* ---- Grad-CAM at the backbone's output (reference captum_vis.py: LayerGradCam(model, layer=model.layer4) with
+ * relu_attributions=False; sloter/utils/grad_cam.py).  feat / dfeat NHWC fp32 [B][N = h*w][C], 16-byte aligned:
+ * wbar[b][c] = (1/N) sum_p dfeat[b][p][c], out[b * out_stride + p] = sum_c wbar[b][c] * feat[b][p][c] (relu != 0: clamped at
+ * 0) -- out is fp32 [B][N] written through a batch stride in elements, e.g. one column of a [B][K][N] tensor.  One workgroup
+ * per image, the channel means in LDS, each input read once, one fixed summation order per element and no atomics:
+ * bit-identical run to run.  Any N >= 1 and 1 <= C <= 8192.  A null or misaligned pointer, B, N or C below 1, or a batch
+ * stride below N: SC_ERR_ARG; C above 8192 or an image past 32-bit offsets: SC_ERR_UNSUPPORTED; nothing is launched then. */
+int scouter_gradcam_f32(const float* feat, const float* dfeat, float* out, int B, int N, int C, long out_stride, int relu,
+                        void* stream);
+/* The heat map the reference draws from an attribution (captum_vis.py:51-59, show_cam_on_image), for M maps in one launch:
+ * cam fp32 [M][h][w] -> out uint8 [M][H][W].  Per map: bilinear resize to H x W (F.interpolate align_corners=False:
+ * src = (dst + 0.5) * in / out - 0.5 clamped at 0, i0 = floor(src), i1 = min(i0 + 1, in - 1)), max(., 0), min-max scaling to
+ * [0, 1], max(., min_level), min-max scaling again, uint8(255 * v) truncating.  A map that is constant at either scaling step
+ * (where the reference divides 0 / 0) is all zeros.  One workgroup per map with the source in LDS (h * w <= 32768); the
+ * resized float map is recomputed, never stored.  Up- and down-sampling. */
+int scouter_cam_maps_u8(const float* cam, unsigned char* out, int M, int h, int w, int H, int W, float min_level,
+                        void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

@@ -1655,3 +1655,44 @@ def resize_normalize(images_u8, out_size, lut, out=None):
         _p(meta), _p(hw32), _p(tmp), _p(meta[B:]), _p(lut), _p(out), B, C, max(hs), max(ws), out_size, out_size,
         _stream()), "resize_normalize")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Grad-CAM (csrc/gradcam.hip; tools/attribution.py gradcam / gradcam_maps)
+# ---------------------------------------------------------------------------------------------------------------
+def gradcam(feat, dfeat, out, relu=False):
+    """out[b, p] = sum_c mean_p'(dfeat[b, p', c]) * feat[b, p, c] (relu: clamped at 0) for NHWC fp32 feat / dfeat [B, h, w, C].
+    `out` is fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride: a column `t[:, k]` of a [B, K, h, w] tensor
+    is filled in place.  One launch, one fixed summation order per element (two calls give the same bits)."""
+    _chk(feat, "gradcam: feat"); _chk(dfeat, "gradcam: dfeat")
+    if feat.dim() != 4 or dfeat.shape != feat.shape:
+        raise RuntimeError("gradcam: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
+                           % (tuple(feat.shape), tuple(dfeat.shape)))
+    B, h, w, C = feat.shape
+    N = h * w
+    if not out.is_cuda or out.dtype != F32 or out.dim() not in (2, 3) or out.shape[0] != B or out[0].numel() != N or \
+            (N > 0 and not out[0].is_contiguous()):
+        raise RuntimeError("gradcam: out must be fp32 [B, h, w] or [B, h * w] on the device, dense within an image (got %s %s, "
+                           "strides %s)" % (out.dtype, tuple(out.shape), out.stride()))
+    _native.check(_native.lib().scouter_gradcam_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(relu)),
+                                                    _stream()), "gradcam")
+    return out
+
+
+def cam_maps(cam, H, W, min_level=0.0):
+    """fp32 maps [..., h, w] -> uint8 [..., H, W] on the device, each map on its own: bilinear resize (align_corners=False),
+    negative values cut to 0, min-max scaled to [0, 1], raised to at least `min_level`, min-max scaled again, times 255
+    (truncated) -- the reference's heat map (captum_vis.py:51-59).  A map that is constant at either scaling is all zeros.
+    One launch; the resized float map is never stored."""
+    _chk(cam, "cam_maps: cam")
+    if cam.dim() < 2:
+        raise RuntimeError("cam_maps: cam must be [..., h, w], got shape %s" % (tuple(cam.shape),))
+    h, w = cam.shape[-2:]
+    lead = tuple(cam.shape[:-2])
+    M = 1
+    for n in lead:
+        M *= n
+    out = torch.empty(lead + (int(H), int(W)), dtype=torch.uint8, device=cam.device)
+    _native.check(_native.lib().scouter_cam_maps_u8(_p(cam), _p(out), M, h, w, int(H), int(W), float(min_level), _stream()),
+                  "cam_maps")
+    return out

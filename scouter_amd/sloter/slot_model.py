@@ -71,6 +71,32 @@ class _FusedStep(torch.autograd.Function):
         return None, None, dx, None
 
 
+class FeaturePass:
+    """What SlotModel.feature_pass returns: the backbone's output, the model's output and the head's backward from one to
+    the other."""
+
+    def __init__(self, model, features, log_probs, hstate):
+        self.features, self.log_probs = features, log_probs
+        self._model, self._hstate = model, hstate
+
+    @torch.no_grad()
+    def grad(self, seed):
+        """seed: fp32 [B, classes] on the device -> d(sum seed * log_probs) / d features, NHWC fp32 [B, h, w, channel]: one
+        head backward (SlotModel._head_backward), nothing of the backbone.  Head parameters that require grad get their
+        `.grad` overwritten, as in any backward of the model; the backbone's parameter gradients are not touched."""
+        m, logp = self._model, self.log_probs
+        if not torch.is_tensor(seed) or seed.shape != logp.shape or seed.dtype != torch.float32 or seed.device != logp.device:
+            raise ValueError("seed must be an fp32 tensor of shape %s on %s" % (tuple(logp.shape), logp.device))
+        arena = m.grad_arena()
+        dfeat = m._head_backward(self._hstate, seed.contiguous(), None, None, None, need_dfeat=True, post=None)
+        K.join_side_stream(dfeat.device)                     # (the head's parameter gradients ran on the side stream)
+        head = "backbone.fc." if not m.use_slot else None
+        for name, p, _, _ in arena.entries:
+            if name.startswith(head) if head else not name.startswith("backbone."):
+                p.grad = arena.views[name]
+        return dfeat
+
+
 class SlotModel(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -334,6 +360,14 @@ class SlotModel(nn.Module):
         if x.dtype != torch.float32:
             x = x.float()
         tracked = []
+        feat, bctx = self._backbone_forward(x, save, tracked)                 # NHWC [B, h, w, channel]
+        logp, stats, hstate = self._head_forward(feat, target, save)
+        if tracked:
+            self._bump_tracked(tracked)                                       # BatchNorm num_batches_tracked
+        return logp, stats, ((bctx, hstate) if save else None)
+
+    def _backbone_forward(self, x, save, tracked):
+        """This step's weight planes, then the layer-by-layer backbone forward -> (NHWC features, backbone state)."""
         items = self._split_items(save)
         if items:      # this step's weight planes of every plane convolution: one launch into persistent buffers ...
             # ... on its own stream NEXT TO the stem's kernels (the stem reads no planes; MFMA-bound next to a byte-moving
@@ -349,11 +383,38 @@ class SlotModel(nn.Module):
                                            items[0][0]._nplanes() or 3)
             for (c, f, d), o in zip(items, outs):
                 c._wsplit = o
-        feat, bctx = self.backbone.features_fwd(x, save, tracked)             # NHWC [B, h, w, channel]
-        logp, stats, hstate = self._head_forward(feat, target, save)
-        if tracked:
-            self._bump_tracked(tracked)                                       # BatchNorm num_batches_tracked
-        return logp, stats, ((bctx, hstate) if save else None)
+        return self.backbone.features_fwd(x, save, tracked)
+
+    def feature_pass(self, x):
+        """One eval-mode forward that keeps the backbone's output and the head's state: what a class activation map needs
+        (tools/attribution.py gradcam).  Returns a FeaturePass: `.log_probs` [B, classes], `.features` (NHWC fp32
+        [B, h, w, channel]) and `.grad(seed)` = d(sum seed * log_probs) / d features, any number of times.
+        The model runs in eval mode (no BatchNorm buffer or counter moves; the caller's mode is restored); the backbone runs
+        folded when set_inference_fold is on and layer by layer otherwise, and saves nothing either way -- the gradient never
+        walks into it.  Works with use_slot on and off."""
+        if not x.is_cuda:
+            raise RuntimeError("scouter_amd.SlotModel runs on a HIP device (got a %s tensor); there is no CPU fallback" % x.device)
+        if x.dim() != 4:
+            raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(x.shape),))
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad():
+                x = x.detach().contiguous()
+                if x.dtype != torch.float32:
+                    x = x.float()
+                if self.inference_fold:
+                    if self._fold_stale or self._folder is None:
+                        self._refold()
+                    feat = self.backbone.features_fwd_folded(x)
+                else:
+                    feat, _ = self._backbone_forward(x, False, [])
+                logp, _, hstate = self._head_forward(feat, None, True)
+        finally:
+            if was_training:
+                self.train(True)
+        return FeaturePass(self, feat, logp, hstate)
 
     def loss_seed(self, loss):
         """A cached tensor of ones shaped like the scalar loss: `loss.backward(model.loss_seed(loss))` spares autograd the

@@ -3,13 +3,15 @@ sloter/utils/slot_attention.py:68-85): eval-mode forward of ONE image on the HIP
 maps written as `<out>/slot_{c}.png`, the input as `<out>/image.png`, and (optionally) the attention-area ratio the
 reference prints with --cal_area_size (test.py:40-44).  `--grad true` adds the per-class gradient attribution maps
 `<out>/grad_{c}.png` (d log-probability / d image through tools/attribution.py, floored at --grad_min_level; also for the
-`--use_slot false` baseline, the model the reference attributes).  The jet-colormap overlay of test.py:33-38 is matplotlib
+`--use_slot false` baseline, the model the reference attributes); `--cam true` the per-class Grad-CAM heat maps at the last
+backbone stage, `<out>/cam_{c}.png` (tools/attribution.py gradcam_maps: one backbone forward, floored at --grad_min_level,
+BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4).  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
-        [--grad true --grad_min_level 0.1]"""
+        [--grad true --grad_min_level 0.1] [--cam true]"""
 import argparse
 import os
 
@@ -17,7 +19,7 @@ import numpy as np
 import torch
 
 from .sloter.slot_model import SlotModel
-from .train import checkpoint_name, get_args_parser
+from .train import _flag, checkpoint_name, get_args_parser
 
 
 def load_image(path, size, channels):
@@ -65,6 +67,19 @@ def run_grad(args, model, image, out_dir):
     return maps
 
 
+def run_cam(args, model, image, out_dir):
+    """--cam true: the Grad-CAM heat map of every class for the one image at the backbone's output (reference captum_vis.py
+    LayerGradCam on layer4) -> `<out>/cam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import gradcam_maps
+    os.makedirs(out_dir, exist_ok=True)
+    maps = gradcam_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
+                        min_level=float(args.grad_min_level))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "cam_%d.png" % c))
+    return maps
+
+
 def main():
     parser = argparse.ArgumentParser("single-image xSlot inference", parents=[get_args_parser()])
     parser.add_argument("--checkpoint", default="", help="checkpoint written by train.py (default: the standard name "
@@ -72,6 +87,8 @@ def main():
     parser.add_argument("--image", default="", help="image file; a seeded synthetic image is used when empty")
     parser.add_argument("--label", default=None, type=int)
     parser.add_argument("--vis_dir", default="sloter/vis")
+    parser.add_argument("--cam", default=False, type=_flag,
+                        help="true: write the Grad-CAM heat map of every class as cam_{c}.png into --vis_dir")
     args = parser.parse_args()
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
@@ -96,6 +113,8 @@ def main():
     out, pred, maps, ratio = run(args, model, image, args.vis_dir, args.label)
     if want_grad:
         run_grad(args, model, image, args.vis_dir)
+    if args.cam:
+        run_cam(args, model, image, args.vis_dir)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:

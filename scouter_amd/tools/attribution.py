@@ -2,9 +2,16 @@
 reference gives every attribution map before it is drawn (`attribution_maps`; reference captum_vis.py:49-59, train.py
 --grad / --grad_min_level).  The gradient comes from SlotModel's own backward, which walks on to the image when the input
 requires grad (ResNet.features_bwd need_input_grad, kernels.stem_dgrad); saliency is this gradient as it is, integrated
-gradients / SmoothGrad / adversarial perturbations are loops over it."""
+gradients / SmoothGrad / adversarial perturbations are loops over it.
+
+Class activation maps at the backbone's output (`gradcam`, `gradcam_maps`): what the reference draws for its FC baseline with
+captum's LayerGradCam(model, layer=model.layer4) (captum_vis.py, sloter/utils/grad_cam.py) and compares the slot maps with.
+One backbone forward per batch (SlotModel.feature_pass), one head backward per class, the channel-mean weighting and the
+uint8 heat maps in two HIP kernels (kernels.gradcam, kernels.cam_maps) -- nothing walks into the backbone."""
 import numpy as np
 import torch
+
+from .. import kernels as K
 
 
 def input_gradients(model, images, classes=None, of="log_prob", target=None):
@@ -74,3 +81,56 @@ def _minmax(m):
     lo = m.min(axis=(2, 3), keepdims=True)
     span = m.max(axis=(2, 3), keepdims=True) - lo
     return np.where(span > 0, (m - lo) / np.where(span > 0, span, 1.0), 0.0)
+
+
+def gradcam(model, images, classes=None, relu=False):
+    """Grad-CAM of `images` [B, C, H, W] at the backbone's output -> fp32 [B, K, h, w] on the images' device:
+    cam[b, k, p] = sum_c mean_p'(d out_k / d features[b, p', c]) * features[b, p, c], captum's LayerGradCam with
+    relu_attributions=False (`relu`: clamped at 0).
+
+    classes=None: every class, K = the number of outputs; a list of ints: K = len(classes), slice [:, k] belongs to the
+    log-probability of classes[k] (one head backward each, with a one-hot column as its seed); a LongTensor [B]: every image
+    its own class, one backward, K = 1.  One SlotModel.feature_pass for the batch -- eval mode, the caller's mode restored,
+    BatchNorm-folded when the model's inference fold is on; head parameters that require grad get their `.grad` overwritten
+    by each backward.  One feature gradient is alive at a time."""
+    if images.dim() != 4:
+        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    B, n = images.shape[0], _num_classes(model, images)
+    per_image = torch.is_tensor(classes)
+    if per_image:
+        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
+                             % (B, classes.dtype, tuple(classes.shape)))
+        cols = classes.detach().cpu().tolist()
+    else:
+        cols = [int(c) for c in (classes if classes is not None else range(n))]
+    for c in cols:
+        if not 0 <= c < n:
+            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    fp = model.feature_pass(images)
+    feat = fp.features
+    _, h, w, _ = feat.shape
+    seed = torch.zeros_like(fp.log_probs)
+    if per_image:
+        seed[torch.arange(B, device=seed.device), classes.to(seed.device)] = 1.0
+        seeds = [None]
+    else:
+        seeds = cols
+    cam = torch.empty((B, len(seeds), h, w), dtype=torch.float32, device=feat.device)
+    for k, c in enumerate(seeds):
+        if c is not None:
+            seed.zero_()
+            seed[:, c] = 1.0
+        dfeat = fp.grad(seed)
+        K.gradcam(feat, dfeat, cam[:, k], relu=relu)
+        del dfeat
+    return cam
+
+
+def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
+    """uint8 Grad-CAM heat maps [B, K, H, W] on the device: `gradcam`, then per map the reference's drawing steps in one
+    launch (kernels.cam_maps; captum_vis.py:51-59) -- bilinear resize to `size` = (H, W) (None: the images' H x W), negative
+    values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled again, times 255.  A map that is constant at
+    either scaling step is all zeros, like attribution_maps."""
+    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    return K.cam_maps(gradcam(model, images, classes), H, W, min_level)
