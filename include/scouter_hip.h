@@ -205,6 +205,29 @@ int scouter_gradcam_f32(const float* feat, const float* dfeat, float* out, int B
 int scouter_cam_maps_u8(const float* cam, unsigned char* out, int M, int h, int w, int H, int W, float min_level,
                         void* stream);
 
+/* ---- RISE (Petsiuk et al. 2018; reference torchcam_vis.py: torchray.attribution.rise): saliency from N random masks.
+ * Mask n is a grid of bytes in {0, 1}, grids u8 [N][s][s], and a shift, shifts i32 [N][2] = (dy, dx).  With
+ * cell = ceil(size / s) and U = (s + 1) * cell per axis, mask_n(y, x) is the bilinear upsampling of the grid to U_h x U_w
+ * (F.interpolate align_corners=False, the convention of scouter_cam_maps_u8) read at (y + dy, x + dx), 0 <= dy < cell_h,
+ * 0 <= dx < cell_w.  Both calls form it by the same expression and never store it; every index is clamped, so a shift outside
+ * its range (the callers check it on the host) reads nothing outside the grid.  1 <= s <= 16 and s <= min(H, W), else
+ * SC_ERR_ARG, like a null or misaligned pointer or a count below 1; nothing is launched then.
+ * out fp32 [N][C][H][W] = image [C][H][W] * mask_n, the mask value formed once per pixel for all C channels; 16-byte accesses
+ * when W is a multiple of 4 and image / out are 16-byte aligned, one pixel per thread otherwise.  Any N >= 1. */
+int scouter_rise_mask_images_f32(const float* image, const unsigned char* grids, const int* shifts, float* out, int N, int C,
+                                 int H, int W, int s, void* stream);
+/* acc fp32 [K][H][W] += sum_n (scale * expf(logp[n][cols[k]])) * mask_n(y, x), logp fp32 [N][n_classes], cols i32 [K] in
+ * [0, n_classes) (checked by the caller; clamped here).  Every output element belongs to one thread, which starts from the
+ * value in acc and adds the N terms one fma at a time in n order: no atomics, no partial sums -- splitting the masks over
+ * several calls at any point gives the bits of one call.  Any N >= 1 (staged through LDS in pieces), any K >= 1. */
+int scouter_rise_accumulate_f32(const float* logp, const int* cols, const unsigned char* grids, const int* shifts, float* acc,
+                                int N, int n_classes, int K, int H, int W, int s, float scale, void* stream);
+/* The drawing steps of scouter_cam_maps_u8 without the resize, for maps of any size H * W < 2^31: maps fp32 [M][H][W] -> out
+ * uint8 [M][H][W]; per map max(., 0), min-max scaling, max(., min_level), min-max scaling again, uint8(255 * v) truncating; a
+ * map constant at either step is all zeros.  One workgroup per map, two passes over it.  The same bytes as
+ * scouter_cam_maps_u8 with H x W = h x w. */
+int scouter_heat_maps_u8(const float* maps, unsigned char* out, int M, int H, int W, float min_level, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

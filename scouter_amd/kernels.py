@@ -1696,3 +1696,75 @@ def cam_maps(cam, H, W, min_level=0.0):
     _native.check(_native.lib().scouter_cam_maps_u8(_p(cam), _p(out), M, h, w, int(H), int(W), float(min_level), _stream()),
                   "cam_maps")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# RISE (csrc/rise.hip; tools/attribution.py rise / rise_maps)
+# ---------------------------------------------------------------------------------------------------------------
+def _rise_masks_chk(what, grids, shifts, H, W, s, check_shifts):
+    """grids u8 [N, s, s] and shifts i32 [N, 2] of one call -> N.  check_shifts: every shift lies in [0, cell) -- read on the
+    host (a copy and a synchronisation; callers that drew the shifts themselves, like tools/attribution.py rise, pass False)."""
+    _chk(grids, what + ": grids", torch.uint8); _chk(shifts, what + ": shifts", torch.int32)
+    s = int(s)
+    if grids.dim() != 3 or tuple(grids.shape[1:]) != (s, s) or tuple(shifts.shape) != (grids.shape[0], 2):
+        raise RuntimeError("%s: grids must be uint8 [N, s = %d, s] and shifts int32 [N, 2] (got %s and %s)"
+                           % (what, s, tuple(grids.shape), tuple(shifts.shape)))
+    if check_shifts and s >= 1 and shifts.numel():
+        cell = torch.tensor([-(-int(H) // s), -(-int(W) // s)], dtype=torch.int32)
+        sh = shifts.cpu()
+        if bool((sh < 0).any()) or bool((sh >= cell).any()):
+            raise RuntimeError("%s: a shift lies outside [0, cell) = [0, %d) x [0, %d)" % (what, int(cell[0]), int(cell[1])))
+    return int(grids.shape[0])
+
+
+def rise_mask_images(image, grids, shifts, out, s, check_shifts=True):
+    """out[n, c] = image[c] * mask_n for fp32 image [C, H, W], grids uint8 [N, s, s] in {0, 1}, shifts int32 [N, 2] and fp32 out
+    [N, C, H, W] (a dense leading slice of a longer buffer is fine).  mask_n: the bilinear upsampling of grid n to
+    (s + 1) * ceil(size / s) per axis (align_corners=False) read from the shift on; formed in registers, never stored.
+    One launch."""
+    _chk(image, "rise_mask_images: image"); _chk(out, "rise_mask_images: out")
+    if image.dim() != 3:
+        raise RuntimeError("rise_mask_images: image must be [C, H, W], got shape %s" % (tuple(image.shape),))
+    C, H, W = image.shape
+    N = _rise_masks_chk("rise_mask_images", grids, shifts, H, W, s, check_shifts)
+    if tuple(out.shape) != (N, C, H, W):
+        raise RuntimeError("rise_mask_images: out must be [N = %d, %d, %d, %d], got shape %s" % (N, C, H, W, tuple(out.shape)))
+    _native.check(_native.lib().scouter_rise_mask_images_f32(_p(image), _p(grids), _p(shifts), _p(out), N, C, H, W, int(s),
+                                                             _stream()), "rise_mask_images")
+    return out
+
+
+def rise_accumulate(logp, cols, grids, shifts, acc, s, scale, check_shifts=True):
+    """acc[k] += sum_n scale * exp(logp[n, cols[k]]) * mask_n for fp32 logp [N, n_classes], cols int32 [K] on the device (the
+    caller keeps them inside [0, n_classes)), the masks of rise_mask_images and fp32 acc [K, H, W].  One thread per element
+    adds the N terms in n order onto the value in acc: calls over consecutive pieces of the masks give the bits of one call.
+    One launch; nothing is read on the host unless check_shifts."""
+    _chk(logp, "rise_accumulate: logp"); _chk(cols, "rise_accumulate: cols", torch.int32); _chk(acc, "rise_accumulate: acc")
+    if logp.dim() != 2 or cols.dim() != 1 or acc.dim() != 3 or acc.shape[0] != cols.shape[0]:
+        raise RuntimeError("rise_accumulate: logp must be [N, n_classes], cols [K] and acc [K, H, W] (got %s, %s and %s)"
+                           % (tuple(logp.shape), tuple(cols.shape), tuple(acc.shape)))
+    K, H, W = acc.shape
+    N = _rise_masks_chk("rise_accumulate", grids, shifts, H, W, s, check_shifts)
+    if logp.shape[0] != N:
+        raise RuntimeError("rise_accumulate: logp has %d rows for %d masks" % (logp.shape[0], N))
+    _native.check(_native.lib().scouter_rise_accumulate_f32(_p(logp), _p(cols), _p(grids), _p(shifts), _p(acc), N,
+                                                            int(logp.shape[1]), K, H, W, int(s), float(scale), _stream()),
+                  "rise_accumulate")
+    return acc
+
+
+def heat_maps(maps, min_level=0.0):
+    """fp32 maps [..., H, W] -> uint8 [..., H, W] on the device, each map on its own: cam_maps' drawing steps without the resize
+    (negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled again, times 255, truncated) for
+    maps of any size; the bytes of cam_maps(maps, H, W, min_level) where that takes the map.  One launch."""
+    _chk(maps, "heat_maps: maps")
+    if maps.dim() < 2:
+        raise RuntimeError("heat_maps: maps must be [..., H, W], got shape %s" % (tuple(maps.shape),))
+    H, W = maps.shape[-2:]
+    lead = tuple(maps.shape[:-2])
+    M = 1
+    for n in lead:
+        M *= n
+    out = torch.empty(tuple(maps.shape), dtype=torch.uint8, device=maps.device)
+    _native.check(_native.lib().scouter_heat_maps_u8(_p(maps), _p(out), M, H, W, float(min_level), _stream()), "heat_maps")
+    return out

@@ -5,13 +5,16 @@ reference prints with --cal_area_size (test.py:40-44).  `--grad true` adds the p
 `<out>/grad_{c}.png` (d log-probability / d image through tools/attribution.py, floored at --grad_min_level; also for the
 `--use_slot false` baseline, the model the reference attributes); `--cam true` the per-class Grad-CAM heat maps at the last
 backbone stage, `<out>/cam_{c}.png` (tools/attribution.py gradcam_maps: one backbone forward, floored at --grad_min_level,
-BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4).  The jet-colormap overlay of test.py:33-38 is matplotlib
+BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4); `--rise true` the per-class
+RISE perturbation maps `<out>/rise_{c}.png` (tools/attribution.py rise_maps: --rise_masks random masks through the model in
+chunks of --rise_batch, floored at --grad_min_level, BatchNorm-folded under --eval_fold; what the reference's torchcam_vis.py
+draws with torchray's rise).  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
-        [--grad true --grad_min_level 0.1] [--cam true]"""
+        [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250]"""
 import argparse
 import os
 
@@ -80,6 +83,19 @@ def run_cam(args, model, image, out_dir):
     return maps
 
 
+def run_rise(args, model, image, out_dir):
+    """--rise true: the RISE saliency map of every class for the one image (reference torchcam_vis.py, torchray.attribution.rise)
+    -> `<out>/rise_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import rise_maps
+    os.makedirs(out_dir, exist_ok=True)
+    maps = rise_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level),
+                     n_masks=int(getattr(args, "rise_masks", 4000)), batch=int(getattr(args, "rise_batch", 250)))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "rise_%d.png" % c))
+    return maps
+
+
 def main():
     parser = argparse.ArgumentParser("single-image xSlot inference", parents=[get_args_parser()])
     parser.add_argument("--checkpoint", default="", help="checkpoint written by train.py (default: the standard name "
@@ -89,6 +105,10 @@ def main():
     parser.add_argument("--vis_dir", default="sloter/vis")
     parser.add_argument("--cam", default=False, type=_flag,
                         help="true: write the Grad-CAM heat map of every class as cam_{c}.png into --vis_dir")
+    parser.add_argument("--rise", default=False, type=_flag,
+                        help="true: write the RISE saliency map of every class as rise_{c}.png into --vis_dir")
+    parser.add_argument("--rise_masks", default=4000, type=int, help="number of random masks of --rise")
+    parser.add_argument("--rise_batch", default=250, type=int, help="masked images per forward of --rise")
     args = parser.parse_args()
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
@@ -115,6 +135,8 @@ def main():
         run_grad(args, model, image, args.vis_dir)
     if args.cam:
         run_cam(args, model, image, args.vis_dir)
+    if args.rise:
+        run_rise(args, model, image, args.vis_dir)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:

@@ -7,7 +7,16 @@ gradients / SmoothGrad / adversarial perturbations are loops over it.
 Class activation maps at the backbone's output (`gradcam`, `gradcam_maps`): what the reference draws for its FC baseline with
 captum's LayerGradCam(model, layer=model.layer4) (captum_vis.py, sloter/utils/grad_cam.py) and compares the slot maps with.
 One backbone forward per batch (SlotModel.feature_pass), one head backward per class, the channel-mean weighting and the
-uint8 heat maps in two HIP kernels (kernels.gradcam, kernels.cam_maps) -- nothing walks into the backbone."""
+uint8 heat maps in two HIP kernels (kernels.gradcam, kernels.cam_maps) -- nothing walks into the backbone.
+
+Perturbation maps (`rise_masks`, `rise`, `rise_maps`): RISE (Petsiuk et al. 2018), what the reference's torchcam_vis.py draws
+with torchray.attribution.rise.  The image is multiplied by thousands of smooth random masks, every masked image goes through
+the model, and every mask is weighted by the class probabilities it produced.  No gradient and no feature hook: the same call
+serves the xSlot model and the FC baseline, and its cost is eval forwards (BatchNorm-folded when the model's inference fold is
+on).  The masks exist only as s x s byte grids and shifts; the masked batch, the weighted sum and the heat maps are three HIP
+kernels (kernels.rise_mask_images, kernels.rise_accumulate, kernels.heat_maps) and nothing comes to the host in between."""
+import collections
+
 import numpy as np
 import torch
 
@@ -134,3 +143,122 @@ def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
     either scaling step is all zeros, like attribution_maps."""
     H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
     return K.cam_maps(gradcam(model, images, classes), H, W, min_level)
+
+
+RiseMasks = collections.namedtuple("RiseMasks", "grids shifts s p size cell")
+RiseMasks.__doc__ = """The draws of `rise_masks`: grids uint8 [N, s, s] in {0, 1}, shifts int32 [N, 2] = (dy, dx) with
+0 <= dy < cell[0], 0 <= dx < cell[1], the grid size s, the keep-probability p, size = (H, W) and cell = (ceil(H / s), ceil(W / s))."""
+
+
+def rise_masks(n_masks, size, s=7, p=0.5, seed=0, device=None):
+    """The N random masks of a RISE run for images of `size` = (H, W), reusable across calls: from a CPU
+    torch.Generator().manual_seed(seed), first every grid (torch.rand(N, s, s) < p), then every shift (torch.randint below the
+    cell, rows then columns), uploaded once to `device`.  Mask n is the bilinear upsampling (align_corners=False) of grid n to
+    (s + 1) * cell per axis, cropped to H x W at its shift; kernels.rise_mask_images / rise_accumulate form it on the fly."""
+    H, W = (int(v) for v in size)
+    n_masks, s, p = int(n_masks), int(s), float(p)
+    if n_masks < 1:
+        raise ValueError("n_masks must be at least 1, got %d" % n_masks)
+    if not 1 <= s <= 16 or s > min(H, W):
+        raise ValueError("the grid size must satisfy 1 <= s <= 16 and s <= min(H, W) = %d, got %d" % (min(H, W), s))
+    if not 0.0 < p < 1.0:
+        raise ValueError("the keep-probability must satisfy 0 < p < 1, got %r" % (p,))
+    cell = (-(-H // s), -(-W // s))
+    gen = torch.Generator().manual_seed(int(seed))
+    grids = (torch.rand(n_masks, s, s, generator=gen) < p).to(torch.uint8)
+    dy = torch.randint(0, cell[0], (n_masks,), generator=gen)
+    dx = torch.randint(0, cell[1], (n_masks,), generator=gen)
+    shifts = torch.stack([dy, dx], dim=1).to(torch.int32).contiguous()
+    if device is not None:
+        grids, shifts = grids.to(device), shifts.to(device)
+    return RiseMasks(grids, shifts, s, p, (H, W), cell)
+
+
+def _check_rise_masks(masks, size, device):
+    """a caller's RiseMasks record against the images of this call, once and before any launch (the one host read of the
+    shifts)"""
+    H, W = size
+    if tuple(masks.size) != (H, W):
+        raise ValueError("the masks were drawn for %s images, these are %d x %d" % (tuple(masks.size), H, W))
+    s = int(masks.s)
+    if not 1 <= s <= 16 or s > min(H, W) or not 0.0 < float(masks.p) < 1.0:
+        raise ValueError("masks: s = %r, p = %r (1 <= s <= 16, s <= min(H, W), 0 < p < 1)" % (masks.s, masks.p))
+    g, sh = masks.grids, masks.shifts
+    if g.dtype != torch.uint8 or sh.dtype != torch.int32 or g.dim() != 3 or tuple(g.shape[1:]) != (s, s) or g.shape[0] < 1 or \
+            tuple(sh.shape) != (g.shape[0], 2):
+        raise ValueError("masks: grids must be uint8 [N, %d, %d] and shifts int32 [N, 2] (got %s %s and %s %s)"
+                         % (s, s, g.dtype, tuple(g.shape), sh.dtype, tuple(sh.shape)))
+    cell = torch.tensor([-(-H // s), -(-W // s)], dtype=torch.int32)
+    shc = sh.cpu()
+    if bool((shc < 0).any()) or bool((shc >= cell).any()):
+        raise ValueError("masks: a shift lies outside [0, cell) = [0, %d) x [0, %d)" % (int(cell[0]), int(cell[1])))
+    return g.to(device).contiguous(), sh.to(device).contiguous()
+
+
+def rise(model, images, classes=None, n_masks=4000, s=7, p=0.5, batch=250, seed=0, masks=None):
+    """RISE saliency of `images` [B, C, H, W] -> fp32 [B, K, H, W] on the images' device:
+    S[b, k] = 1 / (N p) * sum_n exp(log_prob_n[classes[k]]) * mask_n, log_prob_n the eval-mode output for images[b] * mask_n.
+
+    classes as in `gradcam`: None (every class), a list of ints (K = len), or a LongTensor [B] (each image its own class,
+    K = 1).  The N = n_masks masks are `rise_masks(n_masks, (H, W), s, p, seed)` or the record given as `masks` (then n_masks,
+    s, p and seed are taken from it), the same for every image of the call.  Per image they go through the model in chunks of
+    `batch` (the last may be shorter): kernels.rise_mask_images into one reused buffer, the model under torch.no_grad() in eval
+    mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.rise_accumulate onto the
+    result in mask order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied
+    to the host and nothing synchronises inside the loop."""
+    if images.dim() != 4:
+        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    B, C, H, W = images.shape
+    n = _num_classes(model, images)
+    per_image = torch.is_tensor(classes)
+    if per_image:
+        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
+                             % (B, classes.dtype, tuple(classes.shape)))
+        cols = classes.detach().cpu().tolist()
+    else:
+        cols = [int(c) for c in (classes if classes is not None else range(n))]
+    for c in cols:
+        if not 0 <= c < n:
+            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1, got %d" % batch)
+    dev = images.device
+    if masks is None:
+        masks = rise_masks(n_masks, (H, W), s=s, p=p, seed=seed, device=dev)
+        grids, shifts = masks.grids, masks.shifts
+    else:
+        grids, shifts = _check_rise_masks(masks, (H, W), dev)
+    N, s = int(grids.shape[0]), int(masks.s)
+    scale = 1.0 / (N * float(masks.p))
+    x = images.detach().contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    out = torch.zeros((B, Kc, H, W), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for b in range(B):
+                cb = cols_dev[b:b + 1] if per_image else cols_dev
+                for n0 in range(0, N, batch):
+                    g, sh = grids[n0:n0 + batch], shifts[n0:n0 + batch]
+                    chunk = K.rise_mask_images(x[b], g, sh, buf[:g.shape[0]], s, check_shifts=False)
+                    logp = model(chunk)
+                    K.rise_accumulate(logp, cb, g, sh, out[b], s, scale, check_shifts=False)
+    finally:
+        model.train(was_training)
+    return out
+
+
+def rise_maps(model, images, classes=None, min_level=0.0, **rise_kwargs):
+    """uint8 RISE heat maps [B, K, H, W] on the device: `rise`, then per map the drawing steps of `gradcam_maps` at the maps'
+    own size (kernels.heat_maps): negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled
+    again, times 255.  A map that is constant at either scaling step is all zeros."""
+    return K.heat_maps(rise(model, images, classes, **rise_kwargs), min_level)
