@@ -228,6 +228,51 @@ int scouter_rise_accumulate_f32(const float* logp, const int* cols, const unsign
  * scouter_cam_maps_u8 with H x W = h x w. */
 int scouter_heat_maps_u8(const float* maps, unsigned char* out, int M, int H, int W, float min_level, void* stream);
 
+/* ---- Insertion / deletion scores of a saliency map (Petsiuk et al. 2018, section 4.1; the IAUC / DAUC columns of the SCOUTER
+ * paper; csrc/causal.hip, tools/attribution.py causal_metrics).  For an image x [C][H][W], a class c and a map m [H][W]: the
+ * pixels are ordered by saliency, most salient first, equal values by ascending flat index y * W + x, -0 equal to +0, a NaN
+ * less salient than every number (NaNs among themselves by index); rank[p] in [0, HW) is the position of pixel p.  `step`
+ * pixels change per point, a curve has n_points = ceil(HW / step) + 1 points and point j has the min(j * step, HW) first-ranked
+ * pixels changed: DELETION = x with the changed pixels set to 0 in every channel, INSERTION = blur(x) with the changed pixels
+ * taken from x.  p_j = exp(log_prob_j[c]); the score is the trapezoid area (p_0 / 2 + p_1 + ... + p_{n-1} + p_n / 2) / n with
+ * n = n_points - 1.  Every call has one fixed order per output element and no atomics: bit-identical run to run.  A null or
+ * misaligned (4-byte) pointer or a count below 1 is SC_ERR_ARG in every call; nothing is launched after an error.
+ *
+ * in fp32 [M][h][w] -> out fp32 [M][H][W], F.interpolate(mode = "bilinear", align_corners = False): the source coordinate of
+ * scouter_cam_maps_u8 (src = (dst + 0.5) * in / out - 0.5 clamped at 0, i0 = floor(src), i1 = min(i0 + 1, in - 1)) and three
+ * fmas for the blend; up- and down-sampling; h x w = H x W copies the map bit for bit.  M above 65535 or a map past 32-bit
+ * offsets: SC_ERR_UNSUPPORTED. */
+int scouter_resize_bilinear_f32(const float* in, float* out, int M, int h, int w, int H, int W, void* stream);
+/* maps fp32 [M][HW] -> ranks i32 [M][HW], the rank of the definition above.  One workgroup per map: a stable least-significant-
+ * digit radix sort (4-bit digits, 8 passes) of (key, index) pairs, every thread scattering a contiguous run from offsets
+ * scanned in LDS -- the same bits for the same input.  The pairs ping-pong through `ws`, at least
+ * scouter_saliency_ranks_workspace_bytes(M, HW) = 16 * M * HW bytes (less: SC_ERR_WORKSPACE).  1 <= HW <= 2^20; above:
+ * SC_ERR_UNSUPPORTED. */
+size_t scouter_saliency_ranks_workspace_bytes(int M, long HW);
+int scouter_saliency_ranks_i32(const float* maps, int* ranks, int M, long HW, void* ws, size_t ws_bytes, void* stream);
+/* x fp32 [C][H][W], taps fp32 [klen] on the device -> out fp32 [C][H][W]: the klen-tap filter along rows (into tmp fp32
+ * [C][H][W], a buffer of the caller's that is neither x nor out), then along columns; zeros outside the image; per pass klen
+ * fmas in tap order starting from 0, centre tap klen / 2.  Two launches.  klen even, below 1 or above 31, or tmp == x / out:
+ * SC_ERR_ARG; C above 65535 or a plane past 32-bit offsets: SC_ERR_UNSUPPORTED. */
+int scouter_separable_filter_f32(const float* x, const float* taps, float* tmp, float* out, int C, int H, int W, int klen,
+                                 void* stream);
+/* A chunk of the edit stream of ONE image: image / blurred fp32 [C][H][W], ranks i32 [K][HW] -> out fp32 [n][C][H][W].  Stream
+ * index g = first + i, 0 <= i < n, decodes as k = g / (2 * n_points), mode = (g / n_points) % 2 (0 deletion, 1 insertion),
+ * j = g % n_points; out[i] is that point: a select by ranks[k][p] < j * step, made once per pixel for all C channels, so every
+ * value is an exact copy (or 0).  A chunk may start and end anywhere in [0, 2 * K * n_points).  16-byte accesses when W is a
+ * multiple of 4 and all four pointers are 16-byte aligned, one pixel per thread otherwise.  n_points < 2, step < 1, n_points
+ * other than ceil(HW / step) + 1, or a chunk outside the stream: SC_ERR_ARG; an image past 32-bit offsets: SC_ERR_UNSUPPORTED. */
+int scouter_causal_step_images_f32(const float* image, const float* blurred, const int* ranks, float* out, long first, int n,
+                                   int K, int n_points, int step, int C, int H, int W, void* stream);
+/* curve_flat[first + i] = expf(logp[i][cols[(first + i) / (2 * n_points)]]) for the same chunk: logp fp32 [n][n_classes], cols
+ * i32 [K] in [0, n_classes) (checked by the caller; clamped here), curve_flat fp32 [K][2][n_points].  n_points < 2, n_classes
+ * below 1 or a chunk outside the stream: SC_ERR_ARG. */
+int scouter_causal_curve_f32(const float* logp, const int* cols, float* curve_flat, long first, int n, int K, int n_points,
+                             int n_classes, void* stream);
+/* curves fp32 [R][n_points] -> scores fp32 [R], the trapezoid area above: one thread per curve adds the points in j order, the
+ * two ends halved, and divides by n_points - 1.  n_points < 2: SC_ERR_ARG; R above 65535 * 256: SC_ERR_UNSUPPORTED. */
+int scouter_causal_auc_f32(const float* curves, float* scores, long R, int n_points, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

@@ -1768,3 +1768,120 @@ def heat_maps(maps, min_level=0.0):
     out = torch.empty(tuple(maps.shape), dtype=torch.uint8, device=maps.device)
     _native.check(_native.lib().scouter_heat_maps_u8(_p(maps), _p(out), M, H, W, float(min_level), _stream()), "heat_maps")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Insertion / deletion scores (csrc/causal.hip; tools/attribution.py causal_metrics)
+# ---------------------------------------------------------------------------------------------------------------
+def resize_bilinear(maps, H, W):
+    """fp32 maps [..., h, w] -> fp32 [..., H, W] on the device, F.interpolate(mode="bilinear", align_corners=False) per map:
+    the resize of cam_maps with the float value stored (cam_maps quantises it to 256 levels).  Up- and down-sampling; the
+    maps' own size copies them bit for bit.  One launch."""
+    _chk(maps, "resize_bilinear: maps")
+    if maps.dim() < 2:
+        raise RuntimeError("resize_bilinear: maps must be [..., h, w], got shape %s" % (tuple(maps.shape),))
+    h, w = maps.shape[-2:]
+    lead = tuple(maps.shape[:-2])
+    M = 1
+    for n in lead:
+        M *= n
+    out = torch.empty(lead + (int(H), int(W)), dtype=F32, device=maps.device)
+    _native.check(_native.lib().scouter_resize_bilinear_f32(_p(maps), _p(out), M, h, w, int(H), int(W), _stream()),
+                  "resize_bilinear")
+    return out
+
+
+def saliency_ranks(maps, out=None):
+    """fp32 maps [M, HW] (or [M, H, W]) -> int32 ranks of the same shape: rank[m, p] = the position of pixel p when the pixels of
+    map m are ordered most salient first, equal values by ascending flat index, -0.0 equal to +0.0, NaN after every number
+    (NaNs among themselves by index).  A stable radix sort, one workgroup per map: the same bits for the same input.
+    1 <= HW <= 2^20.  One launch."""
+    _chk(maps, "saliency_ranks: maps")
+    if maps.dim() not in (2, 3):
+        raise RuntimeError("saliency_ranks: maps must be [M, HW] or [M, H, W], got shape %s" % (tuple(maps.shape),))
+    M, HW = maps.shape[0], maps[0].numel() if maps.shape[0] else 0
+    if out is None:
+        out = torch.empty(tuple(maps.shape), dtype=torch.int32, device=maps.device)
+    _chk(out, "saliency_ranks: out", torch.int32)
+    if out.shape != maps.shape:
+        raise RuntimeError("saliency_ranks: out must be int32 %s, got shape %s" % (tuple(maps.shape), tuple(out.shape)))
+    lib = _native.lib()
+    nbytes = lib.scouter_saliency_ranks_workspace_bytes(M, HW)
+    ws = workspace(nbytes, maps.device)
+    _native.check(lib.scouter_saliency_ranks_i32(_p(maps), _p(out), M, HW, _p(ws), nbytes, _stream()), "saliency_ranks")
+    return out
+
+
+def separable_filter(x, taps, out=None):
+    """fp32 x [C, H, W] and fp32 taps [klen] on the device -> fp32 [C, H, W]: the taps applied along rows, then along columns,
+    zeros outside the image, klen fmas per pass in tap order (odd klen, 1 <= klen <= 31, centre tap klen // 2).  Two launches;
+    the row pass goes through the stream's workspace."""
+    _chk(x, "separable_filter: x"); _chk(taps, "separable_filter: taps")
+    if x.dim() != 3 or taps.dim() != 1:
+        raise RuntimeError("separable_filter: x must be [C, H, W] and taps [klen] (got %s and %s)"
+                           % (tuple(x.shape), tuple(taps.shape)))
+    C, H, W = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(out, "separable_filter: out")
+    if out.shape != x.shape:
+        raise RuntimeError("separable_filter: out must be %s, got shape %s" % (tuple(x.shape), tuple(out.shape)))
+    tmp = workspace(4 * x.numel(), x.device)
+    _native.check(_native.lib().scouter_separable_filter_f32(_p(x), _p(taps), _p(tmp), _p(out), C, H, W, int(taps.shape[0]),
+                                                             _stream()), "separable_filter")
+    return out
+
+
+def causal_step_images(image, blurred, ranks, out, first, n_points, step):
+    """out[i] = point first + i of the edit stream of ONE image, for fp32 image / blurred [C, H, W], int32 ranks [K, H * W] (or
+    [K, H, W]) and fp32 out [n, C, H, W] (a dense leading slice of a longer buffer is fine).  Stream index g decodes as map
+    k = g // (2 * n_points), mode = (g // n_points) % 2 (0 deletion, 1 insertion), point j = g % n_points with
+    n_points = ceil(H * W / step) + 1: the pixels with ranks[k] < j * step are 0 (deletion: the rest is the image) or the
+    image's (insertion: the rest is `blurred`).  A select, so every value is an exact copy.  One launch."""
+    _chk(image, "causal_step_images: image"); _chk(blurred, "causal_step_images: blurred")
+    _chk(ranks, "causal_step_images: ranks", torch.int32); _chk(out, "causal_step_images: out")
+    if image.dim() != 3 or blurred.shape != image.shape:
+        raise RuntimeError("causal_step_images: image and blurred must be the same [C, H, W] shape (got %s and %s)"
+                           % (tuple(image.shape), tuple(blurred.shape)))
+    C, H, W = image.shape
+    if ranks.dim() not in (2, 3) or ranks.shape[0] < 1 or ranks[0].numel() != H * W:
+        raise RuntimeError("causal_step_images: ranks must be int32 [K, %d], got shape %s" % (H * W, tuple(ranks.shape)))
+    if out.dim() != 4 or tuple(out.shape[1:]) != (C, H, W):
+        raise RuntimeError("causal_step_images: out must be [n, %d, %d, %d], got shape %s" % (C, H, W, tuple(out.shape)))
+    _native.check(_native.lib().scouter_causal_step_images_f32(
+        _p(image), _p(blurred), _p(ranks), _p(out), int(first), int(out.shape[0]), int(ranks.shape[0]), int(n_points), int(step),
+        C, H, W, _stream()), "causal_step_images")
+    return out
+
+
+def causal_curve(logp, cols, curves, first, n_points):
+    """curves.view(-1)[first + i] = exp(logp[i, cols[(first + i) // (2 * n_points)]]) for fp32 logp [n, n_classes], cols int32 [K]
+    on the device (the caller keeps them inside [0, n_classes)) and fp32 curves [K, 2, n_points] -- the probabilities of the
+    chunk causal_step_images built from the same `first`.  One launch; nothing is read on the host."""
+    _chk(logp, "causal_curve: logp"); _chk(cols, "causal_curve: cols", torch.int32); _chk(curves, "causal_curve: curves")
+    if logp.dim() != 2 or cols.dim() != 1 or tuple(curves.shape) != (cols.shape[0], 2, int(n_points)):
+        raise RuntimeError("causal_curve: logp must be [n, n_classes], cols [K] and curves [K, 2, n_points = %d] (got %s, %s and "
+                           "%s)" % (int(n_points), tuple(logp.shape), tuple(cols.shape), tuple(curves.shape)))
+    _native.check(_native.lib().scouter_causal_curve_f32(_p(logp), _p(cols), _p(curves), int(first), int(logp.shape[0]),
+                                                         int(cols.shape[0]), int(n_points), int(logp.shape[1]), _stream()),
+                  "causal_curve")
+    return curves
+
+
+def causal_auc(curves, out=None):
+    """fp32 curves [..., n_points] -> fp32 [...]: the trapezoid area of each curve over [0, 1],
+    (p_0 / 2 + p_1 + ... + p_{n-1} + p_n / 2) / n with n = n_points - 1 >= 1, summed in that order.  One launch."""
+    _chk(curves, "causal_auc: curves")
+    if curves.dim() < 1:
+        raise RuntimeError("causal_auc: curves must be [..., n_points], got shape %s" % (tuple(curves.shape),))
+    lead, n_points = tuple(curves.shape[:-1]), int(curves.shape[-1])
+    R = 1
+    for n in lead:
+        R *= n
+    if out is None:
+        out = torch.empty(lead, dtype=F32, device=curves.device)
+    _chk(out, "causal_auc: out")
+    if tuple(out.shape) != lead:
+        raise RuntimeError("causal_auc: out must be %s, got shape %s" % (lead, tuple(out.shape)))
+    _native.check(_native.lib().scouter_causal_auc_f32(_p(curves), _p(out), R, n_points, _stream()), "causal_auc")
+    return out

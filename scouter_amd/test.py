@@ -8,13 +8,17 @@ backbone stage, `<out>/cam_{c}.png` (tools/attribution.py gradcam_maps: one back
 BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4); `--rise true` the per-class
 RISE perturbation maps `<out>/rise_{c}.png` (tools/attribution.py rise_maps: --rise_masks random masks through the model in
 chunks of --rise_batch, floored at --grad_min_level, BatchNorm-folded under --eval_fold; what the reference's torchcam_vis.py
-draws with torchray's rise).  The jet-colormap overlay of test.py:33-38 is matplotlib
+draws with torchray's rise); `--causal true` prints, for every family of maps drawn in the call (slot under --use_slot true,
+grad, cam, rise), the deletion and insertion scores of the predicted class's map (tools/attribution.py causal_metrics on the
+float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
+`causal <family> class <c>: deletion <d> insertion <i>`.  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
-        [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250]"""
+        [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250] \
+        [--causal true --causal_step 224]"""
 import argparse
 import os
 
@@ -96,6 +100,29 @@ def run_rise(args, model, image, out_dir):
     return maps
 
 
+def run_causal(args, model, image, pred, families, slot_map=None):
+    """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
+    every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
+    mean of input_gradients; cam: gradcam; rise: rise), one printed line each; returns {family: (deletion, insertion)}."""
+    from .tools.attribution import causal_metrics, gradcam, input_gradients, rise
+    x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
+    step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
+    scores = {}
+    for family in families:
+        if family == "slot":
+            maps = slot_map
+        elif family == "grad":
+            maps = input_gradients(model, x, classes=[pred]).mean(dim=2)
+        elif family == "cam":
+            maps = gradcam(model, x, classes=[pred])
+        else:
+            maps = rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)), batch=batch)
+        r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
+        scores[family] = (float(r.deletion[0, 0]), float(r.insertion[0, 0]))
+        print("causal %s class %d: deletion %.6f insertion %.6f" % ((family, pred) + scores[family]))
+    return scores
+
+
 def main():
     parser = argparse.ArgumentParser("single-image xSlot inference", parents=[get_args_parser()])
     parser.add_argument("--checkpoint", default="", help="checkpoint written by train.py (default: the standard name "
@@ -109,6 +136,9 @@ def main():
                         help="true: write the RISE saliency map of every class as rise_{c}.png into --vis_dir")
     parser.add_argument("--rise_masks", default=4000, type=int, help="number of random masks of --rise")
     parser.add_argument("--rise_batch", default=250, type=int, help="masked images per forward of --rise")
+    parser.add_argument("--causal", default=False, type=_flag,
+                        help="true: print the deletion / insertion scores of the predicted class's map of every family drawn")
+    parser.add_argument("--causal_step", default=0, type=int, help="pixels changed per point of --causal (0: --img_size)")
     args = parser.parse_args()
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
@@ -131,12 +161,19 @@ def main():
     else:
         image = torch.from_numpy(np.random.default_rng(0).standard_normal((channels, size, size), dtype=np.float32))
     out, pred, maps, ratio = run(args, model, image, args.vis_dir, args.label)
+    slot_map = None
+    if args.causal and model.use_slot:
+        from .tools.attribution import slot_saliency
+        slot_map = slot_saliency(model)[:, pred:pred + 1].contiguous()       # (before another forward replaces last_attn)
     if want_grad:
         run_grad(args, model, image, args.vis_dir)
     if args.cam:
         run_cam(args, model, image, args.vis_dir)
     if args.rise:
         run_rise(args, model, image, args.vis_dir)
+    if args.causal:
+        families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise)) if on]
+        run_causal(args, model, image, pred, families, slot_map)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:

@@ -14,7 +14,15 @@ with torchray.attribution.rise.  The image is multiplied by thousands of smooth 
 the model, and every mask is weighted by the class probabilities it produced.  No gradient and no feature hook: the same call
 serves the xSlot model and the FC baseline, and its cost is eval forwards (BatchNorm-folded when the model's inference fold is
 on).  The masks exist only as s x s byte grids and shifts; the masked batch, the weighted sum and the heat maps are three HIP
-kernels (kernels.rise_mask_images, kernels.rise_accumulate, kernels.heat_maps) and nothing comes to the host in between."""
+kernels (kernels.rise_mask_images, kernels.rise_accumulate, kernels.heat_maps) and nothing comes to the host in between.
+
+Scores for any of these maps (`causal_metrics`, `slot_saliency`, `gaussian_taps`): the deletion and insertion areas (DAUC / IAUC)
+of the RISE paper's section 4.1, which the SCOUTER paper reports next to the area size.  The pixels of a map are ranked, the
+image is edited a row's worth of pixels at a time -- deleted to zero, or inserted into a blurred copy -- and every edited
+image goes through the model; the score is the area under the class probability.  Like `rise` its cost is eval forwards; the
+resize of a coarse map, the ranking, the blur, the edited batch, the curve and its area are HIP kernels (kernels.resize_bilinear,
+saliency_ranks, separable_filter, causal_step_images, causal_curve, causal_auc).  The blur is the plain sampled Gaussian with
+zero padding, not the kernel the RISE authors' script derives from scipy's reflecting gaussian_filter."""
 import collections
 
 import numpy as np
@@ -262,3 +270,149 @@ def rise_maps(model, images, classes=None, min_level=0.0, **rise_kwargs):
     own size (kernels.heat_maps): negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled
     again, times 255.  A map that is constant at either scaling step is all zeros."""
     return K.heat_maps(rise(model, images, classes, **rise_kwargs), min_level)
+
+
+CausalScores = collections.namedtuple("CausalScores", "deletion insertion deletion_curve insertion_curve step")
+CausalScores.__doc__ = """The result of `causal_metrics`: deletion / insertion fp32 [B, K] (the areas under the curves; low deletion
+and high insertion mean a good map), deletion_curve / insertion_curve fp32 [B, K, n_points] (the class probability at every
+point), all on the images' device, and the `step` (pixels changed per point) that was used."""
+
+
+def gaussian_taps(klen=11, sigma=5.0):
+    """The blur of `causal_metrics` as fp32 taps [klen] (host): w[i] proportional to exp(-(i - klen // 2)^2 / (2 sigma^2)),
+    normalised to sum 1 in float64 and rounded to fp32."""
+    klen, sigma = int(klen), float(sigma)
+    if klen < 1 or klen > 31 or klen % 2 == 0:
+        raise ValueError("klen must be odd with 1 <= klen <= 31, got %d" % klen)
+    if not sigma > 0.0:
+        raise ValueError("sigma must be positive, got %r" % (sigma,))
+    i = torch.arange(klen, dtype=torch.float64) - (klen // 2)
+    w = torch.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (w / w.sum()).to(torch.float32)
+
+
+def slot_saliency(model):
+    """The xSlot attention of the model's last forward as saliency maps, fp32 [B, num_classes, h, w] on the device:
+    model.slot.last_attn with the slots of a class summed, as SlotAttention.vis_maps does, WITHOUT its min-max scaling to bytes
+    (monotone: the ranks, and so `causal_metrics`, do not change).  RuntimeError when the model has no slot head (--use_slot
+    false) or no forward has run yet."""
+    slot = getattr(model, "slot", None)
+    if slot is None or not getattr(model, "use_slot", True):
+        raise RuntimeError("slot_saliency: the model has no slot head (use_slot is false)")
+    a = slot.last_attn
+    if a is None:
+        raise RuntimeError("slot_saliency: no forward has run yet (model.slot.last_attn is None)")
+    a = a.detach().float()
+    if slot.slots_per_class > 1:
+        a = a.reshape(a.shape[0], slot.num_classes, slot.slots_per_class, a.shape[-1]).sum(2)
+    side = int(a.size(2) ** 0.5)
+    return a.reshape(a.shape[0], a.shape[1], side, side).contiguous()
+
+
+def _num_outputs(model, images):
+    """the number of model outputs: SlotModel's own count, or -- for any other module (the metric is black-box) -- the width of
+    one eval-mode forward of the first image"""
+    try:
+        return _num_classes(model, images)
+    except AttributeError:
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                return int(model(images[:1].detach().float()).shape[1])
+        finally:
+            model.train(was_training)
+
+
+def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen=11, sigma=5.0):
+    """Deletion and insertion scores (DAUC / IAUC; Petsiuk et al. 2018, section 4.1, the causal metrics the SCOUTER paper
+    compares explanations with) of saliency `maps` [B, K, h, w] for `images` [B, C, H, W] -> CausalScores.
+
+    Per image, class c and map m: the pixels are ordered by saliency, most salient first (equal values by ascending flat index
+    y * W + x, -0.0 equal to +0.0, NaN after every number).  `step` pixels change per point (None: W, what the RISE authors'
+    script uses at 224 x 224); a curve has n_points = ceil(H W / step) + 1 points and point j has the min(j step, H W)
+    first-ranked pixels changed.  Deletion: the image with the changed pixels set to 0 in all channels.  Insertion: the blurred
+    image with the changed pixels taken from the image.  p_j = exp(log_prob_j[c]) from the eval-mode output for point j, and the
+    score is the trapezoid area over [0, 1], (p_0 / 2 + p_1 + ... + p_{n-1} + p_n / 2) / n with n = n_points - 1.  Low deletion
+    and high insertion mean a good map.
+
+    The blur is the plain sampled Gaussian: a separable filter of `klen` taps w[i] ~ exp(-(i - klen // 2)^2 / (2 sigma^2))
+    (`gaussian_taps`: normalised in float64, rounded to fp32) along rows and then columns, zeros outside the image.  This
+    DEPARTS from the RISE authors' script, which builds its 11 x 11 kernel by pushing a delta through scipy's reflecting
+    gaussian_filter; scipy's border handling is not reproduced.  klen = 11 and sigma = 5 are that script's numbers.
+
+    maps: fp32 or uint8 on the device (uint8 is converted to float; another dtype is a ValueError), resized to H x W with
+    kernels.resize_bilinear when (h, w) != (H, W).  classes as in `gradcam` / `rise`: None -- map k belongs to class k and K must
+    be the number of outputs; a list of K ints; a LongTensor [B] (each image its own class) with K = 1.
+
+    Per image: kernels.saliency_ranks and kernels.separable_filter once, then the 2 K n_points edited images go through the model
+    in chunks of `batch` that may start and end anywhere in the stream (every forward but the last runs at the full batch):
+    kernels.causal_step_images into one reused buffer, the model under torch.no_grad() in eval mode (folded when the model's
+    inference fold is on; the caller's mode is restored), kernels.causal_curve.  kernels.causal_auc at the end.  No BatchNorm
+    buffer moves, no `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop; two calls give
+    the same bits."""
+    if images.dim() != 4:
+        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    B, C, H, W = images.shape
+    if not torch.is_tensor(maps) or maps.dim() != 4 or maps.shape[0] != B or maps.shape[1] < 1 or maps[0, 0].numel() < 1:
+        raise ValueError("maps must be a tensor [B = %d, K, h, w], got %s"
+                         % (B, tuple(maps.shape) if torch.is_tensor(maps) else type(maps).__name__))
+    if maps.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("maps must be fp32 or uint8, got %s" % maps.dtype)
+    Kc = int(maps.shape[1])
+    n = _num_outputs(model, images)
+    per_image = torch.is_tensor(classes)
+    if per_image:
+        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
+                             % (B, classes.dtype, tuple(classes.shape)))
+        if Kc != 1:
+            raise ValueError("a tensor of classes (each image its own class) needs K = 1 map per image, got K = %d" % Kc)
+        cols = classes.detach().cpu().tolist()
+    else:
+        cols = [int(c) for c in (classes if classes is not None else range(n))]
+        if len(cols) != Kc:
+            raise ValueError("%d maps per image for %d classes%s" % (Kc, len(cols), "" if classes is not None else
+                                                                   " (classes=None: one map per model output)"))
+    for c in cols:
+        if not 0 <= c < n:
+            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1, got %d" % batch)
+    step = W if step is None else int(step)
+    if step < 1:
+        raise ValueError("step must be at least 1, got %d" % step)
+    if H * W > 1 << 20:
+        raise ValueError("images of %d x %d pixels: the ranking covers at most 2^20" % (H, W))
+    dev = images.device
+    taps = gaussian_taps(klen, sigma).to(dev)
+    n_points = -(-(H * W) // step) + 1
+    total = 2 * Kc * n_points
+    x = images.detach().contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    m = maps.detach().to(dev)
+    m = (m.float() if m.dtype != torch.float32 else m).contiguous()
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    curves = torch.empty((B, Kc, 2, n_points), dtype=torch.float32, device=dev)
+    buf = torch.empty((min(batch, total), C, H, W), dtype=torch.float32, device=dev)
+    blurred = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    ranks = torch.empty((Kc, H * W), dtype=torch.int32, device=dev)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for b in range(B):
+                cb = cols_dev[b:b + 1] if per_image else cols_dev
+                mb = m[b] if tuple(m.shape[2:]) == (H, W) else K.resize_bilinear(m[b], H, W)
+                K.saliency_ranks(mb.view(Kc, H * W), out=ranks)
+                K.separable_filter(x[b], taps, out=blurred)
+                for first in range(0, total, batch):
+                    chunk = K.causal_step_images(x[b], blurred, ranks, buf[:min(batch, total - first)], first, n_points, step)
+                    K.causal_curve(model(chunk), cb, curves[b], first, n_points)
+    finally:
+        model.train(was_training)
+    scores = K.causal_auc(curves)
+    return CausalScores(scores[:, :, 0].contiguous(), scores[:, :, 1].contiguous(), curves[:, :, 0].contiguous(),
+                        curves[:, :, 1].contiguous(), step)
