@@ -273,6 +273,35 @@ int scouter_causal_curve_f32(const float* logp, const int* cols, float* curve_fl
  * two ends halved, and divides by n_points - 1.  n_points < 2: SC_ERR_ARG; R above 65535 * 256: SC_ERR_UNSUPPORTED. */
 int scouter_causal_auc_f32(const float* curves, float* scores, long R, int n_points, void* stream);
 
+/* ---- Score-CAM (Wang et al., CVPR-W 2020; the gradient-free CAMs of the reference's torchcam_vis.py; csrc/scorecam.hip,
+ * tools/attribution.py scorecam).  For ONE image's backbone output feat NHWC fp32 [h][w][C] and channel c:
+ * U_c = the bilinear resize of feat[:, :, c] to H x W (F.interpolate align_corners=False, the source coordinate and the three
+ * fmas of scouter_resize_bilinear_f32), lo_c / hi_c = the minimum / maximum of the fp32 values U_c(y, x) over the H * W pixels
+ * (NOT the extrema of the h * w source values), span_c = hi_c - lo_c.  The channel is LIVE when span_c > 0 and its mask is
+ * mask_c(y, x) = (U_c(y, x) - lo_c) / span_c -- one subtraction, then one correctly rounded division -- which attains exactly
+ * 0 and exactly 1; otherwise (a constant channel, or a NaN / infinity in its range) it is DEAD: its mask is 0 everywhere and its
+ * weight 0.  U and the mask are formed by the same inlined expressions in all three calls and never stored; every index is
+ * clamped, so no feature value moves an address.  A channel's h * w source values live in LDS: h * w <= 1024, above that (or
+ * features past 32-bit offsets) SC_ERR_UNSUPPORTED.  A null or misaligned (4-byte) pointer, a count below 1 or a channel range
+ * outside [0, C) is SC_ERR_ARG; nothing is launched after an error.  One fixed order per output element and no atomics:
+ * bit-identical run to run.
+ *
+ * ranges fp32 [C][2] = (lo_c, hi_c) for every channel, one launch: a workgroup reads 8 channels for all positions coalesced along
+ * C into LDS, each wave walks the H * W pixels of one channel and ends in a butterfly min / max. */
+int scouter_scorecam_ranges_f32(const float* feat, float* ranges, int h, int w, int C, int H, int W, void* stream);
+/* out fp32 [n][Cin][H][W], out[i] = image [Cin][H][W] * mask_{first + i}, 0 <= first and first + n <= C; the mask value is formed
+ * once per pixel for all Cin channels; a dead channel writes zeros.  16-byte accesses when W is a multiple of 4 and image / out
+ * are 16-byte aligned, one pixel per thread otherwise.  Any n >= 1. */
+int scouter_scorecam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out, int first, int n,
+                                     int Cin, int H, int W, int h, int w, int C, void* stream);
+/* acc fp32 [K][h][w] += sum_i live_{first + i} * expf(logp[i][cols[k]]) * feat[p][first + i], logp fp32 [n][n_classes] (the model's
+ * output for the n images of scouter_scorecam_mask_images_f32 with the same `first`), cols i32 [K] in [0, n_classes) (checked by
+ * the caller; clamped here).  Every output element belongs to one thread, which starts from the value in acc and adds one fma
+ * per live channel in i order (a dead channel is skipped): no atomics, no partial sums -- splitting the channels over several
+ * calls at any point gives the bits of one call.  Any n >= 1 (the weights are staged through LDS in pieces), any K >= 1. */
+int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges, float* acc,
+                                    int first, int n, int n_classes, int K, int h, int w, int C, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

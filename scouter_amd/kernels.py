@@ -1885,3 +1885,71 @@ def causal_auc(curves, out=None):
         raise RuntimeError("causal_auc: out must be %s, got shape %s" % (lead, tuple(out.shape)))
     _native.check(_native.lib().scouter_causal_auc_f32(_p(curves), _p(out), R, n_points, _stream()), "causal_auc")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Score-CAM (csrc/scorecam.hip; tools/attribution.py scorecam / scorecam_maps)
+# ---------------------------------------------------------------------------------------------------------------
+def _scorecam_feat_chk(what, feat, ranges):
+    """feat fp32 [h, w, C] (one image's NHWC features) and, when given, ranges fp32 [C, 2] -> (h, w, C)"""
+    _chk(feat, what + ": feat")
+    if feat.dim() != 3:
+        raise RuntimeError("%s: feat must be one image's NHWC features [h, w, C], got shape %s" % (what, tuple(feat.shape)))
+    h, w, C = feat.shape
+    if ranges is not None:
+        _chk(ranges, what + ": ranges")
+        if tuple(ranges.shape) != (C, 2):
+            raise RuntimeError("%s: ranges must be [C = %d, 2], got shape %s" % (what, C, tuple(ranges.shape)))
+    return h, w, C
+
+
+def scorecam_ranges(feat, H, W, out=None):
+    """fp32 feat [h, w, C] (one image's NHWC features) -> fp32 [C, 2] = (lo_c, hi_c): the minimum and maximum of channel c
+    resized bilinearly to H x W (align_corners=False), taken over the H * W fp32 values of the resized channel -- the ones
+    scorecam_mask_images forms -- not over the h * w source values.  A channel is live when hi - lo > 0.  h * w <= 1024 (a
+    channel's source lives in LDS).  One launch; the resized channel is never stored."""
+    h, w, C = _scorecam_feat_chk("scorecam_ranges", feat, None)
+    if out is None:
+        out = torch.empty((C, 2), dtype=F32, device=feat.device)
+    _chk(out, "scorecam_ranges: out")
+    if tuple(out.shape) != (C, 2):
+        raise RuntimeError("scorecam_ranges: out must be [C = %d, 2], got shape %s" % (C, tuple(out.shape)))
+    _native.check(_native.lib().scouter_scorecam_ranges_f32(_p(feat), _p(out), h, w, C, int(H), int(W), _stream()),
+                  "scorecam_ranges")
+    return out
+
+
+def scorecam_mask_images(image, feat, ranges, out, first):
+    """out[i, ch] = image[ch] * mask_{first + i} for fp32 image [Cin, H, W], feat [h, w, C], ranges [C, 2] of scorecam_ranges at
+    the same H x W and fp32 out [n, Cin, H, W] (a dense leading slice of a longer buffer is fine), 0 <= first and
+    first + n <= C.  mask_c = (U_c - lo_c) / (hi_c - lo_c) with U_c the bilinear resize of channel c, formed in registers,
+    never stored; a dead channel (hi_c - lo_c > 0 is false) gives zeros.  One launch."""
+    _chk(image, "scorecam_mask_images: image"); _chk(out, "scorecam_mask_images: out")
+    if image.dim() != 3:
+        raise RuntimeError("scorecam_mask_images: image must be [Cin, H, W], got shape %s" % (tuple(image.shape),))
+    Cin, H, W = image.shape
+    h, w, C = _scorecam_feat_chk("scorecam_mask_images", feat, ranges)
+    if out.dim() != 4 or tuple(out.shape[1:]) != (Cin, H, W):
+        raise RuntimeError("scorecam_mask_images: out must be [n, %d, %d, %d], got shape %s" % (Cin, H, W, tuple(out.shape)))
+    _native.check(_native.lib().scouter_scorecam_mask_images_f32(_p(image), _p(feat), _p(ranges), _p(out), int(first),
+                                                                 int(out.shape[0]), Cin, H, W, h, w, C, _stream()),
+                  "scorecam_mask_images")
+    return out
+
+
+def scorecam_accumulate(logp, cols, feat, ranges, acc, first):
+    """acc[k, p] += sum_i live_{first + i} * exp(logp[i, cols[k]]) * feat[p, first + i] for fp32 logp [n, n_classes] (the model's
+    output for the n images of scorecam_mask_images at the same `first`), cols int32 [K] on the device (the caller keeps them
+    inside [0, n_classes)), feat [h, w, C], ranges [C, 2] and fp32 acc [K, h, w].  One thread per element adds the live channels
+    one fma at a time in i order onto the value in acc: calls over consecutive pieces of the channels give the bits of one
+    call.  One launch; nothing is read on the host."""
+    _chk(logp, "scorecam_accumulate: logp"); _chk(cols, "scorecam_accumulate: cols", torch.int32)
+    _chk(acc, "scorecam_accumulate: acc")
+    h, w, C = _scorecam_feat_chk("scorecam_accumulate", feat, ranges)
+    if logp.dim() != 2 or cols.dim() != 1 or tuple(acc.shape) != (cols.shape[0], h, w):
+        raise RuntimeError("scorecam_accumulate: logp must be [n, n_classes], cols [K] and acc [K, h = %d, w = %d] (got %s, %s "
+                           "and %s)" % (h, w, tuple(logp.shape), tuple(cols.shape), tuple(acc.shape)))
+    _native.check(_native.lib().scouter_scorecam_accumulate_f32(_p(logp), _p(cols), _p(feat), _p(ranges), _p(acc), int(first),
+                                                                int(logp.shape[0]), int(logp.shape[1]), int(cols.shape[0]),
+                                                                h, w, C, _stream()), "scorecam_accumulate")
+    return acc

@@ -8,8 +8,11 @@ backbone stage, `<out>/cam_{c}.png` (tools/attribution.py gradcam_maps: one back
 BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4); `--rise true` the per-class
 RISE perturbation maps `<out>/rise_{c}.png` (tools/attribution.py rise_maps: --rise_masks random masks through the model in
 chunks of --rise_batch, floored at --grad_min_level, BatchNorm-folded under --eval_fold; what the reference's torchcam_vis.py
-draws with torchray's rise); `--causal true` prints, for every family of maps drawn in the call (slot under --use_slot true,
-grad, cam, rise), the deletion and insertion scores of the predicted class's map (tools/attribution.py causal_metrics on the
+draws with torchray's rise); `--scorecam true` the per-class Score-CAM heat maps `<out>/scorecam_{c}.png`
+(tools/attribution.py scorecam_maps: one eval forward per channel of the last backbone stage, in chunks of --scorecam_batch,
+floored at --grad_min_level, BatchNorm-folded under --eval_fold; the gradient-free CAM family of the reference's
+torchcam_vis.py); `--causal true` prints, for every family of maps drawn in the call (slot under --use_slot true,
+grad, cam, rise, scorecam), the deletion and insertion scores of the predicted class's map (tools/attribution.py causal_metrics on the
 float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`.  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
@@ -18,7 +21,7 @@ post-processing of these PNGs and is not reproduced.
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
         [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250] \
-        [--causal true --causal_step 224]"""
+        [--scorecam true --scorecam_batch 250] [--causal true --causal_step 224]"""
 import argparse
 import os
 
@@ -100,11 +103,26 @@ def run_rise(args, model, image, out_dir):
     return maps
 
 
+def run_scorecam(args, model, image, out_dir):
+    """--scorecam true: the Score-CAM heat map of every class for the one image at the backbone's output (Wang et al. 2020; the
+    gradient-free CAMs of the reference's torchcam_vis.py) -> `<out>/scorecam_{c}.png`, uint8 maps at the input resolution;
+    returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import scorecam_maps
+    os.makedirs(out_dir, exist_ok=True)
+    maps = scorecam_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level),
+                         batch=int(getattr(args, "scorecam_batch", 250)))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "scorecam_%d.png" % c))
+    return maps
+
+
 def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
-    mean of input_gradients; cam: gradcam; rise: rise), one printed line each; returns {family: (deletion, insertion)}."""
-    from .tools.attribution import causal_metrics, gradcam, input_gradients, rise
+    mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam), one printed line each; returns
+    {family: (deletion, insertion)}."""
+    from .tools.attribution import causal_metrics, gradcam, input_gradients, rise, scorecam
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
     step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
     scores = {}
@@ -115,6 +133,8 @@ def run_causal(args, model, image, pred, families, slot_map=None):
             maps = input_gradients(model, x, classes=[pred]).mean(dim=2)
         elif family == "cam":
             maps = gradcam(model, x, classes=[pred])
+        elif family == "scorecam":
+            maps = scorecam(model, x, classes=[pred], batch=int(getattr(args, "scorecam_batch", 250)))
         else:
             maps = rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)), batch=batch)
         r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
@@ -123,7 +143,8 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     return scores
 
 
-def main():
+def get_test_parser():
+    """the training tool's arguments plus this tool's own"""
     parser = argparse.ArgumentParser("single-image xSlot inference", parents=[get_args_parser()])
     parser.add_argument("--checkpoint", default="", help="checkpoint written by train.py (default: the standard name "
                                                          "under --output_dir, if it exists)")
@@ -139,7 +160,14 @@ def main():
     parser.add_argument("--causal", default=False, type=_flag,
                         help="true: print the deletion / insertion scores of the predicted class's map of every family drawn")
     parser.add_argument("--causal_step", default=0, type=int, help="pixels changed per point of --causal (0: --img_size)")
-    args = parser.parse_args()
+    parser.add_argument("--scorecam", default=False, type=_flag,
+                        help="true: write the Score-CAM heat map of every class as scorecam_{c}.png into --vis_dir")
+    parser.add_argument("--scorecam_batch", default=250, type=int, help="masked images per forward of --scorecam")
+    return parser
+
+
+def main():
+    args = get_test_parser().parse_args()
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
     args.vis, args.vis_id = False, 0                  # maps are taken from model.slot.last_attn, image index 0
@@ -171,8 +199,11 @@ def main():
         run_cam(args, model, image, args.vis_dir)
     if args.rise:
         run_rise(args, model, image, args.vis_dir)
+    if args.scorecam:
+        run_scorecam(args, model, image, args.vis_dir)
     if args.causal:
-        families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise)) if on]
+        families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
+                                    ("scorecam", args.scorecam)) if on]
         run_causal(args, model, image, pred, families, slot_map)
     print(out)
     print(pred)

@@ -22,7 +22,16 @@ image is edited a row's worth of pixels at a time -- deleted to zero, or inserte
 image goes through the model; the score is the area under the class probability.  Like `rise` its cost is eval forwards; the
 resize of a coarse map, the ranking, the blur, the edited batch, the curve and its area are HIP kernels (kernels.resize_bilinear,
 saliency_ranks, separable_filter, causal_step_images, causal_curve, causal_auc).  The blur is the plain sampled Gaussian with
-zero padding, not the kernel the RISE authors' script derives from scipy's reflecting gaussian_filter."""
+zero padding, not the kernel the RISE authors' script derives from scipy's reflecting gaussian_filter.
+
+Activation-masked maps (`scorecam`, `scorecam_maps`): Score-CAM (Wang et al., CVPR-W 2020), the method the gradient-free CAMs of
+the reference's torchcam_vis.py (SS-CAM, IS-CAM) are loops over.  Every channel of the backbone's output -- the layer `gradcam`
+reads -- is resized to the image, min-max scaled to [0, 1] and multiplied onto the image; every masked image goes through the
+model, and every channel is weighted by the class probability its mask produced.  No gradient: one feature pass and one eval
+forward per channel (512 for resnet18, 2048 for resnest26d / resnest50d; BatchNorm-folded when the model's inference fold is
+on).  A mask exists only as its channel's h x w source values and its range; the ranges, the masked batch and the weighted sum
+are three HIP kernels (kernels.scorecam_ranges, kernels.scorecam_mask_images, kernels.scorecam_accumulate) and nothing comes
+to the host in between."""
 import collections
 
 import numpy as np
@@ -270,6 +279,81 @@ def rise_maps(model, images, classes=None, min_level=0.0, **rise_kwargs):
     own size (kernels.heat_maps): negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled
     again, times 255.  A map that is constant at either scaling step is all zeros."""
     return K.heat_maps(rise(model, images, classes, **rise_kwargs), min_level)
+
+
+def scorecam(model, images, classes=None, batch=250):
+    """Score-CAM of `images` [B, Cin, H, W] at the backbone's output -> fp32 [B, K, h, w] on the images' device:
+    S[b, k, p] = sum_c live_c * exp(log_prob_c[classes[k]]) * A[b, p, c], A = model.feature_pass(images).features (NHWC
+    [B, h, w, C], the layer `gradcam` reads) and log_prob_c the eval-mode output for images[b] * mask_c.  mask_c is channel c of
+    A[b] resized bilinearly to H x W (align_corners=False), minus its minimum lo_c over the H x W pixels, divided by its span
+    hi_c - lo_c; a channel whose span is not positive (a constant channel) is dead: its mask is all zeros and its weight 0 -- the
+    official implementation's "skip a constant channel", without a host read (its zero image still goes through the model).
+    The channels are summed in ascending order.
+
+    The paper's final ReLU is NOT applied: backbone features are post-ReLU and the weights are probabilities, so it changes
+    nothing there, and `kernels.cam_maps` cuts negative values as its first drawing step anyway.  The result stays at h x w, like
+    `gradcam`: bilinear resizing is linear, so resizing S (what `scorecam_maps` does) equals the official sum of upsampled maps.
+
+    classes as in `gradcam` / `rise`: None (every class), a list of ints (K = len), or a LongTensor [B] (each image its own
+    class, K = 1).  Per image: kernels.scorecam_ranges once, then the C masked images go through the model in chunks of `batch`
+    (the last may be shorter): kernels.scorecam_mask_images into one reused buffer, the model under torch.no_grad() in eval
+    mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.scorecam_accumulate onto the
+    result in channel order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied
+    to the host and nothing synchronises inside the loop."""
+    if images.dim() != 4:
+        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    B, Cin, H, W = images.shape
+    n = _num_classes(model, images)
+    per_image = torch.is_tensor(classes)
+    if per_image:
+        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
+                             % (B, classes.dtype, tuple(classes.shape)))
+        cols = classes.detach().cpu().tolist()
+    else:
+        cols = [int(c) for c in (classes if classes is not None else range(n))]
+    for c in cols:
+        if not 0 <= c < n:
+            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1, got %d" % batch)
+    dev = images.device
+    x = images.detach().contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    feat = model.feature_pass(x).features.detach()          # (the FeaturePass and its head state are dropped here)
+    feat = (feat.float() if feat.dtype != torch.float32 else feat).contiguous()
+    _, h, w, C = feat.shape
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    out = torch.zeros((B, Kc, h, w), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    buf = torch.empty((min(batch, C), Cin, H, W), dtype=torch.float32, device=dev)
+    ranges = torch.empty((C, 2), dtype=torch.float32, device=dev)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for b in range(B):
+                cb = cols_dev[b:b + 1] if per_image else cols_dev
+                K.scorecam_ranges(feat[b], H, W, out=ranges)
+                for first in range(0, C, batch):
+                    chunk = K.scorecam_mask_images(x[b], feat[b], ranges, buf[:min(batch, C - first)], first)
+                    K.scorecam_accumulate(model(chunk), cb, feat[b], ranges, out[b], first)
+    finally:
+        model.train(was_training)
+    return out
+
+
+def scorecam_maps(model, images, classes=None, size=None, min_level=0.0, batch=250):
+    """uint8 Score-CAM heat maps [B, K, H, W] on the device: `scorecam`, then per map the drawing steps of `gradcam_maps` in one
+    launch (kernels.cam_maps) -- bilinear resize to `size` = (H, W) (None: the images' H x W), negative values cut to 0, min-max
+    scaled, raised to at least `min_level`, min-max scaled again, times 255.  A map that is constant at either scaling step is
+    all zeros."""
+    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    return K.cam_maps(scorecam(model, images, classes, batch=batch), H, W, min_level)
 
 
 CausalScores = collections.namedtuple("CausalScores", "deletion insertion deletion_curve insertion_curve step")
