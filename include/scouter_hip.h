@@ -302,6 +302,55 @@ int scouter_scorecam_mask_images_f32(const float* image, const float* feat, cons
 int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges, float* acc,
                                     int first, int n, int n_classes, int K, int h, int w, int C, void* stream);
 
+/* ---- Path and noise batches for the gradient methods that need many gradients per image: Integrated Gradients (Sundararajan
+ * et al., ICML 2017) and SmoothGrad / VarGrad (Smilkov et al. 2017; Adebayo et al. 2018), captum's IntegratedGradients and
+ * NoiseTunnel of the reference's captum_vis.py (csrc/pathgrad.hip, tools/attribution.py integrated_gradients / smoothgrad).
+ * E = C * H * W is the flat element count of ONE image and e the flat index; every image is dense.  The images of a chunk are
+ * written into a batch buffer, the model's own forward and backward turn them into gradients, and the gradients are summed in
+ * fp64.  One thread owns an output element (or four consecutive ones), one fixed order per element and no atomics:
+ * bit-identical run to run.  Each call has a 16-byte form (E, or H * W, a multiple of 4 and every pointer 16-byte aligned) and a
+ * one-element form that give the same bits.  A null or misaligned pointer (fp32: 4 bytes, fp64: 8), a size below 1 or a range
+ * outside [0, N) is SC_ERR_ARG; n * E (or E, or M * C * HW) of 2^31 or more is SC_ERR_UNSUPPORTED; nothing is launched after an
+ * error.
+ *
+ * out fp32 [n][E], out[j][e] = fmaf(alphas[first + j], image[e] - base[e], base[e]): one fp32 subtraction, formed once per
+ * element and reused for the thread's values of j, then one fma.  alphas fp32 [N], 0 <= first and first + n <= N.  base may be
+ * null: all zeros.  A dense leading slice of a longer out is fine. */
+int scouter_path_images_f32(const float* image, const float* base, const float* alphas, float* out, int first, int n, int N,
+                            long E, void* stream);
+/* out fp32 [n][E], out[j][e] = fmaf(sigma, z(seed, first + j, e), image[e]), sigma >= 0 and finite.  z is standard normal:
+ * Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with the key (seed_lo, seed_hi)
+ * -- the two ints are taken as 32-bit patterns -- and the counter (e / 4, first + j, 0, 0); its words r0 .. r3 serve the elements
+ * 4q .. 4q + 3: u_i = (float)(2 * (r_i >> 9) + 1) * 2^-24 (exact, inside (0, 1)), (z0, z1) = rad(u0) * (cosf, sinf)(
+ * 6.283185307179586f * u1), (z2, z3) the same from (u2, u3), rad(u) = sqrtf(-2 * logf(u)), with the accurate device functions.
+ * A partial last group (E not a multiple of 4) uses its leading words.  The value of an element depends on (seed, first + j, e)
+ * alone: not on the chunking and not on the form that wrote it. */
+int scouter_noise_images_f32(const float* image, float* out, float sigma, int seed_lo, int seed_hi, int first, int n, long E,
+                             void* stream);
+/* acc fp64 [E] += sum_j w_j * g[j][e] and, when acc_sq (fp64 [E]) is not null, acc_sq[e] += sum_j w_j * g[j][e]^2, for grads
+ * fp32 [n][E] and w_j = weights[first + j] (fp32 [N]; null: every w_j is 1), 0 <= first and first + n <= N.  The sums run in
+ * ascending j in fp64 and start from the values in acc / acc_sq; w_j * g is exact, (w_j * g) * g takes one rounding inside the
+ * fma that adds it.  No partial sums: splitting the N terms over calls at any point gives the bits of one call. */
+int scouter_grad_accumulate_f64(const float* grads, const float* weights, double* acc, double* acc_sq, int first, int n, int N,
+                                long E, void* stream);
+/* out fp32 [E] by mode -- SCOUTER_ATTR_IG 0: (float)((double)(image[e] - base[e]) * acc[e]), the fp32 difference
+ * scouter_path_images_f32 forms (base null: zeros); SCOUTER_ATTR_MEAN 1: (float)(acc[e] * inv_n); SCOUTER_ATTR_MEAN_SQ 2:
+ * (float)(acc_sq[e] * inv_n); SCOUTER_ATTR_VAR 3: (float)(acc_sq[e] * inv_n - (acc[e] * inv_n)^2), the biased variance of
+ * captum's vargrad (one fma).  Only the inputs a mode reads must be non-null; another mode is SC_ERR_ARG.  When total (fp64 [1])
+ * is not null it receives sum_e (double)out[e]: one partial sum per workgroup into ws (at least
+ * scouter_attr_finish_workspace_bytes() bytes, else SC_ERR_WORKSPACE), added by a second launch in a fixed order -- the grid
+ * depends on E alone, so two calls give the same bits.  ws may be null when total is. */
+#define SCOUTER_ATTR_IG 0
+#define SCOUTER_ATTR_MEAN 1
+#define SCOUTER_ATTR_MEAN_SQ 2
+#define SCOUTER_ATTR_VAR 3
+size_t scouter_attr_finish_workspace_bytes(void);
+int scouter_attr_finish_f32(int mode, const double* acc, const double* acc_sq, const float* image, const float* base,
+                            double inv_n, float* out, double* total, long E, void* ws, size_t ws_bytes, void* stream);
+/* out fp32 [M][HW], out[m][p] = (float)(sum_c v(x[m][c][p]) / C) for x fp32 [M][C][HW]: v the identity, or fabs when `absolute`
+ * is not 0; the sum runs over ascending c in fp64 and is divided by C in fp64. */
+int scouter_channel_mean_f32(const float* x, float* out, long M, int C, long HW, int absolute, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

@@ -1953,3 +1953,119 @@ def scorecam_accumulate(logp, cols, feat, ranges, acc, first):
                                                                 int(logp.shape[0]), int(logp.shape[1]), int(cols.shape[0]),
                                                                 h, w, C, _stream()), "scorecam_accumulate")
     return acc
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# path and noise batches (csrc/pathgrad.hip; tools/attribution.py integrated_gradients / smoothgrad / gradient_maps)
+# ---------------------------------------------------------------------------------------------------------------
+ATTR_IG, ATTR_MEAN, ATTR_MEAN_SQ, ATTR_VAR = 0, 1, 2, 3         # (include/scouter_hip.h SCOUTER_ATTR_*)
+
+
+def _batch_of(what, image, out):
+    """out must be [n, *image.shape] -> (n, E)"""
+    if out.dim() != image.dim() + 1 or tuple(out.shape[1:]) != tuple(image.shape):
+        raise RuntimeError("%s: out must be [n, %s], got shape %s" % (what, ", ".join(str(v) for v in image.shape),
+                                                                      tuple(out.shape)))
+    return int(out.shape[0]), int(image.numel())
+
+
+def path_images(image, base, alphas, out, first):
+    """out[j] = base + alphas[first + j] * (image - base) for fp32 image [C, H, W], base of the same shape (None: zeros), fp32
+    alphas [N] on the device and fp32 out [n, C, H, W] (a dense leading slice of a longer buffer is fine), 0 <= first and
+    first + n <= N: one fp32 subtraction, then one fma per image of the chunk.  One launch."""
+    _chk(image, "path_images: image"); _chk(base, "path_images: base"); _chk(alphas, "path_images: alphas")
+    _chk(out, "path_images: out")
+    n, E = _batch_of("path_images", image, out)
+    if base is not None and tuple(base.shape) != tuple(image.shape):
+        raise RuntimeError("path_images: base must have the image's shape %s, got %s" % (tuple(image.shape), tuple(base.shape)))
+    if alphas.dim() != 1:
+        raise RuntimeError("path_images: alphas must be [N], got shape %s" % (tuple(alphas.shape),))
+    _native.check(_native.lib().scouter_path_images_f32(_p(image), _p(base), _p(alphas), _p(out), int(first), n,
+                                                        int(alphas.shape[0]), E, _stream()), "path_images")
+    return out
+
+
+def _seed_words(seed):
+    """a 64-bit seed as the two 32-bit patterns the C ABI takes (signed ints)"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = seed & 0xFFFFFFFF, seed >> 32
+    return (lo - (1 << 32) if lo >= 1 << 31 else lo), (hi - (1 << 32) if hi >= 1 << 31 else hi)
+
+
+def noise_images(image, out, sigma, seed, first):
+    """out[j] = image + sigma * z(seed, first + j) for fp32 image [C, H, W] and fp32 out [n, C, H, W] (a dense leading slice of
+    a longer buffer is fine): z standard normal from Philox4x32-10 keyed by the 64-bit `seed` (low word, high word), counter
+    (e / 4, first + j, 0, 0), Box-Muller on the four words (include/scouter_hip.h).  An element's value depends on (seed,
+    first + j, e) alone, so chunks written by separate calls equal one call.  sigma >= 0.  One launch."""
+    _chk(image, "noise_images: image"); _chk(out, "noise_images: out")
+    n, E = _batch_of("noise_images", image, out)
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_noise_images_f32(_p(image), _p(out), float(sigma), lo, hi, int(first), n, E, _stream()),
+                  "noise_images")
+    return out
+
+
+def grad_accumulate(grads, weights, acc, acc_sq=None, first=0):
+    """acc += sum_j w_j * grads[j] and, when given, acc_sq += sum_j w_j * grads[j]^2 for fp32 grads [n, ...], fp64 acc / acc_sq of
+    one gradient's shape and w_j = weights[first + j] (fp32 [N] on the device; None: 1, and first is ignored).  fp64 products and
+    sums in ascending j onto the values in acc / acc_sq: calls over consecutive pieces give the bits of one call.  One launch."""
+    _chk(grads, "grad_accumulate: grads"); _chk(weights, "grad_accumulate: weights")
+    _chk(acc, "grad_accumulate: acc", torch.float64); _chk(acc_sq, "grad_accumulate: acc_sq", torch.float64)
+    if grads.dim() < 1 or tuple(grads.shape[1:]) != tuple(acc.shape) or \
+            (acc_sq is not None and tuple(acc_sq.shape) != tuple(acc.shape)):
+        raise RuntimeError("grad_accumulate: grads must be [n, *acc.shape] and acc_sq like acc (got %s, %s and %s)"
+                           % (tuple(grads.shape), tuple(acc.shape), None if acc_sq is None else tuple(acc_sq.shape)))
+    n = int(grads.shape[0])
+    if weights is None:
+        first, N = 0, n
+    else:
+        if weights.dim() != 1:
+            raise RuntimeError("grad_accumulate: weights must be [N], got shape %s" % (tuple(weights.shape),))
+        N = int(weights.shape[0])
+    _native.check(_native.lib().scouter_grad_accumulate_f64(_p(grads), _p(weights), _p(acc), _p(acc_sq), int(first), n, N,
+                                                            int(acc.numel()), _stream()), "grad_accumulate")
+    return acc
+
+
+def attr_finish(mode, acc=None, acc_sq=None, image=None, base=None, inv_n=1.0, out=None, total=None):
+    """The fp32 result of a gradient method from its fp64 sums -> out (None: a new tensor of the sums' shape).  mode ATTR_IG:
+    (image - base) * acc, the fp32 difference of path_images (base None: zeros); ATTR_MEAN: acc * inv_n; ATTR_MEAN_SQ:
+    acc_sq * inv_n; ATTR_VAR: acc_sq * inv_n - (acc * inv_n)^2.  total: an fp64 tensor of one element that receives the sum of
+    out in fp64 (two launches with a fixed order: two calls give the same bits)."""
+    _chk(acc, "attr_finish: acc", torch.float64); _chk(acc_sq, "attr_finish: acc_sq", torch.float64)
+    _chk(image, "attr_finish: image"); _chk(base, "attr_finish: base"); _chk(out, "attr_finish: out")
+    _chk(total, "attr_finish: total", torch.float64)
+    like = acc if acc is not None else acc_sq
+    if like is None:
+        raise RuntimeError("attr_finish: neither acc nor acc_sq is given")
+    for name, t in (("acc_sq", acc_sq), ("image", image), ("base", base), ("out", out)):
+        if t is not None and tuple(t.shape) != tuple(like.shape):
+            raise RuntimeError("attr_finish: %s must have the sums' shape %s, got %s" % (name, tuple(like.shape), tuple(t.shape)))
+    if total is not None and total.numel() != 1:
+        raise RuntimeError("attr_finish: total must hold one element, got shape %s" % (tuple(total.shape),))
+    if out is None:
+        out = torch.empty(like.shape, dtype=F32, device=like.device)
+    L = _native.lib()
+    ws = workspace(L.scouter_attr_finish_workspace_bytes(), like.device) if total is not None else None
+    _native.check(L.scouter_attr_finish_f32(int(mode), _p(acc), _p(acc_sq), _p(image), _p(base), float(inv_n), _p(out), _p(total),
+                                            int(like.numel()), _p(ws), 0 if ws is None else ws.numel(), _stream()), "attr_finish")
+    return out
+
+
+def channel_mean(x, absolute=False, out=None):
+    """fp32 x [..., C, H, W] -> fp32 [..., H, W]: the mean over the channels (absolute: of the magnitudes), summed over ascending
+    c and divided in fp64 -- what attribution_maps does on the host before it draws.  One launch."""
+    _chk(x, "channel_mean: x"); _chk(out, "channel_mean: out")
+    if x.dim() < 3:
+        raise RuntimeError("channel_mean: x must be [..., C, H, W], got shape %s" % (tuple(x.shape),))
+    lead, (C, H, W) = tuple(x.shape[:-3]), x.shape[-3:]
+    if out is None:
+        out = torch.empty(lead + (H, W), dtype=F32, device=x.device)
+    if tuple(out.shape) != lead + (H, W):
+        raise RuntimeError("channel_mean: out must be %s, got shape %s" % (lead + (H, W), tuple(out.shape)))
+    M = 1
+    for v in lead:
+        M *= int(v)
+    _native.check(_native.lib().scouter_channel_mean_f32(_p(x), _p(out), M, int(C), int(H) * int(W), 1 if absolute else 0,
+                                                         _stream()), "channel_mean")
+    return out

@@ -11,9 +11,13 @@ chunks of --rise_batch, floored at --grad_min_level, BatchNorm-folded under --ev
 draws with torchray's rise); `--scorecam true` the per-class Score-CAM heat maps `<out>/scorecam_{c}.png`
 (tools/attribution.py scorecam_maps: one eval forward per channel of the last backbone stage, in chunks of --scorecam_batch,
 floored at --grad_min_level, BatchNorm-folded under --eval_fold; the gradient-free CAM family of the reference's
-torchcam_vis.py); `--causal true` prints, for every family of maps drawn in the call (slot under --use_slot true,
-grad, cam, rise, scorecam), the deletion and insertion scores of the predicted class's map (tools/attribution.py causal_metrics on the
-float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
+torchcam_vis.py); `--ig true` the per-class Integrated Gradients maps `<out>/ig_{c}.png` (tools/attribution.py
+integrated_gradients: --ig_steps Gauss-Legendre steps from a zero baseline in chunks of --ig_batch, drawn by gradient_maps,
+floored at --grad_min_level; captum's IntegratedGradients of the reference's captum_vis.py); `--smoothgrad true` the per-class
+SmoothGrad maps `<out>/smoothgrad_{c}.png` (tools/attribution.py smoothgrad: --smoothgrad_samples noisy copies at
+--smoothgrad_sigma in chunks of --smoothgrad_batch; captum's NoiseTunnel); `--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad), the deletion and insertion scores of
+the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`.  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
 
@@ -21,7 +25,9 @@ post-processing of these PNGs and is not reproduced.
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
         [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250] \
-        [--scorecam true --scorecam_batch 250] [--causal true --causal_step 224]"""
+        [--scorecam true --scorecam_batch 250] [--ig true --ig_steps 50 --ig_batch 50] \
+        [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
+        [--causal true --causal_step 224]"""
 import argparse
 import os
 
@@ -117,11 +123,49 @@ def run_scorecam(args, model, image, out_dir):
     return maps
 
 
+def _ig(args, model, x, classes=None):
+    from .tools.attribution import integrated_gradients
+    return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
+                                batch=int(getattr(args, "ig_batch", 50)))
+
+
+def _smoothgrad(args, model, x, classes=None):
+    from .tools.attribution import smoothgrad
+    return smoothgrad(model, x, classes=classes, n_samples=int(getattr(args, "smoothgrad_samples", 50)),
+                      sigma=float(getattr(args, "smoothgrad_sigma", 1.0)), batch=int(getattr(args, "smoothgrad_batch", 50)))
+
+
+def _run_gradient_family(args, model, image, out_dir, attribute, stem):
+    from PIL import Image
+    from .tools.attribution import gradient_maps
+    os.makedirs(out_dir, exist_ok=True)
+    attr = attribute(args, model, image.unsqueeze(0).to(args.device, dtype=torch.float32))
+    maps = gradient_maps(attr, min_level=float(args.grad_min_level))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "%s_%d.png" % (stem, c)))
+    return maps
+
+
+def run_ig(args, model, image, out_dir):
+    """--ig true: the Integrated Gradients attribution of every class for the one image (captum's IntegratedGradients of the
+    reference's captum_vis.py: zero baseline, Gauss-Legendre, --ig_steps steps) -> `<out>/ig_{c}.png`, uint8 maps at the input
+    resolution drawn on the device (tools/attribution.py gradient_maps, floored at --grad_min_level); returns them [C, H, W]."""
+    return _run_gradient_family(args, model, image, out_dir, _ig, "ig")
+
+
+def run_smoothgrad(args, model, image, out_dir):
+    """--smoothgrad true: the SmoothGrad attribution of every class for the one image (captum's NoiseTunnel of the reference's
+    captum_vis.py: --smoothgrad_samples noisy copies at --smoothgrad_sigma) -> `<out>/smoothgrad_{c}.png`, drawn like run_ig;
+    returns the uint8 maps [C, H, W]."""
+    return _run_gradient_family(args, model, image, out_dir, _smoothgrad, "smoothgrad")
+
+
 def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
-    mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam), one printed line each; returns
-    {family: (deletion, insertion)}."""
+    mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
+    integrated_gradients / smoothgrad), one printed line each; returns {family: (deletion, insertion)}."""
+    from . import kernels as K
     from .tools.attribution import causal_metrics, gradcam, input_gradients, rise, scorecam
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
     step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
@@ -135,6 +179,10 @@ def run_causal(args, model, image, pred, families, slot_map=None):
             maps = gradcam(model, x, classes=[pred])
         elif family == "scorecam":
             maps = scorecam(model, x, classes=[pred], batch=int(getattr(args, "scorecam_batch", 250)))
+        elif family == "ig":
+            maps = K.channel_mean(_ig(args, model, x, classes=[pred]))
+        elif family == "smoothgrad":
+            maps = K.channel_mean(_smoothgrad(args, model, x, classes=[pred]))
         else:
             maps = rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)), batch=batch)
         r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
@@ -163,6 +211,15 @@ def get_test_parser():
     parser.add_argument("--scorecam", default=False, type=_flag,
                         help="true: write the Score-CAM heat map of every class as scorecam_{c}.png into --vis_dir")
     parser.add_argument("--scorecam_batch", default=250, type=int, help="masked images per forward of --scorecam")
+    parser.add_argument("--ig", default=False, type=_flag,
+                        help="true: write the Integrated Gradients map of every class as ig_{c}.png into --vis_dir")
+    parser.add_argument("--ig_steps", default=50, type=int, help="Gauss-Legendre steps of --ig")
+    parser.add_argument("--ig_batch", default=50, type=int, help="path images per forward and backward of --ig")
+    parser.add_argument("--smoothgrad", default=False, type=_flag,
+                        help="true: write the SmoothGrad map of every class as smoothgrad_{c}.png into --vis_dir")
+    parser.add_argument("--smoothgrad_samples", default=50, type=int, help="noisy copies per class of --smoothgrad")
+    parser.add_argument("--smoothgrad_sigma", default=1.0, type=float, help="standard deviation of the noise of --smoothgrad")
+    parser.add_argument("--smoothgrad_batch", default=50, type=int, help="noisy copies per forward and backward of --smoothgrad")
     return parser
 
 
@@ -201,9 +258,13 @@ def main():
         run_rise(args, model, image, args.vis_dir)
     if args.scorecam:
         run_scorecam(args, model, image, args.vis_dir)
+    if args.ig:
+        run_ig(args, model, image, args.vis_dir)
+    if args.smoothgrad:
+        run_smoothgrad(args, model, image, args.vis_dir)
     if args.causal:
         families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
-                                    ("scorecam", args.scorecam)) if on]
+                                    ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad)) if on]
         run_causal(args, model, image, pred, families, slot_map)
     print(out)
     print(pred)

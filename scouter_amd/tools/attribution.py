@@ -31,8 +31,20 @@ model, and every channel is weighted by the class probability its mask produced.
 forward per channel (512 for resnet18, 2048 for resnest26d / resnest50d; BatchNorm-folded when the model's inference fold is
 on).  A mask exists only as its channel's h x w source values and its range; the ranges, the masked batch and the weighted sum
 are three HIP kernels (kernels.scorecam_ranges, kernels.scorecam_mask_images, kernels.scorecam_accumulate) and nothing comes
-to the host in between."""
+to the host in between.
+
+Gradient methods that need many gradients per image (`integrated_gradients`, `smoothgrad`, `gradient_maps`, `ig_quadrature`):
+Integrated Gradients (Sundararajan et al. 2017) and SmoothGrad / SmoothGrad-squared / VarGrad (Smilkov et al. 2017), what the
+reference's captum_vis.py runs with captum's IntegratedGradients and NoiseTunnel.  The images on the path from a baseline to
+the image, or the image plus Gaussian noise, are written straight into one reused batch buffer (kernels.path_images,
+kernels.noise_images: Philox4x32-10 and Box-Muller, a value per (seed, sample, element)), the model's own eval forward and
+backward give the gradients of a chunk, and they are summed in float64 in sample order (kernels.grad_accumulate), so the
+chunking does not change a bit; kernels.attr_finish forms the result and, for Integrated Gradients, its sum for the
+completeness check.  kernels.channel_mean and kernels.heat_maps draw the result on the device (`gradient_maps`, the device
+counterpart of `attribution_maps`).  Nothing comes to the host in between.  Both work for any module whose eval forward
+returns [n, n_outputs]."""
 import collections
+import functools
 
 import numpy as np
 import torch
@@ -500,3 +512,207 @@ def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen
     scores = K.causal_auc(curves)
     return CausalScores(scores[:, :, 0].contiguous(), scores[:, :, 1].contiguous(), curves[:, :, 0].contiguous(),
                         curves[:, :, 1].contiguous(), step)
+
+
+def ig_quadrature(n_steps=50, method="gausslegendre"):
+    """The nodes and weights of `integrated_gradients` on [0, 1] as fp32 CPU tensors (alphas [n_steps], weights [n_steps]), built
+    in float64 and rounded once.  "gausslegendre": numpy.polynomial.legendre.leggauss(n_steps) mapped from [-1, 1] (captum's
+    default); "riemann_trapezoid": linspace(0, 1, n_steps) with the end weights 1 / (2 (n - 1)) and the inner weights
+    1 / (n - 1), n_steps >= 2."""
+    n_steps = int(n_steps)
+    if method not in ("gausslegendre", "riemann_trapezoid"):
+        raise ValueError("method must be 'gausslegendre' or 'riemann_trapezoid', got %r" % (method,))
+    if n_steps < 1 or (method == "riemann_trapezoid" and n_steps < 2):
+        raise ValueError("n_steps must be at least %d for %s, got %d" % (2 if method == "riemann_trapezoid" else 1, method, n_steps))
+    alphas, weights = _quadrature_fp32(n_steps, method)
+    return torch.from_numpy(alphas.copy()), torch.from_numpy(weights.copy())
+
+
+@functools.lru_cache(maxsize=32)
+def _quadrature_fp32(n_steps, method):
+    """the float64 tables of ig_quadrature rounded to fp32 (kept: leggauss solves an eigenproblem of size n_steps)"""
+    if method == "gausslegendre":
+        x, w = np.polynomial.legendre.leggauss(n_steps)
+        alphas, weights = 0.5 * (x + 1.0), 0.5 * w
+    else:
+        alphas = np.linspace(0.0, 1.0, n_steps)
+        weights = np.full(n_steps, 1.0 / (n_steps - 1))
+        weights[0] = weights[-1] = 0.5 / (n_steps - 1)
+    return alphas.astype(np.float32), weights.astype(np.float32)
+
+
+def _class_columns(classes, B, n):
+    """the `classes` argument of gradcam / rise -> (per_image, cols): None (every output), a list of ints, or a LongTensor [B]"""
+    per_image = torch.is_tensor(classes)
+    if per_image:
+        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
+                             % (B, classes.dtype, tuple(classes.shape)))
+        cols = classes.detach().cpu().tolist()
+    else:
+        cols = [int(c) for c in (classes if classes is not None else range(n))]
+    for c in cols:
+        if not 0 <= c < n:
+            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    return per_image, cols
+
+
+def _chunk_gradient(model, chunk, seed):
+    """d sum(out * seed) / d chunk for a batch that lives in the reused buffer: the chunk becomes a leaf (no copy), one eval
+    forward, one backward with the leading rows of the one-hot `seed` [batch, n_outputs]"""
+    x = chunk.detach().requires_grad_(True)
+    g = torch.autograd.grad(model(x), x, seed[:x.shape[0]])[0]
+    return g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()
+
+
+def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, want_sq, finish, totals=None):
+    """the loop shared by integrated_gradients and smoothgrad: image, then class, then chunk.  (per_image, cols) come from
+    _class_columns for a model of n outputs; fill(b, buf, first) writes the images first .. first + len(buf) - 1 of image b's
+    batch of N into buf; finish(b, acc, acc_sq, out, total) forms out[b, k]."""
+    B, C, H, W = images.shape
+    dev = images.device
+    Kc = 1 if per_image else len(cols)
+    out = torch.empty((B, Kc, C, H, W), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
+    seed = torch.zeros((min(batch, N), n), dtype=torch.float32, device=dev)
+    acc = torch.empty((C, H, W), dtype=torch.float64, device=dev)
+    acc_sq = torch.empty_like(acc) if want_sq else None
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.enable_grad():
+            for b in range(B):
+                for k, c in enumerate(cols[b:b + 1] if per_image else cols):
+                    acc.zero_()
+                    if want_sq:
+                        acc_sq.zero_()
+                    seed.zero_()
+                    seed[:, c] = 1.0
+                    for first in range(0, N, batch):
+                        chunk = fill(b, buf[:min(batch, N - first)], first)
+                        K.grad_accumulate(_chunk_gradient(model, chunk, seed), weights, acc, acc_sq, first)
+                    finish(b, acc, acc_sq, out[b, k], None if totals is None else totals[b, k:k + 1])
+    finally:
+        model.train(was_training)
+    return out
+
+
+def _check_images_batch(images, batch):
+    if images.dim() != 4:
+        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1, got %d" % batch)
+    x = images.detach().contiguous()
+    return (x.float() if x.dtype != torch.float32 else x), batch
+
+
+def integrated_gradients(model, images, classes=None, baseline=None, n_steps=50, method="gausslegendre", batch=50,
+                         return_delta=False):
+    """Integrated Gradients (Sundararajan et al., ICML 2017; captum's IntegratedGradients) of `images` [B, C, H, W] -> fp32
+    [B, K, C, H, W] on the images' device:
+    attr[b, k] = (x_b - x'_b) * sum_i w_i * d out[:, c_k] / dx at x'_b + alpha_i (x_b - x'_b),
+    out the eval-mode model output as in input_gradients(of="log_prob"), (alpha_i, w_i) = ig_quadrature(n_steps, method) (built
+    on the host in float64, rounded to fp32, uploaded once) and x' the `baseline`: None (zeros), [C, H, W] (one for the batch) or
+    [B, C, H, W].  classes as in `gradcam` / `rise`: None (every output), a list of ints (K = len), or a LongTensor [B] (each
+    image its own class, K = 1).
+
+    Per image and class the n_steps path images go through the model in chunks of `batch` (the last may be shorter):
+    kernels.path_images into one reused buffer, which becomes the leaf of an eval-mode forward (the caller's mode is restored)
+    and of one backward with a one-hot column, kernels.grad_accumulate onto float64 sums in step order -- the chunking does not
+    change a bit -- and kernels.attr_finish at the end of the class.  return_delta=True: also `delta` fp32 [B, K] =
+    sum(attr[b, k]) - (out(x_b)[c_k] - out(x'_b)[c_k]), the completeness gap, from the float64 sum of attr_finish and one extra
+    no_grad forward of [x'_b, x_b] per image.  No BatchNorm buffer moves, nothing is copied to the host and nothing synchronises
+    inside the loop; parameters that require grad get their `.grad` overwritten by each backward, as in `input_gradients`.  Any
+    module whose eval forward returns [n, n_outputs] will do."""
+    x, batch = _check_images_batch(images, batch)
+    B, C, H, W = x.shape
+    alphas, weights = ig_quadrature(n_steps, method)
+    dev = x.device
+    if baseline is not None:
+        if not torch.is_tensor(baseline) or tuple(baseline.shape) not in ((C, H, W), (B, C, H, W)):
+            raise ValueError("baseline must be None, [%d, %d, %d] or [%d, %d, %d, %d], got %s"
+                             % (C, H, W, B, C, H, W, tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__))
+        baseline = baseline.detach().to(dev, dtype=torch.float32).contiguous()
+    alphas, weights = alphas.to(dev), weights.to(dev)
+
+    def base_of(b):
+        return None if baseline is None else baseline if baseline.dim() == 3 else baseline[b]
+
+    def fill(b, buf, first):
+        return K.path_images(x[b], base_of(b), alphas, buf, first)
+
+    def finish(b, acc, acc_sq, out, total):
+        K.attr_finish(K.ATTR_IG, acc, image=x[b], base=base_of(b), out=out, total=total)
+
+    n = _num_outputs(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    Kc = 1 if per_image else len(cols)
+    totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    attr = _path_method(model, x, n, per_image, cols, batch, int(alphas.shape[0]), fill, weights, False, finish, totals)
+    if not return_delta:
+        return attr
+    delta = torch.zeros((B, Kc), dtype=torch.float32, device=dev)
+    if Kc:
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                for b in range(B):
+                    base = base_of(b)
+                    ends = model(torch.stack([torch.zeros_like(x[b]) if base is None else base, x[b]])).double()
+                    cb = cols[b:b + 1] if per_image else cols
+                    delta[b] = (totals[b] - (ends[1, cb] - ends[0, cb])).float()
+        finally:
+            model.train(was_training)
+    return attr, delta
+
+
+_SMOOTHGRAD_KINDS = {"smoothgrad": K.ATTR_MEAN, "smoothgrad_sq": K.ATTR_MEAN_SQ, "vargrad": K.ATTR_VAR}
+
+
+def smoothgrad(model, images, classes=None, n_samples=50, sigma=1.0, kind="smoothgrad", batch=50, seed=0):
+    """SmoothGrad (Smilkov et al. 2017; captum's NoiseTunnel over Saliency with stdevs = sigma) of `images` [B, C, H, W] -> fp32
+    [B, K, C, H, W] on the images' device, from the gradients g_s = d out[:, c_k] / dx at x_b + sigma * z_s, s < n_samples, out
+    the eval-mode model output as in input_gradients(of="log_prob"): kind "smoothgrad" is their mean, "smoothgrad_sq" the mean
+    of their squares, "vargrad" their biased variance (mean of squares minus squared mean).  z_s is standard normal, a function
+    of (seed, s, element) alone (kernels.noise_images): sample s of every image and class uses the same noise, and the same
+    seed repeats bit for bit.  sigma is absolute (>= 0), not relative to the image's range.  classes as in `gradcam` / `rise`.
+
+    The loop is that of `integrated_gradients`: kernels.noise_images into one reused buffer in chunks of `batch`, an eval-mode
+    forward and one backward with a one-hot column, kernels.grad_accumulate onto float64 sums in sample order,
+    kernels.attr_finish at the end of the class, with the same guarantees -- no BatchNorm buffer moves, the caller's mode is
+    restored, nothing is copied to the host or synchronises inside the loop, `.grad` of parameters that require grad is
+    overwritten."""
+    x, batch = _check_images_batch(images, batch)
+    n_samples, sigma = int(n_samples), float(sigma)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    if not 0.0 <= sigma < float("inf"):
+        raise ValueError("sigma must be finite and not negative, got %r" % (sigma,))
+    if kind not in _SMOOTHGRAD_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(_SMOOTHGRAD_KINDS), kind))
+    mode = _SMOOTHGRAD_KINDS[kind]
+
+    def fill(b, buf, first):
+        return K.noise_images(x[b], buf, sigma, seed, first)
+
+    def finish(b, acc, acc_sq, out, total):
+        K.attr_finish(mode, acc, acc_sq, inv_n=1.0 / n_samples, out=out)
+
+    n = _num_outputs(model, x)
+    per_image, cols = _class_columns(classes, x.shape[0], n)
+    return _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, mode != K.ATTR_MEAN, finish)
+
+
+def gradient_maps(attr, min_level=0.0, absolute=False):
+    """[B, K, C, H, W] attributions on the device -> uint8 maps [B, K, H, W] on the device, the device counterpart of
+    `attribution_maps`: the mean over the channels (absolute: of the magnitudes; kernels.channel_mean), then the drawing steps of
+    kernels.heat_maps -- negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled again, times
+    255.  A map that is constant at either scaling step is all zeros."""
+    if not torch.is_tensor(attr) or attr.dim() != 5:
+        raise ValueError("attr must be a tensor [B, K, C, H, W], got %s"
+                         % (tuple(attr.shape) if torch.is_tensor(attr) else type(attr).__name__,))
+    return K.heat_maps(K.channel_mean(attr.detach().contiguous(), absolute=absolute), min_level)
