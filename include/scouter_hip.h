@@ -351,6 +351,33 @@ int scouter_attr_finish_f32(int mode, const double* acc, const double* acc_sq, c
  * is not 0; the sum runs over ascending c in fp64 and is divided by C in fp64. */
 int scouter_channel_mean_f32(const float* x, float* out, long M, int C, long HW, int absolute, void* stream);
 
+/* ---- Grad-CAM++ (Chattopadhay et al., WACV 2018) and Smooth Grad-CAM++ (Omeiza et al. 2019) at the backbone's output: torchcam's
+ * GradCAMpp / SmoothGradCAMpp of the reference's torchcam_vis.py (torchcam/cams/gradcam.py:104-272; csrc/gradcampp.hip,
+ * tools/attribution.py gradcampp / smooth_gradcampp).  feat = A and dfeat = g NHWC fp32 [B][N = h*w][C], 16-byte aligned.  Per
+ * image: S[c] = sum_p g[p][c]^3 * A[p][c], den[p][c] = 2 * g[p][c]^2 + S[c], alpha[p][c] = g[p][c]^2 / den[p][c] and 0 where
+ * den == 0 (the reference divides 0 / 0 there and later replaces the NaN product by 1), w[c] = sum_p alpha[p][c] * max(g[p][c], 0),
+ * out[b * out_stride + p] = sum_c w[c] * A[p][c] (relu != 0: clamped at 0) -- out is fp32 [B][N] written through a batch stride
+ * in elements, as in scouter_gradcam_f32.  All in fp32.  One workgroup per image and three passes: S and w by column (dfeat is
+ * read twice, feat twice), then one wave per position; S and w live in LDS.  One fixed summation order per element and no
+ * atomics: bit-identical run to run.  Any N >= 1 and 1 <= C <= 8192.  A null or misaligned pointer, B, N or C below 1, or a batch
+ * stride below N: SC_ERR_ARG; C above 8192 or an image past 32-bit offsets: SC_ERR_UNSUPPORTED; nothing is launched then. */
+int scouter_gradcampp_f32(const float* feat, const float* dfeat, float* out, int B, int N, int C, long out_stride, int relu,
+                          void* stream);
+/* acc2 fp64 [E] += sum_j g[j][e]^2 and acc3 fp64 [E] += sum_j g[j][e]^3 for grads fp32 [n][E]: the sums run in ascending j in
+ * fp64 and start from the values in acc2 / acc3; g^2 is exact, g^2 * g takes one rounding inside the fma that adds it.  No
+ * partial sums: splitting the terms over calls at any point gives the bits of one call (the contract of
+ * scouter_grad_accumulate_f64).  A null or misaligned pointer (fp32: 4 bytes, fp64: 8), acc2 == acc3, n or E below 1:
+ * SC_ERR_ARG; n * E of 2^31 or more: SC_ERR_UNSUPPORTED. */
+int scouter_grad_powers_accumulate(const float* grads, double* acc2, double* acc3, int n, long E, void* stream);
+/* Smooth Grad-CAM++ from the sums of scouter_grad_powers_accumulate over the n_samples noisy copies of an image: q = acc2 /
+ * n_samples and t = acc3 / n_samples (fp64 [B][N][C]; 16-byte aligned when C is a multiple of 4, like glast), S[c] = sum_p t[p][c] * A[p][c], alpha = q / (2 * q + S[c])
+ * and 0 where the denominator is 0, w[c] = sum_p alpha[p][c] * max(glast[p][c], 0) -- glast fp32 [B][N][C] is the gradient of the
+ * LAST sample, as the reference has it (gradcam.py:272) -- all in fp64, w rounded to fp32 once; out as above from the clean
+ * image's features feat, in fp32.  The same kernel plan, argument rules and errors as scouter_gradcampp_f32; n_samples below 1:
+ * SC_ERR_ARG. */
+int scouter_gradcampp_smooth_f32(const float* feat, const double* acc2, const double* acc3, const float* glast, float* out,
+                                 int n_samples, int B, int N, int C, long out_stride, int relu, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

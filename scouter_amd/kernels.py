@@ -1660,6 +1660,17 @@ def resize_normalize(images_u8, out_size, lut, out=None):
 # ---------------------------------------------------------------------------------------------------------------
 # Grad-CAM (csrc/gradcam.hip; tools/attribution.py gradcam / gradcam_maps)
 # ---------------------------------------------------------------------------------------------------------------
+def _cam_out_chk(what, feat, out):
+    """feat NHWC [B, h, w, C], out fp32 [B, h, w] or [B, h * w] dense within an image -> (B, N, C)"""
+    B, h, w, C = feat.shape
+    N = h * w
+    if not out.is_cuda or out.dtype != F32 or out.dim() not in (2, 3) or out.shape[0] != B or out[0].numel() != N or \
+            (N > 0 and not out[0].is_contiguous()):
+        raise RuntimeError("%s: out must be fp32 [B, h, w] or [B, h * w] on the device, dense within an image (got %s %s, "
+                           "strides %s)" % (what, out.dtype, tuple(out.shape), out.stride()))
+    return B, N, C
+
+
 def gradcam(feat, dfeat, out, relu=False):
     """out[b, p] = sum_c mean_p'(dfeat[b, p', c]) * feat[b, p, c] (relu: clamped at 0) for NHWC fp32 feat / dfeat [B, h, w, C].
     `out` is fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride: a column `t[:, k]` of a [B, K, h, w] tensor
@@ -1668,12 +1679,7 @@ def gradcam(feat, dfeat, out, relu=False):
     if feat.dim() != 4 or dfeat.shape != feat.shape:
         raise RuntimeError("gradcam: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
                            % (tuple(feat.shape), tuple(dfeat.shape)))
-    B, h, w, C = feat.shape
-    N = h * w
-    if not out.is_cuda or out.dtype != F32 or out.dim() not in (2, 3) or out.shape[0] != B or out[0].numel() != N or \
-            (N > 0 and not out[0].is_contiguous()):
-        raise RuntimeError("gradcam: out must be fp32 [B, h, w] or [B, h * w] on the device, dense within an image (got %s %s, "
-                           "strides %s)" % (out.dtype, tuple(out.shape), out.stride()))
+    B, N, C = _cam_out_chk("gradcam", feat, out)
     _native.check(_native.lib().scouter_gradcam_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(relu)),
                                                     _stream()), "gradcam")
     return out
@@ -1695,6 +1701,55 @@ def cam_maps(cam, H, W, min_level=0.0):
     out = torch.empty(lead + (int(H), int(W)), dtype=torch.uint8, device=cam.device)
     _native.check(_native.lib().scouter_cam_maps_u8(_p(cam), _p(out), M, h, w, int(H), int(W), float(min_level), _stream()),
                   "cam_maps")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Grad-CAM++ / Smooth Grad-CAM++ (csrc/gradcampp.hip; tools/attribution.py gradcampp / smooth_gradcampp)
+# ---------------------------------------------------------------------------------------------------------------
+def gradcampp(feat, dfeat, out, relu=True):
+    """Grad-CAM++ for NHWC fp32 feat = A / dfeat = g [B, h, w, C]: S[c] = sum_p g^3 A, alpha = g^2 / (2 g^2 + S[c]) (0 where the
+    denominator is 0), w[c] = sum_p alpha max(g, 0), out[b, p] = sum_c w[c] A[b, p, c] (relu: clamped at 0), all in fp32.  `out`
+    as in `gradcam`: fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride.  One launch, one fixed summation
+    order per element (two calls give the same bits)."""
+    _chk(feat, "gradcampp: feat"); _chk(dfeat, "gradcampp: dfeat")
+    if feat.dim() != 4 or dfeat.shape != feat.shape:
+        raise RuntimeError("gradcampp: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
+                           % (tuple(feat.shape), tuple(dfeat.shape)))
+    B, N, C = _cam_out_chk("gradcampp", feat, out)
+    _native.check(_native.lib().scouter_gradcampp_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(relu)),
+                                                      _stream()), "gradcampp")
+    return out
+
+
+def grad_powers_accumulate(grads, acc2, acc3):
+    """acc2 += sum_j grads[j]^2 and acc3 += sum_j grads[j]^3 for fp32 grads [n, ...] and fp64 acc2 / acc3 of one gradient's
+    shape.  fp64 products and sums in ascending j onto the values in acc2 / acc3: calls over consecutive pieces give the bits
+    of one call (the contract of `grad_accumulate`).  One launch."""
+    _chk(grads, "grad_powers_accumulate: grads")
+    _chk(acc2, "grad_powers_accumulate: acc2", torch.float64); _chk(acc3, "grad_powers_accumulate: acc3", torch.float64)
+    if grads.dim() < 1 or tuple(grads.shape[1:]) != tuple(acc2.shape) or tuple(acc3.shape) != tuple(acc2.shape):
+        raise RuntimeError("grad_powers_accumulate: grads must be [n, *acc2.shape] and acc3 like acc2 (got %s, %s and %s)"
+                           % (tuple(grads.shape), tuple(acc2.shape), tuple(acc3.shape)))
+    _native.check(_native.lib().scouter_grad_powers_accumulate(_p(grads), _p(acc2), _p(acc3), int(grads.shape[0]),
+                                                               int(acc2.numel()), _stream()), "grad_powers_accumulate")
+    return acc2, acc3
+
+
+def gradcampp_smooth(feat, acc2, acc3, glast, out, n_samples, relu=True):
+    """Smooth Grad-CAM++ from the sums of `grad_powers_accumulate` over `n_samples` noisy copies: q = acc2 / n, t = acc3 / n (fp64
+    [B, h, w, C]), S[c] = sum_p t A, alpha = q / (2 q + S[c]) (0 where the denominator is 0), w[c] = sum_p alpha max(glast, 0) in
+    fp64 -- glast fp32 [B, h, w, C] is the LAST sample's gradient -- and out[b, p] = sum_c w[c] A[b, p, c] in fp32 (relu: clamped
+    at 0) with feat = A the clean image's features.  `out` as in `gradcampp`.  One launch, two calls give the same bits."""
+    _chk(feat, "gradcampp_smooth: feat"); _chk(glast, "gradcampp_smooth: glast")
+    _chk(acc2, "gradcampp_smooth: acc2", torch.float64); _chk(acc3, "gradcampp_smooth: acc3", torch.float64)
+    if feat.dim() != 4 or glast.shape != feat.shape or acc2.shape != feat.shape or acc3.shape != feat.shape:
+        raise RuntimeError("gradcampp_smooth: feat %s, acc2 %s, acc3 %s and glast %s must be the same NHWC [B, h, w, C] shape"
+                           % (tuple(feat.shape), tuple(acc2.shape), tuple(acc3.shape), tuple(glast.shape)))
+    B, N, C = _cam_out_chk("gradcampp_smooth", feat, out)
+    _native.check(_native.lib().scouter_gradcampp_smooth_f32(_p(feat), _p(acc2), _p(acc3), _p(glast), _p(out), int(n_samples), B,
+                                                             N, C, out.stride(0), int(bool(relu)), _stream()),
+                  "gradcampp_smooth")
     return out
 
 

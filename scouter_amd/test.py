@@ -15,8 +15,12 @@ torchcam_vis.py); `--ig true` the per-class Integrated Gradients maps `<out>/ig_
 integrated_gradients: --ig_steps Gauss-Legendre steps from a zero baseline in chunks of --ig_batch, drawn by gradient_maps,
 floored at --grad_min_level; captum's IntegratedGradients of the reference's captum_vis.py); `--smoothgrad true` the per-class
 SmoothGrad maps `<out>/smoothgrad_{c}.png` (tools/attribution.py smoothgrad: --smoothgrad_samples noisy copies at
---smoothgrad_sigma in chunks of --smoothgrad_batch; captum's NoiseTunnel); `--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad), the deletion and insertion scores of
+--smoothgrad_sigma in chunks of --smoothgrad_batch; captum's NoiseTunnel); `--campp true` the per-class Grad-CAM++ heat maps
+`<out>/campp_{c}.png` (tools/attribution.py gradcampp_maps: one backbone forward, floored at --grad_min_level, BatchNorm-folded
+under --eval_fold; torchcam's GradCAMpp of the reference's torchcam_vis.py); `--smoothcampp true` the per-class Smooth Grad-CAM++
+heat maps `<out>/smoothcampp_{c}.png` (tools/attribution.py smooth_gradcampp: --smoothcampp_samples noisy copies at
+--smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`.  The jet-colormap overlay of test.py:33-38 is matplotlib
 post-processing of these PNGs and is not reproduced.
@@ -27,6 +31,7 @@ post-processing of these PNGs and is not reproduced.
         [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250] \
         [--scorecam true --scorecam_batch 250] [--ig true --ig_steps 50 --ig_batch 50] \
         [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
+        [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
         [--causal true --causal_step 224]"""
 import argparse
 import os
@@ -123,6 +128,38 @@ def run_scorecam(args, model, image, out_dir):
     return maps
 
 
+def run_campp(args, model, image, out_dir):
+    """--campp true: the Grad-CAM++ heat map of every class for the one image at the backbone's output (torchcam's GradCAMpp of
+    the reference's torchcam_vis.py) -> `<out>/campp_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import gradcampp_maps
+    os.makedirs(out_dir, exist_ok=True)
+    maps = gradcampp_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
+                          min_level=float(args.grad_min_level))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "campp_%d.png" % c))
+    return maps
+
+
+def _smoothcampp_kwargs(args):
+    return dict(n_samples=int(getattr(args, "smoothcampp_samples", 4)), sigma=float(getattr(args, "smoothcampp_sigma", 0.3)),
+                batch=int(getattr(args, "smoothcampp_batch", 4)))
+
+
+def run_smoothcampp(args, model, image, out_dir):
+    """--smoothcampp true: the Smooth Grad-CAM++ heat map of every class for the one image (torchcam's SmoothGradCAMpp:
+    --smoothcampp_samples noisy copies at --smoothcampp_sigma in chunks of --smoothcampp_batch) -> `<out>/smoothcampp_{c}.png`,
+    uint8 maps at the input resolution; returns them [C, H, W]."""
+    from PIL import Image
+    from .tools.attribution import smooth_gradcampp_maps
+    os.makedirs(out_dir, exist_ok=True)
+    maps = smooth_gradcampp_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
+                                 min_level=float(args.grad_min_level), **_smoothcampp_kwargs(args))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "smoothcampp_%d.png" % c))
+    return maps
+
+
 def _ig(args, model, x, classes=None):
     from .tools.attribution import integrated_gradients
     return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
@@ -164,9 +201,10 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
-    integrated_gradients / smoothgrad), one printed line each; returns {family: (deletion, insertion)}."""
+    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp), one printed line each; returns
+    {family: (deletion, insertion)}."""
     from . import kernels as K
-    from .tools.attribution import causal_metrics, gradcam, input_gradients, rise, scorecam
+    from .tools.attribution import causal_metrics, gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
     step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
     scores = {}
@@ -183,6 +221,10 @@ def run_causal(args, model, image, pred, families, slot_map=None):
             maps = K.channel_mean(_ig(args, model, x, classes=[pred]))
         elif family == "smoothgrad":
             maps = K.channel_mean(_smoothgrad(args, model, x, classes=[pred]))
+        elif family == "campp":
+            maps = gradcampp(model, x, classes=[pred])
+        elif family == "smoothcampp":
+            maps = smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
         else:
             maps = rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)), batch=batch)
         r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
@@ -220,6 +262,13 @@ def get_test_parser():
     parser.add_argument("--smoothgrad_samples", default=50, type=int, help="noisy copies per class of --smoothgrad")
     parser.add_argument("--smoothgrad_sigma", default=1.0, type=float, help="standard deviation of the noise of --smoothgrad")
     parser.add_argument("--smoothgrad_batch", default=50, type=int, help="noisy copies per forward and backward of --smoothgrad")
+    parser.add_argument("--campp", default=False, type=_flag,
+                        help="true: write the Grad-CAM++ heat map of every class as campp_{c}.png into --vis_dir")
+    parser.add_argument("--smoothcampp", default=False, type=_flag,
+                        help="true: write the Smooth Grad-CAM++ heat map of every class as smoothcampp_{c}.png into --vis_dir")
+    parser.add_argument("--smoothcampp_samples", default=4, type=int, help="noisy copies per class of --smoothcampp")
+    parser.add_argument("--smoothcampp_sigma", default=0.3, type=float, help="standard deviation of the noise of --smoothcampp")
+    parser.add_argument("--smoothcampp_batch", default=4, type=int, help="noisy copies per feature pass of --smoothcampp")
     return parser
 
 
@@ -262,9 +311,14 @@ def main():
         run_ig(args, model, image, args.vis_dir)
     if args.smoothgrad:
         run_smoothgrad(args, model, image, args.vis_dir)
+    if args.campp:
+        run_campp(args, model, image, args.vis_dir)
+    if args.smoothcampp:
+        run_smoothcampp(args, model, image, args.vis_dir)
     if args.causal:
         families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
-                                    ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad)) if on]
+                                    ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
+                                    ("campp", args.campp), ("smoothcampp", args.smoothcampp)) if on]
         run_causal(args, model, image, pred, families, slot_map)
     print(out)
     print(pred)

@@ -42,7 +42,17 @@ backward give the gradients of a chunk, and they are summed in float64 in sample
 chunking does not change a bit; kernels.attr_finish forms the result and, for Integrated Gradients, its sum for the
 completeness check.  kernels.channel_mean and kernels.heat_maps draw the result on the device (`gradient_maps`, the device
 counterpart of `attribution_maps`).  Nothing comes to the host in between.  Both work for any module whose eval forward
-returns [n, n_outputs]."""
+returns [n, n_outputs].
+
+Second-order class activation maps (`gradcampp`, `gradcampp_maps`, `smooth_gradcampp`, `smooth_gradcampp_maps`): Grad-CAM++
+(Chattopadhay et al. 2018) and Smooth Grad-CAM++ (Omeiza et al. 2019), the GradCAMpp and SmoothGradCAMpp the reference's
+torchcam_vis.py draws and the SCOUTER paper tabulates beside the slot maps.  They read the layer and the gradient `gradcam` reads
+-- one feature pass, one head backward per class, nothing walks into the backbone -- and weight every position of a channel by
+alpha = g^2 / (2 g^2 + sum_p g^3 A) before the rectified gradient is summed; the smooth variant averages g^2 and g^3 over noisy
+copies of the image (kernels.noise_images, float64 sums in sample order by kernels.grad_powers_accumulate, so the chunking does
+not change a bit) and rectifies the last sample's gradient, as the reference does.  The weighting and the contraction are HIP
+kernels (kernels.gradcampp, kernels.gradcampp_smooth); alpha is 0 where the reference divides 0 / 0.  Nothing comes to the host
+in between."""
 import collections
 import functools
 
@@ -121,30 +131,13 @@ def _minmax(m):
     return np.where(span > 0, (m - lo) / np.where(span > 0, span, 1.0), 0.0)
 
 
-def gradcam(model, images, classes=None, relu=False):
-    """Grad-CAM of `images` [B, C, H, W] at the backbone's output -> fp32 [B, K, h, w] on the images' device:
-    cam[b, k, p] = sum_c mean_p'(d out_k / d features[b, p', c]) * features[b, p, c], captum's LayerGradCam with
-    relu_attributions=False (`relu`: clamped at 0).
-
-    classes=None: every class, K = the number of outputs; a list of ints: K = len(classes), slice [:, k] belongs to the
-    log-probability of classes[k] (one head backward each, with a one-hot column as its seed); a LongTensor [B]: every image
-    its own class, one backward, K = 1.  One SlotModel.feature_pass for the batch -- eval mode, the caller's mode restored,
-    BatchNorm-folded when the model's inference fold is on; head parameters that require grad get their `.grad` overwritten
-    by each backward.  One feature gradient is alive at a time."""
+def _gradient_cam(model, images, classes, fill):
+    """the loop shared by gradcam and gradcampp: one feature pass, one head backward per column of `classes`, and
+    fill(features, feature gradient, cam[:, k]) for each -- one feature gradient alive at a time"""
     if images.dim() != 4:
         raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
-    B, n = images.shape[0], _num_classes(model, images)
-    per_image = torch.is_tensor(classes)
-    if per_image:
-        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
-            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
-                             % (B, classes.dtype, tuple(classes.shape)))
-        cols = classes.detach().cpu().tolist()
-    else:
-        cols = [int(c) for c in (classes if classes is not None else range(n))]
-    for c in cols:
-        if not 0 <= c < n:
-            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+    B = images.shape[0]
+    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
     fp = model.feature_pass(images)
     feat = fp.features
     _, h, w, _ = feat.shape
@@ -160,9 +153,22 @@ def gradcam(model, images, classes=None, relu=False):
             seed.zero_()
             seed[:, c] = 1.0
         dfeat = fp.grad(seed)
-        K.gradcam(feat, dfeat, cam[:, k], relu=relu)
+        fill(feat, dfeat, cam[:, k])
         del dfeat
     return cam
+
+
+def gradcam(model, images, classes=None, relu=False):
+    """Grad-CAM of `images` [B, C, H, W] at the backbone's output -> fp32 [B, K, h, w] on the images' device:
+    cam[b, k, p] = sum_c mean_p'(d out_k / d features[b, p', c]) * features[b, p, c], captum's LayerGradCam with
+    relu_attributions=False (`relu`: clamped at 0).
+
+    classes=None: every class, K = the number of outputs; a list of ints: K = len(classes), slice [:, k] belongs to the
+    log-probability of classes[k] (one head backward each, with a one-hot column as its seed); a LongTensor [B]: every image
+    its own class, one backward, K = 1.  One SlotModel.feature_pass for the batch -- eval mode, the caller's mode restored,
+    BatchNorm-folded when the model's inference fold is on; head parameters that require grad get their `.grad` overwritten
+    by each backward.  One feature gradient is alive at a time."""
+    return _gradient_cam(model, images, classes, lambda feat, dfeat, out: K.gradcam(feat, dfeat, out, relu=relu))
 
 
 def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
@@ -172,6 +178,99 @@ def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
     either scaling step is all zeros, like attribution_maps."""
     H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
     return K.cam_maps(gradcam(model, images, classes), H, W, min_level)
+
+
+def gradcampp(model, images, classes=None, relu=True):
+    """Grad-CAM++ (Chattopadhay et al., WACV 2018; torchcam's GradCAMpp) of `images` [B, C, H, W] at the backbone's output -> fp32
+    [B, K, h, w] on the images' device.  With A = features[b] (NHWC, p over the h w positions) and g = d out_k / d A:
+    S[c] = sum_p g[p, c]^3 A[p, c], alpha[p, c] = g[p, c]^2 / (2 g[p, c]^2 + S[c]), w[c] = sum_p alpha[p, c] max(g[p, c], 0),
+    cam[b, k, p] = sum_c w[c] A[p, c], clamped at 0 when `relu` is set (torchcam's final _relu; the default).
+
+    g is the gradient `gradcam` uses: out_k is the LOG-PROBABILITY of class k, the model's output, not the raw score the paper
+    and torchcam differentiate.  alpha is 0 where its denominator is 0 (a channel whose gradient vanishes): this DEPARTS from
+    the reference, which divides 0 / 0 there and whose _CAM.compute_cams then replaces the NaN product by 1, adding a constant
+    to the map -- the choice `attribution_maps` makes for its own 0 / 0.
+
+    classes, the feature pass, the head backwards and their side effects as in `gradcam`: None, a list of ints or a LongTensor
+    [B]; one SlotModel.feature_pass, one head backward per class, one feature gradient alive at a time; the weighting and the
+    contraction are one HIP kernel (kernels.gradcampp) that fills cam[:, k] in place."""
+    return _gradient_cam(model, images, classes, lambda feat, dfeat, out: K.gradcampp(feat, dfeat, out, relu=relu))
+
+
+def gradcampp_maps(model, images, classes=None, size=None, min_level=0.0, relu=True):
+    """uint8 Grad-CAM++ heat maps [B, K, H, W] on the device: `gradcampp`, then the drawing steps of `gradcam_maps` in one launch
+    (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W).  A map that is constant at either scaling step is all
+    zeros."""
+    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    return K.cam_maps(gradcampp(model, images, classes, relu=relu), H, W, min_level)
+
+
+def smooth_gradcampp(model, images, classes=None, n_samples=4, sigma=0.3, batch=4, seed=0, relu=True):
+    """Smooth Grad-CAM++ (Omeiza et al. 2019; torchcam's SmoothGradCAMpp, whose defaults num_samples = 4 and std = 0.3 these are)
+    of `images` [B, C, H, W] at the backbone's output -> fp32 [B, K, h, w] on the images' device.  The samples are
+    x_j = x_b + sigma z(seed, j), j < n_samples (kernels.noise_images: the noise of `smoothgrad`, added to the normalised model
+    input; sigma is absolute), g_j = d out_k / d features at x_j, q = mean_j g_j^2 and t = mean_j g_j^3.  With A the features of
+    the CLEAN image: S[c] = sum_p t[p, c] A[p, c], alpha = q / (2 q + S[c]), w[c] = sum_p alpha[p, c] max(g_last[p, c], 0),
+    cam[b, k, p] = sum_c w[c] A[p, c], clamped at 0 when `relu` is set.  g_last is the gradient of the LAST sample, j =
+    n_samples - 1, alone: that is what the reference rectifies (torchcam/cams/gradcam.py:272), not a mean over the samples.
+
+    As in `gradcampp`, out_k is the log-probability of class k and alpha is 0 where its denominator is 0.  classes as in
+    `gradcam`.  Per image: one clean SlotModel.feature_pass for A, then the noisy copies in chunks of `batch` (the last may be
+    shorter) written into one reused buffer, one feature pass per chunk and one head backward per class per chunk, whose
+    gradients are summed into per-class float64 sums of squares and cubes in sample order (kernels.grad_powers_accumulate), so
+    the chunking does not change a bit; kernels.gradcampp_smooth forms S, alpha and w in float64 and the map in fp32.  Eval
+    mode, the caller's mode restored, no BatchNorm buffer moves, nothing is copied to the host and nothing synchronises inside
+    the loop; head parameters that require grad get their `.grad` overwritten by each backward."""
+    x, batch = _check_images_batch(images, batch)
+    n_samples, sigma = int(n_samples), float(sigma)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    if not 0.0 <= sigma < float("inf"):
+        raise ValueError("sigma must be finite and not negative, got %r" % (sigma,))
+    B = x.shape[0]
+    n = _num_classes(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    Kc = 1 if per_image else len(cols)
+    dev = x.device
+    rows = min(batch, n_samples)
+    buf = torch.empty((rows,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+    onehot = torch.zeros((rows, n), dtype=torch.float32, device=dev)
+    out = acc2 = acc3 = glast = None
+    for b in range(B):
+        feat = model.feature_pass(x[b:b + 1]).features
+        if out is None:
+            _, h, w, C = feat.shape
+            out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+            acc2 = torch.empty((Kc, 1, h, w, C), dtype=torch.float64, device=dev)
+            acc3 = torch.empty_like(acc2)
+            glast = torch.empty((Kc, 1, h, w, C), dtype=torch.float32, device=dev)
+        if Kc == 0:
+            break
+        cb = cols[b:b + 1] if per_image else cols
+        acc2.zero_()
+        acc3.zero_()
+        for first in range(0, n_samples, batch):
+            m = min(batch, n_samples - first)
+            fp = model.feature_pass(K.noise_images(x[b], buf[:m], sigma, seed, first))
+            for k, c in enumerate(cb):
+                onehot.zero_()
+                onehot[:, c] = 1.0
+                g = fp.grad(onehot[:m])
+                K.grad_powers_accumulate(g, acc2[k, 0], acc3[k, 0])
+                if first + m == n_samples:
+                    glast[k, 0].copy_(g[m - 1])
+                del g
+            del fp
+        for k in range(Kc):
+            K.gradcampp_smooth(feat, acc2[k], acc3[k], glast[k], out[b:b + 1, k], n_samples, relu=relu)
+    return out
+
+
+def smooth_gradcampp_maps(model, images, classes=None, size=None, min_level=0.0, **smooth_kwargs):
+    """uint8 Smooth Grad-CAM++ heat maps [B, K, H, W] on the device: `smooth_gradcampp` (its keyword arguments pass through), then
+    the drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
+    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    return K.cam_maps(smooth_gradcampp(model, images, classes, **smooth_kwargs), H, W, min_level)
 
 
 RiseMasks = collections.namedtuple("RiseMasks", "grids shifts s p size cell")
