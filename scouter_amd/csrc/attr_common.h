@@ -1,0 +1,252 @@
+// The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
+// pathgrad.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
+// scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
+// same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
+#pragma once
+#include "common.h"
+
+// the class-map kernels (gradcam_kernel, gradcampp_kernel): one workgroup per image, the channel weights in LDS
+constexpr int AT_THREADS = 1024, AT_WAVES = AT_THREADS / 64, AT_MAX_C = 8192, AT_PART = AT_THREADS * 4;
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Bilinear resize, align_corners = False: src = (dst + 0.5) scale - 0.5 clamped at 0 with scale = in / out, the lower index
+// clamped to n - 1, the upper one min(lower + 1, n - 1).  Every index is clamped, so no value moves an address.
+
+// source coordinate of destination index d: the lower neighbour, the upper one and its weight
+__device__ __forceinline__ void at_source(int d, float scale, int n, int& i0, int& i1, float& t) {
+    float s = fmaf((float)d + 0.5f, scale, -0.5f);
+    s = fmaxf(s, 0.f);
+    i0 = min((int)s, n - 1);
+    i1 = min(i0 + 1, n - 1);
+    t = s - (float)i0;
+}
+
+// the blend of the upper row's neighbours a0 / a1 and the lower row's b0 / b1 with column weight tx and row weight ty: three fmas
+__device__ __forceinline__ float at_bilerp(float a0, float a1, float b0, float b1, float tx, float ty) {
+    const float top = fmaf(tx, a1 - a0, a0), bot = fmaf(tx, b1 - b0, b0);
+    return fmaf(ty, bot - top, top);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// minimum and maximum over a wave (butterfly; valid in every lane) ...
+__device__ __forceinline__ void at_wave_minmax(float& lo, float& hi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+    }
+}
+
+// ... and over a workgroup of WAVES waves, the waves in order through s_lo / s_hi [WAVES]; valid in every thread
+template <int WAVES>
+__device__ __forceinline__ void at_block_minmax(float& lo, float& hi, float* s_lo, float* s_hi) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    at_wave_minmax(lo, hi);
+    if (lane == 0) { s_lo[wv] = lo; s_hi[wv] = hi; }
+    __syncthreads();
+    lo = s_lo[0]; hi = s_hi[0];
+#pragma unroll
+    for (int k = 1; k < WAVES; ++k) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); }
+}
+
+// The two min-max scalings of a heat map as one affine map of v: ((v - lo) / span1 raised to lo2, minus lo2) / span2, to a byte.
+// After the first scaling the minimum is exactly 0 and the maximum exactly 1, so the extrema of max(., min_level) are
+// lo2 = max(0, min_level) and max(1, min_level).  A map that is constant at either step (or has a NaN / infinity in it) is flat.
+struct AtHeatScale {
+    float lo, span1, lo2, span2, min_level;
+    bool flat;
+    __device__ __forceinline__ AtHeatScale(float lo_, float hi, float min_level_) : lo(lo_), min_level(min_level_) {
+        span1 = hi - lo;
+        lo2 = fmaxf(0.f, min_level);
+        span2 = fmaxf(1.f, min_level) - lo2;
+        flat = !(span1 > 0.f) || !(span2 > 0.f);
+    }
+    __device__ __forceinline__ unsigned char byte(float v) const {
+        float c = 0.f;
+        if (!flat) {
+            const float a = fmaxf((v - lo) / span1, min_level);
+            c = fminf(fmaxf((a - lo2) / span2, 0.f), 1.f);
+        }
+        return (unsigned char)(int)(255.f * c);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// V = 1 or 4 consecutive elements with the widest access V allows (at most 16 bytes each); NT: streamed once, non-temporal
+template <int V, bool NT = false>
+__device__ __forceinline__ void at_load(const float* __restrict__ p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        f32x4 t;
+        if constexpr (NT) t = __builtin_nontemporal_load((const f32x4*)p);
+        else t = *(const f32x4*)p;
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+        v[0] = *p;
+    }
+}
+template <int V>
+__device__ __forceinline__ void at_load(const double* __restrict__ p, double (&v)[V]) {
+    if constexpr (V == 1) {
+        v[0] = *p;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; k += 2) {
+            const f64x2 t = *(const f64x2*)(p + k);
+            v[k] = t[0]; v[k + 1] = t[1];
+        }
+    }
+}
+template <int V>
+__device__ __forceinline__ void at_store(double* __restrict__ p, const double (&v)[V]) {
+    if constexpr (V == 1) {
+        *p = v[0];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; k += 2) *(f64x2*)(p + k) = f64x2{v[k], v[k + 1]};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The two passes of a class-map kernel, for a workgroup of AT_THREADS threads.
+//
+// Per column c: dst[c] = (D) finish(sum_p term(p, c)), term formed by `add(p, q, s, a)` for the V channels of column group q
+// onto the running sums a, with s = the V values src[V q ..] of a per-channel LDS array (null: zeros).  The column groups are
+// spread over the threads; when there are fewer of them than threads the positions are dealt to G = threads / groups groups,
+// whose partial sums meet in part [AT_PART] and are added in group order.  Ends in a barrier.
+template <int V, typename T, typename D, typename Add, typename Finish>
+__device__ __forceinline__ void at_column_sums(Add add, Finish finish, const T* __restrict__ src, D* __restrict__ dst,
+                                               T* __restrict__ part, int N, int C) {
+    const int tid = threadIdx.x, cols = C / V;                // (V == 4: C is a multiple of 4)
+    if (cols >= AT_THREADS) {
+        for (int q = tid; q < cols; q += AT_THREADS) {
+            T a[V], s[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) { a[k] = (T)0; s[k] = src ? src[V * q + k] : (T)0; }
+#pragma unroll 4
+            for (int p = 0; p < N; ++p) add(p, q, s, a);
+#pragma unroll
+            for (int k = 0; k < V; ++k) dst[V * q + k] = (D)finish(a[k]);
+        }
+    } else {
+        int G = AT_THREADS / cols;
+        if (G > N) G = N;
+        const int g = tid / cols, q = tid - g * cols;
+        if (g < G) {
+            T a[V], s[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) { a[k] = (T)0; s[k] = src ? src[V * q + k] : (T)0; }
+#pragma unroll 4
+            for (int p = g; p < N; p += G) add(p, q, s, a);
+#pragma unroll
+            for (int k = 0; k < V; ++k) part[g * C + V * q + k] = a[k];          // (G * C <= AT_THREADS * V = AT_PART)
+        }
+        __syncthreads();
+        for (int c = tid; c < C; c += AT_THREADS) {
+            T a = part[c];
+            for (int j = 1; j < G; ++j) a += part[j * C + c];
+            dst[c] = (D)finish(a);
+        }
+    }
+    __syncthreads();
+}
+
+// out[p] = sum_c s_w[c] ft[p][c] (relu: clamped at 0), one wave per position: a lane takes every 64th of the cols = C / V column
+// groups, the 64 partial sums meet in a butterfly.  s_w is the LDS array [C] a column-sum pass left behind.
+template <bool VEC>
+__device__ __forceinline__ void at_contract_positions(const float* __restrict__ ft, const float* __restrict__ s_w,
+                                                      float* __restrict__ o, int N, int C, int cols, int relu) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int p = wv; p < N; p += AT_WAVES) {
+        const float* __restrict__ row = ft + (long)p * C;
+        float a = 0.f;
+        for (int q = lane; q < cols; q += 64) {
+            if constexpr (VEC) {
+                const f32x4 v = *(const f32x4*)(row + 4 * q);
+                const f32x4 w = *(const f32x4*)(s_w + 4 * q);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a = fmaf(v[k], w[k], a);
+            } else {
+                a = fmaf(row[q], s_w[q], a);
+            }
+        }
+        a = wave_sum(a);
+        if (lane == 0) o[p] = relu ? fmaxf(a, 0.f) : a;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// One mask value per pixel times every image channel: out[c][p ..] = image[c][p ..] m, V = 1 or 4 pixels of a row from flat
+// index p (VEC: 16-byte loads and stores).
+template <bool VEC>
+__device__ __forceinline__ void at_scale_channels(const float* __restrict__ image, float* __restrict__ o, long plane, long p,
+                                                  int Cin, const float (&m)[VEC ? 4 : 1]) {
+    for (int c = 0; c < Cin; ++c) {
+        if constexpr (VEC) {
+            f32x4 v = *(const f32x4*)(image + c * plane + p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] *= m[k];
+            *(f32x4*)(o + c * plane + p) = v;
+        } else {
+            o[c * plane + p] = image[c * plane + p] * m[0];
+        }
+    }
+}
+
+// The launch geometry of a kernel that walks an H x W plane 1 or 4 pixels per thread: vec when W is a multiple of 4 and no
+// pointer (their bits or-ed) has a low address bit set, items = the threads' work items, tiles = the grid's y extent (<= 65535;
+// the kernels stride over the rest).
+struct AtPixelGrid {
+    bool vec;
+    long items;
+    unsigned tiles;
+};
+static inline AtPixelGrid at_pixel_grid(int H, int W, int threads, uintptr_t pointer_bits) {
+    AtPixelGrid g;
+    g.vec = W % 4 == 0 && (pointer_bits & 15) == 0;
+    g.items = (long)H * (g.vec ? W / 4 : W);
+    const long tiles = (g.items + threads - 1) / threads;
+    g.tiles = (unsigned)(tiles > 65535 ? 65535 : tiles);
+    return g;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The halves the accumulate kernels share (rise_accumulate_kernel, scorecam_accumulate_kernel): KT class accumulators in
+// registers per thread that START from acc, the weights of a piece of terms staged in LDS, the class columns clamped.
+
+// s_col[k] = the clamped column of class k0 + k, k < kt (the host refuses an index outside [0, n_classes))
+template <int KT>
+__device__ __forceinline__ void at_stage_columns(const int* __restrict__ cols, int k0, int kt, int n_classes, int* s_col) {
+    const int tid = threadIdx.x;
+    if (tid < KT) {
+        int c = tid < kt ? cols[k0 + tid] : 0;
+        s_col[tid] = min(max(c, 0), n_classes - 1);
+    }
+}
+
+// s_w[j][k] = factor(expf(logp[n0 + j][s_col[k]])) for the np terms of a piece, 0 for k >= kt
+template <int KT, int THREADS, typename Factor>
+__device__ __forceinline__ void at_stage_weights(const float* __restrict__ logp, int n0, int np, int kt, int n_classes,
+                                                 const int* s_col, float (*s_w)[KT], Factor factor) {
+    for (int i = threadIdx.x; i < np * KT; i += THREADS) {
+        const int j = i / KT, k = i - j * KT;
+        s_w[j][k] = k < kt ? factor(expf(logp[(long)(n0 + j) * n_classes + s_col[k]])) : 0.f;
+    }
+}
+
+// a[k] = acc[k0 + k][p] for the kt classes of a thread that owns element p of the plane (mine), else 0 ...
+template <int KT>
+__device__ __forceinline__ void at_load_acc(const float* __restrict__ acc, long plane, long p, int k0, int kt, bool mine,
+                                            float (&a)[KT]) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k) a[k] = (mine && k < kt) ? acc[(long)(k0 + k) * plane + p] : 0.f;
+}
+
+// ... and back
+template <int KT>
+__device__ __forceinline__ void at_store_acc(float* __restrict__ acc, long plane, long p, int k0, int kt, const float (&a)[KT]) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+        if (k < kt) acc[(long)(k0 + k) * plane + p] = a[k];
+}

@@ -9,7 +9,7 @@
 //
 // resize_bilinear_kernel: F.interpolate(mode = "bilinear", align_corners = False) of M maps, the value STORED as fp32 (cam_maps
 //   of gradcam.hip recomputes it and quantises it to 256 levels, whose ties raster order would then decide): the source
-//   coordinate is cm_source of gradcam.hip / rs_source of rise.hip, the blend is three fmas.  One thread per output pixel.
+//   coordinate and the blend are at_source / at_bilerp of attr_common.h, as in cam_maps.  One thread per output pixel.
 // saliency_ranks_kernel: ONE workgroup of 1024 threads per map, a least-significant-digit radix sort of (key, index) pairs with
 //   4-bit digits, eight passes.  key = the float's bits mapped so that an ascending unsigned order is the definition's order
 //   (cz_key).  A thread owns a CONTIGUOUS run of the elements in every pass; it counts its digits into its own column of an LDS
@@ -22,11 +22,11 @@
 // causal_step_images_kernel: out[i] = point (k, mode, j) of the edit stream, decoded from g = first + i as k = g / (2 n_points),
 //   mode = (g / n_points) % 2 (0 deletion, 1 insertion), j = g % n_points.  A pure select by ranks[k][p] < j step between the
 //   image and zero or between the image and its blur, formed once per pixel for all C channels; W a multiple of 4 and 16-byte
-//   aligned pointers: four pixels of a row per thread, 16-byte loads and stores (as rise_mask_images_kernel); else one pixel
+//   aligned pointers: four pixels of a row per thread, 16-byte loads and stores (at_pixel_grid of attr_common.h); else one pixel
 //   per thread.
 // causal_curve_kernel: curve[first + i] = expf(logp[i][cols[k]]) for the same chunk.
 // causal_auc_kernel: one thread per curve, the trapezoid summed in j order.
-#include "common.h"
+#include "attr_common.h"
 
 constexpr int CZ_THREADS = 256;
 constexpr int CZ_SORT_THREADS = 1024, CZ_SORT_WAVES = CZ_SORT_THREADS / 64;
@@ -37,16 +37,6 @@ constexpr int CZ_MAX_KLEN = 31;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// source coordinate of destination index d (align_corners = False): the lower neighbour, the upper one and its weight
-// (cm_source of gradcam.hip, rs_source of rise.hip)
-__device__ __forceinline__ void cz_source(int d, float scale, int n, int& i0, int& i1, float& t) {
-    float s = fmaf((float)d + 0.5f, scale, -0.5f);
-    s = fmaxf(s, 0.f);
-    i0 = min((int)s, n - 1);
-    i1 = min(i0 + 1, n - 1);
-    t = s - (float)i0;
-}
-
 __global__ __launch_bounds__(CZ_THREADS) void resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int h,
                                                                      int w, int H, int W) {
     const long p = (long)blockIdx.x * CZ_THREADS + threadIdx.x;
@@ -55,12 +45,11 @@ __global__ __launch_bounds__(CZ_THREADS) void resize_bilinear_kernel(const float
     const float* __restrict__ src = in + (long)blockIdx.y * h * w;
     int y0, y1, x0, x1;
     float ty, tx;
-    cz_source(y, (float)h / (float)H, h, y0, y1, ty);
-    cz_source(x, (float)w / (float)W, w, x0, x1, tx);
-    const float a0 = src[(long)y0 * w + x0], a1 = src[(long)y0 * w + x1];
-    const float b0 = src[(long)y1 * w + x0], b1 = src[(long)y1 * w + x1];
-    const float top = fmaf(tx, a1 - a0, a0), bot = fmaf(tx, b1 - b0, b0);
-    out[(long)blockIdx.y * H * W + p] = fmaf(ty, bot - top, top);
+    at_source(y, (float)h / (float)H, h, y0, y1, ty);
+    at_source(x, (float)w / (float)W, w, x0, x1, tx);
+    const float* r0 = src + (long)y0 * w;
+    const float* r1 = src + (long)y1 * w;
+    out[(long)blockIdx.y * H * W + p] = at_bilerp(r0[x0], r0[x1], r1[x0], r1[x1], tx, ty);
 }
 
 extern "C" int scouter_resize_bilinear_f32(const float* in, float* out, int M, int h, int w, int H, int W, void* stream) {
@@ -309,14 +298,12 @@ extern "C" int scouter_causal_step_images_f32(const float* image, const float* b
     SC_UNSUPPORTED((long)C * H * W < (1L << 31), "causal_step_images: image of %d x %d x %d elements is past the 32-bit offsets", C,
                    H, W);
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = W % 4 == 0 && (((uintptr_t)image | (uintptr_t)blurred | (uintptr_t)ranks | (uintptr_t)out) & 15) == 0;
-    const long items = (long)H * W / (vec ? 4 : 1);
-    long tiles = (items + CZ_THREADS - 1) / CZ_THREADS;
-    if (tiles > 65535) tiles = 65535;
+    const AtPixelGrid px =
+        at_pixel_grid(H, W, CZ_THREADS, (uintptr_t)image | (uintptr_t)blurred | (uintptr_t)ranks | (uintptr_t)out);
     const double elems = (double)n * C * H * W;
     ScProfScope prof("causal_step_images", st, elems, 4.0 * (elems + 2.0 * C * (double)H * W + (double)K * H * W));
-    const dim3 grid((unsigned)n, (unsigned)tiles);
-    if (vec)
+    const dim3 grid((unsigned)n, px.tiles);
+    if (px.vec)
         hipLaunchKernelGGL(causal_step_images_kernel<true>, grid, dim3(CZ_THREADS), 0, st, image, blurred, ranks, out, first,
                            n_points, step, C, H, W);
     else

@@ -10,7 +10,8 @@
 //                      (grad_powers_accumulate below), gr = the LAST sample's gradient, A the clean image's features; S, den,
 //                      alpha and the sum of w in fp64, w rounded to fp32 once.
 //
-// gradcampp_kernel: ONE workgroup of 1024 threads per image, three passes, one template for both methods.
+// gradcampp_kernel: ONE workgroup of 1024 threads per image, three passes, one template for both methods; the column sums and
+//   the contraction are at_column_sums / at_contract_positions of attr_common.h, which gradcam_kernel runs too.
 //   pass 1a: S[c].  The columns (float4 columns when C is a multiple of 4, single channels otherwise) are spread over the
 //            threads, a wave reads 64 consecutive columns of one position; when there are fewer columns than threads the
 //            positions are dealt to G = threads / columns groups, whose partial sums meet in LDS and are added in group order.
@@ -27,74 +28,13 @@
 //   owns an element (or four consecutive ones): the n terms split over calls at any point give the bits of one call.
 #include <type_traits>
 
-#include "common.h"
+#include "attr_common.h"
 
-constexpr int GP_THREADS = 1024, GP_WAVES = GP_THREADS / 64, GP_MAX_C = 8192, GP_PART = GP_THREADS * 4;
 constexpr int GP_ACC_THREADS = 256;
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-template <int V>
-__device__ __forceinline__ void gp_load_f32(const float* __restrict__ p, float (&v)[V]) {
-    if constexpr (V == 4) {
-        const f32x4 t = *(const f32x4*)p;
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void gp_load_f64(const double* __restrict__ p, double (&v)[V]) {
-    if constexpr (V == 4) {
-        const f64x2 a = *(const f64x2*)p, b = *(const f64x2*)(p + 2);
-        v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
-    } else {
-        v[0] = *p;
-    }
-}
-
-// Per column c: dst[c] = (D) sum_p term(p, c), term formed by `add(p, q, s, a)` for the V channels of column group q onto the
-// running sums a, with s = the V values src[V q ..] of a per-channel LDS array (null: zeros).  Ends in a barrier.
-template <int V, typename T, typename D, typename Add>
-__device__ __forceinline__ void gp_column_sums(Add add, const T* __restrict__ src, D* __restrict__ dst, T* __restrict__ part,
-                                               int N, int C) {
-    const int tid = threadIdx.x, cols = C / V;                // (V == 4: C is a multiple of 4)
-    if (cols >= GP_THREADS) {
-        for (int q = tid; q < cols; q += GP_THREADS) {
-            T a[V], s[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) { a[k] = (T)0; s[k] = src ? src[V * q + k] : (T)0; }
-#pragma unroll 4
-            for (int p = 0; p < N; ++p) add(p, q, s, a);
-#pragma unroll
-            for (int k = 0; k < V; ++k) dst[V * q + k] = (D)a[k];
-        }
-    } else {
-        int G = GP_THREADS / cols;
-        if (G > N) G = N;
-        const int g = tid / cols, q = tid - g * cols;
-        if (g < G) {
-            T a[V], s[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) { a[k] = (T)0; s[k] = src ? src[V * q + k] : (T)0; }
-#pragma unroll 4
-            for (int p = g; p < N; p += G) add(p, q, s, a);
-#pragma unroll
-            for (int k = 0; k < V; ++k) part[g * C + V * q + k] = a[k];          // (G * C <= GP_THREADS * V = GP_PART)
-        }
-        __syncthreads();
-        for (int c = tid; c < C; c += GP_THREADS) {
-            T a = part[c];
-            for (int j = 1; j < G; ++j) a += part[j * C + c];
-            dst[c] = (D)a;
-        }
-    }
-    __syncthreads();
-}
 
 // SMOOTH false: gr = dfeat, acc2 / acc3 unused.  SMOOTH true: gr = the last sample's gradient, acc2 / acc3 the fp64 sums.
 template <bool VEC, bool SMOOTH>
-__global__ __launch_bounds__(GP_THREADS) void gradcampp_kernel(const float* __restrict__ feat, const float* __restrict__ gr,
+__global__ __launch_bounds__(AT_THREADS) void gradcampp_kernel(const float* __restrict__ feat, const float* __restrict__ gr,
                                                                const double* __restrict__ acc2, const double* __restrict__ acc3,
                                                                double n_samples, float* __restrict__ out, int N, int C,
                                                                long out_stride, int relu) {
@@ -103,42 +43,42 @@ __global__ __launch_bounds__(GP_THREADS) void gradcampp_kernel(const float* __re
     constexpr int V = VEC ? 4 : 1;
     float* __restrict__ s_w = (float*)s_raw;                                  // [C], padded to 16 bytes
     T* __restrict__ s_S = (T*)(s_raw + (size_t)((C + 3) / 4) * 16);          // [C]
-    T* __restrict__ s_part = s_S + C;                                         // [GP_PART], when cols < GP_THREADS
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    T* __restrict__ s_part = s_S + C;                                         // [AT_PART], when cols < AT_THREADS
     const long img = (long)blockIdx.x * N * C;
     const float* __restrict__ ft = feat + img;
     const float* __restrict__ gp = gr + img;
-    const int cols = C / V;
+
+    const auto keep = [](T a) { return a; };                                  // (a column's total is stored as it is)
 
     // ---- pass 1a: S[c] = sum_p g3 A
-    gp_column_sums<V, T, T>(
+    at_column_sums<V, T, T>(
         [&](int p, int q, const T (&)[V], T (&a)[V]) {
             const long e = (long)p * C + V * q;
             float A[V];
-            gp_load_f32<V>(ft + e, A);
+            at_load<V>(ft + e, A);
             if constexpr (SMOOTH) {
                 double t[V];
-                gp_load_f64<V>(acc3 + img + e, t);
+                at_load<V>(acc3 + img + e, t);
 #pragma unroll
                 for (int k = 0; k < V; ++k) a[k] = fma(t[k] / n_samples, (double)A[k], a[k]);
             } else {
                 float g[V];
-                gp_load_f32<V>(gp + e, g);
+                at_load<V>(gp + e, g);
 #pragma unroll
                 for (int k = 0; k < V; ++k) a[k] = fmaf(g[k] * g[k] * g[k], A[k], a[k]);
             }
         },
-        (const T*)nullptr, s_S, s_part, N, C);
+        keep, (const T*)nullptr, s_S, s_part, N, C);
 
     // ---- pass 1b: w[c] = sum_p alpha max(gr, 0), alpha = g2 / (2 g2 + S[c]) and 0 where the denominator is 0
-    gp_column_sums<V, T, float>(
+    at_column_sums<V, T, float>(
         [&](int p, int q, const T (&S)[V], T (&a)[V]) {
             const long e = (long)p * C + V * q;
             float g[V];
-            gp_load_f32<V>(gp + e, g);
+            at_load<V>(gp + e, g);
             T g2[V];
             if constexpr (SMOOTH) {
-                gp_load_f64<V>(acc2 + img + e, g2);
+                at_load<V>(acc2 + img + e, g2);
 #pragma unroll
                 for (int k = 0; k < V; ++k) g2[k] = g2[k] / n_samples;
             } else {
@@ -154,31 +94,15 @@ __global__ __launch_bounds__(GP_THREADS) void gradcampp_kernel(const float* __re
                 else a[k] = fmaf(alpha, fmaxf(g[k], 0.f), a[k]);
             }
         },
-        (const T*)s_S, s_w, s_part, N, C);
+        keep, (const T*)s_S, s_w, s_part, N, C);
 
     // ---- pass 2: one wave per position
-    float* __restrict__ o = out + (long)blockIdx.x * out_stride;
-    for (int p = wv; p < N; p += GP_WAVES) {
-        const float* __restrict__ row = ft + (long)p * C;
-        float a = 0.f;
-        for (int q = lane; q < cols; q += 64) {
-            if constexpr (VEC) {
-                const f32x4 v = *(const f32x4*)(row + 4 * q);
-                const f32x4 w = *(const f32x4*)(s_w + 4 * q);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) a = fmaf(v[k], w[k], a);
-            } else {
-                a = fmaf(row[q], s_w[q], a);
-            }
-        }
-        a = wave_sum(a);
-        if (lane == 0) o[p] = relu ? fmaxf(a, 0.f) : a;
-    }
+    at_contract_positions<VEC>(ft, s_w, out + (long)blockIdx.x * out_stride, N, C, C / V, relu);
 }
 
 static size_t gp_lds_bytes(int C, size_t elem) {
     const int cols = C % 4 == 0 ? C / 4 : C;
-    return (size_t)((C + 3) / 4) * 16 + ((size_t)C + (cols < GP_THREADS ? GP_PART : 0)) * elem;
+    return (size_t)((C + 3) / 4) * 16 + ((size_t)C + (cols < AT_THREADS ? AT_PART : 0)) * elem;
 }
 
 extern "C" int scouter_gradcampp_f32(const float* feat, const float* dfeat, float* out, int B, int N, int C, long out_stride,
@@ -189,7 +113,7 @@ extern "C" int scouter_gradcampp_f32(const float* feat, const float* dfeat, floa
     SC_REQUIRE(((uintptr_t)feat & 15) == 0 && ((uintptr_t)dfeat & 15) == 0 && ((uintptr_t)out & 3) == 0,
                "gradcampp: misaligned pointer (feat and dfeat 16-byte, out 4-byte aligned)");
     SC_REQUIRE(out_stride >= N || B == 1, "gradcampp: output batch stride %ld is below N = %d", out_stride, N);
-    SC_UNSUPPORTED(C <= GP_MAX_C, "gradcampp: C = %d channels (the channel weights live in LDS: at most %d)", C, GP_MAX_C);
+    SC_UNSUPPORTED(C <= AT_MAX_C, "gradcampp: C = %d channels (the channel weights live in LDS: at most %d)", C, AT_MAX_C);
     SC_UNSUPPORTED((long)N * C < (1L << 31), "gradcampp: image of %d x %d elements is past the 32-bit offsets", N, C);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = gp_lds_bytes(C, sizeof(float));
@@ -197,11 +121,11 @@ extern "C" int scouter_gradcampp_f32(const float* feat, const float* dfeat, floa
     ScProfScope prof("gradcampp", st, 13.0 * B * (double)N * C, 4.0 * B * (4.0 * (double)N * C + N));
     if (C % 4 == 0) {
         sc_dyn_lds((const void*)gradcampp_kernel<true, false>, lds);
-        hipLaunchKernelGGL((gradcampp_kernel<true, false>), dim3((unsigned)B), dim3(GP_THREADS), lds, st, feat, dfeat,
+        hipLaunchKernelGGL((gradcampp_kernel<true, false>), dim3((unsigned)B), dim3(AT_THREADS), lds, st, feat, dfeat,
                            (const double*)nullptr, (const double*)nullptr, 1.0, out, N, C, out_stride, relu);
     } else {
         sc_dyn_lds((const void*)gradcampp_kernel<false, false>, lds);
-        hipLaunchKernelGGL((gradcampp_kernel<false, false>), dim3((unsigned)B), dim3(GP_THREADS), lds, st, feat, dfeat,
+        hipLaunchKernelGGL((gradcampp_kernel<false, false>), dim3((unsigned)B), dim3(AT_THREADS), lds, st, feat, dfeat,
                            (const double*)nullptr, (const double*)nullptr, 1.0, out, N, C, out_stride, relu);
     }
     return sc_check_launch("gradcampp");
@@ -221,7 +145,7 @@ extern "C" int scouter_gradcampp_smooth_f32(const float* feat, const double* acc
                "gradcampp_smooth: misaligned pointer (feat 16-byte, out 4-byte; acc2 / acc3 / glast 16-byte when C is a multiple "
                "of 4, else 8 / 8 / 4-byte aligned)");
     SC_REQUIRE(out_stride >= N || B == 1, "gradcampp_smooth: output batch stride %ld is below N = %d", out_stride, N);
-    SC_UNSUPPORTED(C <= GP_MAX_C, "gradcampp_smooth: C = %d channels (the channel weights live in LDS: at most %d)", C, GP_MAX_C);
+    SC_UNSUPPORTED(C <= AT_MAX_C, "gradcampp_smooth: C = %d channels (the channel weights live in LDS: at most %d)", C, AT_MAX_C);
     SC_UNSUPPORTED((long)N * C < (1L << 31), "gradcampp_smooth: image of %d x %d elements is past the 32-bit offsets", N, C);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = gp_lds_bytes(C, sizeof(double));
@@ -229,11 +153,11 @@ extern "C" int scouter_gradcampp_smooth_f32(const float* feat, const double* acc
     ScProfScope prof("gradcampp_smooth", st, 11.0 * B * (double)N * C, B * (28.0 * (double)N * C + 4.0 * N));
     if (C % 4 == 0) {
         sc_dyn_lds((const void*)gradcampp_kernel<true, true>, lds);
-        hipLaunchKernelGGL((gradcampp_kernel<true, true>), dim3((unsigned)B), dim3(GP_THREADS), lds, st, feat, glast, acc2, acc3,
+        hipLaunchKernelGGL((gradcampp_kernel<true, true>), dim3((unsigned)B), dim3(AT_THREADS), lds, st, feat, glast, acc2, acc3,
                            (double)n_samples, out, N, C, out_stride, relu);
     } else {
         sc_dyn_lds((const void*)gradcampp_kernel<false, true>, lds);
-        hipLaunchKernelGGL((gradcampp_kernel<false, true>), dim3((unsigned)B), dim3(GP_THREADS), lds, st, feat, glast, acc2, acc3,
+        hipLaunchKernelGGL((gradcampp_kernel<false, true>), dim3((unsigned)B), dim3(AT_THREADS), lds, st, feat, glast, acc2, acc3,
                            (double)n_samples, out, N, C, out_stride, relu);
     }
     return sc_check_launch("gradcampp_smooth");
@@ -247,11 +171,11 @@ __global__ __launch_bounds__(GP_ACC_THREADS) void grad_powers_accumulate_kernel(
     const long e = ((long)blockIdx.x * GP_ACC_THREADS + threadIdx.x) * V;
     if (e >= E) return;
     double a2[V], a3[V];
-    gp_load_f64<V>(acc2 + e, a2);
-    gp_load_f64<V>(acc3 + e, a3);
+    at_load<V>(acc2 + e, a2);
+    at_load<V>(acc3 + e, a3);
     for (int j = 0; j < n; ++j) {
         float g[V];
-        gp_load_f32<V>(grads + (long)j * E + e, g);
+        at_load<V>(grads + (long)j * E + e, g);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const double d = (double)g[k], sq = d * d;         // (exact)
@@ -259,15 +183,8 @@ __global__ __launch_bounds__(GP_ACC_THREADS) void grad_powers_accumulate_kernel(
             a3[k] = fma(sq, d, a3[k]);
         }
     }
-    if constexpr (V == 4) {
-        *(f64x2*)(acc2 + e) = f64x2{a2[0], a2[1]};
-        *(f64x2*)(acc2 + e + 2) = f64x2{a2[2], a2[3]};
-        *(f64x2*)(acc3 + e) = f64x2{a3[0], a3[1]};
-        *(f64x2*)(acc3 + e + 2) = f64x2{a3[2], a3[3]};
-    } else {
-        acc2[e] = a2[0];
-        acc3[e] = a3[0];
-    }
+    at_store<V>(acc2 + e, a2);
+    at_store<V>(acc3 + e, a3);
 }
 
 extern "C" int scouter_grad_powers_accumulate(const float* grads, double* acc2, double* acc3, int n, long E, void* stream) {

@@ -20,14 +20,12 @@
 //
 // Every kernel has a 16-byte form (E, or H W, a multiple of 4 and every pointer 16-byte aligned) and a one-element form; the
 // arithmetic of an element is one inlined expression shared by both, so they give the same bits.
-#include "common.h"
+#include "attr_common.h"
 
 constexpr int PG_THREADS = 256;
 constexpr int PG_JT = 8;                      // images of a chunk per thread (path / noise): the per-element work is shared
 constexpr int PG_ROWS = 8;                    // gradient rows a thread of grad_accumulate has in flight
 constexpr int PG_FIN_BLOCKS = 1024;           // at most this many partial sums of attr_finish's total (8 KB of workspace)
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 static inline bool pg_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
                                 const void* e = nullptr) {
@@ -188,38 +186,6 @@ __device__ __forceinline__ void pg_add_term(double w, float g, double& a, double
     if (sq) s = fma(p, (double)g, s);
 }
 
-// V consecutive elements of one fp32 row / of an fp64 sum, with the widest access V allows (at most 16 bytes each)
-template <int V>
-__device__ __forceinline__ void pg_load_row(const float* __restrict__ p, float (&v)[V]) {
-    if constexpr (V == 4) {
-        const f32x4 t = __builtin_nontemporal_load((const f32x4*)p);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void pg_load_sum(const double* __restrict__ p, double (&v)[V]) {
-    if constexpr (V == 1) {
-        v[0] = *p;
-    } else {
-#pragma unroll
-        for (int k = 0; k < V; k += 2) {
-            const f64x2 t = *(const f64x2*)(p + k);
-            v[k] = t[0]; v[k + 1] = t[1];
-        }
-    }
-}
-template <int V>
-__device__ __forceinline__ void pg_store_sum(double* __restrict__ p, const double (&v)[V]) {
-    if constexpr (V == 1) {
-        *p = v[0];
-    } else {
-#pragma unroll
-        for (int k = 0; k < V; k += 2) *(f64x2*)(p + k) = f64x2{v[k], v[k + 1]};
-    }
-}
-
 template <int V>
 __global__ __launch_bounds__(PG_THREADS) void grad_accumulate_kernel(const float* __restrict__ grads,
                                                                      const float* __restrict__ weights,
@@ -229,9 +195,9 @@ __global__ __launch_bounds__(PG_THREADS) void grad_accumulate_kernel(const float
     if (e >= E) return;
     const bool sq = acc_sq != nullptr;                         // (uniform over the launch)
     double a[V], s[V];
-    pg_load_sum<V>(acc + e, a);
+    at_load<V>(acc + e, a);
     if (sq) {
-        pg_load_sum<V>(acc_sq + e, s);
+        at_load<V>(acc_sq + e, s);
     } else {
 #pragma unroll
         for (int k = 0; k < V; ++k) s[k] = 0.0;
@@ -242,7 +208,7 @@ __global__ __launch_bounds__(PG_THREADS) void grad_accumulate_kernel(const float
     for (; j + U <= n; j += U) {                               // U rows in flight; the additions stay in j order
         float v[U][V];
 #pragma unroll
-        for (int u = 0; u < U; ++u) pg_load_row<V>(g + (long)(j + u) * E, v[u]);
+        for (int u = 0; u < U; ++u) at_load<V, true>(g + (long)(j + u) * E, v[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const double w = weights ? (double)weights[first + j + u] : 1.0;
@@ -253,12 +219,12 @@ __global__ __launch_bounds__(PG_THREADS) void grad_accumulate_kernel(const float
     for (; j < n; ++j) {
         const double w = weights ? (double)weights[first + j] : 1.0;
         float v[V];
-        pg_load_row<V>(g + (long)j * E, v);
+        at_load<V, true>(g + (long)j * E, v);
 #pragma unroll
         for (int k = 0; k < V; ++k) pg_add_term(w, v[k], a[k], s[k], sq);
     }
-    pg_store_sum<V>(acc + e, a);
-    if (sq) pg_store_sum<V>(acc_sq + e, s);
+    at_store<V>(acc + e, a);
+    if (sq) at_store<V>(acc_sq + e, s);
 }
 
 extern "C" int scouter_grad_accumulate_f64(const float* grads, const float* weights, double* acc, double* acc_sq, int first,

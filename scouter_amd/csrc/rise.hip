@@ -4,8 +4,8 @@
 //
 // Mask n is an s x s grid of bytes in {0, 1} and a shift (dy, dx).  With cell = ceil(size / s) and U = (s + 1) cell per axis,
 //   mask_n(y, x) = bilinear(grid_n, U_h x U_w, align_corners = False)[y + dy, x + dx],  0 <= dy < cell_h, 0 <= dx < cell_w
-// (src = (d + 0.5) s / U - 0.5 clamped at 0, lower index clamped to s - 1, upper index min(lower + 1, s - 1): cm_source of
-// gradcam.hip).  The value is formed by ONE inlined expression (rs_source / rs_mask) wherever it is needed and never stored:
+// (src = (d + 0.5) s / U - 0.5 clamped at 0, lower index clamped to s - 1, upper index min(lower + 1, s - 1): at_source of
+// attr_common.h).  The value is formed by ONE inlined expression (at_source / rs_mask) wherever it is needed and never stored:
 // N full-resolution masks never exist.  Every index is clamped, so a shift outside its range reads no byte outside the grid.
 //
 // rise_mask_images_kernel: out[n][c][y][x] = image[c][y][x] mask_n(y, x).  A workgroup belongs to ONE mask (blockIdx.x) and
@@ -16,9 +16,9 @@
 //   order: splitting the masks over several calls at any point gives the bits of one call.  The weights and grid bytes of
 //   RS_NP masks at a time are staged in LDS, so N is unbounded.
 // heat_maps_kernel: the drawing steps of cam_maps_kernel (gradcam.hip) without the resize and without an LDS source: ONE
-//   workgroup per map reads it twice from memory (extrema of max(v, 0), then the bytes).  The same expressions as cam_maps_kernel
-//   in the same order: a map cam_maps takes at its own size gets the same bytes.
-#include "common.h"
+//   workgroup per map reads it twice from memory (extrema of max(v, 0), then the bytes).  Both kernels reduce with
+//   at_block_minmax and scale with AtHeatScale of attr_common.h: a map cam_maps takes at its own size gets the same bytes.
+#include "attr_common.h"
 
 constexpr int RS_MAX_S = 16;
 constexpr int RS_THREADS = 256;
@@ -26,25 +26,13 @@ constexpr int RS_KT = 16;                     // classes per thread (accumulator
 constexpr int RS_NP = 32;                     // masks staged in LDS at a time
 constexpr int HM_THREADS = 1024, HM_WAVES = HM_THREADS / 64;
 
-// source coordinate of destination index d (align_corners = False): the lower neighbour, the upper one and its weight
-__device__ __forceinline__ void rs_source(int d, float scale, int n, int& i0, int& i1, float& t) {
-    float s = fmaf((float)d + 0.5f, scale, -0.5f);
-    s = fmaxf(s, 0.f);
-    i0 = min((int)s, n - 1);
-    i1 = min(i0 + 1, n - 1);
-    t = s - (float)i0;
-}
-
 // bilinear value of the byte grid g [s][s] (LDS) between rows y0 / y1 (weight ty) and columns x0 / x1 (weight tx)
 __device__ __forceinline__ float rs_mask(const unsigned char* __restrict__ g, int s, int y0, int y1, float ty, int x0, int x1,
                                          float tx) {
-    const float a0 = (float)g[y0 * s + x0], a1 = (float)g[y0 * s + x1];
-    const float b0 = (float)g[y1 * s + x0], b1 = (float)g[y1 * s + x1];
-    const float top = fmaf(tx, a1 - a0, a0), bot = fmaf(tx, b1 - b0, b0);
-    return fmaf(ty, bot - top, top);
+    return at_bilerp((float)g[y0 * s + x0], (float)g[y0 * s + x1], (float)g[y1 * s + x0], (float)g[y1 * s + x1], tx, ty);
 }
 
-// s / U of one axis: the scale every kernel hands to rs_source
+// s / U of one axis: the scale every kernel hands to at_source
 __host__ __device__ __forceinline__ float rs_scale(int size, int s) {
     const int cell = (size + s - 1) / s;
     return (float)s / (float)((s + 1) * cell);
@@ -70,26 +58,16 @@ __global__ __launch_bounds__(RS_THREADS) void rise_mask_images_kernel(const floa
         const int y = (int)(i / wq), x = (int)(i - (long)y * wq) * V;
         int y0, y1;
         float ty;
-        rs_source(y + dy, sy, s, y0, y1, ty);
+        at_source(y + dy, sy, s, y0, y1, ty);
         float m[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             int x0, x1;
             float tx;
-            rs_source(x + k + dx, sx, s, x0, x1, tx);
+            at_source(x + k + dx, sx, s, x0, x1, tx);
             m[k] = rs_mask(s_g, s, y0, y1, ty, x0, x1, tx);
         }
-        const long p = (long)y * W + x;
-        for (int c = 0; c < C; ++c) {
-            if constexpr (VEC) {
-                f32x4 v = *(const f32x4*)(image + c * plane + p);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] *= m[k];
-                *(f32x4*)(o + c * plane + p) = v;
-            } else {
-                o[c * plane + p] = image[c * plane + p] * m[0];
-            }
-        }
+        at_scale_channels<VEC>(image, o, plane, (long)y * W + x, C, m);
     }
 }
 
@@ -111,14 +89,11 @@ extern "C" int scouter_rise_mask_images_f32(const float* image, const unsigned c
     SC_UNSUPPORTED((long)C * H * W < (1L << 31), "rise_mask_images: image of %d x %d x %d elements is past the 32-bit offsets", C,
                    H, W);
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = W % 4 == 0 && (((uintptr_t)image | (uintptr_t)out) & 15) == 0;
-    const long items = (long)H * (vec ? W / 4 : W);
-    long tiles = (items + RS_THREADS - 1) / RS_THREADS;
-    if (tiles > 65535) tiles = 65535;
+    const AtPixelGrid px = at_pixel_grid(H, W, RS_THREADS, (uintptr_t)image | (uintptr_t)out);
     const double elems = (double)N * C * H * W;
     ScProfScope prof("rise_mask_images", st, elems + 14.0 * N * (double)H * W, 4.0 * (elems + (double)C * H * W));
-    const dim3 grid((unsigned)N, (unsigned)tiles);
-    if (vec)
+    const dim3 grid((unsigned)N, px.tiles);
+    if (px.vec)
         hipLaunchKernelGGL(rise_mask_images_kernel<true>, grid, dim3(RS_THREADS), 0, st, image, grids, shifts, out, C, H, W, s);
     else
         hipLaunchKernelGGL(rise_mask_images_kernel<false>, grid, dim3(RS_THREADS), 0, st, image, grids, shifts, out, C, H, W, s);
@@ -137,26 +112,19 @@ __global__ __launch_bounds__(RS_THREADS) void rise_accumulate_kernel(const float
     __shared__ int s_col[RS_KT];
     const int tid = threadIdx.x;
     const int k0 = blockIdx.y * RS_KT, kt = min(RS_KT, K - k0), ss = s * s;
-    if (tid < RS_KT) {
-        int c = tid < kt ? cols[k0 + tid] : 0;
-        s_col[tid] = min(max(c, 0), n_classes - 1);            // (the host refuses an index outside [0, n_classes))
-    }
+    at_stage_columns<RS_KT>(cols, k0, kt, n_classes, s_col);
     const long plane = (long)H * W;
     const long p = (long)blockIdx.x * RS_THREADS + tid;
     const bool live = p < plane;
     const int y = live ? (int)(p / W) : 0, x = live ? (int)(p - (long)y * W) : 0;
     const float sy = rs_scale(H, s), sx = rs_scale(W, s);
     float a[RS_KT];
-#pragma unroll
-    for (int k = 0; k < RS_KT; ++k) a[k] = (live && k < kt) ? acc[(long)(k0 + k) * plane + p] : 0.f;
+    at_load_acc<RS_KT>(acc, plane, p, k0, kt, live, a);
 
     for (int n0 = 0; n0 < N; n0 += RS_NP) {
         const int np = min(RS_NP, N - n0);
         __syncthreads();                                        // (s_col is written; the previous piece is consumed)
-        for (int i = tid; i < np * RS_KT; i += RS_THREADS) {
-            const int j = i / RS_KT, k = i - j * RS_KT;
-            s_w[j][k] = k < kt ? scale * expf(logp[(long)(n0 + j) * n_classes + s_col[k]]) : 0.f;
-        }
+        at_stage_weights<RS_KT, RS_THREADS>(logp, n0, np, kt, n_classes, s_col, s_w, [scale](float e) { return scale * e; });
         for (int i = tid; i < np * ss; i += RS_THREADS) {
             const int j = i / ss;
             s_g[j][i - j * ss] = grids[(long)n0 * ss + i];
@@ -167,19 +135,15 @@ __global__ __launch_bounds__(RS_THREADS) void rise_accumulate_kernel(const float
             for (int j = 0; j < np; ++j) {
                 int y0, y1, x0, x1;
                 float ty, tx;
-                rs_source(y + s_shift[j][0], sy, s, y0, y1, ty);
-                rs_source(x + s_shift[j][1], sx, s, x0, x1, tx);
+                at_source(y + s_shift[j][0], sy, s, y0, y1, ty);
+                at_source(x + s_shift[j][1], sx, s, x0, x1, tx);
                 const float m = rs_mask(s_g[j], s, y0, y1, ty, x0, x1, tx);
 #pragma unroll
                 for (int k = 0; k < RS_KT; ++k) a[k] = fmaf(s_w[j][k], m, a[k]);
             }
         }
     }
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < RS_KT; ++k)
-            if (k < kt) acc[(long)(k0 + k) * plane + p] = a[k];
-    }
+    if (live) at_store_acc<RS_KT>(acc, plane, p, k0, kt, a);
 }
 
 extern "C" int scouter_rise_accumulate_f32(const float* logp, const int* cols, const unsigned char* grids, const int* shifts,
@@ -210,7 +174,7 @@ extern "C" int scouter_rise_accumulate_f32(const float* logp, const int* cols, c
 __global__ __launch_bounds__(HM_THREADS) void heat_maps_kernel(const float* __restrict__ maps, unsigned char* __restrict__ out,
                                                                long plane, float min_level) {
     __shared__ float s_lo[HM_WAVES], s_hi[HM_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const float* __restrict__ src = maps + (long)blockIdx.x * plane;
 
     // ---- the extrema of v = max(map, 0)
@@ -220,31 +184,12 @@ __global__ __launch_bounds__(HM_THREADS) void heat_maps_kernel(const float* __re
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0) { s_lo[wv] = lo; s_hi[wv] = hi; }
-    __syncthreads();
-    lo = s_lo[0]; hi = s_hi[0];
-#pragma unroll
-    for (int k = 1; k < HM_WAVES; ++k) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); }
+    at_block_minmax<HM_WAVES>(lo, hi, s_lo, s_hi);
 
-    // ---- the two scalings as one affine map of v, as in cam_maps_kernel
-    const float span1 = hi - lo;
-    const float lo2 = fmaxf(0.f, min_level), span2 = fmaxf(1.f, min_level) - lo2;
-    const bool flat = !(span1 > 0.f) || !(span2 > 0.f);                   // (also a map with a NaN / infinity in it)
+    // ---- the bytes
+    const AtHeatScale scale(lo, hi, min_level);
     unsigned char* __restrict__ dst = out + (long)blockIdx.x * plane;
-    for (long i = tid; i < plane; i += HM_THREADS) {
-        float c = 0.f;
-        if (!flat) {
-            const float v = fmaxf(src[i], 0.f);
-            const float a = fmaxf((v - lo) / span1, min_level);
-            c = fminf(fmaxf((a - lo2) / span2, 0.f), 1.f);
-        }
-        dst[i] = (unsigned char)(int)(255.f * c);
-    }
+    for (long i = tid; i < plane; i += HM_THREADS) dst[i] = scale.byte(fmaxf(src[i], 0.f));
 }
 
 extern "C" int scouter_heat_maps_u8(const float* maps, unsigned char* out, int M, int H, int W, float min_level, void* stream) {

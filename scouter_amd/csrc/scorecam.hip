@@ -5,13 +5,13 @@
 //
 // For one image's features feat NHWC [h][w][C] and channel c,
 //   U_c(y, x) = bilinear(feat[:, :, c], H x W, align_corners = False)
-// (src = (d + 0.5) in / out - 0.5 clamped at 0, lower index clamped to in - 1, upper index min(lower + 1, in - 1): cm_source /
-// cm_value of gradcam.hip WITHOUT the clamp at 0), lo_c / hi_c = the minimum / maximum of the fp32 values U_c(y, x) over the H W
-// pixels, span_c = hi_c - lo_c (one fp32 subtraction), and
+// (src = (d + 0.5) in / out - 0.5 clamped at 0, lower index clamped to in - 1, upper index min(lower + 1, in - 1): at_source /
+// at_bilerp of attr_common.h, the resize of cam_maps WITHOUT its clamp at 0), lo_c / hi_c = the minimum / maximum of the fp32
+// values U_c(y, x) over the H W pixels, span_c = hi_c - lo_c (one fp32 subtraction), and
 //   mask_c(y, x) = (U_c(y, x) - lo_c) / span_c        -- ONE subtraction, then ONE correctly rounded division, in this order,
 // when span_c > 0 (the channel is LIVE; its mask attains exactly 0 and exactly 1, since U takes the values lo and hi and
 // span / span = 1), and 0 everywhere otherwise (DEAD: a constant channel, or one with a NaN / infinity in its range).  U is
-// formed by ONE inlined expression (sc_source / sc_value) and the mask by one more (sc_mask) wherever they are needed; neither
+// formed by ONE inlined expression (at_source / sc_value) and the mask by one more (sc_mask) wherever they are needed; neither
 // is ever stored: C full-resolution masks never exist.  Every index is clamped, so no feature value moves an address.
 //
 // scorecam_ranges_kernel: ranges[c] = (lo_c, hi_c).  A workgroup takes SC_TC consecutive channels: it reads them for all h w
@@ -25,7 +25,7 @@
 //   position and per tile of SC_KT classes (blockIdx.y), SC_KT accumulators in registers that START from acc and take one fma per
 //   live channel in i order (a dead channel is skipped): splitting the channels over several calls at any point gives the bits
 //   of one call.  The weights of SC_NP channels at a time are staged in LDS, so n is unbounded.
-#include "common.h"
+#include "attr_common.h"
 
 constexpr int SC_MAX_SRC = 1024;              // source positions h w per channel (they live in LDS)
 constexpr int SC_TC = 8, SC_RANGE_THREADS = SC_TC * 64;      // channels per workgroup of the range kernel, one wave each
@@ -33,24 +33,13 @@ constexpr int SC_THREADS = 256;
 constexpr int SC_KT = 16;                     // classes per thread (accumulators in registers)
 constexpr int SC_NP = 32;                     // channels whose weights are staged in LDS at a time
 
-// source coordinate of destination index d (align_corners = False): the lower neighbour, the upper one and its weight
-__device__ __forceinline__ void sc_source(int d, float scale, int n, int& i0, int& i1, float& t) {
-    float s = fmaf((float)d + 0.5f, scale, -0.5f);
-    s = fmaxf(s, 0.f);
-    i0 = min((int)s, n - 1);
-    i1 = min(i0 + 1, n - 1);
-    t = s - (float)i0;
-}
-
 // bilinear value at column (x0, x1, tx) of the two source rows r0 / r1 (LDS) with row weight ty
 __device__ __forceinline__ float sc_value(const float* __restrict__ r0, const float* __restrict__ r1, float ty, int x0, int x1,
                                           float tx) {
-    const float a0 = r0[x0], a1 = r0[x1], b0 = r1[x0], b1 = r1[x1];
-    const float top = fmaf(tx, a1 - a0, a0), bot = fmaf(tx, b1 - b0, b0);
-    return fmaf(ty, bot - top, top);
+    return at_bilerp(r0[x0], r0[x1], r1[x0], r1[x1], tx, ty);
 }
 
-// in / out of one axis: the scale every kernel hands to sc_source
+// in / out of one axis: the scale every kernel hands to at_source
 __device__ __forceinline__ float sc_scale(int in, int out) { return (float)in / (float)out; }
 
 __device__ __forceinline__ bool sc_live(float lo, float hi) { return hi - lo > 0.f; }      // (false with a NaN / infinity)
@@ -78,23 +67,19 @@ __global__ __launch_bounds__(SC_RANGE_THREADS) void scorecam_ranges_kernel(const
     for (int y = 0; y < H; ++y) {
         int y0, y1;
         float ty;
-        sc_source(y, sy, h, y0, y1, ty);
+        at_source(y, sy, h, y0, y1, ty);
         const float* r0 = src + y0 * w;
         const float* r1 = src + y1 * w;
         for (int x = lane; x < W; x += 64) {
             int x0, x1;
             float tx;
-            sc_source(x, sx, w, x0, x1, tx);
+            at_source(x, sx, w, x0, x1, tx);
             const float v = sc_value(r0, r1, ty, x0, x1, tx);
             lo = fminf(lo, v);
             hi = fmaxf(hi, v);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    }
+    at_wave_minmax(lo, hi);
     if (lane == 0) {
         ranges[2 * (long)c] = lo;
         ranges[2 * (long)c + 1] = hi;
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_mask_images_kernel(const 
         }
         int y0, y1;
         float ty;
-        sc_source(y, sy, h, y0, y1, ty);
+        at_source(y, sy, h, y0, y1, ty);
         const float* r0 = s_src + y0 * w;
         const float* r1 = s_src + y1 * w;
         float m[V];
@@ -164,19 +149,10 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_mask_images_kernel(const 
         for (int k = 0; k < V; ++k) {
             int x0, x1;
             float tx;
-            sc_source(x + k, sx, w, x0, x1, tx);
+            at_source(x + k, sx, w, x0, x1, tx);
             m[k] = sc_mask(sc_value(r0, r1, ty, x0, x1, tx), lo, span);
         }
-        for (int ch = 0; ch < Cin; ++ch) {
-            if constexpr (VEC) {
-                f32x4 v = *(const f32x4*)(image + ch * plane + p);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] *= m[k];
-                *(f32x4*)(o + ch * plane + p) = v;
-            } else {
-                o[ch * plane + p] = image[ch * plane + p] * m[0];
-            }
-        }
+        at_scale_channels<VEC>(image, o, plane, p, Cin, m);
     }
 }
 
@@ -194,15 +170,12 @@ extern "C" int scouter_scorecam_mask_images_f32(const float* image, const float*
     SC_UNSUPPORTED((long)Cin * H * W < (1L << 31), "scorecam_mask_images: image of %d x %d x %d elements is past the 32-bit offsets",
                    Cin, H, W);
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = W % 4 == 0 && (((uintptr_t)image | (uintptr_t)out) & 15) == 0;
-    const long items = (long)H * (vec ? W / 4 : W);
-    long tiles = (items + SC_THREADS - 1) / SC_THREADS;
-    if (tiles > 65535) tiles = 65535;
+    const AtPixelGrid px = at_pixel_grid(H, W, SC_THREADS, (uintptr_t)image | (uintptr_t)out);
     const double elems = (double)n * Cin * H * W;
     ScProfScope prof("scorecam_mask_images", st, elems + 18.0 * n * (double)H * W,
                      4.0 * (elems + (double)Cin * H * W + (double)n * (h * w + 2)));
-    const dim3 grid((unsigned)n, (unsigned)tiles);
-    if (vec)
+    const dim3 grid((unsigned)n, px.tiles);
+    if (px.vec)
         hipLaunchKernelGGL(scorecam_mask_images_kernel<true>, grid, dim3(SC_THREADS), 0, st, image, feat, ranges, out, first, Cin,
                            H, W, h, w, C);
     else
@@ -223,24 +196,17 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_accumulate_kernel(const f
     __shared__ int s_col[SC_KT];
     const int tid = threadIdx.x;
     const int k0 = blockIdx.y * SC_KT, kt = min(SC_KT, K - k0);
-    if (tid < SC_KT) {
-        int c = tid < kt ? cols[k0 + tid] : 0;
-        s_col[tid] = min(max(c, 0), n_classes - 1);            // (the host refuses an index outside [0, n_classes))
-    }
+    at_stage_columns<SC_KT>(cols, k0, kt, n_classes, s_col);
     const int p = blockIdx.x * SC_THREADS + tid;
     const bool mine = p < hw;
     const float* __restrict__ f = feat + (long)(mine ? p : 0) * C + first;
     float a[SC_KT];
-#pragma unroll
-    for (int k = 0; k < SC_KT; ++k) a[k] = (mine && k < kt) ? acc[(long)(k0 + k) * hw + p] : 0.f;
+    at_load_acc<SC_KT>(acc, hw, p, k0, kt, mine, a);
 
     for (int n0 = 0; n0 < n; n0 += SC_NP) {
         const int np = min(SC_NP, n - n0);
         __syncthreads();                                        // (s_col is written; the previous piece is consumed)
-        for (int i = tid; i < np * SC_KT; i += SC_THREADS) {
-            const int j = i / SC_KT, k = i - j * SC_KT;
-            s_w[j][k] = k < kt ? expf(logp[(long)(n0 + j) * n_classes + s_col[k]]) : 0.f;
-        }
+        at_stage_weights<SC_KT, SC_THREADS>(logp, n0, np, kt, n_classes, s_col, s_w, [](float e) { return e; });
         if (tid < np) {
             const long c = (long)first + n0 + tid;
             s_live[tid] = sc_live(ranges[2 * c], ranges[2 * c + 1]) ? 1 : 0;
@@ -255,11 +221,7 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_accumulate_kernel(const f
             }
         }
     }
-    if (mine) {
-#pragma unroll
-        for (int k = 0; k < SC_KT; ++k)
-            if (k < kt) acc[(long)(k0 + k) * hw + p] = a[k];
-    }
+    if (mine) at_store_acc<SC_KT>(acc, hw, p, k0, kt, a);
 }
 
 extern "C" int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges,

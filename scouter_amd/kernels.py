@@ -1660,6 +1660,24 @@ def resize_normalize(images_u8, out_size, lut, out=None):
 # ---------------------------------------------------------------------------------------------------------------
 # Grad-CAM (csrc/gradcam.hip; tools/attribution.py gradcam / gradcam_maps)
 # ---------------------------------------------------------------------------------------------------------------
+def _lead(shape, keep):
+    """a shape whose last `keep` dimensions belong to one item -> (the leading dimensions, their product = the item count)"""
+    lead = tuple(int(n) for n in shape[:len(shape) - keep])
+    count = 1
+    for n in lead:
+        count *= n
+    return lead, count
+
+
+def _cam_pair_chk(what, feat, dfeat, out):
+    """feat / dfeat of gradcam and gradcampp: the same NHWC fp32 shape -> (B, N, C) of _cam_out_chk"""
+    _chk(feat, what + ": feat"); _chk(dfeat, what + ": dfeat")
+    if feat.dim() != 4 or dfeat.shape != feat.shape:
+        raise RuntimeError("%s: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
+                           % (what, tuple(feat.shape), tuple(dfeat.shape)))
+    return _cam_out_chk(what, feat, out)
+
+
 def _cam_out_chk(what, feat, out):
     """feat NHWC [B, h, w, C], out fp32 [B, h, w] or [B, h * w] dense within an image -> (B, N, C)"""
     B, h, w, C = feat.shape
@@ -1675,11 +1693,7 @@ def gradcam(feat, dfeat, out, relu=False):
     """out[b, p] = sum_c mean_p'(dfeat[b, p', c]) * feat[b, p, c] (relu: clamped at 0) for NHWC fp32 feat / dfeat [B, h, w, C].
     `out` is fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride: a column `t[:, k]` of a [B, K, h, w] tensor
     is filled in place.  One launch, one fixed summation order per element (two calls give the same bits)."""
-    _chk(feat, "gradcam: feat"); _chk(dfeat, "gradcam: dfeat")
-    if feat.dim() != 4 or dfeat.shape != feat.shape:
-        raise RuntimeError("gradcam: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
-                           % (tuple(feat.shape), tuple(dfeat.shape)))
-    B, N, C = _cam_out_chk("gradcam", feat, out)
+    B, N, C = _cam_pair_chk("gradcam", feat, dfeat, out)
     _native.check(_native.lib().scouter_gradcam_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(relu)),
                                                     _stream()), "gradcam")
     return out
@@ -1694,10 +1708,7 @@ def cam_maps(cam, H, W, min_level=0.0):
     if cam.dim() < 2:
         raise RuntimeError("cam_maps: cam must be [..., h, w], got shape %s" % (tuple(cam.shape),))
     h, w = cam.shape[-2:]
-    lead = tuple(cam.shape[:-2])
-    M = 1
-    for n in lead:
-        M *= n
+    lead, M = _lead(cam.shape, 2)
     out = torch.empty(lead + (int(H), int(W)), dtype=torch.uint8, device=cam.device)
     _native.check(_native.lib().scouter_cam_maps_u8(_p(cam), _p(out), M, h, w, int(H), int(W), float(min_level), _stream()),
                   "cam_maps")
@@ -1712,11 +1723,7 @@ def gradcampp(feat, dfeat, out, relu=True):
     denominator is 0), w[c] = sum_p alpha max(g, 0), out[b, p] = sum_c w[c] A[b, p, c] (relu: clamped at 0), all in fp32.  `out`
     as in `gradcam`: fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride.  One launch, one fixed summation
     order per element (two calls give the same bits)."""
-    _chk(feat, "gradcampp: feat"); _chk(dfeat, "gradcampp: dfeat")
-    if feat.dim() != 4 or dfeat.shape != feat.shape:
-        raise RuntimeError("gradcampp: feat %s and dfeat %s must be the same NHWC [B, h, w, C] shape"
-                           % (tuple(feat.shape), tuple(dfeat.shape)))
-    B, N, C = _cam_out_chk("gradcampp", feat, out)
+    B, N, C = _cam_pair_chk("gradcampp", feat, dfeat, out)
     _native.check(_native.lib().scouter_gradcampp_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(relu)),
                                                       _stream()), "gradcampp")
     return out
@@ -1816,10 +1823,7 @@ def heat_maps(maps, min_level=0.0):
     if maps.dim() < 2:
         raise RuntimeError("heat_maps: maps must be [..., H, W], got shape %s" % (tuple(maps.shape),))
     H, W = maps.shape[-2:]
-    lead = tuple(maps.shape[:-2])
-    M = 1
-    for n in lead:
-        M *= n
+    lead, M = _lead(maps.shape, 2)
     out = torch.empty(tuple(maps.shape), dtype=torch.uint8, device=maps.device)
     _native.check(_native.lib().scouter_heat_maps_u8(_p(maps), _p(out), M, H, W, float(min_level), _stream()), "heat_maps")
     return out
@@ -1836,10 +1840,7 @@ def resize_bilinear(maps, H, W):
     if maps.dim() < 2:
         raise RuntimeError("resize_bilinear: maps must be [..., h, w], got shape %s" % (tuple(maps.shape),))
     h, w = maps.shape[-2:]
-    lead = tuple(maps.shape[:-2])
-    M = 1
-    for n in lead:
-        M *= n
+    lead, M = _lead(maps.shape, 2)
     out = torch.empty(lead + (int(H), int(W)), dtype=F32, device=maps.device)
     _native.check(_native.lib().scouter_resize_bilinear_f32(_p(maps), _p(out), M, h, w, int(H), int(W), _stream()),
                   "resize_bilinear")
@@ -1929,10 +1930,7 @@ def causal_auc(curves, out=None):
     _chk(curves, "causal_auc: curves")
     if curves.dim() < 1:
         raise RuntimeError("causal_auc: curves must be [..., n_points], got shape %s" % (tuple(curves.shape),))
-    lead, n_points = tuple(curves.shape[:-1]), int(curves.shape[-1])
-    R = 1
-    for n in lead:
-        R *= n
+    (lead, R), n_points = _lead(curves.shape, 1), int(curves.shape[-1])
     if out is None:
         out = torch.empty(lead, dtype=F32, device=curves.device)
     _chk(out, "causal_auc: out")
@@ -2113,14 +2111,11 @@ def channel_mean(x, absolute=False, out=None):
     _chk(x, "channel_mean: x"); _chk(out, "channel_mean: out")
     if x.dim() < 3:
         raise RuntimeError("channel_mean: x must be [..., C, H, W], got shape %s" % (tuple(x.shape),))
-    lead, (C, H, W) = tuple(x.shape[:-3]), x.shape[-3:]
+    (lead, M), (C, H, W) = _lead(x.shape, 3), x.shape[-3:]
     if out is None:
         out = torch.empty(lead + (H, W), dtype=F32, device=x.device)
     if tuple(out.shape) != lead + (H, W):
         raise RuntimeError("channel_mean: out must be %s, got shape %s" % (lead + (H, W), tuple(out.shape)))
-    M = 1
-    for v in lead:
-        M *= int(v)
     _native.check(_native.lib().scouter_channel_mean_f32(_p(x), _p(out), M, int(C), int(H) * int(W), 1 if absolute else 0,
                                                          _stream()), "channel_mean")
     return out

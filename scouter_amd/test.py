@@ -34,6 +34,7 @@ post-processing of these PNGs and is not reproduced.
         [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
         [--causal true --causal_step 224]"""
 import argparse
+import functools
 import os
 
 import numpy as np
@@ -88,57 +89,47 @@ def run_grad(args, model, image, out_dir):
     return maps
 
 
+def _run_maps(args, model, image, out_dir, stem, maps_fn):
+    """one attribution family for the one image: maps_fn(images [1, C, H, W] on the device, min_level=) -> uint8 maps [1, C, H, W]
+    on the device, saved as `<out>/<stem>_{c}.png`; returns them [C, H, W] (host)"""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    maps = maps_fn(image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level))[0].cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "%s_%d.png" % (stem, c)))
+    return maps
+
+
 def run_cam(args, model, image, out_dir):
     """--cam true: the Grad-CAM heat map of every class for the one image at the backbone's output (reference captum_vis.py
     LayerGradCam on layer4) -> `<out>/cam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from PIL import Image
     from .tools.attribution import gradcam_maps
-    os.makedirs(out_dir, exist_ok=True)
-    maps = gradcam_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
-                        min_level=float(args.grad_min_level))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "cam_%d.png" % c))
-    return maps
+    return _run_maps(args, model, image, out_dir, "cam", functools.partial(gradcam_maps, model))
 
 
 def run_rise(args, model, image, out_dir):
     """--rise true: the RISE saliency map of every class for the one image (reference torchcam_vis.py, torchray.attribution.rise)
     -> `<out>/rise_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from PIL import Image
     from .tools.attribution import rise_maps
-    os.makedirs(out_dir, exist_ok=True)
-    maps = rise_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level),
-                     n_masks=int(getattr(args, "rise_masks", 4000)), batch=int(getattr(args, "rise_batch", 250)))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "rise_%d.png" % c))
-    return maps
+    return _run_maps(args, model, image, out_dir, "rise",
+                     functools.partial(rise_maps, model, n_masks=int(getattr(args, "rise_masks", 4000)),
+                                       batch=int(getattr(args, "rise_batch", 250))))
 
 
 def run_scorecam(args, model, image, out_dir):
     """--scorecam true: the Score-CAM heat map of every class for the one image at the backbone's output (Wang et al. 2020; the
     gradient-free CAMs of the reference's torchcam_vis.py) -> `<out>/scorecam_{c}.png`, uint8 maps at the input resolution;
     returns them [C, H, W]."""
-    from PIL import Image
     from .tools.attribution import scorecam_maps
-    os.makedirs(out_dir, exist_ok=True)
-    maps = scorecam_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level),
-                         batch=int(getattr(args, "scorecam_batch", 250)))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "scorecam_%d.png" % c))
-    return maps
+    return _run_maps(args, model, image, out_dir, "scorecam",
+                     functools.partial(scorecam_maps, model, batch=int(getattr(args, "scorecam_batch", 250))))
 
 
 def run_campp(args, model, image, out_dir):
     """--campp true: the Grad-CAM++ heat map of every class for the one image at the backbone's output (torchcam's GradCAMpp of
     the reference's torchcam_vis.py) -> `<out>/campp_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from PIL import Image
     from .tools.attribution import gradcampp_maps
-    os.makedirs(out_dir, exist_ok=True)
-    maps = gradcampp_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
-                          min_level=float(args.grad_min_level))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "campp_%d.png" % c))
-    return maps
+    return _run_maps(args, model, image, out_dir, "campp", functools.partial(gradcampp_maps, model))
 
 
 def _smoothcampp_kwargs(args):
@@ -150,14 +141,9 @@ def run_smoothcampp(args, model, image, out_dir):
     """--smoothcampp true: the Smooth Grad-CAM++ heat map of every class for the one image (torchcam's SmoothGradCAMpp:
     --smoothcampp_samples noisy copies at --smoothcampp_sigma in chunks of --smoothcampp_batch) -> `<out>/smoothcampp_{c}.png`,
     uint8 maps at the input resolution; returns them [C, H, W]."""
-    from PIL import Image
     from .tools.attribution import smooth_gradcampp_maps
-    os.makedirs(out_dir, exist_ok=True)
-    maps = smooth_gradcampp_maps(model, image.unsqueeze(0).to(args.device, dtype=torch.float32),
-                                 min_level=float(args.grad_min_level), **_smoothcampp_kwargs(args))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "smoothcampp_%d.png" % c))
-    return maps
+    return _run_maps(args, model, image, out_dir, "smoothcampp",
+                     functools.partial(smooth_gradcampp_maps, model, **_smoothcampp_kwargs(args)))
 
 
 def _ig(args, model, x, classes=None):
@@ -173,14 +159,9 @@ def _smoothgrad(args, model, x, classes=None):
 
 
 def _run_gradient_family(args, model, image, out_dir, attribute, stem):
-    from PIL import Image
     from .tools.attribution import gradient_maps
-    os.makedirs(out_dir, exist_ok=True)
-    attr = attribute(args, model, image.unsqueeze(0).to(args.device, dtype=torch.float32))
-    maps = gradient_maps(attr, min_level=float(args.grad_min_level))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "%s_%d.png" % (stem, c)))
-    return maps
+    return _run_maps(args, model, image, out_dir, stem,
+                     lambda x, min_level: gradient_maps(attribute(args, model, x), min_level=min_level))
 
 
 def run_ig(args, model, image, out_dir):

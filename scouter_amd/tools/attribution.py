@@ -54,6 +54,7 @@ not change a bit) and rectifies the last sample's gradient, as the reference doe
 kernels (kernels.gradcampp, kernels.gradcampp_smooth); alpha is 0 where the reference divides 0 / 0.  Nothing comes to the host
 in between."""
 import collections
+import contextlib
 import functools
 
 import numpy as np
@@ -73,13 +74,10 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None):
     restored.  Parameters that require grad get their `.grad` overwritten by each backward, as in any backward of the model."""
     if of not in ("log_prob", "loss"):
         raise ValueError("of must be 'log_prob' or 'loss', got %r" % (of,))
-    if images.dim() != 4:
-        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    _check_images(images)
     if of == "loss" and target is None:
         raise ValueError("of='loss' needs target= labels")
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         grads = []
         with torch.enable_grad():
             if of == "loss":
@@ -99,6 +97,15 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None):
                     seed[:, int(c)] = 1.0
                     grads.append(torch.autograd.grad(out, x, seed)[0])
         return torch.stack(grads, dim=1)
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """the model in eval mode (BatchNorm uses its running statistics and no buffer moves); the caller's mode is restored"""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
     finally:
         model.train(was_training)
 
@@ -134,9 +141,7 @@ def _minmax(m):
 def _gradient_cam(model, images, classes, fill):
     """the loop shared by gradcam and gradcampp: one feature pass, one head backward per column of `classes`, and
     fill(features, feature gradient, cam[:, k]) for each -- one feature gradient alive at a time"""
-    if images.dim() != 4:
-        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
-    B = images.shape[0]
+    B = _check_images(images).shape[0]
     per_image, cols = _class_columns(classes, B, _num_classes(model, images))
     fp = model.feature_pass(images)
     feat = fp.features
@@ -176,7 +181,7 @@ def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
     launch (kernels.cam_maps; captum_vis.py:51-59) -- bilinear resize to `size` = (H, W) (None: the images' H x W), negative
     values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled again, times 255.  A map that is constant at
     either scaling step is all zeros, like attribution_maps."""
-    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    H, W = _out_size(size, images)
     return K.cam_maps(gradcam(model, images, classes), H, W, min_level)
 
 
@@ -201,7 +206,7 @@ def gradcampp_maps(model, images, classes=None, size=None, min_level=0.0, relu=T
     """uint8 Grad-CAM++ heat maps [B, K, H, W] on the device: `gradcampp`, then the drawing steps of `gradcam_maps` in one launch
     (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W).  A map that is constant at either scaling step is all
     zeros."""
-    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    H, W = _out_size(size, images)
     return K.cam_maps(gradcampp(model, images, classes, relu=relu), H, W, min_level)
 
 
@@ -269,7 +274,7 @@ def smooth_gradcampp(model, images, classes=None, n_samples=4, sigma=0.3, batch=
 def smooth_gradcampp_maps(model, images, classes=None, size=None, min_level=0.0, **smooth_kwargs):
     """uint8 Smooth Grad-CAM++ heat maps [B, K, H, W] on the device: `smooth_gradcampp` (its keyword arguments pass through), then
     the drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
-    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    H, W = _out_size(size, images)
     return K.cam_maps(smooth_gradcampp(model, images, classes, **smooth_kwargs), H, W, min_level)
 
 
@@ -334,24 +339,9 @@ def rise(model, images, classes=None, n_masks=4000, s=7, p=0.5, batch=250, seed=
     mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.rise_accumulate onto the
     result in mask order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied
     to the host and nothing synchronises inside the loop."""
-    if images.dim() != 4:
-        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
-    B, C, H, W = images.shape
-    n = _num_classes(model, images)
-    per_image = torch.is_tensor(classes)
-    if per_image:
-        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
-            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
-                             % (B, classes.dtype, tuple(classes.shape)))
-        cols = classes.detach().cpu().tolist()
-    else:
-        cols = [int(c) for c in (classes if classes is not None else range(n))]
-    for c in cols:
-        if not 0 <= c < n:
-            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
-    batch = int(batch)
-    if batch < 1:
-        raise ValueError("batch must be at least 1, got %d" % batch)
+    B, C, H, W = _check_images(images).shape
+    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
+    x, batch = _check_images_batch(images, batch)
     dev = images.device
     if masks is None:
         masks = rise_masks(n_masks, (H, W), s=s, p=p, seed=seed, device=dev)
@@ -360,28 +350,20 @@ def rise(model, images, classes=None, n_masks=4000, s=7, p=0.5, batch=250, seed=
         grids, shifts = _check_rise_masks(masks, (H, W), dev)
     N, s = int(grids.shape[0]), int(masks.s)
     scale = 1.0 / (N * float(masks.p))
-    x = images.detach().contiguous()
-    if x.dtype != torch.float32:
-        x = x.float()
     cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
     Kc = 1 if per_image else len(cols)
     out = torch.zeros((B, Kc, H, W), dtype=torch.float32, device=dev)
     if Kc == 0:
         return out
     buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for b in range(B):
-                cb = cols_dev[b:b + 1] if per_image else cols_dev
-                for n0 in range(0, N, batch):
-                    g, sh = grids[n0:n0 + batch], shifts[n0:n0 + batch]
-                    chunk = K.rise_mask_images(x[b], g, sh, buf[:g.shape[0]], s, check_shifts=False)
-                    logp = model(chunk)
-                    K.rise_accumulate(logp, cb, g, sh, out[b], s, scale, check_shifts=False)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            for n0 in range(0, N, batch):
+                g, sh = grids[n0:n0 + batch], shifts[n0:n0 + batch]
+                chunk = K.rise_mask_images(x[b], g, sh, buf[:g.shape[0]], s, check_shifts=False)
+                logp = model(chunk)
+                K.rise_accumulate(logp, cb, g, sh, out[b], s, scale, check_shifts=False)
     return out
 
 
@@ -411,28 +393,10 @@ def scorecam(model, images, classes=None, batch=250):
     mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.scorecam_accumulate onto the
     result in channel order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied
     to the host and nothing synchronises inside the loop."""
-    if images.dim() != 4:
-        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
-    B, Cin, H, W = images.shape
-    n = _num_classes(model, images)
-    per_image = torch.is_tensor(classes)
-    if per_image:
-        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
-            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
-                             % (B, classes.dtype, tuple(classes.shape)))
-        cols = classes.detach().cpu().tolist()
-    else:
-        cols = [int(c) for c in (classes if classes is not None else range(n))]
-    for c in cols:
-        if not 0 <= c < n:
-            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
-    batch = int(batch)
-    if batch < 1:
-        raise ValueError("batch must be at least 1, got %d" % batch)
+    B, Cin, H, W = _check_images(images).shape
+    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
+    x, batch = _check_images_batch(images, batch)
     dev = images.device
-    x = images.detach().contiguous()
-    if x.dtype != torch.float32:
-        x = x.float()
     feat = model.feature_pass(x).features.detach()          # (the FeaturePass and its head state are dropped here)
     feat = (feat.float() if feat.dtype != torch.float32 else feat).contiguous()
     _, h, w, C = feat.shape
@@ -443,18 +407,13 @@ def scorecam(model, images, classes=None, batch=250):
         return out
     buf = torch.empty((min(batch, C), Cin, H, W), dtype=torch.float32, device=dev)
     ranges = torch.empty((C, 2), dtype=torch.float32, device=dev)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for b in range(B):
-                cb = cols_dev[b:b + 1] if per_image else cols_dev
-                K.scorecam_ranges(feat[b], H, W, out=ranges)
-                for first in range(0, C, batch):
-                    chunk = K.scorecam_mask_images(x[b], feat[b], ranges, buf[:min(batch, C - first)], first)
-                    K.scorecam_accumulate(model(chunk), cb, feat[b], ranges, out[b], first)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            K.scorecam_ranges(feat[b], H, W, out=ranges)
+            for first in range(0, C, batch):
+                chunk = K.scorecam_mask_images(x[b], feat[b], ranges, buf[:min(batch, C - first)], first)
+                K.scorecam_accumulate(model(chunk), cb, feat[b], ranges, out[b], first)
     return out
 
 
@@ -463,7 +422,7 @@ def scorecam_maps(model, images, classes=None, size=None, min_level=0.0, batch=2
     launch (kernels.cam_maps) -- bilinear resize to `size` = (H, W) (None: the images' H x W), negative values cut to 0, min-max
     scaled, raised to at least `min_level`, min-max scaled again, times 255.  A map that is constant at either scaling step is
     all zeros."""
-    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    H, W = _out_size(size, images)
     return K.cam_maps(scorecam(model, images, classes, batch=batch), H, W, min_level)
 
 
@@ -510,13 +469,8 @@ def _num_outputs(model, images):
     try:
         return _num_classes(model, images)
     except AttributeError:
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                return int(model(images[:1].detach().float()).shape[1])
-        finally:
-            model.train(was_training)
+        with _eval_mode(model), torch.no_grad():
+            return int(model(images[:1].detach().float()).shape[1])
 
 
 def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen=11, sigma=5.0):
@@ -546,9 +500,7 @@ def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen
     inference fold is on; the caller's mode is restored), kernels.causal_curve.  kernels.causal_auc at the end.  No BatchNorm
     buffer moves, no `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop; two calls give
     the same bits."""
-    if images.dim() != 4:
-        raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
-    B, C, H, W = images.shape
+    B, C, H, W = _check_images(images).shape
     if not torch.is_tensor(maps) or maps.dim() != 4 or maps.shape[0] != B or maps.shape[1] < 1 or maps[0, 0].numel() < 1:
         raise ValueError("maps must be a tensor [B = %d, K, h, w], got %s"
                          % (B, tuple(maps.shape) if torch.is_tensor(maps) else type(maps).__name__))
@@ -556,25 +508,14 @@ def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen
         raise ValueError("maps must be fp32 or uint8, got %s" % maps.dtype)
     Kc = int(maps.shape[1])
     n = _num_outputs(model, images)
-    per_image = torch.is_tensor(classes)
-    if per_image:
-        if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
-            raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
-                             % (B, classes.dtype, tuple(classes.shape)))
-        if Kc != 1:
-            raise ValueError("a tensor of classes (each image its own class) needs K = 1 map per image, got K = %d" % Kc)
-        cols = classes.detach().cpu().tolist()
-    else:
-        cols = [int(c) for c in (classes if classes is not None else range(n))]
-        if len(cols) != Kc:
-            raise ValueError("%d maps per image for %d classes%s" % (Kc, len(cols), "" if classes is not None else
-                                                                   " (classes=None: one map per model output)"))
-    for c in cols:
-        if not 0 <= c < n:
-            raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
-    batch = int(batch)
-    if batch < 1:
-        raise ValueError("batch must be at least 1, got %d" % batch)
+    per_image, cols = _class_list(classes, B, n)
+    if per_image and Kc != 1:
+        raise ValueError("a tensor of classes (each image its own class) needs K = 1 map per image, got K = %d" % Kc)
+    if not per_image and len(cols) != Kc:
+        raise ValueError("%d maps per image for %d classes%s" % (Kc, len(cols), "" if classes is not None else
+                                                               " (classes=None: one map per model output)"))
+    _check_class_range(cols, n)
+    x, batch = _check_images_batch(images, batch)
     step = W if step is None else int(step)
     if step < 1:
         raise ValueError("step must be at least 1, got %d" % step)
@@ -584,9 +525,6 @@ def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen
     taps = gaussian_taps(klen, sigma).to(dev)
     n_points = -(-(H * W) // step) + 1
     total = 2 * Kc * n_points
-    x = images.detach().contiguous()
-    if x.dtype != torch.float32:
-        x = x.float()
     m = maps.detach().to(dev)
     m = (m.float() if m.dtype != torch.float32 else m).contiguous()
     cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
@@ -594,20 +532,15 @@ def causal_metrics(model, images, maps, classes=None, step=None, batch=250, klen
     buf = torch.empty((min(batch, total), C, H, W), dtype=torch.float32, device=dev)
     blurred = torch.empty((C, H, W), dtype=torch.float32, device=dev)
     ranks = torch.empty((Kc, H * W), dtype=torch.int32, device=dev)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for b in range(B):
-                cb = cols_dev[b:b + 1] if per_image else cols_dev
-                mb = m[b] if tuple(m.shape[2:]) == (H, W) else K.resize_bilinear(m[b], H, W)
-                K.saliency_ranks(mb.view(Kc, H * W), out=ranks)
-                K.separable_filter(x[b], taps, out=blurred)
-                for first in range(0, total, batch):
-                    chunk = K.causal_step_images(x[b], blurred, ranks, buf[:min(batch, total - first)], first, n_points, step)
-                    K.causal_curve(model(chunk), cb, curves[b], first, n_points)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            mb = m[b] if tuple(m.shape[2:]) == (H, W) else K.resize_bilinear(m[b], H, W)
+            K.saliency_ranks(mb.view(Kc, H * W), out=ranks)
+            K.separable_filter(x[b], taps, out=blurred)
+            for first in range(0, total, batch):
+                chunk = K.causal_step_images(x[b], blurred, ranks, buf[:min(batch, total - first)], first, n_points, step)
+                K.causal_curve(model(chunk), cb, curves[b], first, n_points)
     scores = K.causal_auc(curves)
     return CausalScores(scores[:, :, 0].contiguous(), scores[:, :, 1].contiguous(), curves[:, :, 0].contiguous(),
                         curves[:, :, 1].contiguous(), step)
@@ -640,19 +573,27 @@ def _quadrature_fp32(n_steps, method):
     return alphas.astype(np.float32), weights.astype(np.float32)
 
 
-def _class_columns(classes, B, n):
-    """the `classes` argument of gradcam / rise -> (per_image, cols): None (every output), a list of ints, or a LongTensor [B]"""
+def _class_list(classes, B, n):
+    """the `classes` argument of every method -> (per_image, cols): None (every output), a list of ints, or a LongTensor [B]"""
     per_image = torch.is_tensor(classes)
     if per_image:
         if classes.dtype != torch.int64 or classes.dim() != 1 or classes.shape[0] != B:
             raise ValueError("a tensor of classes must be a LongTensor [B = %d], got %s %s"
                              % (B, classes.dtype, tuple(classes.shape)))
-        cols = classes.detach().cpu().tolist()
-    else:
-        cols = [int(c) for c in (classes if classes is not None else range(n))]
+        return True, classes.detach().cpu().tolist()
+    return False, [int(c) for c in (classes if classes is not None else range(n))]
+
+
+def _check_class_range(cols, n):
     for c in cols:
         if not 0 <= c < n:
             raise IndexError("class %d out of range (the model has %d outputs)" % (c, n))
+
+
+def _class_columns(classes, B, n):
+    """_class_list with every column checked against the model's n outputs"""
+    per_image, cols = _class_list(classes, B, n)
+    _check_class_range(cols, n)
     return per_image, cols
 
 
@@ -678,29 +619,36 @@ def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, wan
     seed = torch.zeros((min(batch, N), n), dtype=torch.float32, device=dev)
     acc = torch.empty((C, H, W), dtype=torch.float64, device=dev)
     acc_sq = torch.empty_like(acc) if want_sq else None
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.enable_grad():
-            for b in range(B):
-                for k, c in enumerate(cols[b:b + 1] if per_image else cols):
-                    acc.zero_()
-                    if want_sq:
-                        acc_sq.zero_()
-                    seed.zero_()
-                    seed[:, c] = 1.0
-                    for first in range(0, N, batch):
-                        chunk = fill(b, buf[:min(batch, N - first)], first)
-                        K.grad_accumulate(_chunk_gradient(model, chunk, seed), weights, acc, acc_sq, first)
-                    finish(b, acc, acc_sq, out[b, k], None if totals is None else totals[b, k:k + 1])
-    finally:
-        model.train(was_training)
+    with _eval_mode(model), torch.enable_grad():
+        for b in range(B):
+            for k, c in enumerate(cols[b:b + 1] if per_image else cols):
+                acc.zero_()
+                if want_sq:
+                    acc_sq.zero_()
+                seed.zero_()
+                seed[:, c] = 1.0
+                for first in range(0, N, batch):
+                    chunk = fill(b, buf[:min(batch, N - first)], first)
+                    K.grad_accumulate(_chunk_gradient(model, chunk, seed), weights, acc, acc_sq, first)
+                finish(b, acc, acc_sq, out[b, k], None if totals is None else totals[b, k:k + 1])
     return out
 
 
-def _check_images_batch(images, batch):
+def _check_images(images):
     if images.dim() != 4:
         raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(images.shape),))
+    return images
+
+
+def _out_size(size, images):
+    """the `size` = (H, W) argument of the *_maps functions as two ints; None: the images' H x W"""
+    H, W = (int(v) for v in (size if size is not None else images.shape[-2:]))
+    return H, W
+
+
+def _check_images_batch(images, batch):
+    """images [B, C, H, W] and the chunk length of a batched method -> (the images detached, contiguous and fp32, int(batch))"""
+    _check_images(images)
     batch = int(batch)
     if batch < 1:
         raise ValueError("batch must be at least 1, got %d" % batch)
@@ -755,17 +703,12 @@ def integrated_gradients(model, images, classes=None, baseline=None, n_steps=50,
         return attr
     delta = torch.zeros((B, Kc), dtype=torch.float32, device=dev)
     if Kc:
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                for b in range(B):
-                    base = base_of(b)
-                    ends = model(torch.stack([torch.zeros_like(x[b]) if base is None else base, x[b]])).double()
-                    cb = cols[b:b + 1] if per_image else cols
-                    delta[b] = (totals[b] - (ends[1, cb] - ends[0, cb])).float()
-        finally:
-            model.train(was_training)
+        with _eval_mode(model), torch.no_grad():
+            for b in range(B):
+                base = base_of(b)
+                ends = model(torch.stack([torch.zeros_like(x[b]) if base is None else base, x[b]])).double()
+                cb = cols[b:b + 1] if per_image else cols
+                delta[b] = (totals[b] - (ends[1, cb] - ends[0, cb])).float()
     return attr, delta
 
 

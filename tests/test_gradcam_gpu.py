@@ -22,7 +22,10 @@ from oracle.gen_golden import MODEL_CASES, LAMBDA, model_inputs             # no
 
 
 # ------------------------------------------------------------------------------------------------------ 1: K.gradcam
-GRADCAM_SHAPES = [(1, 1, 1, 1), (2, 1, 1, 70), (3, 2, 3, 65), (2, 7, 7, 512), (2, 7, 7, 2048), (1, 9, 9, 2048), (2, 3, 3, 130)]
+GRADCAM_SHAPES = [(1, 1, 1, 1), (2, 1, 1, 70), (3, 2, 3, 65), (2, 7, 7, 512), (2, 7, 7, 2048), (1, 9, 9, 2048), (2, 3, 3, 130),
+                  # the routes of the column sums gradcam shares with gradcampp (MORE_SHAPES of test_gradcampp_gpu.py): at least
+                  # as many columns as threads with and without 16-byte loads, and the largest C
+                  (1, 4, 4, 4100), (1, 5, 5, 1030), (1, 5, 5, 8192)]
 SENTINEL = -777.25
 
 

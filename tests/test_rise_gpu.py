@@ -184,6 +184,19 @@ def test_heat_maps_equal_cam_maps_at_the_maps_own_size(size):
         assert torch.equal(K.heat_maps(x, min_level), K.cam_maps(x, h, w, min_level))
 
 
+@pytest.mark.parametrize("size", [(5, 3, 33, 47), (7, 7, 224, 224), (9, 9, 5, 7)], ids=lambda s: "%dx%d_to_%dx%d" % s)
+def test_cam_maps_equal_heat_maps_of_the_resized_maps(size):
+    """cam_maps never stores the resized map; resize_bilinear stores it.  Both form it with the same expression, so drawing the
+    stored one gives cam_maps' bytes."""
+    from scouter_amd import kernels as K
+    h, w, H, W = size
+    x = torch.randn((3, h, w), generator=torch.Generator().manual_seed(37)).cuda()
+    assert bool(torch.isfinite(x).all()) and bool((x > 0).any()) and bool((x < 0).any())
+    resized = K.resize_bilinear(x, H, W)
+    for min_level in (0.0, 0.3):
+        assert torch.equal(K.cam_maps(x, H, W, min_level), K.heat_maps(resized, min_level))
+
+
 def test_heat_maps_edge_cases():
     from scouter_amd import kernels as K
     gen = torch.Generator().manual_seed(23)

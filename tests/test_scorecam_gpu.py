@@ -111,6 +111,20 @@ def test_scorecam_ranges_against_fp64(case):
     _check_ranges(case)
 
 
+@pytest.mark.parametrize("case", [CASES[3], CASES[0]], ids=[CASE_IDS[3], CASE_IDS[0]])
+def test_scorecam_ranges_are_the_extrema_of_resize_bilinear(case):
+    """ranges[c] = (min, max) of the resized channel, bit for bit: the range kernel and kernels.resize_bilinear form the resized
+    value with the same expression.  randn features: finite, no constant channel, so no +0 / -0 tie enters."""
+    from scouter_amd import kernels as K
+    _, H, W, h, w, C, _, _ = case
+    A = torch.randn((h, w, C), generator=torch.Generator().manual_seed(7300)).cuda()
+    assert bool(torch.isfinite(A).all()) and bool((A.amax(dim=(0, 1)) > A.amin(dim=(0, 1))).all())
+    U = K.resize_bilinear(A.permute(2, 0, 1).contiguous(), H, W)                            # [C, H, W]
+    got = K.scorecam_ranges(A, H, W)
+    torch.cuda.synchronize()
+    assert torch.equal(got[:, 0], U.amin(dim=(1, 2))) and torch.equal(got[:, 1], U.amax(dim=(1, 2)))
+
+
 # ------------------------------------------------------------------------------------------------ 2: K.scorecam_mask_images
 def _check_mask_images(case, seed=0):
     from scouter_amd import kernels as K
