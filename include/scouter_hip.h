@@ -174,6 +174,62 @@ size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Co
 int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int kh,
                              int kw, int stride, int pad, int groups, int plan_hint, void* ws, size_t ws_bytes,
                              void* stream);
+/* ---- ROUTE QUERIES: what a convolution entry point answers to a shape, asked without calling it.  Each returns 1 or 0 and is
+ * a pure function of its integer arguments -- no HIP call, no routing switch, no error text -- so it can be called before a
+ * device exists and on a machine without one.  Each is defined next to its entry point and evaluates the SAME host predicate
+ * that entry point rejects through (csrc/conv_common.h): a wrapper that routes on a query cannot drift from the kernel.
+ * *_tile_ok(shape, tile, epilogue[, io]): naming `tile` runs that tile's kernel for a call with this shape, epilogue and
+ * storage.  Tiles that are HINTS answer 0 where the library runs another tile instead (SC_OK): tiles 0-3 of the fp32 /
+ * bf16-input kernels and the register-split family, plane tiles 0-5, and fp32 tile 4 on a SHAPE it does not cover (its
+ * partial rows come from the same choice: scouter_conv2d_*_bn_partial_rows).  Tiles that are REFUSED answer 0 exactly where
+ * the call returns SC_ERR_UNSUPPORTED: fp32 tile 4 on a covered shape with an epilogue that is not its own (forward: bias /
+ * addend / ReLU), fp32 tile 5, tile 4 of the typed kernels, tile 7 of the register-split family, plane tile 6.  Arguments no
+ * tensor reaches (2^36 pixels, 2^20 channels) answer 0.  Shape arguments are those of the entry point (B, H, W: the INPUT map).
+ * epilogue: SCOUTER_EPI_* bits of the call; io: SCOUTER_IO_* (forward) / SCOUTER_DGRAD_IO_* (typed input gradient). */
+#define SCOUTER_EPI_BIAS 1      /* bias != NULL */
+#define SCOUTER_EPI_ADDEND 2    /* addend != NULL */
+#define SCOUTER_EPI_RELU 4
+#define SCOUTER_EPI_BN_STATS 8  /* forward: bn_partial != NULL */
+#define SCOUTER_EPI_BN_BWD 16   /* input gradient: part1 != NULL (one fused BatchNorm backward) */
+#define SCOUTER_EPI_BN_BWD2 32  /* part2 != NULL too */
+int scouter_conv2d_fwd_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                               int tile, int epilogue);
+int scouter_conv2d_dgrad_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                 int tile, int epilogue);
+/* resident_rows != 0 asks instead: with switch bhalo on, the resident-rows kernel (csrc/conv_halo_dgrad_bf16.h) runs BEHIND
+ * `tile` (forward: tile 1 / 3 by the columns per group, x stored as bf16; input gradient: tile 3, dy stored as bf16) */
+int scouter_conv2d_fwd_bf16_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                    int tile, int epilogue, int io, int resident_rows);
+int scouter_conv2d_dgrad_bf16_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                      int groups, int tile, int epilogue, int io, int resident_rows);
+/* tile < 0: the entry point takes this shape at all (its own choice of tile) */
+int scouter_conv2d_fwd_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                  int tile, int epilogue);
+int scouter_conv2d_dgrad_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                    int tile, int epilogue);
+int scouter_conv2d_wgrad_x3_ok(int B, int H, int W, int Cin, int Cout);
+int scouter_conv2d_fwd_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                      int nplanes, int tile, int epilogue, int io);
+int scouter_conv2d_dgrad_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                        int groups, int nplanes, int tile, int epilogue);
+/* the plane weight gradient takes this shape with this plan (bit 6: the tap-fused plans) */
+int scouter_conv2d_wgrad_planes_plan_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int pad, int groups,
+                                        int nplanes, int plan);
+/* rows of fused BatchNorm partials plane tile 0..6 writes for M GEMM rows */
+int scouter_conv2d_planes_partial_rows(long M, int tile);
+/* which weight-gradient kernels take this shape: F32 / BF16 -- the entry point does; TAPS / XWT -- scouter_conv2d_wgrad_f32's
+ * own plan (plan_hint < 0) is the tap-fused fp32 kernel / behind switch xwt the register-split one; BWT -- with both operands
+ * stored as bf16 and switch bwt on, scouter_conv2d_wgrad_bf16_io's own plan is the tap-fused one-plane kernel.  Otherwise the
+ * own plan runs one workgroup per tap.  ROWS32 -- the layer shape XWT and BWT share (3x3 / stride 1 / pad 1, 32 input channels
+ * per group, a map at most 112 wide and two rows high), without their map-size and byte guards. */
+#define SCOUTER_WGRAD_F32 0
+#define SCOUTER_WGRAD_BF16 1
+#define SCOUTER_WGRAD_TAPS 2
+#define SCOUTER_WGRAD_XWT 3
+#define SCOUTER_WGRAD_BWT 4
+#define SCOUTER_WGRAD_ROWS32 5
+int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                   int kernel);
 /* stem (Cin < 32): im2col of the NCHW image into [M][Kpad] rows so the stem runs as a 1x1 conv on the same path */
 int scouter_im2col_nchw_f32(const float* x, float* col, int B, int Cin, int H, int W, int k, int stride, int pad,
                             int Kpad, void* stream);

@@ -247,10 +247,7 @@ static void launch_bf16(const void* src, const void* w, const float* bias, const
                         double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz, int io) {
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
     dim3 grid(mtiles * ntiles * g.groups);
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     const size_t epi = (size_t)4 * WM * (WN + 4) * sizeof(float);
     auto go = [&](auto kern, int kt) {
         // one LDS stage (half the LDS, up to twice the resident workgroups) for launches that live on loads in flight rather
@@ -292,11 +289,15 @@ static void launch_bhalo_fwd(const void* src, const void* w, const float* bias, 
     hipLaunchKernelGGL(kern, dim3(bhalo_grid(NB == 1 ? 768 : 512, mtiles, g.groups)), dim3(256), blds, st, (const unsigned short*)src,
                        (const unsigned short*)w, bias, addend, dst, bn_part, g, relu, mtiles, (io & SC_IO_Y_BF16) ? 1 : 0);
 }
+// what both entry points ask of every shape
+static bool bf16_entry_ok(const ConvGeom& g) {
+    return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28);
+}
 template <bool DGRAD>
 static int dispatch_bf16(const void* src, const void* w, const float* bias, const float* addend, float* dst,
                          double* bn_part, const ConvGeom& g, int relu, int tile, hipStream_t st,
                          const BnBwdFuse& fz, int io, bool bhalo) {   // bhalo: the caller's resident-rows decision
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28),
+    SC_UNSUPPORTED(bf16_entry_ok(g),
                    "conv2d_bf16: more than 2^31 output pixels or an image above 2^28 elements is not supported");
     if (!DGRAD && bhalo) {
         // resident x rows for all nine taps (conv_halo_dgrad_bf16.h): bit-identical to tiles 1 / 3, same partial rows
@@ -325,25 +326,24 @@ static int dispatch_bf16(const void* src, const void* w, const float* bias, cons
     return sc_check_launch(DGRAD ? "conv2d_dgrad_bf16" : "conv2d_fwd_bf16");
 }
 static int bf16_tile(const ConvGeom& g, int hint) {       // 0: 128x128  1: 128x64  2: 64x64  3: 128x32
-    auto ok = [&](int t) { return (t == 0 && g.Ng % 128 == 0) || ((t == 1 || t == 2) && g.Ng % 64 == 0) || t == 3; };
-    if (hint >= 0 && hint <= 3 && ok(hint)) return hint;
+    if (hint >= 0 && hint <= 3 && sc_igemm_tile_ok(g.Ng, hint)) return hint;
     auto blocks = [&](int bm, int bn) { return (long)sc_cdiv(g.M, bm) * (g.Ng / bn) * g.groups; };
     if (g.Ng % 128 == 0 && blocks(128, 128) >= 768) return 0;
     if (g.Ng % 64 == 0 && blocks(128, 64) >= 768) return 1;
     if (g.Ng % 64 == 0) return 2;
     return 3;
 }
-static int conv_out_b(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 
 // ---- tile 4: the persistent pointwise input gradient with the fused BatchNorm-backward epilogue, all tensors bf16-stored
 // (conv_pw_persist_bf16.h)
 struct PwbPlan { int ks, wg_per_col; };
-static bool pwb_geom_ok(const ConvGeom& g, bool has_addend, const BnBwdFuse& fz, int io) {
+// epi: SC_EPI_*; io: the entry point's SCOUTER_DGRAD_IO_* bits (1 / 2: x1 / x2, 4: addend, 8: dy, 16: dx)
+static bool pwb_geom_ok(const ConvGeom& g, int epi, int io) {
     const bool pointwise = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
     const bool k_ok = g.Cg == 64 || g.Cg == 128 || g.Cg == 256 || g.Cg == 512;
-    const bool stored_bf16 = (io & SC_IO_X_BF16) && (io & SC_IO_Y_BF16) && (fz.io & 1) && (!fz.part2 || (fz.io & 2)) &&
-                             (!has_addend || (fz.io & 4));
-    return pointwise && k_ok && g.Ng % 128 == 0 && fz.part1 != nullptr && stored_bf16 &&
+    const bool stored_bf16 = (io & 8) && (io & 16) && (io & 1) && (!(epi & SC_EPI_BN_BWD2) || (io & 2)) &&
+                             (!(epi & SC_EPI_ADDEND) || (io & 4));
+    return pointwise && k_ok && g.Ng % 128 == 0 && (epi & SC_EPI_BN_BWD) && stored_bf16 &&
            (g.M + 128) * g.Ng < (1L << 30) &&      // (every bf16 tensor < 2 GiB: the kernel clamps scalar row offsets at 2^31 - 1)
            g.M * g.Cg < (1L << 30);
 }
@@ -377,10 +377,10 @@ static void launch_pwb_fused(const void* src, const float* w, const void* addend
 }
 
 // ---- tile 4 of the typed input gradient WITHOUT the fused epilogue (conv_pw_persist_bf16.h pwb_dgrad_kernel): dY bf16, dx fp32
-static bool pwb_plain_geom_ok(const ConvGeom& g, int io_xy) {
+static bool pwb_plain_geom_ok(const ConvGeom& g, int io) {         // (io as pwb_geom_ok)
     const bool pointwise = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
     const bool k_ok = g.Cg == 64 || g.Cg == 128 || g.Cg == 256 || g.Cg == 512 || g.Cg == 1024;
-    return pointwise && k_ok && g.Ng % 64 == 0 && (io_xy & SC_IO_X_BF16) && !(io_xy & SC_IO_Y_BF16) &&
+    return pointwise && k_ok && g.Ng % 64 == 0 && (io & 8) && !(io & 16) &&
            (g.M + 128) * g.Ng < (1L << 30) && g.M * g.Cg < (1L << 30);
 }
 static void launch_pwb_dgrad(const void* src, const float* w, const void* addend, float* dst, const ConvGeom& g, hipStream_t st,
@@ -438,6 +438,40 @@ static void launch_pwb_fwd(const void* src, const void* wt, void* dst, double* b
 #undef PWF
 }
 
+// naming `tile` runs that tile's kernel for this shape, epilogue (SC_EPI_*) and storage: tiles 0-3 are hints (bf16_tile), the
+// persistent tile 4 is refused where it does not apply
+static bool bf16_fwd_named_tile_ok(const ConvGeom& g, int tile, int epi, int io) {
+    if (tile == 4) return pwb_fwd_geom_ok(g, !(epi & (SC_EPI_BIAS | SC_EPI_ADDEND | SC_EPI_RELU)), io);
+    return tile >= 0 && tile <= 3 && sc_igemm_tile_ok(g.Ng, tile);
+}
+static bool bf16_dgrad_named_tile_ok(const ConvGeom& g, int tile, int epi, int io) {
+    if (tile == 4) return (epi & SC_EPI_BN_BWD) ? pwb_geom_ok(g, epi, io) : pwb_plain_geom_ok(g, io);
+    return tile >= 0 && tile <= 3 && sc_igemm_tile_ok(g.Ng, tile);
+}
+// the resident-rows kernels (conv_halo_dgrad_bf16.h) run BEHIND a tile of the same 128-pixel partial rows, switch bhalo on:
+// the forward behind tile 1 (64 columns per group) / 3 (32), the input gradient behind tile 3 with at most one fused BatchNorm
+static bool bhalo_fwd_runs(const ConvGeom& g, int tile, int io) { return tile == (g.Ng == 64 ? 1 : 3) && bhalo_fwd_ok(g, io); }
+static bool bhalo_dgrad_runs(const ConvGeom& g, int tile, int epi, int io) {
+    return tile == 3 && !(epi & SC_EPI_BN_BWD2) && bhalo_dgrad_ok(g, (io & 8) ? SC_IO_X_BF16 : 0);
+}
+
+// the queries of the two entry points below (include/scouter_hip.h).  resident_rows != 0: "the resident-rows kernel runs behind
+// `tile`" instead of "naming `tile` runs it"
+extern "C" int scouter_conv2d_fwd_bf16_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                               int groups, int tile, int epilogue, int io, int resident_rows) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups) || (io & ~(SC_IO_X_BF16 | SC_IO_Y_BF16))) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    if (!bf16_entry_ok(g) || !bf16_fwd_named_tile_ok(g, tile, epilogue, io)) return 0;
+    return !resident_rows || bhalo_fwd_runs(g, tile, io);
+}
+extern "C" int scouter_conv2d_dgrad_bf16_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                                 int groups, int tile, int epilogue, int io, int resident_rows) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups) || (io & ~31) || stride != 1) return 0;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    if (!bf16_entry_ok(g) || !bf16_dgrad_named_tile_ok(g, tile, epilogue, io)) return 0;
+    return !resident_rows || bhalo_dgrad_runs(g, tile, epilogue, io);
+}
+
 extern "C" int scouter_conv2d_weight_bf16t(const float* w, void* wt, int kh, int kw, int Cin, int Cout, int groups,
                                            void* stream) {
     SC_REQUIRE(w && wt && groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_weight_bf16t: bad arguments");
@@ -458,19 +492,17 @@ extern "C" int scouter_conv2d_fwd_bf16_io(const void* x, const void* wt_bf16, co
     SC_REQUIRE((io & ~(SC_IO_X_BF16 | SC_IO_Y_BF16)) == 0, "conv2d_fwd_bf16: unknown io bits %d", io);
     SC_REQUIRE(!(bn_partial && relu), "conv2d_fwd_bf16: fused BatchNorm statistics are taken before any activation");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd_bf16: channels not divisible by groups");
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    SC_UNSUPPORTED(Cg % 32 == 0 && Ng % 32 == 0, "conv2d_fwd_bf16: per-group channels must be multiples of 32");
-    ConvGeom g{B, H, W, Cin, conv_out_b(H, kh, stride, pad), conv_out_b(W, kw, stride, pad), Cout, kh, kw, stride, pad,
-               groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * g.Ho * g.Wo;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    SC_UNSUPPORTED(g.Cg % 32 == 0 && g.Ng % 32 == 0, "conv2d_fwd_bf16: per-group channels must be multiples of 32");
     static const char* names[5] = {"igemm_fwd_bf16<128x128>", "igemm_fwd_bf16<128x64>", "igemm_fwd_bf16<64x64>", "igemm_fwd_bf16<128x32>",
                                    "igemm_fwd_bf16<persistent>"};
-    SC_UNSUPPORTED(tile_hint != 4 || pwb_fwd_geom_ok(g, !bias && !addend && !relu, io),
+    const int epi = sc_epi_bits(bias, addend, relu, bn_partial);
+    SC_UNSUPPORTED(tile_hint != 4 || bf16_fwd_named_tile_ok(g, 4, epi, io),
                    "conv2d_fwd_bf16: tile 4 (persistent) covers 1x1 / stride 1 / groups 1 layers with 64 / 128 / 256 / 512 input "
                    "channels stored as bf16, 128-multiples of output channels, no bias / addend / ReLU");
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
     // tiles 1 (128 x 64) / 3 (128 x 32): the same 128-pixel partial rows (SCOUTER_BHALO=0: the tile kernel)
-    const bool bhalo = tile == (g.Ng == 64 ? 1 : 3) && sc_switch(SC_SW_BHALO) && bhalo_fwd_ok(g, io);
+    const bool bhalo = sc_switch(SC_SW_BHALO) && bhalo_fwd_runs(g, tile, io);
     ScProfScope prof(bhalo ? "bhalo_fwd<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cout * g.Cg * kh * kw,
                      ((io & SC_IO_X_BF16) ? 2.0 : 4.0) * B * H * W * Cin + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0) * g.M * Cout);
     if (tile == 4) {
@@ -484,10 +516,7 @@ extern "C" int scouter_conv2d_fwd_bf16_io(const void* x, const void* wt_bf16, co
 extern "C" int scouter_conv2d_fwd_bn_partial_rows_bf16(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                                                        int pad, int groups, int tile_hint) {
     if (!(groups > 0 && Cin % groups == 0 && Cout % groups == 0)) return 0;
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    ConvGeom g{B, H, W, Cin, conv_out_b(H, kh, stride, pad), conv_out_b(W, kw, stride, pad), Cout, kh, kw, stride, pad,
-               groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * g.Ho * g.Wo;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     if (tile_hint == 4) return pwb_fwd_wg_per_col(g);
     return sc_cdiv(g.M, bf16_tile(g, tile_hint) == 2 ? 64 : 128);
 }
@@ -513,9 +542,8 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
     SC_UNSUPPORTED(stride == 1, "conv2d_dgrad_bf16: strided input gradients use the fp32 kernel");
     const int Cig = Cin / groups, Cog = Cout / groups;
     SC_UNSUPPORTED(Cig % 32 == 0 && Cog % 32 == 0, "conv2d_dgrad_bf16: per-group channels must be multiples of 32");
-    const int Ho = conv_out_b(H, kh, stride, pad), Wo = conv_out_b(W, kw, stride, pad);
-    ConvGeom g{B, Ho, Wo, Cout, H, W, Cin, kh, kw, stride, pad, groups, Cog, Cig, 0, Cout, Cig * Cout};
-    g.M = (long)B * H * W;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    const int Ho = g.H, Wo = g.W;
     static const char* names[5] = {"igemm_dgrad_bf16<128x128>", "igemm_dgrad_bf16<128x64>", "igemm_dgrad_bf16<64x64>", "igemm_dgrad_bf16<128x32>",
                                    "igemm_dgrad_bf16<persistent>"};
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, (const float*)x1, saved1, part1,
@@ -523,14 +551,15 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
     const int io_xy = ((io & 8) ? SC_IO_X_BF16 : 0) | ((io & 16) ? SC_IO_Y_BF16 : 0);
     // (the caller named the persistent kernel: its partial-row layout differs, so an unsupported request is an error, never a
     // silent re-route)
-    SC_UNSUPPORTED(tile_hint != 4 || (part1 ? pwb_geom_ok(g, addend != nullptr, fz, io_xy) : pwb_plain_geom_ok(g, io_xy)),
+    const int epi = sc_epi_bits(nullptr, addend, 0, nullptr, part1, part2);
+    SC_UNSUPPORTED(tile_hint != 4 || bf16_dgrad_named_tile_ok(g, 4, epi, io),
                    "conv2d_dgrad_bf16: tile 4 (persistent) covers 1x1 / stride 1 / groups 1 input gradients -- with the fused "
                    "BatchNorm-backward epilogue: Cout of 64 / 128 / 256 / 512, 128-multiples of Cin, every tensor stored as bf16; "
                    "without: Cout of 64 ... 1024, 64-multiples of Cin, dy stored as bf16, dx fp32");
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
     // algorithmic bytes: dy, dx and -- the fused launch -- the shortcut gradient, the BatchNorm input(s) and the ReLU bits
     const double out_elems = (double)g.M * Cin;
-    const bool bhalo = tile == 3 && !part2 && sc_switch(SC_SW_BHALO) && bhalo_dgrad_ok(g, io_xy);   // (SCOUTER_BHALO=0: the tile kernel)
+    const bool bhalo = sc_switch(SC_SW_BHALO) && bhalo_dgrad_runs(g, tile, epi, io);      // (SCOUTER_BHALO=0: the tile kernel)
     ScProfScope prof(bhalo ? "bhalo_dgrad<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cin * Cog * kh * kw,
                      ((io & 8) ? 2.0 : 4.0) * B * Ho * Wo * Cout + ((io & 16) ? 2.0 : 4.0) * out_elems +
                          (addend ? ((io & 4) ? 2.0 : 4.0) * out_elems : 0.0) +
@@ -549,10 +578,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
 extern "C" int scouter_conv2d_dgrad_bn_partial_rows_bf16(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                                                          int pad, int groups, int tile_hint, int two_batchnorms) {
     if (!(groups > 0 && Cin % groups == 0 && Cout % groups == 0) || stride != 1) return 0;
-    const int Cig = Cin / groups, Cog = Cout / groups;
-    const int Ho = conv_out_b(H, kh, stride, pad), Wo = conv_out_b(W, kw, stride, pad);
-    ConvGeom g{B, Ho, Wo, Cout, H, W, Cin, kh, kw, stride, pad, groups, Cog, Cig, 0, Cout, Cig * Cout};
-    g.M = (long)B * H * W;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     if (tile_hint == 4) return pwb_plan(g, two_batchnorms != 0).wg_per_col;
     return sc_cdiv(g.M, bf16_tile(g, tile_hint) == 2 ? 64 : 128);
 }

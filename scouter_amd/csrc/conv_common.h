@@ -17,6 +17,69 @@ struct ConvGeom {
     float inv_wo, inv_ho;
 };
 
+// ---- host side: geometry construction and what the acceptance rules share.  Every kernel's rule is ONE named host predicate
+// over a ConvGeom (next to its launcher); the entry point rejects through it and the exported *_tile_ok / *_ok query of the
+// same .hip file answers with it -- pure integer functions: no HIP call, no switch, no error text.
+inline int sc_conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+
+// a pixel count no tensor reaches (2^36 pixels of one bf16 channel are 128 GiB): keeps every product of the rules inside 64 bits
+inline bool sc_pixels_ok(int B, int H, int W) {
+    return B > 0 && H > 0 && W > 0 && H <= (1 << 24) && W <= (1 << 24) && (long)B * H <= (1L << 36) / W;
+}
+// arguments every convolution entry point requires, for the QUERIES, which take any integers: they answer 0 instead of
+// dividing by a zero stride / group count, and to sizes no tensor has (2^20 channels, 2^16-wide filters, a weight tap past the
+// int ConvGeom.wtap holds) instead of overflowing a product
+inline bool sc_conv_args_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups) {
+    const int lim = 1 << 16;
+    return kh > 0 && kw > 0 && kh < lim && kw < lim && stride > 0 && pad >= 0 && pad < lim && sc_pixels_ok(B, H, W) &&
+           sc_pixels_ok(B, H + 2 * pad, W + 2 * pad) && Cin > 0 && Cout > 0 && Cin <= (1 << 20) && Cout <= (1 << 20) && groups > 0 &&
+           Cin % groups == 0 && Cout % groups == 0 && (long)(Cin / groups) * Cout < (1L << 31) && H + 2 * pad >= kh &&
+           W + 2 * pad >= kw;
+}
+
+// forward (and weight gradient): A = x [B][H][W][Cin], GEMM rows = output pixels, columns = Cout
+inline ConvGeom sc_fwd_geom(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups) {
+    const int Cg = Cin / groups, Ng = Cout / groups;
+    ConvGeom g{B, H, W, Cin, sc_conv_out(H, kh, stride, pad), sc_conv_out(W, kw, stride, pad), Cout, kh, kw, stride, pad,
+               groups, Cg, Ng, 0, Cout, Cg * Cout};
+    g.M = (long)B * g.Ho * g.Wo;
+    return g;
+}
+
+// input gradient: A = dY [B][Ho][Wo][Cout], GEMM rows = input pixels (H x W), columns = Cin
+inline ConvGeom sc_dgrad_geom(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups) {
+    const int Cig = Cin / groups, Cog = Cout / groups;
+    ConvGeom g{B, sc_conv_out(H, kh, stride, pad), sc_conv_out(W, kw, stride, pad), Cout, H, W, Cin, kh, kw, stride, pad,
+               groups, Cog, Cig, 0, Cout, Cig * Cout};
+    g.M = (long)B * H * W;
+    return g;
+}
+
+inline ConvGeom sc_with_reciprocals(ConvGeom g) {
+    g.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
+    g.inv_wo = 1.0f / (float)g.Wo;
+    g.inv_ho = 1.0f / (float)g.Ho;
+    return g;
+}
+
+// block tiles 0-3 of the fp32 and the bf16-input implicit-GEMM kernels: 128x128, 128x64, 64x64, 128x32 (Ng a multiple of 32)
+inline bool sc_igemm_tile_ok(int Ng, int tile) {
+    return (tile == 0 && Ng % 128 == 0) || ((tile == 1 || tile == 2) && Ng % 64 == 0) || tile == 3;
+}
+
+// epilogue of a call as the rules read it (include/scouter_hip.h SCOUTER_EPI_*)
+#define SC_EPI_BIAS 1
+#define SC_EPI_ADDEND 2
+#define SC_EPI_RELU 4
+#define SC_EPI_BN_STATS 8
+#define SC_EPI_BN_BWD 16
+#define SC_EPI_BN_BWD2 32
+inline int sc_epi_bits(const void* bias, const void* addend, int relu, const void* bn_part, const void* part1 = nullptr,
+                       const void* part2 = nullptr) {
+    return (bias ? SC_EPI_BIAS : 0) | (addend ? SC_EPI_ADDEND : 0) | (relu ? SC_EPI_RELU : 0) | (bn_part ? SC_EPI_BN_STATS : 0) |
+           (part1 ? SC_EPI_BN_BWD : 0) | (part2 ? SC_EPI_BN_BWD2 : 0);
+}
+
 // floor(n / d) for 0 <= n < 2^20 with inv = 1/d: (n + 0.5) / d is at least 0.5/d away from every integer, far more
 // than the float rounding error at these magnitudes, so truncation is exact (3 VALU instead of ~40 for a division)
 __device__ __forceinline__ int fast_div(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }

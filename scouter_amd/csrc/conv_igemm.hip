@@ -641,10 +641,7 @@ static void launch_igemm_s(const float* src, const float* w, const float* bias, 
                            double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
     dim3 grid(mtiles * ntiles * g.groups);
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     if (DGRAD && fz.part1)
         hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, DGRAD, STRIDED, PW, DGRAD>), grid, dim3(256), 0, st, src, w, bias,
                            addend, dst, bn_part, gg, relu, mtiles, ntiles, fz);
@@ -798,15 +795,25 @@ static void launch_xpw_fwd(const float* src, const float* w, float* dst, double*
 #undef XPF
 }
 
-// tile choice: largest tile that still fills the chip (>= ~1.5 rounds of 256 CUs x 2 blocks); Ng is a multiple of 32
-static bool igemm_tile_ok(const ConvGeom& g, int t) {
-    return (t == 0 && g.Ng % 128 == 0) || ((t == 1 || t == 2) && g.Ng % 64 == 0) || t == 3;
+// what both entry points ask of every shape
+static bool igemm_entry_ok(const ConvGeom& g) {
+    return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28);
 }
+// naming `tile` runs that tile's kernel for this shape and epilogue (SC_EPI_*).  Tiles 0-3 are hints: where one does not divide
+// Ng the heuristic below picks another; the persistent tiles 4 / 5 are refused where the epilogue is not theirs
+template <bool DGRAD>
+static bool igemm_named_tile_ok(const ConvGeom& g, int tile, int epi) {
+    const bool no_bias_relu = !(epi & (SC_EPI_BIAS | SC_EPI_RELU)), plain_fwd = !(epi & (SC_EPI_ADDEND | SC_EPI_BN_BWD));
+    if (tile == 4) return pwp_geom_ok(g) && no_bias_relu && (DGRAD || plain_fwd);
+    if (tile == 5) return xpw_geom_ok(g) && no_bias_relu && (DGRAD ? (epi & SC_EPI_BN_BWD) != 0 : plain_fwd);
+    return tile >= 0 && tile <= 3 && sc_igemm_tile_ok(g.Ng, tile);
+}
+// tile choice: largest tile that still fills the chip (>= ~1.5 rounds of 256 CUs x 2 blocks); Ng is a multiple of 32
 // hint >= 0: the caller's (autotuned) choice if legal for this shape; otherwise the static heuristic
 static int igemm_tile(const ConvGeom& g, int hint = -1) {     // 0: 128x128  1: 128x64  2: 64x64  3: 128x32  4: persistent
     if (hint == 4 && pwp_geom_ok(g)) return 4;                //                                  5: persistent bf16x3 (fused dgrad)
     if (hint == 5 && xpw_geom_ok(g)) return 5;
-    if (hint >= 0 && hint <= 3 && igemm_tile_ok(g, hint)) return hint;
+    if (hint >= 0 && hint <= 3 && sc_igemm_tile_ok(g.Ng, hint)) return hint;
     auto blocks = [&](int bm, int bn) { return (long)sc_cdiv(g.M, bm) * (g.Ng / bn) * g.groups; };
     const long want = 768;
     if (g.Ng % 128 == 0 && blocks(128, 128) >= want) return 0;
@@ -819,12 +826,12 @@ template <bool DGRAD>
 static int dispatch_igemm(const float* src, const float* w, const float* bias, const float* addend, float* dst,
                           double* bn_part, const ConvGeom& g, int relu, int tile, hipStream_t st,
                           const BnBwdFuse& fz = BnBwdFuse{}) {
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28),
-                   "conv2d: more than 2^31 output pixels or an image above 2^28 elements is not supported");
+    SC_UNSUPPORTED(igemm_entry_ok(g), "conv2d: more than 2^31 output pixels or an image above 2^28 elements is not supported");
+    const int epi = sc_epi_bits(bias, addend, relu, bn_part, fz.part1, fz.part2);
     if (tile == 4) {
         // (the caller named the persistent kernel: its partial-row layout differs, so an unsupported request is an error,
         // never a silent re-route)
-        SC_UNSUPPORTED(pwp_geom_ok(g) && !bias && !relu && (DGRAD || (!addend && !fz.part1)),
+        SC_UNSUPPORTED(igemm_named_tile_ok<DGRAD>(g, 4, epi),
                        "conv2d: tile 4 (persistent pointwise kernel) covers 1x1 / stride 1 / groups 1 convolutions with 64, 128 "
                        "or 256 GEMM-K channels, no bias / ReLU (forward: no addend)");
         if (DGRAD && fz.part1) launch_pwp_fused(src, w, addend, dst, g, st, fz);
@@ -832,7 +839,7 @@ static int dispatch_igemm(const float* src, const float* w, const float* bias, c
         return sc_check_launch(DGRAD ? "conv2d_dgrad(persistent)" : "conv2d_fwd(persistent)");
     }
     if (tile == 5) {
-        SC_UNSUPPORTED(xpw_geom_ok(g) && !bias && !relu && (DGRAD ? fz.part1 != nullptr : (!addend && !fz.part1)),
+        SC_UNSUPPORTED(igemm_named_tile_ok<DGRAD>(g, 5, epi),
                        "conv2d: tile 5 (persistent bf16x3 kernel) covers 1x1 / stride 1 / groups 1 layers with GEMM-K of 64 / 128 / "
                        "256 and 64-multiples of output columns: the forward without bias / addend / ReLU, the input gradient with "
                        "the fused BatchNorm-backward epilogue");
@@ -849,24 +856,25 @@ static int dispatch_igemm(const float* src, const float* w, const float* bias, c
     return sc_check_launch(DGRAD ? "conv2d_dgrad" : "conv2d_fwd");
 }
 
-static int conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
-
-static int conv_fwd_geom(ConvGeom& g, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
-                         int groups) {
-    if (!(groups > 0 && Cin % groups == 0 && Cout % groups == 0)) return SC_ERR_ARG;
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    if (!(Cg % 32 == 0 && Ng % 32 == 0)) return SC_ERR_UNSUPPORTED;
-    g = ConvGeom{B, H, W, Cin, conv_out(H, kh, stride, pad), conv_out(W, kw, stride, pad), Cout, kh, kw, stride, pad,
-                 groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * g.Ho * g.Wo;
-    return SC_OK;
+// the shape and epilogue queries of the two entry points below (include/scouter_hip.h): what they would answer to `tile`
+extern "C" int scouter_conv2d_fwd_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                          int groups, int tile, int epilogue) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return igemm_entry_ok(g) && igemm_named_tile_ok<false>(g, tile, epilogue);
+}
+extern "C" int scouter_conv2d_dgrad_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                            int groups, int tile, int epilogue) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return igemm_entry_ok(g) && igemm_named_tile_ok<true>(g, tile, epilogue);
 }
 
 // number of [Cout][2] fp64 rows the fused BatchNorm-statistics epilogue writes (= M tiles of the chosen kernel)
 extern "C" int scouter_conv2d_fwd_bn_partial_rows(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                                                   int pad, int groups, int tile_hint) {
-    ConvGeom g;
-    if (conv_fwd_geom(g, B, H, W, Cin, Cout, kh, kw, stride, pad, groups) != SC_OK) return 0;
+    if (!(groups > 0 && Cin % groups == 0 && Cout % groups == 0 && Cin / groups % 32 == 0 && Cout / groups % 32 == 0)) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     const int t = igemm_tile(g, tile_hint);
     if (t == 4) { const PwpPlan p = pwp_plan(g); return p.wg_per_col * p.waves_m; }    // one row per (workgroup, wave row)
     if (t == 5) return xpw_plan(g).wg_per_col;                                         // one row per workgroup row
@@ -878,13 +886,10 @@ extern "C" int scouter_conv2d_fwd_f32(const float* x, const float* w, const floa
                                       int kw, int stride, int pad, int groups, int relu, int tile_hint, void* stream) {
     SC_REQUIRE(x && w && y && B > 0 && H > 0 && W > 0, "conv2d_fwd: null pointer or empty shape");
     SC_REQUIRE(!(bn_partial && relu), "conv2d_fwd: fused BatchNorm statistics are taken before any activation");
-    ConvGeom g;
-    const int rc = conv_fwd_geom(g, B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    if (rc == SC_ERR_ARG) { sc_set_error("conv2d_fwd: channels not divisible by groups"); return rc; }
-    if (rc == SC_ERR_UNSUPPORTED) {
-        sc_set_error("conv2d_fwd: per-group channels must be multiples of 32 (got %d -> %d)", Cin / groups, Cout / groups);
-        return rc;
-    }
+    SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd: channels not divisible by groups");
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    SC_UNSUPPORTED(g.Cg % 32 == 0 && g.Ng % 32 == 0, "conv2d_fwd: per-group channels must be multiples of 32 (got %d -> %d)",
+                   g.Cg, g.Ng);
     static const char* names[6] = {"igemm_fwd<128x128>", "igemm_fwd<128x64>", "igemm_fwd<64x64>", "igemm_fwd<128x32>",
                                    "igemm_fwd<persistent>", "xpw_fwd<bf16x3>"};
     SC_UNSUPPORTED(tile_hint != 5 || xpw_geom_ok(g), "conv2d_fwd: tile 5 (persistent bf16x3 kernel) covers 1x1 / stride 1 / groups 1 "
@@ -895,20 +900,11 @@ extern "C" int scouter_conv2d_fwd_f32(const float* x, const float* w, const floa
     return dispatch_igemm<false>(x, w, bias, addend, y, bn_partial, g, relu, tile, (hipStream_t)stream);
 }
 
-static ConvGeom dgrad_geom(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups) {
-    const int Cig = Cin / groups, Cog = Cout / groups;
-    const int Ho = conv_out(H, kh, stride, pad), Wo = conv_out(W, kw, stride, pad);
-    // A operand = dY [B][Ho][Wo][Cout]; GEMM rows = input pixels (H x W); columns = Cin
-    ConvGeom g{B, Ho, Wo, Cout, H, W, Cin, kh, kw, stride, pad, groups, Cog, Cig, 0, Cout, Cig * Cout};
-    g.M = (long)B * H * W;
-    return g;
-}
-
 // rows of the [rows][Cin][2] fp64 partials the fused BatchNorm-backward epilogue writes (= M tiles of the chosen kernel)
 extern "C" int scouter_conv2d_dgrad_bn_partial_rows(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride,
                                                     int pad, int groups, int tile_hint) {
     if (!(groups > 0 && Cin % groups == 0 && Cout % groups == 0)) return 0;
-    const ConvGeom g = dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     const int t = igemm_tile(g, tile_hint);
     if (t == 4) { const PwpPlan p = pwp_fused_plan(g); return p.wg_per_col * p.waves_m; }   // one row per (workgroup, wave row)
     if (t == 5) return xpw_plan(g).wg_per_col;                                              // one row per workgroup row
@@ -926,8 +922,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_f32(const float* dy, const float* w, c
     SC_REQUIRE(!part2 || (part1 && x2 && saved2), "conv2d_dgrad: second fused BatchNorm needs the first, x2 and saved2");
     const int Cig = Cin / groups, Cog = Cout / groups;
     SC_UNSUPPORTED(Cig % 32 == 0 && Cog % 32 == 0, "conv2d_dgrad: per-group channels must be multiples of 32");
-    const int Ho = conv_out(H, kh, stride, pad), Wo = conv_out(W, kw, stride, pad);
-    const ConvGeom g = dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     static const char* names[5] = {"igemm_dgrad<128x128>", "igemm_dgrad<128x64>", "igemm_dgrad<64x64>",
                                    "igemm_dgrad<128x32>", "igemm_dgrad<persistent>"};
     // with the BatchNorm-backward reductions in the epilogue the kernel is a different piece of work (it also reads the
@@ -942,7 +937,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_f32(const float* dy, const float* w, c
     const double out_elems = (double)g.M * Cin;
     ScProfScope prof(part1 ? names_bn[tile] : names[tile], (hipStream_t)stream,
                      2.0 * g.M * Cin * Cog * kh * kw / (stride * stride),
-                     4.0 * ((double)B * Ho * Wo * Cout + out_elems) + (addend ? 4.0 * out_elems : 0.0) +
+                     4.0 * ((double)B * g.H * g.W * Cout + out_elems) + (addend ? 4.0 * out_elems : 0.0) +
                          (part1 ? (part2 ? 8.0 : 4.0) * out_elems + out_elems / 8 : 0.0));
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2};
     return dispatch_igemm<true>(dy, w, nullptr, addend, dx, nullptr, g, 0, tile, (hipStream_t)stream, fz);
@@ -989,14 +984,50 @@ static WgradPlan wgrad_plan(const ConvGeom& g, int plan_hint, bool chunk64 = fal
 }
 
 static ConvGeom wgrad_geom(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups) {
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    ConvGeom g{B, H, W, Cin, conv_out(H, kh, stride, pad), conv_out(W, kw, stride, pad), Cout, kh, kw, stride, pad,
-               groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * g.Ho * g.Wo;
-    g.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    g.inv_wo = 1.0f / (float)g.Wo;
-    g.inv_ho = 1.0f / (float)g.Ho;
-    return g;
+    return sc_with_reciprocals(sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups));
+}
+
+// ---- which kernel the library's own plan (plan_hint < 0) is.  3x3 / stride 1 / pad 1 layers with 32 input channels per group
+// have tap-fused kernels: fp32 (conv_wgrad_taps.h), behind switch xwt the register-split bf16x3 one on maps up to 112 wide
+// (conv_wgrad_taps_x3.h), and -- the bf16-input entry point, both operands STORED as bf16, switch bwt -- the one-plane kernel
+// (conv_wgrad_taps_bf16.h).  Everything else: one workgroup per tap (wgrad_plan).
+static bool wgrad_entry_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0; }
+static bool wgrad_taps_geom_ok(const ConvGeom& g) {
+    return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Cg == 32 && BK / g.Wo + 1 < g.Ho && g.M < (1L << 31) &&
+           (long)(2 * g.W + 2) * g.C * 4 < (1L << 31);
+}
+// the layers whose plan the wrappers leave to the library (the deep stem, layer1's radix convolutions): 3x3 / stride 1 / pad 1 with
+// 32 input channels per group on a map at most 112 pixels wide -- the shape the register-split and the one-plane kernel share
+static bool wgrad_rows32_ok(const ConvGeom& g) {
+    return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Cg == 32 && g.W <= 112 && g.H >= 2;
+}
+static bool xwt_geom_ok(const ConvGeom& g) { return wgrad_rows32_ok(g) && wgrad_taps_geom_ok(g) && BK == 32; }
+// "same" stride-1 convolutions: 2 = pointwise, 1 = at most one row wrap and one image wrap per `chunk` pixels, 0 = neither
+static int wgrad_same_mode(const ConvGeom& g, int chunk) {
+    const bool same = g.stride == 1 && g.Ho == g.H && g.Wo == g.W;
+    return !same ? 0 : (g.R == 1 && g.S == 1 && g.pad == 0) ? 2 : (chunk / g.Wo + 1 < g.Ho ? 1 : 0);
+}
+static bool wgrad_bf16_geom_ok(const ConvGeom& g) {
+    return wgrad_same_mode(g, 64) != 0 && g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31);
+}
+static bool bwt_geom_ok(const ConvGeom& g, int io) {
+    return wgrad_bf16_geom_ok(g) && (io & SC_IO_X_BF16) && (io & SC_IO_R_BF16) && wgrad_rows32_ok(g) && BWT_CH / g.Wo + 1 < g.Ho &&
+           (g.M + 512) * (long)(g.C > g.N ? g.C : g.N) * 2 < (1L << 31);
+}
+// kernel: SCOUTER_WGRAD_* (include/scouter_hip.h); the switches xwt / bwt are the caller's to read
+extern "C" int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                              int groups, int kernel) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    switch (kernel) {
+        case 0: return wgrad_entry_ok(g);
+        case 1: return wgrad_bf16_geom_ok(g);
+        case 2: return wgrad_entry_ok(g) && wgrad_taps_geom_ok(g);
+        case 3: return wgrad_entry_ok(g) && xwt_geom_ok(g);
+        case 4: return bwt_geom_ok(g, SC_IO_X_BF16 | SC_IO_R_BF16);
+        case 5: return wgrad_entry_ok(g) && wgrad_rows32_ok(g);
+        default: return 0;
+    }
 }
 
 extern "C" size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw,
@@ -1005,7 +1036,7 @@ extern "C" size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int 
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     WgradPlan p = wgrad_plan(g, plan_hint);
     size_t need = p.splits <= 1 ? 0 : (size_t)p.splits * kh * kw * g.Cg * Cout * sizeof(float);
-    if (plan_hint < 0 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && g.Cg == 32) {     // tap-fused plan (see wgrad_f32)
+    if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {                                           // tap-fused plan (see wgrad_f32)
         const long tiles = (long)(g.Ng / (g.Ng % 64 == 0 ? 64 : 32)) * groups;
         long want = 1024 / tiles;
         if (want < 1) want = 1;
@@ -1024,16 +1055,15 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     SC_REQUIRE(x && dy && dw && B > 0, "conv2d_wgrad: null pointer or empty shape");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad: channels not divisible by groups");
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    SC_UNSUPPORTED(g.Cg % 32 == 0 && g.Ng % 32 == 0, "conv2d_wgrad: per-group channels must be multiples of 32");
+    SC_UNSUPPORTED(wgrad_entry_ok(g), "conv2d_wgrad: per-group channels must be multiples of 32");
     // 3x3 / stride 1 / pad 1 with 32 input channels per group: tap-fused kernel (conv_wgrad_taps.h)
-    if (plan_hint < 0 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && g.Cg == 32 && BK / g.Wo + 1 < g.Ho &&
-        g.M < (1L << 31) && (long)(2 * g.W + 2) * g.C * 4 < (1L << 31)) {
+    if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {
         const int bn = g.Ng % 64 == 0 ? 64 : 32;
         const int co_tiles = g.Ng / bn;
         const long tiles = (long)co_tiles * groups;
         // default (SCOUTER_XWT=0: off): the register-split bf16x3 kernel (64-pixel chunks, rows up to 112 pixels wide).  One workgroup per CU
         // (147 KB of LDS) and a five-unit prologue per workgroup: ONE round of long pixel ranges, not four of short ones
-        const bool xwt = sc_switch(SC_SW_XWT) && g.W <= 112 && g.H >= 2 && BK == 32;
+        const bool xwt = sc_switch(SC_SW_XWT) && xwt_geom_ok(g);
         long want = (xwt ? 256 : 1024) / tiles;
         if (want < 1) want = 1;
         long chunks = (g.M + BK - 1) / BK, cps = (chunks + want - 1) / want;
@@ -1096,8 +1126,7 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
                      4.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
     // "same" stride-1 convolutions take the scalar-addressed paths (see wgrad_kernel); the branch-free pixel walk of
     // mode 1 needs at most one row wrap and one image wrap per 32-pixel chunk
-    const bool same = stride == 1 && g.Ho == H && g.Wo == W;
-    const int mode = !same ? 0 : (kh == 1 && kw == 1 && pad == 0) ? 2 : (BK / g.Wo + 1 < g.Ho ? 1 : 0);
+    const int mode = wgrad_same_mode(g, BK);
 #define WG(BM_, BN_, WM_, WN_)                                                                                      \
     do {                                                                                                            \
         if (mode == 2)                                                                                              \
@@ -1148,14 +1177,11 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     const bool xb = (io & SC_IO_X_BF16) != 0, db = (io & SC_IO_R_BF16) != 0;
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad_bf16: channels not divisible by groups");
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    const bool same = stride == 1 && g.Ho == H && g.Wo == W;
-    const int mode = !same ? 0 : (kh == 1 && kw == 1 && pad == 0) ? 2 : (64 / g.Wo + 1 < g.Ho ? 1 : 0);
-    SC_UNSUPPORTED(mode != 0 && g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31),
-                   "conv2d_wgrad_bf16: shape not covered by the bf16 kernel");
+    const int mode = wgrad_same_mode(g, 64);
+    SC_UNSUPPORTED(wgrad_bf16_geom_ok(g), "conv2d_wgrad_bf16: shape not covered by the bf16 kernel");
     // 3x3 / stride 1 / pad 1 with 32 input channels per group, both operands stored as bf16: tap-fused kernel (conv_wgrad_taps_bf16.h;
     // the library's own plan, SCOUTER_BWT=0: off) -- every X row fetched once per workgroup instead of once per tap
-    if (plan_hint < 0 && xb && db && kh == 3 && kw == 3 && stride == 1 && pad == 1 && g.Cg == 32 && g.W <= 112 && g.H >= 2 &&
-        BWT_CH / g.Wo + 1 < g.Ho && (g.M + 512) * (long)(g.C > g.N ? g.C : g.N) * 2 < (1L << 31)) {
+    if (plan_hint < 0 && bwt_geom_ok(g, io)) {
         const int bn = g.Ng % 64 == 0 ? 64 : 32;
         const int co_tiles = g.Ng / bn;
         const long tiles = (long)co_tiles * groups;

@@ -664,7 +664,6 @@ __global__ __launch_bounds__(512, 1) void phalo_kernel(const unsigned short* __r
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int conv_out_p(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 
 extern "C" int scouter_planes_split_f32(const float* x, void* planes, long n, int nplanes, void* stream) {
     SC_REQUIRE(x && planes && n > 0 && n % 4 == 0 && (nplanes == 1 || nplanes == 3), "planes_split: bad arguments");
@@ -720,10 +719,7 @@ template <int BM, int BN, int NP, int NSTAGE, bool DGRAD, int NWM = 2>
 static void launch_pconv(const void* a, long a_pe, const void* w, long w_pe, const float* bias, const float* addend,
                          float* dst, double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     constexpr int STAGE_BYTES = NP * (BM + BN) * 64;
     constexpr int EPI_BYTES = 2 * NWM * (BM / NWM) * (BN / 2 + 4) * 4;
     const size_t lds = (size_t)(NSTAGE * STAGE_BYTES > EPI_BYTES ? NSTAGE * STAGE_BYTES : EPI_BYTES);
@@ -749,10 +745,7 @@ static void launch_ppersist(const void* a, long a_pe, const void* w, long w_pe, 
                             float* dst, double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
     constexpr int BM = 256;
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     constexpr int LDS = 2 * NP * (BM + BN) * 64 + 1024;
     auto kern = ppersist_kernel<BN, NP, DGRAD>;
     sc_dyn_lds((const void*)kern, LDS);
@@ -766,10 +759,7 @@ static void launch_phalo(const void* a, long a_pe, const void* w, long w_pe, con
                          float* dst, double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
     constexpr int BM = 256;
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     constexpr int IMG = 2 * NP * 13 * 1024, WST = 2 * 3 * NP * BN * 32, EPI = 8 * 64 * (BN / 2 + 4) * 4;
     constexpr int LDS = IMG + WST > EPI ? IMG + WST : EPI;
     auto kern = phalo_kernel<BN, NP, DGRAD>;
@@ -784,7 +774,42 @@ static bool phalo_ok(const ConvGeom& g) {
            g.Cg % 32 == 0 && g.Ng % 64 == 0;
 }
 
-// tile: 0 = 128x128, 1 = 128x64 (N per group must be a multiple of the tile's N)
+// the persistent tile 6 takes BatchNorm statistics from the raw accumulators (none of bias / addend-shifted outputs), needs two
+// K-tiles of 32 channels x taps for its DMA pipeline, and its register epilogue writes fp32 only
+static bool ppersist_ok(const ConvGeom& g, int epi) {
+    return !((epi & SC_EPI_BN_STATS) && (epi & (SC_EPI_BIAS | SC_EPI_ADDEND))) && g.R * g.S * (g.Cg / 32) >= 2;
+}
+static bool ppersist_stores(int io) { return !(io & SC_IO_Y_BF16); }
+// what both passes ask of every shape (g as for the GEMM; the input gradient: stride 1)
+static bool pconv_channels_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 64 == 0; }
+static bool pconv_size_ok(const ConvGeom& g, int nplanes) {
+    const long img = (long)g.H * g.W * g.C, a_pe = g.B * img;
+    return g.M < (1L << 31) && (long)nplanes * a_pe * 2 < (1L << 31) + img * 2 && img < (1L << 28);
+}
+// naming `tile` runs that tile's kernel (dispatch_pconv below, which maps every other request to the 128 x (128 | 64) kernel):
+// 0 = 128x128, 1 = 128x64 with three LDS stages, three planes only 2 = 128x64 with two, 3 = 64x64, 4 = 256x128; 5 = resident
+// rows, 6 = persistent
+static bool pconv_named_tile_ok(const ConvGeom& g, int nplanes, int tile, int epi, int io) {
+    switch (tile) {
+        case 0: return g.Ng % 128 == 0;
+        case 1: return true;
+        case 2: case 3: return nplanes == 3;
+        case 4: return nplanes == 3 && g.Ng % 128 == 0;
+        case 5: return phalo_ok(g);
+        case 6: return ppersist_stores(io) && ppersist_ok(g, epi);
+        default: return false;
+    }
+}
+// rows of fused BatchNorm partials a tile writes: one per M tile -- tile 6 one per 64-row WAVE row of its 256-row tiles, incl.
+// the all-zero ones beyond M
+static int pconv_partial_rows(long M, int tile) {
+    if (tile == 6) return 4 * sc_cdiv(M, 256);
+    return sc_cdiv(M, tile == 3 ? 64 : (tile == 4 || tile == 5) ? 256 : 128);
+}
+extern "C" int scouter_conv2d_planes_partial_rows(long M, int tile) {
+    return M > 0 && M < (1L << 31) && tile >= 0 && tile <= 6 ? pconv_partial_rows(M, tile) : 0;
+}
+
 template <bool DGRAD>
 static int dispatch_pconv(const void* a, long a_pe, const void* w, long w_pe, const float* bias, const float* addend,
                           float* dst, double* bn_part, const ConvGeom& g, int relu, int nplanes, int tile,
@@ -794,7 +819,7 @@ static int dispatch_pconv(const void* a, long a_pe, const void* w, long w_pe, co
     // launch that wants statistics of bias / addend-shifted values keeps the LDS-staged epilogue of tile 4 / 2
     // -- that request is REFUSED, not silently re-routed: the caller sized bn_part / the fused partial rows for the tile
     // it named (tile 6: four rows per 256-row tile), another tile writes another row layout
-    if (tile == 6 && ((bn_part && (bias || addend)) || g.R * g.S * (g.Cg / 32) < 2)) {
+    if (tile == 6 && !ppersist_ok(g, sc_epi_bits(bias, addend, relu, bn_part))) {
         sc_set_error("conv planes: tile 6 (persistent) cannot take BatchNorm statistics of bias / addend-shifted outputs "
                      "and needs at least two K-tiles of 32 channels x taps; name another tile");
         return SC_ERR_UNSUPPORTED;
@@ -832,7 +857,7 @@ static int dispatch_pconv(const void* a, long a_pe, const void* w, long w_pe, co
 extern "C" int scouter_conv2d_fwd_planes_bn_partial_rows(int B, int H, int W, int kh, int kw, int stride, int pad) {
     // upper bound over every tile: tile 6 writes one row per 64-row WAVE row of each 256-row tile, incl. the all-zero
     // ones beyond M (4 * ceil(M / 256) >= ceil(M / 64), the count of the 64-row tile 3)
-    return 4 * sc_cdiv((long)B * conv_out_p(H, kh, stride, pad) * conv_out_p(W, kw, stride, pad), 256);
+    return pconv_partial_rows((long)B * sc_conv_out(H, kh, stride, pad) * sc_conv_out(W, kw, stride, pad), 6);
 }
 
 // x_planes: [nplanes][B*H*W][Cin] bf16; w_planes: scouter_planes_split_weight_f32's forward layout.
@@ -844,17 +869,14 @@ extern "C" int scouter_conv2d_fwd_planes_io(const void* x_planes, const void* w_
     SC_REQUIRE(x_planes && w_planes && y && B > 0 && H > 0 && W > 0 && (nplanes == 1 || nplanes == 3),
                "conv2d_fwd_planes: bad arguments");
     SC_REQUIRE((io & ~SC_IO_Y_BF16) == 0, "conv2d_fwd_planes: unsupported io bits %d (only y may be bf16)", io);
-    SC_UNSUPPORTED(!(io & SC_IO_Y_BF16) || tile != 6, "conv2d_fwd_planes: the persistent tile 6 writes fp32 only");
+    SC_UNSUPPORTED(tile != 6 || ppersist_stores(io), "conv2d_fwd_planes: the persistent tile 6 writes fp32 only");
     SC_REQUIRE(!(bn_partial && (relu & 1)), "conv2d_fwd_planes: fused BatchNorm statistics are taken before any activation");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd_planes: channels not divisible by groups");
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    SC_UNSUPPORTED(Cg % 32 == 0 && Ng % 64 == 0, "conv2d_fwd_planes: needs Cin/groups %% 32 == 0 and Cout/groups %% 64 == 0");
-    ConvGeom g{B, H, W, Cin, conv_out_p(H, kh, stride, pad), conv_out_p(W, kw, stride, pad), Cout, kh, kw, stride, pad,
-               groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * g.Ho * g.Wo;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    const int Cg = g.Cg;
+    SC_UNSUPPORTED(pconv_channels_ok(g), "conv2d_fwd_planes: needs Cin/groups %% 32 == 0 and Cout/groups %% 64 == 0");
     const long a_pe = (long)B * H * W * Cin, w_pe = (long)kh * kw * Cg * Cout;
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)nplanes * a_pe * 2 < (1L << 31) + ((long)H * W * Cin * 2) &&
-                   (long)H * W * Cin < (1L << 28), "conv2d_fwd_planes: tensor too large for 32-bit plane offsets");
+    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_fwd_planes: tensor too large for 32-bit plane offsets");
     ScProfScope prof(nplanes == 3 ? "pconv_fwd<bf16x3>" : "pconv_fwd<bf16>", (hipStream_t)stream,
                      2.0 * g.M * Cout * Cg * kh * kw,
                      2.0 * nplanes * ((double)a_pe) + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0) * (double)g.M * Cout);
@@ -884,13 +906,10 @@ extern "C" int scouter_conv2d_dgrad_planes_bnbwd(const void* dy_planes, const vo
     SC_REQUIRE(!part2 || (part1 && x2 && saved2), "conv2d_dgrad_planes: second fused BatchNorm needs the first, x2 and saved2");
     SC_UNSUPPORTED(stride == 1, "conv2d_dgrad_planes: stride-1 convolutions only");
     const int Cig = Cin / groups, Cog = Cout / groups;
-    SC_UNSUPPORTED(Cog % 32 == 0 && Cig % 64 == 0, "conv2d_dgrad_planes: needs Cout/groups %% 32 == 0 and Cin/groups %% 64 == 0");
-    const int Ho = conv_out_p(H, kh, stride, pad), Wo = conv_out_p(W, kw, stride, pad);
-    ConvGeom g{B, Ho, Wo, Cout, H, W, Cin, kh, kw, stride, pad, groups, Cog, Cig, 0, Cout, Cig * Cout};
-    g.M = (long)B * H * W;
-    const long a_pe = (long)B * Ho * Wo * Cout, w_pe = (long)kh * kw * Cig * Cout;
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)nplanes * a_pe * 2 < (1L << 31) + ((long)Ho * Wo * Cout * 2) &&
-                   (long)Ho * Wo * Cout < (1L << 28), "conv2d_dgrad_planes: tensor too large for 32-bit plane offsets");
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    SC_UNSUPPORTED(pconv_channels_ok(g), "conv2d_dgrad_planes: needs Cout/groups %% 32 == 0 and Cin/groups %% 64 == 0");
+    const long a_pe = (long)B * g.H * g.W * Cout, w_pe = (long)kh * kw * Cig * Cout;
+    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_dgrad_planes: tensor too large for 32-bit plane offsets");
     ScProfScope prof(nplanes == 3 ? "pconv_dgrad<bf16x3>" : "pconv_dgrad<bf16>", (hipStream_t)stream,
                      2.0 * g.M * Cin * Cog * kh * kw, 2.0 * nplanes * ((double)a_pe) + 4.0 * (double)g.M * Cin);
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2};
@@ -904,6 +923,21 @@ extern "C" int scouter_conv2d_dgrad_planes(const void* dy_planes, const void* w_
     return scouter_conv2d_dgrad_planes_bnbwd(dy_planes, w_planes, addend, dx, B, H, W, Cin, Cout, kh, kw, stride, pad,
                                              groups, nplanes, tile, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                              nullptr, stream);
+}
+
+// the queries of the two passes (include/scouter_hip.h): naming `tile` runs that tile's kernel
+extern "C" int scouter_conv2d_fwd_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                                 int groups, int nplanes, int tile, int epilogue, int io) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups) || (nplanes != 1 && nplanes != 3) || (io & ~SC_IO_Y_BF16))
+        return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return pconv_channels_ok(g) && pconv_size_ok(g, nplanes) && pconv_named_tile_ok(g, nplanes, tile, epilogue, io);
+}
+extern "C" int scouter_conv2d_dgrad_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                                   int groups, int nplanes, int tile, int epilogue) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups) || (nplanes != 1 && nplanes != 3) || stride != 1) return 0;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return pconv_channels_ok(g) && pconv_size_ok(g, nplanes) && pconv_named_tile_ok(g, nplanes, tile, epilogue & ~SC_EPI_BN_STATS, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1184,6 +1218,24 @@ static PwgPlan pwg_plan(long M, int Cg, int Ng, int groups, int taps, int plan_h
     return p;
 }
 
+// same-size convolutions with 64-multiples of channels per group, at most one row wrap and one image wrap per 32-pixel chunk
+static bool pwgrad_shape_ok(const ConvGeom& g) {
+    return g.R == g.S && 2 * g.pad == g.R - 1 && g.Cg % 64 == 0 && g.Ng % 64 == 0 && 32 / g.W + 1 < g.H;
+}
+static bool pwgrad_size_ok(const ConvGeom& g, int nplanes) {
+    return g.M < (1L << 31) && (long)nplanes * g.M * g.C * 2 < (1L << 32) && (long)nplanes * g.M * g.N * 2 < (1L << 32);
+}
+// the tap-fused plans (bit 6): 3x3 / pad 1 on maps up to 63 wide, 31-bit byte offsets inside a plane
+static bool pwgrad_fused_ok(const ConvGeom& g) {
+    return g.R == 3 && g.S == 3 && g.pad == 1 && g.W <= 63 && g.M * g.C * 2 < (1L << 31) && g.M * g.N * 2 < (1L << 31);
+}
+extern "C" int scouter_conv2d_wgrad_planes_plan_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int pad, int groups,
+                                                   int nplanes, int plan) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, 1, pad, groups) || (nplanes != 1 && nplanes != 3) || plan > 127) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
+    return pwgrad_shape_ok(g) && pwgrad_size_ok(g, nplanes) && (plan < 64 || pwgrad_fused_ok(g));
+}
+
 extern "C" size_t scouter_conv2d_wgrad_planes_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw,
                                                               int groups, int plan_hint) {
     if (groups <= 0 || Cin % groups || Cout % groups) return 0;
@@ -1203,16 +1255,10 @@ extern "C" int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_
     SC_REQUIRE(x_planes && dy_planes && dw && B > 0 && (nplanes == 1 || nplanes == 3), "conv2d_wgrad_planes: bad arguments");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad_planes: channels not divisible by groups");
     const int Cg = Cin / groups, Ng = Cout / groups;
-    SC_UNSUPPORTED(kh == kw && 2 * pad == kh - 1 && Cg % 64 == 0 && Ng % 64 == 0 && 32 / W + 1 < H,
-                   "conv2d_wgrad_planes: same-size convolutions with 64-multiples of channels per group only");
-    ConvGeom g{B, H, W, Cin, H, W, Cout, kh, kw, 1, pad, groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * H * W;
-    g.inv_hw = 1.0 / ((double)H * W);
-    g.inv_wo = 1.0f / (float)W;
-    g.inv_ho = 1.0f / (float)H;
+    const ConvGeom g = sc_with_reciprocals(sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups));
+    SC_UNSUPPORTED(pwgrad_shape_ok(g), "conv2d_wgrad_planes: same-size convolutions with 64-multiples of channels per group only");
     const long x_pe = g.M * Cin, dy_pe = g.M * Cout;
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)nplanes * x_pe * 2 < (1L << 32) && (long)nplanes * dy_pe * 2 < (1L << 32),
-                   "conv2d_wgrad_planes: tensor too large for 32-bit plane offsets");
+    SC_UNSUPPORTED(pwgrad_size_ok(g, nplanes), "conv2d_wgrad_planes: tensor too large for 32-bit plane offsets");
     const PwgPlan plan = pwg_plan(g.M, Cg, Ng, groups, kh * kw, plan_hint);
     const int bm = plan.bm, bn = plan.bn;
     const int ci_tiles = Cg / bm, co_tiles = Ng / bn;
@@ -1229,7 +1275,7 @@ extern "C" int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_
     float* out = splits > 1 ? (float*)ws : dw;
     dim3 grid((unsigned)tiles, (unsigned)splits);
     if (plan.fused) {
-        SC_UNSUPPORTED(kh == 3 && kw == 3 && pad == 1 && W <= 63 && x_pe * 2 < (1L << 31) && dy_pe * 2 < (1L << 31),
+        SC_UNSUPPORTED(pwgrad_fused_ok(g),
                        "conv2d_wgrad_planes: the tap-fused plan covers 3x3 / pad 1 layers on maps up to 63 pixels wide");
         ScProfScope prof(nplanes == 3 ? "pwgrad<bf16x3>" : "pwgrad<bf16>", st, 2.0 * g.M * Cout * Cg * kh * kw,
                          2.0 * nplanes * ((double)x_pe + (double)dy_pe));

@@ -343,10 +343,7 @@ template <int BM, int BN, int NWM, int NWN, int MINB, bool DGRAD, bool CONV>
 static void launch_x3(const float* a, const void* w, long w_pe, const float* bias, const float* addend, float* dst,
                       double* bn_part, const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
     const int mtiles = sc_cdiv(g.M, BM), ntiles = g.Ng / BN;
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     constexpr int STAGE_BYTES = 3 * (BM + BN) * 64;
     constexpr int EPI_BYTES = NWM * NWN * (BM / NWM) * (BN / NWN + 4) * 4;
     const size_t lds = (size_t)(2 * STAGE_BYTES > EPI_BYTES ? 2 * STAGE_BYTES : EPI_BYTES);
@@ -389,6 +386,33 @@ static int dispatch_x3(const float* a, const void* w, long w_pe, const float* bi
     return sc_check_launch(DGRAD ? "conv2d_dgrad_x3" : "conv2d_fwd_x3");
 }
 
+// what the two entry points take at all (g as for the GEMM: C / Cg the K-side channels, wtap the elements of one weight tap)
+static bool x3_filter_ok(const ConvGeom& g) { return g.R == g.S && (g.R & 1) && 2 * g.pad == g.R - 1 && g.R <= 5 && g.stride == 1; }
+static bool x3_channels_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.R * g.S * (g.Cg / 32) >= 2; }
+static bool x3_size_ok(const ConvGeom& g) {
+    return g.M < (1L << 31) && (long)g.R * g.S * g.wtap * 2 * 3 < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28) &&
+           256L * g.C * 4 < (1L << 31);
+}
+// naming `tile` runs that tile's kernel; tile 7 = the resident-rows kernel of conv_xhalo.hip (the forward: no bias / addend).
+// tile < 0: the library's choice
+template <bool DGRAD>
+static bool x3_named_tile_ok(const ConvGeom& g, int tile, int epi) {
+    if (tile == 7) return sc_xhalo_ok(g) && (DGRAD || !(epi & (SC_EPI_BIAS | SC_EPI_ADDEND)));
+    return tile < 0 || x3_tile_ok(tile, g.Ng);
+}
+extern "C" int scouter_conv2d_fwd_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                             int groups, int tile, int epilogue) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return x3_filter_ok(g) && x3_channels_ok(g) && x3_size_ok(g) && x3_named_tile_ok<false>(g, tile, epilogue);
+}
+extern "C" int scouter_conv2d_dgrad_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                               int groups, int tile, int epilogue) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    return x3_filter_ok(g) && x3_channels_ok(g) && x3_size_ok(g) && x3_named_tile_ok<true>(g, tile, epilogue);
+}
+
 extern "C" int scouter_conv2d_x3_tile(long M, int N, int tile_hint) { return tile_hint == 7 && N == 32 ? 7 : x3_tile(M, N, tile_hint); }
 extern "C" int scouter_conv2d_x3_partial_rows(long M, int N, int tile_hint) {
     return sc_cdiv(M, x3_tile_rows(x3_tile(M, N, tile_hint)));
@@ -403,16 +427,14 @@ extern "C" int scouter_conv2d_fwd_x3(const float* x, const void* w_planes_fwd, c
     SC_REQUIRE(x && w_planes_fwd && y && B > 0 && H > 0 && W > 0, "conv2d_fwd_x3: null pointer or empty shape");
     SC_REQUIRE(!(bn_partial && relu), "conv2d_fwd_x3: fused BatchNorm statistics are taken before any activation");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd_x3: channels not divisible by groups");
-    const int Cg = Cin / groups, Ng = Cout / groups;
-    SC_UNSUPPORTED(kh == kw && (kh & 1) && 2 * pad == kh - 1 && kh <= 5, "conv2d_fwd_x3: 1x1 or odd same-size filters only");
-    SC_UNSUPPORTED(Cg % 32 == 0 && Ng % 32 == 0 && kh * kw * (Cg / 32) >= 2, "conv2d_fwd_x3: needs 32-multiples of channels per group and two K-tiles");
-    ConvGeom g{B, H, W, Cin, H, W, Cout, kh, kw, 1, pad, groups, Cg, Ng, 0, Cout, Cg * Cout};
-    g.M = (long)B * H * W;
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)kh * kw * Cg * Cout * 2 * 3 < (1L << 31) && (long)H * W * Cin < (1L << 28) &&
-                   256L * Cin * 4 < (1L << 31), "conv2d_fwd_x3: tensor too large for 32-bit offsets");
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
+    const int Cg = g.Cg, Ng = g.Ng;
+    SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_fwd_x3: 1x1 or odd same-size filters only");
+    SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_fwd_x3: needs 32-multiples of channels per group and two K-tiles");
+    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_fwd_x3: tensor too large for 32-bit offsets");
     const long w_pe = (long)kh * kw * Cg * Cout;
     if (tile_hint == 7) {           // resident rows, split once per element, persistent (conv_xhalo.hip): 32 columns per group
-        SC_UNSUPPORTED(sc_xhalo_ok(g) && !bias && !addend, "conv2d_fwd_x3: tile 7 covers 3x3 / pad 1 layers with 32 output channels per "
+        SC_UNSUPPORTED(x3_named_tile_ok<false>(g, 7, sc_epi_bits(bias, addend, relu, bn_partial)), "conv2d_fwd_x3: tile 7 covers 3x3 / pad 1 layers with 32 output channels per "
                        "group, 16-multiples of input channels per group, maps up to 126 wide, no bias / addend");
         ScProfScope prof("xhalo_fwd<bf16x3>", (hipStream_t)stream, 2.0 * g.M * Cout * Cg * kh * kw, 4.0 * g.M * Cin + 4.0 * g.M * Cout);
         sc_launch_xhalo(false, x, w_planes_fwd, w_pe, nullptr, y, bn_partial, g, relu, (hipStream_t)stream, BnBwdFuse{});
@@ -436,16 +458,14 @@ extern "C" int scouter_conv2d_dgrad_x3_bnbwd(const float* dy, const void* w_plan
     SC_REQUIRE(!part2 || (part1 && x2 && saved2), "conv2d_dgrad_x3: second fused BatchNorm needs the first, x2 and saved2");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_dgrad_x3: channels not divisible by groups");
     const int Cig = Cin / groups, Cog = Cout / groups;
-    SC_UNSUPPORTED(kh == kw && (kh & 1) && 2 * pad == kh - 1 && kh <= 5, "conv2d_dgrad_x3: 1x1 or odd same-size filters only");
-    SC_UNSUPPORTED(Cog % 32 == 0 && Cig % 32 == 0 && kh * kw * (Cog / 32) >= 2, "conv2d_dgrad_x3: needs 32-multiples of channels per group and two K-tiles");
-    ConvGeom g{B, H, W, Cout, H, W, Cin, kh, kw, 1, pad, groups, Cog, Cig, 0, Cout, Cig * Cout};
-    g.M = (long)B * H * W;
-    SC_UNSUPPORTED(g.M < (1L << 31) && (long)kh * kw * Cig * Cout * 2 * 3 < (1L << 31) && (long)H * W * Cout < (1L << 28) &&
-                   256L * Cout * 4 < (1L << 31), "conv2d_dgrad_x3: tensor too large for 32-bit offsets");
+    const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
+    SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_dgrad_x3: 1x1 or odd same-size filters only");
+    SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_dgrad_x3: needs 32-multiples of channels per group and two K-tiles");
+    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_dgrad_x3: tensor too large for 32-bit offsets");
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2, 0};
     const long w_pe = (long)kh * kw * Cig * Cout;
     if (tile_hint == 7) {           // (conv_xhalo.hip: 32 input channels per group = 32 GEMM columns)
-        SC_UNSUPPORTED(sc_xhalo_ok(g), "conv2d_dgrad_x3: tile 7 covers 3x3 / pad 1 layers with 32 input channels per group, "
+        SC_UNSUPPORTED(x3_named_tile_ok<true>(g, 7, 0), "conv2d_dgrad_x3: tile 7 covers 3x3 / pad 1 layers with 32 input channels per group, "
                        "16-multiples of output channels per group, maps up to 126 wide");
         ScProfScope prof(part1 ? "xhalo_dgrad+bn_bwd<bf16x3>" : "xhalo_dgrad<bf16x3>", (hipStream_t)stream,
                          2.0 * g.M * Cin * Cog * kh * kw, 4.0 * g.M * Cout + 4.0 * g.M * Cin);
@@ -674,6 +694,10 @@ static XwPlan xw_plan(long M, int Cin, int Cout, int plan_hint) {
     p.splits = (int)((M + p.pix_per_split - 1) / p.pix_per_split);
     return p;
 }
+static bool x3_wgrad_channels_ok(int Cin, int Cout) { return Cin % 128 == 0 && Cout % 128 == 0; }
+extern "C" int scouter_conv2d_wgrad_x3_ok(int B, int H, int W, int Cin, int Cout) {
+    return sc_pixels_ok(B, H, W) && Cin > 0 && Cout > 0 && x3_wgrad_channels_ok(Cin, Cout) && (long)B * H * W < (1L << 31);
+}
 extern "C" size_t scouter_conv2d_wgrad_x3_workspace_bytes(int B, int H, int W, int Cin, int Cout, int plan_hint) {
     if (Cin % 128 || Cout % 128 || B <= 0) return 0;
     const XwPlan p = xw_plan((long)B * H * W, Cin, Cout, plan_hint);
@@ -684,9 +708,8 @@ extern "C" size_t scouter_conv2d_wgrad_x3_workspace_bytes(int B, int H, int W, i
 extern "C" int scouter_conv2d_wgrad_x3(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                        int plan_hint, void* ws, size_t ws_bytes, void* stream) {
     SC_REQUIRE(x && dy && dw && B > 0 && H > 0 && W > 0, "conv2d_wgrad_x3: null pointer or empty shape");
-    SC_UNSUPPORTED(Cin % 128 == 0 && Cout % 128 == 0, "conv2d_wgrad_x3: needs 128-multiples of Cin and Cout");
-    ConvGeom g{B, H, W, Cin, H, W, Cout, 1, 1, 1, 0, 1, Cin, Cout, 0, Cout, Cin * Cout};
-    g.M = (long)B * H * W;
+    SC_UNSUPPORTED(x3_wgrad_channels_ok(Cin, Cout), "conv2d_wgrad_x3: needs 128-multiples of Cin and Cout");
+    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, 1, 1, 1, 0, 1);
     SC_UNSUPPORTED(g.M < (1L << 31), "conv2d_wgrad_x3: more than 2^31 pixels");
     const XwPlan p = xw_plan(g.M, Cin, Cout, plan_hint);
     const long slab = (long)Cin * Cout;

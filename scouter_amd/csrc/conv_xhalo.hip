@@ -399,10 +399,7 @@ int sc_xhalo_partial_rows(int groups) { return xh_grid(groups) / groups; }
 template <int AG, bool DGRAD>
 static void launch_xhalo_ag(const float* a, const void* w, long w_pe, const float* addend, float* dst, double* bn_part,
                             const ConvGeom& g, int relu, hipStream_t st, const BnBwdFuse& fz) {
-    ConvGeom gg = g;
-    gg.inv_hw = 1.0 / ((double)g.Ho * g.Wo);
-    gg.inv_wo = 1.0f / (float)g.Wo;
-    gg.inv_ho = 1.0f / (float)g.Ho;
+    const ConvGeom gg = sc_with_reciprocals(g);
     constexpr int LDS = 2 * 3 * (AG + 1) * 1024 + 2 * 27 * 1024 + (AG < 16 ? 3 * 1024 : 0);
     auto kern = xhalo_kernel<AG, DGRAD>;
     sc_dyn_lds((const void*)kern, LDS);

@@ -321,16 +321,42 @@ def _fuse_wanted(post, kh, plane_kernel=False):
     return bool(BN_BWD_FUSE & bit)
 
 
+# ---- what the library's convolution kernels take.  Every acceptance rule -- a shape condition plus 31 / 32-bit byte guards -- is
+# stated ONCE, in csrc/, as the host predicate its entry point rejects through; the wrappers ASK it through the route queries of
+# include/scouter_hip.h (scouter_conv2d_*_tile_ok / *_ok: pure functions of their integers, no device needed) and keep only
+# POLICY here: the switches, the measured thresholds and which legal kernel a layer is sent to.
+EPI_BIAS, EPI_ADDEND, EPI_RELU, EPI_BN_STATS, EPI_BN_BWD, EPI_BN_BWD2 = 1, 2, 4, 8, 16, 32          # (SCOUTER_EPI_*)
+WGRAD_F32, WGRAD_BF16, WGRAD_TAPS, WGRAD_XWT, WGRAD_BWT, WGRAD_ROWS32 = 0, 1, 2, 3, 4, 5             # (SCOUTER_WGRAD_*)
+_asked = {}
+
+
+def ask(name, *args):
+    """scouter_conv2d_<name>(*args) -- a route query or a partial-row count -- memoised by its argument tuple.  (An eager step
+    makes about 170 convolution calls and is close to host-bound: a ctypes call with a dozen int arguments is 2.4 us, the dict
+    hit 0.1 us.)"""
+    key = (name,) + args
+    v = _asked.get(key)
+    if v is None:
+        v = _asked[key] = getattr(_native.lib(), "scouter_conv2d_" + name)(*args)
+    return v
+
+
+def _epi(bias=None, addend=None, relu=False, bn_stats=False, post=None):
+    """SCOUTER_EPI_* bits of a call (post: the BnBwdFuse its fused BatchNorm-backward epilogue serves, else None)"""
+    return ((EPI_BIAS if bias is not None else 0) | (EPI_ADDEND if addend is not None else 0) | (EPI_RELU if relu else 0) |
+            (EPI_BN_STATS if bn_stats else 0) |
+            (0 if post is None else EPI_BN_BWD | (EPI_BN_BWD2 if len(post.entries) > 1 else 0)))
+
+
 def _tile_legal(ng, t):
-    return (t == 0 and ng % 128 == 0) or (t in (1, 2) and ng % 64 == 0) or t == 3
+    """block tile t (0-3) of the fp32 / bf16-input kernels divides ng GEMM columns per group (a 1x1 layer of nominal size)"""
+    return bool(ask("fwd_tile_ok", 1, 8, 8, 32, ng, 1, 1, 1, 0, 1, t, 0))
 
 
 def _pw_persist_legal(M, K_, N_, kh, kw, stride, pad, groups, plain):
-    """tile 4 = persistent pointwise kernel with the weight tile resident in LDS (csrc/conv_pw_persist.h): 1x1 / stride 1 /
-    groups 1, GEMM-K of 64 / 128 / 256 channels, 64-multiples of output columns, plain epilogue (forward: optional
-    BatchNorm statistics; input gradient: optional addend), byte offsets within 31 bits."""
-    return bool(plain and kh == 1 and kw == 1 and stride == 1 and pad == 0 and groups == 1 and K_ in (64, 128, 256) and
-                N_ % 64 == 0 and 4 * M * max(K_, N_) < (1 << 31))
+    """tile 4 = persistent pointwise kernel with the weight tile resident in LDS (csrc/conv_pw_persist.h) takes M pixels of a
+    K_ -> N_ GEMM: the forward's query (the input gradient's rule is the same with K and N exchanged by its caller)"""
+    return bool(ask("fwd_tile_ok", M, 1, 1, K_, N_, kh, kw, stride, pad, groups, 4, 0 if plain else EPI_BIAS))
 
 
 PWB_FWD = os.environ.get("SCOUTER_PWB_FWD", "1") != "0"
@@ -339,17 +365,27 @@ PWB_DGRAD = os.environ.get("SCOUTER_PWB_DGRAD", "1") != "0"
 
 def xpw_fwd_eligible(cin, cout, kh, kw, stride, pad, groups, has_bias):
     """Short-K pointwise layers whose FORWARD runs on the persistent bf16x3 kernel (csrc/conv_pw_persist_x3.h, tile 5 of the
-    fp32 forward): 64 / 128 / 256 input channels, 64-multiples of output channels, no bias.  A STATIC rule (the forward
-    is a function of the layer shapes alone, whatever the batch); SCOUTER_X3 bit 5."""
-    return bool(kh == 1 and kw == 1 and stride == 1 and pad == 0 and groups == 1 and not has_bias and
-                cin in (64, 128, 256) and cout % 64 == 0)
+    fp32 forward; the library: 64 / 128 / 256 input channels, 64-multiples of output channels), no bias.  A STATIC rule (the
+    forward is a function of the layer shapes alone, whatever the batch: asked for a nominal one); SCOUTER_X3 bit 5."""
+    return bool(not has_bias and ask("fwd_tile_ok", 1, 8, 8, cin, cout, kh, kw, stride, pad, groups, 5, 0))
 
 
-def _rows32_3x3(kh, kw, stride, pad, cg, H, W):
-    """3x3 / stride 1 / pad 1 with 32 input channels per group on an H x W map at most 112 pixels wide (the deep stem, layer1's
-    radix convolutions): the shape rule of the library's resident-rows bf16 forward / input gradient (bhalo) and of its tap-fused
-    weight gradients (xwt, bwt).  Each caller adds its own byte guard and switch."""
-    return kh == 3 and kw == 3 and stride == 1 and pad == 1 and cg == 32 and W <= 112 and H >= 2
+# POLICY, not capability: an fp32-STORED operand is rounded to bf16 by one extra pass in front of the library's resident-rows
+# input gradient (bhalo) / tap-fused weight gradient (bwt) only while it has fewer bytes, as bf16, than this -- 2 GiB less 1 MiB,
+# deliberately tighter than the kernels' own guards (the queries), which add their look-ahead rows to the 2^31 bound
+PREROUND_MAX_BYTES = 0x7FF00000
+
+
+def dgrad_prerounds(B, H, W, Cin, Cout, kh, kw, stride, pad, groups):
+    """bf16 mode, dy stored as fp32: round it for the resident-rows input gradient (the library's shape rule, switch aside)"""
+    return bool(ask("dgrad_bf16_tile_ok", B, H, W, Cin, Cout, kh, kw, stride, pad, groups, 3, 0, DGRAD_IO_DY, 1) and
+                B * H * W * Cout * 2 < PREROUND_MAX_BYTES)
+
+
+def wgrad_prerounds(B, H, W, Cin, Cout, kh, kw, stride, pad, groups):
+    """bf16 mode: round fp32-stored operands for the tap-fused one-plane weight gradient (the library's shape rule, switch aside)"""
+    return bool(ask("wgrad_kernel_ok", B, H, W, Cin, Cout, kh, kw, stride, pad, groups, WGRAD_BWT) and
+                B * H * W * max(Cin, Cout) * 2 < PREROUND_MAX_BYTES)
 
 
 def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, relu=False, bn_stats=False,
@@ -378,15 +414,15 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
     if bf16 and wt is None:       # W^T as bf16 [taps][Cout][Cin/groups], rebuilt per call (weights change every step)
         wt = weight_bf16t(w_hwio, groups)
 
-    plain = bias is None and addend is None and not relu
+    shape = (B, H, W, Cin, Cout, kh, kw, stride, pad, groups)
+    epi = _epi(bias, addend, relu, bn_stats)
     picking = [AUTOTUNE != "1"]       # the table lookup asks whether the SHAPE admits tile 4; this call's epilogue is checked below
 
     def launch(tile, dry=False, part=None):
         if dry:
-            if tile == 4:
-                return not bf16 and _pw_persist_legal(B * H * W, Cin, Cout, kh, kw, stride, pad, groups,
-                                                      plain or picking[0])
-            return _tile_legal(Cout // groups, tile)
+            if bf16:          # (tile 4 of the typed forward is named by the static rule below, never by the table)
+                return bool(tile != 4 and ask("fwd_bf16_tile_ok", *shape, tile, 0, 0, 0))
+            return bool(ask("fwd_tile_ok", *shape, tile, 0 if picking[0] else epi))
         if bf16:
             _native.check(L.scouter_conv2d_fwd_bf16_io(_p(x), _p(wt), _p(bias), _p(addend), _p(y), _p(part), B, H, W, Cin,
                                                        Cout, kh, kw, stride, pad, groups, int(relu), tile, io, st),
@@ -401,15 +437,12 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
     # (the cached choice is a function of the layer shape alone -- the key has no epilogue in it, and a first call with
     #  bias / addend / ReLU must not cache "-1" for the plain calls of the same shape, ADVICE r4 -- legality of tile 4 for
     #  THIS call's epilogue is decided here, per call)
-    if tile == 5 and not (plain and not bf16 and xpw_fwd_eligible(Cin, Cout, kh, kw, stride, pad, groups, False) and
-                          (B * H * W + 128) * Cout < (1 << 29) and B * H * W * Cin < (1 << 29)):
+    if tile == 5 and (bf16 or not ask("fwd_tile_ok", *shape, 5, epi)):
         tile = None
     # bf16 mode, input STORED as bf16: the pointwise layers with up to 512 input channels run on the persistent typed kernel
     # (csrc/conv_pw_persist_bf16.h pwb_fwd_kernel; tile 4 of the typed forward) -- a static rule of shape and storage, never of
     # timing.  SCOUTER_PWB_FWD=0: the tile kernels.
-    if (tile is None and bf16 and PWB_FWD and plain and x.dtype == BF16 and kh == 1 and kw == 1 and stride == 1 and pad == 0 and
-            groups == 1 and Cin in (64, 128, 256, 512) and Cout % 128 == 0 and B * H * W * Cin < (1 << 30) and
-            (B * H * W + 128) * Cout * (2 if out_dtype == BF16 else 4) < (1 << 32)):
+    if tile is None and bf16 and PWB_FWD and ask("fwd_bf16_tile_ok", *shape, 4, epi, io, 0):
         tile = 4
     if tile is None:
         tile = _pick_tile(("fwd", bf16, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, (0, 1, 2, 3, 4))
@@ -420,12 +453,14 @@ def conv2d_fwd(x, w_hwio, bias=None, addend=None, stride=1, pad=0, groups=1, rel
         # tiles (1: 64 columns per group, 3: 32), behind which the library runs the persistent resident-rows kernel when x is STORED
         # as bf16 (csrc/conv_halo_dgrad_bf16.h bhalo_fwd_kernel) -- bit-identical to the tile kernels, output and statistics rows,
         # so the rule names the tile by the SHAPE (behind the table's lookup, whose entry it overrides) and storage stays bit-neutral.
-        if bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and Cout // groups in (32, 64) and get_switch("bhalo"):
-            tile = 1 if Cout // groups == 64 else 3
+        # (asked for a nominal batch of one and a bf16-stored x: the kernel's shape rule without its byte guard)
+        if bf16 and get_switch("bhalo"):
+            for t in (1, 3):
+                if ask("fwd_bf16_tile_ok", 1, *shape[1:], t, 0, IO_X_BF16, 1):
+                    tile = t
     part, rows = None, 0
     if bn_stats:
-        rows_fn = L.scouter_conv2d_fwd_bn_partial_rows_bf16 if bf16 else L.scouter_conv2d_fwd_bn_partial_rows
-        rows = rows_fn(B, H, W, Cin, Cout, kh, kw, stride, pad, groups, tile)
+        rows = ask("fwd_bn_partial_rows_bf16" if bf16 else "fwd_bn_partial_rows", *shape, tile)
         part = torch.empty((rows, Cout, 2), dtype=torch.float64, device=x.device)
     launch(tile, part=part)
     return (y, (part, rows)) if bn_stats else y
@@ -460,8 +495,8 @@ def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, pr
     # (BatchNorm inputs stored as bf16: only the bf16-input kernel's epilogue reads them; otherwise that BatchNorm's own
     #  backward -- typed -- does the reduction)
     fuse = _fuse_wanted(post, kh) and (bf16 or post.x_io() == 0)
-    if (bf16 and dy.dtype == F32 and _rows32_3x3(kh, kw, stride, pad, Cin // groups, H, W) and Cout // groups in (32, 64) and
-            get_switch("bhalo") and B * H * W * Cout * 2 < (1 << 31) - (1 << 20)):
+    shape = (B, H, W, Cin, Cout, kh, kw, stride, pad, groups)
+    if bf16 and dy.dtype == F32 and get_switch("bhalo") and dgrad_prerounds(*shape):
         # 3x3 layers with 32 input channels per group: the library's resident-rows input gradient (csrc/conv_halo_dgrad_bf16.h)
         # reads a bf16-STORED dy.  The rule is a function of the shape only -- an fp32-stored dy (SCOUTER_BF16_GRADS=0) is rounded
         # to bf16 (RNE: the value the tile kernel's loader rounds it to) by one extra pass first: storage stays bit-neutral
@@ -476,22 +511,15 @@ def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, pr
                            "stride 1, >= %d pixels); got precision %r, stride %d, %d pixels"
                            % (BF16_MIN_PIXELS, precision, stride, B * H * W))
 
+    epi = _epi(addend=addend, post=post if fuse else None)
+
     def launch(tile, dry=False, fuse=_NO_FUSE):
         if dry:
-            if tile == 4 and bf16:
-                # the persistent typed kernel (csrc/conv_pw_persist_bf16.h): fused launches with every tensor stored as bf16
-                return bool(will_fuse and kh == 1 and kw == 1 and pad == 0 and groups == 1 and Cout in (64, 128, 256, 512) and
-                            Cin % 128 == 0 and (B * H * W + 128) * Cin < (1 << 30) and B * H * W * Cout < (1 << 30) and
-                            (io & DGRAD_IO_DY) and (io & DGRAD_IO_DX) and (addend is None or io & DGRAD_IO_ADDEND) and
-                            post.x_io() == (1 << len(post.entries)) - 1)
-            if tile == 4:        # (GEMM-K of the input gradient = Cout)
-                return _pw_persist_legal(B * H * W, Cout, Cin, kh, kw, stride, pad, groups, True)
-            if tile == 5:
-                # the persistent bf16x3 kernel (csrc/conv_pw_persist_x3.h): fused fp32 launches of the short-K 1x1 layers
-                return bool(will_fuse and not bf16 and kh == 1 and kw == 1 and stride == 1 and pad == 0 and groups == 1 and
-                            Cout in (64, 128, 256) and Cin % 64 == 0 and (B * H * W + 128) * Cin < (1 << 29) and
-                            B * H * W * Cout < (1 << 29))
-            return _tile_legal(Cin // groups, tile)
+            if bf16:          # (the table names tile 4 of the typed input gradient for FUSED launches -- every tensor stored as
+                #                bf16, csrc/conv_pw_persist_bf16.h; the plain one is the static rule below)
+                return bool((tile != 4 or will_fuse) and
+                            ask("dgrad_bf16_tile_ok", *shape, tile, epi, io | (post.x_io() if will_fuse else 0), 0))
+            return bool(ask("dgrad_tile_ok", *shape, tile, epi))
         if bf16:
             _native.check(L.scouter_conv2d_dgrad_bnbwd_bf16_io(
                 _p(dy), _p(w_hwio), _p(addend), _p(dx), B, H, W, Cin, Cout, kh, kw, stride, pad, groups, tile, *fuse,
@@ -517,18 +545,15 @@ def conv2d_dgrad(dy, w_hwio, x_shape, addend=None, stride=1, pad=0, groups=1, pr
         if tile < 0:                              # autotuning disabled: name a tile, the partial rows depend on it
             tile = 2 if (Cin // groups) % 64 == 0 else 3
         if bf16:
-            rows = L.scouter_conv2d_dgrad_bn_partial_rows_bf16(B, H, W, Cin, Cout, kh, kw, stride, pad, groups, tile,
-                                                               int(len(post.entries) > 1))
+            rows = ask("dgrad_bn_partial_rows_bf16", *shape, tile, int(len(post.entries) > 1))
         else:
-            rows = L.scouter_conv2d_dgrad_bn_partial_rows(B, H, W, Cin, Cout, kh, kw, stride, pad, groups, tile)
+            rows = ask("dgrad_bn_partial_rows", *shape, tile)
         post.alloc(rows, x_shape)
         launch(tile, fuse=post.args())
-    elif (bf16 and PWB_DGRAD and kh == 1 and kw == 1 and pad == 0 and groups == 1 and Cout in (64, 128, 256, 512) and
-          Cin % 64 == 0 and (io & DGRAD_IO_DY) and not (io & DGRAD_IO_DX) and (B * H * W + 128) * Cin < (1 << 30) and
-          B * H * W * Cout < (1 << 30)):
+    elif bf16 and PWB_DGRAD and Cout <= 512 and ask("dgrad_bf16_tile_ok", *shape, 4, epi, io, 0):
         # bf16 mode, dy STORED as bf16: the plain pointwise input gradients (conv3 / downsample) run on the persistent typed
-        # kernel (csrc/conv_pw_persist_bf16.h pwb_dgrad_kernel) -- a static rule of shape and storage (Cout <= 512: at 1024 the
-        # tile kernel is level, tools_dev/pwb_dgrad_bench.py: 64 <- 256 at 56 x 56 141 -> 115 us, 64 <- 64 87 -> 49, 128 <- 512
+        # kernel (csrc/conv_pw_persist_bf16.h pwb_dgrad_kernel) -- a static rule of shape and storage (the library takes Cout up
+        # to 1024; POLICY: Cout <= 512 -- at 1024 the tile kernel is level, tools_dev/pwb_dgrad_bench.py: 64 <- 256 at 56 x 56 141 -> 115 us, 64 <- 64 87 -> 49, 128 <- 512
         # at 28 x 28 91 -> 76; +0.15 % on config 5, most of whose plain input gradients read an fp32 dy).  SCOUTER_PWB_DGRAD=0:
         # the tile kernels
         launch(4)
@@ -624,29 +649,21 @@ class PlaneWeightSplitter:
         return [t for table, outs, _ in self._entries.values() for t in [table] + [b for o in outs for b in o if b is not None]]
 
 
-_PLANE_TILE_ROWS = {0: 128, 1: 128, 2: 128, 3: 64, 4: 256, 5: 256, 6: 64}
-
-
-def _plane_part_rows(tile, M):
-    """Partial rows the plane kernels write for fused BatchNorm sums: one per M tile -- tile 6 (persistent 256-row tiles)
-    one per 64-row WAVE row of every tile, 4 per tile, incl. the all-zero ones beyond M."""
-    if tile == 6:
-        return (M + 255) // 256 * 4
-    return (M + _PLANE_TILE_ROWS[tile] - 1) // _PLANE_TILE_ROWS[tile]
+# Block tiles of the plane kernels the wrappers time / name, per plane count (csrc/conv_planes.hip dispatch_pconv): 0 = 128x128,
+# 1 = 128x64 (three LDS stages), and for three planes 2 = 128x64 (two workgroups per CU), 3 = 64x64 (three), 4 = 256x128 with
+# eight waves, 5 (same-size 3x3 layers on maps up to 63 wide) = 256 x (128 | 64) with the input rows resident in LDS for all
+# nine taps, 6 = PERSISTENT 256 x (128 | 64): one workgroup per CU walks the tile list, the DMA stream prefetches the next tile
+# under the current one, register epilogue (csrc/conv_planes_persist.h).  Tiles 0-4 and 6 sum each output ELEMENT in the same
+# order (bit-identical convolution outputs; the fused BatchNorm partial sums are grouped per tile, so statistics agree between
+# tiles to fp64 rounding, not bit for bit); tile 5 sums over K in a different order (16-channel chunk outer, tap inner): equal
+# to fp32 rounding.  Which of them a shape and epilogue admit: the library (scouter_conv2d_{fwd,dgrad}_planes_tile_ok).
+_PLANE_TILES = {1: (0, 1, 5, 6), 3: (0, 2, 3, 4, 5, 6)}
 
 
 def _plane_tiles(ng, nplanes=3, halo=False):
-    """Block tiles of the plane kernels (csrc/conv_planes.hip dispatch_pconv): 0 = 128x128, 1 = 128x64 (three LDS
-    stages), and for three planes 2 = 128x64 (two workgroups per CU), 3 = 64x64 (three), 4 = 256x128 with eight waves,
-    5 (halo=True: same-size 3x3 layers on maps up to 63 wide) = 256 x (128 | 64) with the input rows resident in LDS for
-    all nine taps, 6 = PERSISTENT 256 x (128 | 64): one workgroup per CU walks the tile list, the DMA stream prefetches
-    the next tile under the current one, register epilogue (csrc/conv_planes_persist.h).  Tiles 0-4 and 6 sum each output
-    ELEMENT in the same order (bit-identical convolution outputs; the fused BatchNorm partial sums are grouped per tile,
-    so statistics agree between tiles to fp64 rounding, not bit for bit); tile 5 sums over K in a different order
-    (16-channel chunk outer, tap inner): equal to fp32 rounding."""
-    if nplanes == 1:
-        return ((0, 1) if ng % 128 == 0 else (1,)) + ((5,) if halo else ()) + (6,)
-    return ((0, 2, 3, 4) if ng % 128 == 0 else (2, 3)) + ((5,) if halo else ()) + (6,)
+    """the candidates for ng GEMM columns per group (a 3x3 layer of nominal size; halo: with the resident-rows tile 5)"""
+    return tuple(t for t in _PLANE_TILES[nplanes]
+                 if (t != 5 or halo) and ask("fwd_planes_tile_ok", 1, 8, 8, 64, ng, 3, 3, 1, 1, 1, nplanes, t, 0, 0))
 
 
 # Plane tile 5 (input rows resident in LDS) sums K in another order than tiles 0-4.  bit 1: the input gradient may use it
@@ -666,7 +683,8 @@ HALO_FWD_MIN_PIXELS = 196
 
 
 def _halo_ok(kh, kw, stride, pad, H, W, mode=3):
-    return bool(HALO_TILE & mode) and kh == 3 and kw == 3 and stride == 1 and pad == 1 and W <= 63
+    """SCOUTER_HALO wants plane tile 5 for this pass (mode 1 forward, 2 input gradient) and the map admits it (nominal channels)"""
+    return bool(HALO_TILE & mode and ask("fwd_planes_tile_ok", 1, H, W, 64, 64, kh, kw, stride, pad, 1, 3, 5, 0, 0))
 
 
 def conv2d_fwd_planes(xp, wf, kh, kw, stride=1, pad=0, groups=1, bias=None, addend=None, relu=False, bn_stats=False,
@@ -678,17 +696,14 @@ def conv2d_fwd_planes(xp, wf, kh, kw, stride=1, pad=0, groups=1, bias=None, adde
     Cout = wf.shape[2]
     y = torch.empty((B, conv_out(H, kh, stride, pad), conv_out(W, kw, stride, pad), Cout), dtype=out_dtype, device=xp.device)
     L = _native.lib()
-    cands = _plane_tiles(Cout // groups, nplanes, False)
-    if out_dtype == BF16:
-        cands = tuple(t for t in cands if t != 6)      # (the persistent tile's register epilogue writes fp32 only)
-    if tile is None and _halo_ok(kh, kw, stride, pad, H, W, 1) and H * W >= HALO_FWD_MIN_PIXELS:
+    query = (B, H, W, Cin, Cout, kh, kw, stride, pad, groups, nplanes)
+    epi, io = _epi(bias, addend, relu, bn_stats), IO_Y_BF16 if out_dtype == BF16 else 0
+    if tile is None and HALO_TILE & 1 and H * W >= HALO_FWD_MIN_PIXELS and ask("fwd_planes_tile_ok", *query, 5, epi, io):
         tile = 5                                   # static rule (see HALO_TILE): no timing, same bits for every batch
-    if tile == 5:
-        cands = cands + (5,)
+    # (tile 5 is never timed against the others in the forward; tile 6 writes fp32 only, takes the statistics from the raw
+    #  accumulators and needs two K-tiles of 32 channels x taps for its DMA pipeline: the library's rules)
+    cands = tuple(t for t in _PLANE_TILES[nplanes] if (t != 5 or tile == 5) and ask("fwd_planes_tile_ok", *query, t, epi, io))
     M = y.numel() // Cout
-    if (bn_stats and (bias is not None or addend is not None)) or kh * kw * (Cin // groups // 32) < 2:
-        cands = tuple(t for t in cands if t != 6)      # (tile 6 takes the statistics from the raw accumulators and needs
-        #                                                  two K-tiles of 32 channels x taps for its DMA pipeline)
     # scratch for the statistics of the largest partial count (64-row tiles) while the tiles are being timed
     scratch = [None]
 
@@ -700,17 +715,16 @@ def conv2d_fwd_planes(xp, wf, kh, kw, stride=1, pad=0, groups=1, bias=None, adde
                 scratch[0] = torch.empty(((M + 255) // 256 * 4, Cout, 2), dtype=torch.float64, device=xp.device)
             part = scratch[0]
         _native.check(L.scouter_conv2d_fwd_planes_io(_p(xp), _p(wf), _p(bias), _p(addend), _p(y), _p(part), B, H, W, Cin,
-                                                     Cout, kh, kw, stride, pad, groups, int(relu), nplanes, t,
-                                                     IO_Y_BF16 if out_dtype == BF16 else 0, _stream()),
+                                                     Cout, kh, kw, stride, pad, groups, int(relu), nplanes, t, io, _stream()),
                       "conv2d_fwd_planes")
         return True
     if tile is None:
         tile = _pick_tile(("pfwd", nplanes, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, cands)
         if tile < 0:
-            tile = cands[0]
+            tile = cands[0] if cands else 0           # (no tile admits the call: the entry point says why)
     part, rows = None, 0
     if bn_stats:
-        rows = _plane_part_rows(tile, M)                                       # one partial per M tile of the kernel
+        rows = ask("planes_partial_rows", M, tile)                             # one partial per M tile of the kernel
         part = torch.empty((rows, Cout, 2), dtype=torch.float64, device=xp.device)
     launch(tile, part=part)
     return (y, (part, rows)) if bn_stats else y
@@ -721,9 +735,8 @@ def conv2d_dgrad_planes(dyp, wd, x_shape, kh, kw, stride=1, pad=0, groups=1, add
     B, H, W, Cin = x_shape
     Cout = dyp.shape[-1]
     dx = torch.empty(x_shape, dtype=F32, device=dyp.device)
-    cands = _plane_tiles(Cin // groups, nplanes, _halo_ok(kh, kw, stride, pad, H, W, 2))
-    if kh * kw * (Cout // groups // 32) < 2:
-        cands = tuple(t for t in cands if t != 6)      # (tile 6 needs two K-tiles of 32 channels x taps)
+    query = (B, H, W, Cin, Cout, kh, kw, stride, pad, groups, nplanes)
+    cands = tuple(t for t in _PLANE_TILES[nplanes] if (t != 5 or HALO_TILE & 2) and ask("dgrad_planes_tile_ok", *query, t, 0))
 
     def launch(t, dry=False, fuse=_NO_FUSE):
         if dry:
@@ -749,9 +762,9 @@ def conv2d_dgrad_planes(dyp, wd, x_shape, kh, kw, stride=1, pad=0, groups=1, add
     if tile is None:
         tile = _pick_tile(("pdgrad", nplanes, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, cands)
         if tile < 0:
-            tile = cands[0]
+            tile = cands[0] if cands else 0           # (no tile admits the call: the entry point says why)
     if fused:
-        post.alloc(_plane_part_rows(tile, B * H * W), x_shape)
+        post.alloc(ask("planes_partial_rows", B * H * W, tile), x_shape)
         launch(tile, fuse=post.args())
     else:
         launch(tile)
@@ -824,37 +837,34 @@ def x3_halo_eligible(cin, cout, kh, kw, stride, pad, groups, has_bias):
     return bool(ng == 32 and cg % 32 == 0 and not has_bias), bool(cg == 32 and ng % 32 == 0)
 
 
-X3_HALO_MAX_W = 126
+def x3_halo_ok(dgrad, B, H, W, cin, cout, groups=1):
+    """Tile 7 (csrc/conv_xhalo.hip sc_xhalo_ok) takes this call: the map width (<= 126) and the byte guards of its buffer
+    descriptors, which cover the whole input and output tensor and the weight planes in 31-bit byte counts.  Past them the layer
+    keeps the route it had before tile 7 (nn_hip.Conv2d.fwd / bwd); the entry points would refuse the call."""
+    return bool(ask("dgrad_x3_tile_ok" if dgrad else "fwd_x3_tile_ok", B, H, W, cin, cout, 3, 3, 1, 1, groups, 7, 0))
 
 
 def x3_halo_fits(M, cin, cout, groups=1):
-    """The byte guards of tile 7 (csrc/conv_xhalo.hip sc_xhalo_ok), per call: its buffer descriptors cover the whole input and
-    output tensor (M pixels, fp32) and the weight planes in 31-bit byte counts.  Past them the layer keeps the route it had
-    before tile 7 (nn_hip.Conv2d.fwd / bwd); the entry points would refuse the call (SC_ERR_UNSUPPORTED)."""
-    return bool(4 * M * max(cin, cout) < (1 << 31) and 9 * cin * (cout // groups) * 2 * 3 < (1 << 31))
+    """tile 7 takes M pixels of a cin -> cout layer in one of its directions (input gradient: 32 input channels per group, forward:
+    32 output channels per group) -- its channel rule and its byte guards, asked for M images of one pixel"""
+    return M.bit_length() <= 31 and (x3_halo_ok(True, M, 1, 1, cin, cout, groups) or x3_halo_ok(False, M, 1, 1, cin, cout, groups))
 
 
 def _x3_tile_ok(t, n):
-    if t == 7:
-        return n == 32
-    return n % 128 == 0 if t in (0, 1) else (n % 64 == 0 if t in (2, 3, 4) else (n % 32 == 0 and t in (5, 6)))
+    """tile t of the register-split kernels divides n GEMM columns per group (a 3x3 layer of nominal size)"""
+    return bool(ask("fwd_x3_tile_ok", 1, 8, 8, 64, n, 3, 3, 1, 1, 1, t, 0))
 
 
 def x3_fwd_abi_ok(cin, cout, k, stride, pad, groups):
     """What scouter_conv2d_fwd_x3 takes at all (wider than the training routes' x3_eligible / x3_conv_eligible, which also
-    weigh speed against the plain-epilogue kernels): 1x1 or odd same-size filters up to 5x5, stride 1, 32-multiples of
-    channels per group, two 32-channel K-tiles."""
-    if stride != 1 or not (k & 1) or k > 5 or 2 * pad != k - 1 or cin % groups or cout % groups:
-        return False
-    cg, ng = cin // groups, cout // groups
-    return cg % 32 == 0 and ng % 32 == 0 and k * k * (cg // 32) >= 2
+    weigh speed against the plain-epilogue kernels): asked for a nominal batch."""
+    return bool(ask("fwd_x3_tile_ok", 1, 8, 8, cin, cout, k, k, stride, pad, groups, -1, 0))
 
 
 def x3_fwd_fits(B, H, W, cin, cout, k, groups):
-    """The per-call size guards of scouter_conv2d_fwd_x3 (csrc/conv_x3.hip: 32-bit offsets): past them a caller keeps the
-    igemm kernels instead of running into SC_ERR_UNSUPPORTED."""
-    return bool(B * H * W < (1 << 31) and k * k * (cin // groups) * cout * 6 < (1 << 31) and H * W * cin < (1 << 28) and
-                1024 * cin < (1 << 31))
+    """The per-call size guards of scouter_conv2d_fwd_x3 (32-bit offsets): past them a caller keeps the igemm kernels instead
+    of running into SC_ERR_UNSUPPORTED."""
+    return bool(ask("fwd_x3_tile_ok", B, H, W, cin, cout, k, k, 1, (k - 1) // 2, groups, -1, 0))
 
 
 def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=1, pad=0, groups=1, bias=None):
@@ -873,7 +883,7 @@ def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=
 
     def launch(t, dry=False, part=None):
         if dry:
-            return _x3_tile_ok(t, Ng)
+            return bool(ask("fwd_x3_tile_ok", B, H, W, Cin, Cout, kh, kh, 1, pad, groups, t, 0))      # (the cache key has no epilogue)
         if bn_stats and part is None:
             if scratch[0] is None:
                 scratch[0] = torch.empty((max((M + 63) // 64, 512), Cout, 2), dtype=torch.float64, device=x.device)
@@ -884,10 +894,10 @@ def conv2d_fwd_x3(x, wf, addend=None, relu=False, bn_stats=False, tile=None, kh=
     if tile is None:
         key = ("xfwd", 3, B, H, W, Cin, Cout) if kh == 1 and groups == 1 else ("xfwd", 3, B, H, W, Cin, Cout, kh, groups)
         tile = _pick_tile(key, launch, _X3_TILES)
-    tile = L.scouter_conv2d_x3_tile(M, Ng, tile)
+    tile = ask("x3_tile", M, Ng, tile)
     part, rows = None, 0
     if bn_stats:
-        rows = L.scouter_conv2d_x3_halo_partial_rows(groups) if tile == 7 else L.scouter_conv2d_x3_partial_rows(M, Ng, tile)
+        rows = L.scouter_conv2d_x3_halo_partial_rows(groups) if tile == 7 else ask("x3_partial_rows", M, Ng, tile)
         part = torch.empty((rows, Cout, 2), dtype=torch.float64, device=x.device)
     launch(tile, part=part)
     return (y, (part, rows)) if bn_stats else y
@@ -907,7 +917,7 @@ def conv2d_dgrad_x3(dy, wd, x_shape, addend=None, post=None, tile=None, kh=1, pa
 
     def launch(t, dry=False, fuse=_NO_FUSE):
         if dry:
-            return _x3_tile_ok(t, Ng)
+            return bool(ask("dgrad_x3_tile_ok", B, H, W, Cin, Cout, kh, kh, 1, pad, groups, t, 0))
         _native.check(L.scouter_conv2d_dgrad_x3_bnbwd(_p(dy), _p(wd), _p(addend), _p(dx), B, H, W, Cin, Cout, kh, kh, pad,
                                                       groups, t, *fuse, _stream()), "conv2d_dgrad_x3")
         return True
@@ -921,14 +931,13 @@ def conv2d_dgrad_x3(dy, wd, x_shape, addend=None, post=None, tile=None, kh=1, pa
             return launch(t, fuse=post.args())
         if tile is None:
             tile = _pick_tile(("xdgrad+bn", len(post.entries), addend is not None, 3) + shape_key, launch_fused, _X3_TILES)
-        tile = L.scouter_conv2d_x3_tile(M, Ng, tile)
-        post.alloc(L.scouter_conv2d_x3_halo_partial_rows(groups) if tile == 7 else L.scouter_conv2d_x3_partial_rows(M, Ng, tile),
-                   x_shape)
+        tile = ask("x3_tile", M, Ng, tile)
+        post.alloc(L.scouter_conv2d_x3_halo_partial_rows(groups) if tile == 7 else ask("x3_partial_rows", M, Ng, tile), x_shape)
         launch(tile, fuse=post.args())
     else:
         if tile is None:
             tile = _pick_tile(("xdgrad", 3) + shape_key, launch, _X3_TILES)
-        launch(L.scouter_conv2d_x3_tile(M, Ng, tile))
+        launch(ask("x3_tile", M, Ng, tile))
     return dx
 
 
@@ -936,7 +945,7 @@ _X3_WGRAD_PLANS = (-1, 0, 1, 2, 3)
 
 
 def x3_wgrad_ok(cin, cout):
-    return cin % 128 == 0 and cout % 128 == 0
+    return bool(ask("wgrad_x3_ok", 1, 8, 8, cin, cout))
 
 
 def conv2d_wgrad_x3(x, dy, dw_hwio, plan=None):
@@ -970,9 +979,8 @@ def conv2d_wgrad_planes(xp, dyp, dw_hwio, pad, groups=1):
     L = _native.lib()
 
     def launch(plan, dry=False):
-        if dry:         # tap-fused plans (bit 6): 3x3 / pad 1 on maps up to 63 wide, 31-bit byte offsets inside a plane
-            return plan < 64 or (kh == 3 and kw == 3 and pad == 1 and W <= 63 and
-                                 2 * B * H * W * max(Cin, Cout) < (1 << 31))
+        if dry:
+            return bool(ask("wgrad_planes_plan_ok", B, H, W, Cin, Cout, kh, kw, pad, groups, nplanes, plan))
         ws = workspace(L.scouter_conv2d_wgrad_planes_workspace_bytes(B, H, W, Cin, Cout, kh, kw, groups, plan), xp.device)
         _native.check(L.scouter_conv2d_wgrad_planes(_p(xp), _p(dyp), _p(dw_hwio), B, H, W, Cin, Cout, kh, kw, pad, groups,
                                                     nplanes, plan, _p(ws), ws.numel(), _stream()), "conv2d_wgrad_planes")
@@ -1068,9 +1076,8 @@ def conv2d_wgrad(x, dy, dw_hwio, stride=1, pad=0, groups=1, precision="fp32"):
 
     # bf16 matrix inputs where the bf16 kernel applies (same-size stride-1 convolutions, 32-multiples of channels per
     # group -- 32-channel groups on ragged 64-wide tiles); the remaining layers (strided convolutions) keep the fp32 kernel
-    same = stride == 1 and dy.shape[1] == H and dy.shape[2] == W
-    bf16 = (precision == "bf16" and same and cg % 32 == 0 and (Cout // groups) % 32 == 0 and
-            B * H * W >= BF16_MIN_PIXELS and ((kh == 1 and kw == 1 and pad == 0) or 64 // W + 1 < H))
+    shape = (B, H, W, Cin, Cout, kh, kw, stride, pad, groups)
+    bf16 = bool(precision == "bf16" and B * H * W >= BF16_MIN_PIXELS and ask("wgrad_kernel_ok", *shape, WGRAD_BF16))
     if (x.dtype != F32 or dy.dtype != F32) and not bf16:
         raise RuntimeError("scouter_amd: a bf16-stored activation / gradient needs the bf16-input weight-gradient kernel "
                            "(precision 'bf16', same-size stride-1 layer); got %s" % (tuple(x.shape),))
@@ -1089,13 +1096,12 @@ def conv2d_wgrad(x, dy, dw_hwio, stride=1, pad=0, groups=1, precision="fp32"):
         return True
 
     plan = _pick_tile(("wgrad", bf16, B, H, W, Cin, Cout, kh, kw, stride, pad, groups), launch, _WGRAD_PLANS)
-    if not bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and get_switch("xwt"):
+    if not bf16 and get_switch("xwt") and ask("wgrad_kernel_ok", *shape, WGRAD_ROWS32):
         # the 32-channel-group 3x3 layers (deep stem, layer1's radix convolutions): the library's own plan, which is the tap-fused
         # register-split bf16x3 kernel (csrc/conv_wgrad_taps_x3.h) -- a static rule of the shape that overrides the table's
         # (tile, split-K) entry for the exact-fp32 kernels, like SCOUTER_X3 does for the layers it moves
         plan = -1
-    if (bf16 and _rows32_3x3(kh, kw, stride, pad, cg, H, W) and B * H * W * max(Cin, Cout) * 2 < (1 << 31) - (1 << 20) and
-            get_switch("bwt")):
+    if bf16 and get_switch("bwt") and wgrad_prerounds(*shape):
         # the same layers in bf16 mode (BASELINE configs[4]): the library's own plan for bf16-STORED operands is the tap-fused
         # one-plane kernel (csrc/conv_wgrad_taps_bf16.h) instead of one workgroup per tap.  The rule is a function of the SHAPE
         # only: an operand stored as fp32 (SCOUTER_BF16_STORAGE=0 / SCOUTER_BF16_GRADS=0) is rounded to bf16 (RNE: the value

@@ -179,11 +179,10 @@ class Conv2d(nn.Module):
             return ws
         return K.planes_split_weight(K.hwio(self.weight), self.groups, 3, fwd=want_fwd, dgrad=want_dgrad)
 
-    def _halo_fits(self, shape):
-        """The resident-rows kernel takes a B x H x W map: width and byte guards (K.x3_halo_fits); past them the layer keeps
-        the fp32 MFMA kernels it had before tile 7."""
-        B, H, W = shape[:3]
-        return W <= K.X3_HALO_MAX_W and K.x3_halo_fits(B * H * W, self.in_channels, self.out_channels, self.groups)
+    def _halo_fits(self, dgrad, shape):
+        """The resident-rows kernel takes this pass on a B x H x W map (the library's width and byte guards, K.x3_halo_ok);
+        past them the layer keeps the fp32 MFMA kernels it had before tile 7."""
+        return K.x3_halo_ok(dgrad, *shape[:3], self.in_channels, self.out_channels, self.groups)
 
     def _fwd_fits(self, fam, x, relu, addend, out_dtype):
         """This forward call fits family `fam` of the route: fp32 tensors in and out; the persistent pointwise kernel has the
@@ -193,7 +192,7 @@ class Conv2d(nn.Module):
         if fam == "xpw":
             return addend is None and not relu
         if fam == "xhalo":
-            return addend is None and self._halo_fits(x.shape)
+            return addend is None and self._halo_fits(False, x.shape)
         return fam == "x3"
 
     def _dgrad_fits(self, fam, dy, dyp, wd, post, dx_dtype, xshape):
@@ -207,7 +206,7 @@ class Conv2d(nn.Module):
         if dy is None or dy.dtype != K.F32:
             return False
         if fam == "xhalo":
-            return dx_dtype in (None, K.F32) and self._halo_fits(xshape)
+            return dx_dtype in (None, K.F32) and self._halo_fits(True, xshape)
         fused = post is not None and K._fuse_wanted(post, self.kernel_size) and post.x_io() == 0
         return dyp is None and (fused and self.out_channels >= K.X3_FUSED_MIN_K if fam == "x3_fused" else not fused)
 

@@ -12,7 +12,9 @@ every route below is launched just below and just above its threshold:
     the last image, its last 64 pixels, the last 32 channels -- where offsets pass 2^31 and a clipped descriptor would
     read zeros; no tail sample may be exactly zero unless its fp64 value is.
 
-THRESHOLDS (C guard / Python guard; kernel names as the profiler reports them; the shape below / above):
+THRESHOLDS (the C guard and, for the convolution routes, the route query of include/scouter_hip.h through which the wrappers ask
+it -- tests/test_route_queries_cpu.py flips each of those queries between the same two shapes without a device; kernel names as
+the profiler reports them; the shape below / above):
 
   route                     guard                                          below kernel            above kernel
   ------------------------  ---------------------------------------------  ----------------------  ---------------------
@@ -32,30 +34,35 @@ THRESHOLDS (C guard / Python guard; kernel names as the profiler reports them; t
       rows:  13107 x 3 x 10 x 10, 3x3 / 2 (65 535 rows)  /  16384 x 3 x 8 x 8 (65 536 rows)
       Kpad:  7 channels, 3x3 (Kpad 64)                   /  10 channels, 3x3 (Kpad 96); the 7x7 stem (Kpad 160)
   resident-rows register-   4*M*max(Cin, Cout) < 2^31 (csrc/conv_xhalo.hip  xhalo_fwd<bf16x3>       igemm_fwd<...>
-  split kernel, tile 7:     sc_xhalo_ok; Python: kernels.x3_halo_fits, at  xhalo_dgrad<bf16x3>     igemm_dgrad<...>
-  forward (x3 bit 7) and    nn_hip.Conv2d.fwd / .bwd)                                              (the fp32 MFMA kernels
+  split kernel, tile 7:     sc_xhalo_ok; query: scouter_conv2d_{fwd,dgrad}  xhalo_dgrad<bf16x3>     igemm_dgrad<...>
+  forward (x3 bit 7) and    _x3_tile_ok, asked by nn_hip.Conv2d.fwd / .bwd)                        (the fp32 MFMA kernels
   input gradient (bit 6)                                                                           that served them before)
       32 -> 32 forward + gradients, 64 x 64 maps:  4095 images (M*128 = 2^31 - 2^19)  /  4096 images (M*128 = 2^31)
       32 -> 64 input gradient, 64 x 64 maps:       2047 images (M*256 = 2^31 - 2^20)  /  2048 images (M*256 = 2^31)
       layer-level: the deep stem's 32 -> 64 module at 680 x 112 x 112 with default switches (above)
 
-  persistent pointwise tile 4 4*M*max(K, N) < 2^31 (kernels._pw_persist_legal  igemm_fwd<persistent>   igemm_fwd<...>
-                            = csrc/conv_igemm.hip pwp_geom_ok)             igemm_dgrad<persistent> igemm_dgrad<...>
+  persistent pointwise tile 4 4*M*max(K, N) < 2^31 (csrc/conv_igemm.hip        igemm_fwd<persistent>   igemm_fwd<...>
+                            pwp_geom_ok; query: scouter_conv2d_{fwd,dgrad} igemm_dgrad<persistent> igemm_dgrad<...>
+                            _tile_ok)
       1x1, 64 <-> 256 channels, 56 x 56:  668 images  /  669 images
   bf16 resident-rows input  M*Cout*2 < 2^31 - 2^20 for fp32-stored dy       bhalo_dgrad<bf16>       igemm_dgrad_bf16<...>
-  gradient (BHALO)          (kernels.conv2d_dgrad), (M + 512)*Cout*2 < 2^31
-                            for bf16-stored dy (conv_halo_dgrad_bf16.h
-                            bhalo_dgrad_ok)
+  gradient (BHALO)          (policy: kernels.dgrad_prerounds), (M + 512)*
+                            Cout*2 < 2^31 for bf16-stored dy (conv_halo_
+                            dgrad_bf16.h bhalo_dgrad_ok; query: scouter_
+                            conv2d_dgrad_bf16_tile_ok, resident_rows = 1)
       32 -> 64, 64 x 64:  fp32 dy 4093 / 4094 images;  bf16 dy 4095 / 4096 images
-  bf16 tap-fused weight     M*max(Cin, Cout)*2 < 2^31 - 2^20 (kernels.        bwgrad_taps<bf16>       wgrad_bf16
-  gradient (BWT)            conv2d_wgrad; conv_igemm.hip the taps plan)
+  bf16 tap-fused weight     M*max(Cin, Cout)*2 < 2^31 - 2^20 (policy:         bwgrad_taps<bf16>       wgrad_bf16
+  gradient (BWT)            kernels.wgrad_prerounds, over conv_igemm.hip
+                            bwt_geom_ok = scouter_conv2d_wgrad_kernel_ok)
       32 -> 64, 64 x 64, fp32-stored operands:  4093 / 4094 images
-  tap-fused plane weight    2*M*max(Cin, Cout) < 2^31, W <= 63 (kernels.      plan >= 64 (tap-fused)  plan < 64 (per tap)
-  gradient                  conv2d_wgrad_planes = conv_planes.hip)         (both report pwgrad<bf16>: read from the plan cache)
+  tap-fused plane weight    2*M*max(Cin, Cout) < 2^31, W <= 63 (conv_planes.  plan >= 64 (tap-fused)  plan < 64 (per tap)
+  gradient                  hip pwgrad_fused_ok; query: scouter_conv2d_    (both report pwgrad<bf16>: read from the plan cache)
+                            wgrad_planes_plan_ok)
       one plane, 128 -> 256 in two groups, 56 x 56:  1337 / 1338 images
   plane forward / input     nplanes*B*H*W*C*2 < 2^31 + H*W*C*2               pconv_fwd<bf16>         RuntimeError "tensor too
-  gradient                  (csrc/conv_planes.hip): no other kernel takes  pconv_dgrad<bf16>       large for 32-bit plane
-                            plane operands                                                         offsets"
+  gradient                  (csrc/conv_planes.hip pconv_size_ok; query:    pconv_dgrad<bf16>       large for 32-bit plane
+                            scouter_conv2d_{fwd,dgrad}_planes_tile_ok): no                         offsets"
+                            other kernel takes plane operands
       one plane, 64 channels, 32 x 32:  16384 images (the largest batch, PLANE_MAX_B)  /  16385
 
 Peak device memory per test, as measured (torch.cuda.max_memory_allocated): at most 12.4 GB (the tile-7 rows and the layer-level
@@ -521,7 +528,7 @@ def _check_sampled(name, out, ref_fn, gen, k):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# persistent pointwise kernel, tile 4 (kernels._pw_persist_legal = csrc/conv_igemm.hip pwp_geom_ok): 4*M*max(K, N) < 2^31.
+# persistent pointwise kernel, tile 4 (csrc/conv_igemm.hip pwp_geom_ok, which kernels._pw_persist_legal asks): 4*M*max(K, N) < 2^31.
 # The static table picks tile 4 for 56 x 56, 64 <-> 256 channels; past the guard the lookup falls back to the library's tile.
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [668, 669], ids=["M4x256_below", "M4x256_above"])
@@ -601,8 +608,8 @@ def test_bf16_halo_input_gradient_of_a_bf16_stored_dy_both_sides(B):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# tap-fused plane weight gradient (kernels.conv2d_wgrad_planes: 2*B*H*W*max(Cin, Cout) < 2^31 = csrc/conv_planes.hip, the
-# fused plan's guard).  Both plans report the profile row "pwgrad<bf16>" (bench.py's kernel classes list that name), so the
+# tap-fused plane weight gradient (kernels.conv2d_wgrad_planes asks csrc/conv_planes.hip pwgrad_fused_ok, the fused plan's
+# guard: 2*B*H*W*max(Cin, Cout) < 2^31).  Both plans report the profile row "pwgrad<bf16>" (bench.py's kernel classes list that name), so the
 # switch is read from the plan the dispatcher cached: >= 64 = tap-fused (bit 6), < 64 = per-tap.
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [1337, 1338], ids=["below", "above"])
@@ -684,3 +691,201 @@ def test_plane_input_gradient_at_its_largest_batch_and_the_error_past_it(B):
         del dx
     del dyp, wd
     _free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The route queries against the entry points themselves, at a size that costs nothing (B = 2, 8 x 8 maps): for every tile that
+# is an ERROR when named where it does not apply, query 1 <=> the call runs that tile's kernel and matches fp64 (the bound of
+# this file: _k_for relative to V), query 0 <=> the call returns the library's "unsupported" error -- before any launch.  For
+# the hint tiles 0-3, query 0 <=> the profiler shows that another tile ran.  fp32 tile 4 is BOTH: a hint on a shape it does
+# not cover (96 -> 128: another tile runs, on either pass), an error on a covered shape with an epilogue that is not its own
+# (the forward with bias / addend / ReLU; the input gradient has no such epilogue, so naming its tile 4 never raises).  (tests/test_route_queries_cpu.py asks the same
+# queries at the thresholds, without a device.)
+# ---------------------------------------------------------------------------------------------------------------
+QB, QH = 2, 8
+EPI_BIAS, EPI_ADDEND, EPI_RELU, EPI_STATS, EPI_BWD = 1, 2, 4, 8, 16
+
+
+def _full_ref(a, w, pad, dgrad, bf16):
+    """fp64 convolution (dgrad: transposed) of NHWC `a` with HWIO `w` (stride 1, groups 1) and V = sqrt(sum of squared terms);
+    bf16: both operands as the bf16-input kernels round them"""
+    import torch.nn.functional as F
+    op = (lambda t: t.bfloat16().double()) if bf16 else (lambda t: t.double())
+    a64, w64 = op(a).permute(0, 3, 1, 2), op(w).permute(3, 2, 0, 1)          # NCHW, OIHW
+    f = (lambda u, v: F.conv_transpose2d(u, v, padding=pad)) if dgrad else (lambda u, v: F.conv2d(u, v, padding=pad))
+    return f(a64, w64).permute(0, 2, 3, 1), f(a64 * a64, w64 * w64).sqrt().permute(0, 2, 3, 1)
+
+
+def _raw(fn_name, *args):
+    from scouter_amd import _native
+    _native.check(getattr(_native.lib(), fn_name)(*args), fn_name)
+
+
+def _route_case(name, cin, cout):
+    """-> (query name, query arguments after the shape, run() -> the result tensor, dgrad, bf16 operands, kernel name, K, pad)
+    for the GEMM cin -> cout (an input gradient's layer has the channels exchanged)"""
+    kk = K()
+    from scouter_amd import kernels as k_
+    p, st = k_._p, k_._stream
+    gen = _gen(cin * 7 + cout + len(name))
+    rnd = lambda *s, dtype=torch.float32: torch.randn(*s, device="cuda", generator=gen).to(dtype)
+    if name in ("fwd tile 4", "fwd tile 5", "fwd tile 4 + relu", "fwd tile 4 + addend", "fwd tile 5 + bias"):
+        tile = 4 if "4" in name else 5
+        x, w = rnd(QB, QH, QH, cin), rnd(1, 1, cin, cout) / 8
+        bias = rnd(cout) if "bias" in name else None
+        add = rnd(QB, QH, QH, cout) if "addend" in name else None
+        relu = int("relu" in name)
+        y = torch.empty(QB, QH, QH, cout, device="cuda")
+        run = lambda: (_raw("scouter_conv2d_fwd_f32", p(x), p(w), p(bias), p(add), p(y), None, QB, QH, QH, cin, cout, 1, 1, 1, 0, 1,
+                            relu, tile, st()), y)[1]
+        epi = (EPI_BIAS if bias is not None else 0) | (EPI_ADDEND if add is not None else 0) | (EPI_RELU if relu else 0)
+        return ("fwd_tile_ok", (QB, QH, QH, cin, cout, 1, 1, 1, 0, 1, tile, epi), run, (x, w, 0, False, False),
+                "igemm_fwd<persistent>" if tile == 4 else "xpw_fwd<bf16x3>")
+    if name in ("dgrad tile 4", "dgrad tile 5", "dgrad tile 5 plain"):
+        tile = 4 if "4" in name else 5
+        Cin, Cout = cout, cin                                                   # (GEMM-K of the input gradient = Cout)
+        dy, w = rnd(QB, QH, QH, Cout), rnd(1, 1, Cin, Cout) / 8
+        dx = torch.empty(QB, QH, QH, Cin, device="cuda")
+        fused = tile == 5 and "plain" not in name
+        x1 = rnd(QB, QH, QH, Cin) if fused else None
+        saved = torch.stack([torch.zeros(Cin), torch.ones(Cin), torch.ones(Cin), torch.zeros(Cin)]).cuda() if fused else None
+        shape = (QB, QH, QH, Cin, Cout, 1, 1, 1, 0, 1)
+        part = torch.zeros(max(kk.ask("dgrad_bn_partial_rows", *shape, tile), 1), Cin, 2, dtype=torch.float64, device="cuda") if fused else None
+        run = lambda: (_raw("scouter_conv2d_dgrad_bnbwd_f32", p(dy), p(w), None, p(dx), *shape, tile, None, p(x1), p(saved), p(part),
+                            None, None, None, st()), dx)[1]
+        return ("dgrad_tile_ok", (*shape, tile, EPI_BWD if fused else 0), run, (dy, w, 0, True, False),
+                {4: "igemm_dgrad<persistent>", 5: "xpw_dgrad+bn_bwd<bf16x3>"}[tile])
+    if name in ("typed fwd tile 4", "typed fwd tile 4, x fp32"):
+        io = 0 if "fp32" in name else 1
+        x, w = rnd(QB, QH, QH, cin, dtype=torch.float32 if not io else torch.bfloat16), rnd(1, 1, cin, cout) / 8
+        wt = kk.weight_bf16t(w)
+        y = torch.empty(QB, QH, QH, cout, device="cuda")
+        shape = (QB, QH, QH, cin, cout, 1, 1, 1, 0, 1)
+        run = lambda: (_raw("scouter_conv2d_fwd_bf16_io", p(x), p(wt), None, None, p(y), None, *shape, 0, 4, io, st()), y)[1]
+        return ("fwd_bf16_tile_ok", (*shape, 4, 0, io, 0), run, (x.float(), w, 0, False, True), "igemm_fwd_bf16<persistent>")
+    if name in ("typed dgrad tile 4 plain", "typed dgrad tile 4 plain, dy fp32", "typed dgrad tile 4 fused", "typed dgrad tile 4 fused, x1 fp32"):
+        Cin, Cout = cout, cin
+        fused = "fused" in name
+        io = (0 if "dy fp32" in name else 8) | (16 if fused else 0) | (1 if fused and "x1 fp32" not in name else 0)
+        dy = rnd(QB, QH, QH, Cout, dtype=torch.bfloat16 if io & 8 else torch.float32)
+        w = rnd(1, 1, Cin, Cout) / 8
+        dx = torch.empty(QB, QH, QH, Cin, device="cuda", dtype=torch.bfloat16 if io & 16 else torch.float32)
+        x1 = rnd(QB, QH, QH, Cin, dtype=torch.bfloat16 if io & 1 else torch.float32) if fused else None
+        saved = torch.stack([torch.zeros(Cin), torch.ones(Cin), torch.ones(Cin), torch.zeros(Cin)]).cuda() if fused else None
+        shape = (QB, QH, QH, Cin, Cout, 1, 1, 1, 0, 1)
+        part = torch.zeros(max(kk.ask("dgrad_bn_partial_rows_bf16", *shape, 4, 0), 1), Cin, 2, dtype=torch.float64, device="cuda") if fused else None
+        run = lambda: (_raw("scouter_conv2d_dgrad_bnbwd_bf16_io", p(dy), p(w), None, p(dx), *shape, 4, None, p(x1), p(saved), p(part),
+                            None, None, None, io, st()), dx)[1]
+        return ("dgrad_bf16_tile_ok", (*shape, 4, EPI_BWD if fused else 0, io, 0), run, (dy.float(), w, 0, True, True),
+                "igemm_dgrad_bf16<persistent>")
+    if name in ("x3 fwd tile 7", "x3 fwd tile 7 + addend"):
+        x, w = rnd(QB, QH, QH, cin), rnd(3, 3, cin, cout) / 24
+        wf = kk.planes_split_weight(w, 1, 3, fwd=True, dgrad=False)[0]
+        add = rnd(QB, QH, QH, cout) if "addend" in name else None
+        y = torch.empty(QB, QH, QH, cout, device="cuda")
+        run = lambda: (_raw("scouter_conv2d_fwd_x3", p(x), p(wf), None, p(add), p(y), None, QB, QH, QH, cin, cout, 3, 3, 1, 1, 0, 7,
+                            st()), y)[1]
+        return ("fwd_x3_tile_ok", (QB, QH, QH, cin, cout, 3, 3, 1, 1, 1, 7, EPI_ADDEND if add is not None else 0), run,
+                (x, w, 1, False, False), "xhalo_fwd<bf16x3>")
+    if name == "x3 dgrad tile 7":
+        Cin, Cout = cout, cin
+        dy, w = rnd(QB, QH, QH, Cout), rnd(3, 3, Cin, Cout) / 24
+        wd = kk.planes_split_weight(w, 1, 3, fwd=False, dgrad=True)[1]
+        dx = torch.empty(QB, QH, QH, Cin, device="cuda")
+        run = lambda: (_raw("scouter_conv2d_dgrad_x3_bnbwd", p(dy), p(wd), None, p(dx), QB, QH, QH, Cin, Cout, 3, 3, 1, 1, 7, None,
+                            None, None, None, None, None, None, st()), dx)[1]
+        return ("dgrad_x3_tile_ok", (QB, QH, QH, Cin, Cout, 3, 3, 1, 1, 1, 7, 0), run, (dy, w, 1, True, False),
+                "xhalo_dgrad<bf16x3>")
+    assert name in ("plane tile 6", "plane tile 6, bf16 output"), name
+    out = torch.bfloat16 if "bf16" in name else torch.float32
+    x, w = rnd(QB, QH, QH, cin), rnd(3, 3, cin, cout) / 24
+    xp, wf = kk.planes_split(x, 3), kk.planes_split_weight(w, 1, 3, fwd=True, dgrad=False)[0]
+    run = lambda: kk.conv2d_fwd_planes(xp, wf, 3, 3, 1, 1, 1, tile=6, out_dtype=out)
+    return ("fwd_planes_tile_ok", (QB, QH, QH, cin, cout, 3, 3, 1, 1, 1, 3, 6, 0, 2 if out == torch.bfloat16 else 0), run,
+            (x, w, 1, False, False), "pconv_fwd<bf16x3>")
+
+
+ROUTE_CASES = [  # (case, GEMM K -> N, the query's answer; "hint": 0, and the library runs another tile instead of refusing)
+    ("fwd tile 4", 64, 128, 1), ("fwd tile 4", 96, 128, "hint"), ("fwd tile 4 + relu", 64, 128, 0), ("fwd tile 4 + addend", 64, 128, 0),
+    ("fwd tile 5", 64, 128, 1), ("fwd tile 5", 96, 128, 0), ("fwd tile 5 + bias", 64, 128, 0),
+    ("dgrad tile 4", 64, 128, 1), ("dgrad tile 4", 96, 128, "hint"),
+    ("dgrad tile 5", 64, 128, 1), ("dgrad tile 5", 96, 128, 0), ("dgrad tile 5 plain", 64, 128, 0),
+    ("typed fwd tile 4", 64, 128, 1), ("typed fwd tile 4", 96, 128, 0), ("typed fwd tile 4, x fp32", 64, 128, 0),
+    ("typed dgrad tile 4 plain", 64, 128, 1), ("typed dgrad tile 4 plain", 96, 128, 0), ("typed dgrad tile 4 plain, dy fp32", 64, 128, 0),
+    ("typed dgrad tile 4 fused", 64, 128, 1), ("typed dgrad tile 4 fused", 96, 128, 0), ("typed dgrad tile 4 fused, x1 fp32", 64, 128, 0),
+    ("x3 fwd tile 7", 64, 32, 1), ("x3 fwd tile 7", 64, 128, 0), ("x3 fwd tile 7 + addend", 64, 32, 0),
+    ("x3 dgrad tile 7", 64, 32, 1), ("x3 dgrad tile 7", 64, 128, 0),
+    ("plane tile 6", 64, 128, 1), ("plane tile 6, bf16 output", 64, 128, 0),
+]
+
+
+@pytest.mark.parametrize("case", ROUTE_CASES, ids=lambda c: "%s_%dto%d" % (c[0].replace(" ", "_").replace(",", "").replace("+", "and"), c[1], c[2]))   # noqa: E501
+def test_named_tile_runs_where_its_query_says_so_and_is_refused_where_not(case):
+    """Tile 7 and the plane tile need 32 / 64 GEMM columns: their accepted shapes are 64 -> 32 and 64 -> 128, refused 64 -> 128 (tile
+    7) and the bf16-stored output (plane tile 6).  A bf16-stored result (the typed fused input gradient) adds its storage
+    rounding -- at most half a bf16 ulp, the unit roundoff 2^-8 of its 8-bit significand, of the value -- to the bound."""
+    name, cin, cout, want = case
+    kk = K()
+    query, qargs, run, (a, w, pad, dgrad, bf16), kernel = _route_case(name, cin, cout)
+    assert kk.ask(query, *qargs) == (1 if want == 1 else 0), (query, qargs)
+    if want == 0:
+        with pytest.raises(RuntimeError, match="rc=-3"):            # SC_ERR_UNSUPPORTED
+            _, names = _profiled(run)
+        return
+    out, names = _profiled(run)
+    if want == "hint":
+        assert len(names) == 1 and names[0] != kernel and names[0].startswith(kernel.split("<")[0] + "<"), names
+    else:
+        assert kernel in names, names
+    ref, mag = _full_ref(a, w, pad, dgrad, bf16)
+    k = _k_for(a.shape[-1] * w.shape[0] * w.shape[1])
+    if out.dtype == torch.bfloat16:
+        mag = mag + ref.abs() * 2.0 ** -8 / k
+    _check(name, out, ref, mag, k)
+
+
+@pytest.mark.parametrize("cout", [96, 64, 128])
+def test_hint_tiles_run_where_their_query_says_so_and_another_tile_where_not(cout):
+    """Tiles 0-3 of the fp32 forward and input gradient are hints: a tile that does not divide the GEMM columns (the forward's
+    output channels, the input gradient's input channels) is replaced, never refused -- and the query tells which.  (The typed
+    kernels share the rule, sc_igemm_tile_ok; tests/test_route_queries_cpu.py asks their queries.)"""
+    kk = K()
+    gen = _gen(cout)
+    x = torch.randn(QB, QH, QH, 64, device="cuda", generator=gen)
+    w = torch.randn(1, 1, 64, cout, device="cuda", generator=gen) / 8
+    ref, mag = _full_ref(x, w, 0, False, False)
+    fwd_names = ["igemm_fwd<128x128>", "igemm_fwd<128x64>", "igemm_fwd<64x64>", "igemm_fwd<128x32>"]
+    for t in range(4):
+        y, names = _profiled(lambda: kk.conv2d_fwd(x, w, tile=t))
+        assert (fwd_names[t] in names) == bool(kk.ask("fwd_tile_ok", QB, QH, QH, 64, cout, 1, 1, 1, 0, 1, t, 0)), (t, names)
+        assert len(names) == 1 and names[0] in fwd_names, names
+        _check("forward, tile hint %d" % t, y, ref, mag, _k_for(64))
+    from scouter_amd import kernels as k_
+    dy = torch.randn(QB, QH, QH, 64, device="cuda", generator=gen)
+    wd = torch.randn(1, 1, cout, 64, device="cuda", generator=gen) / 8          # the layer cout -> 64: `cout` GEMM columns
+    dx = torch.empty(QB, QH, QH, cout, device="cuda")
+    ref, mag = _full_ref(dy, wd, 0, True, False)
+    shape = (QB, QH, QH, cout, 64, 1, 1, 1, 0, 1)
+    for t in range(4):
+        _, names = _profiled(lambda: _raw("scouter_conv2d_dgrad_f32", k_._p(dy), k_._p(wd), None, k_._p(dx), *shape, t, k_._stream()))
+        assert (fwd_names[t].replace("fwd", "dgrad") in names) == bool(kk.ask("dgrad_tile_ok", *shape, t, 0)), (t, names)
+        assert len(names) == 1 and names[0].replace("dgrad", "fwd") in fwd_names, names
+        _check("input gradient, tile hint %d" % t, dx, ref, mag, _k_for(64))
+
+
+def test_plane_call_no_tile_admits_reaches_the_entry_point_for_its_error():
+    """A plane convolution whose shape no tile's query accepts (96 output channels: not a 64-multiple per group) is still handed
+    to the entry point, which says why -- as past the size guard at 16 385 images above."""
+    kk = K()
+    gen = _gen(96)
+    x = torch.randn(QB, QH, QH, 64, device="cuda", generator=gen)
+    w = torch.randn(3, 3, 64, 96, device="cuda", generator=gen) / 24
+    xp = kk.planes_split(x, 3)
+    wf = torch.zeros(3, 9, 96, 64, device="cuda", dtype=torch.bfloat16)
+    assert not any(kk.ask("fwd_planes_tile_ok", QB, QH, QH, 64, 96, 3, 3, 1, 1, 1, 3, t, 0, 0) for t in range(7))
+    with pytest.raises(RuntimeError, match="Cout/groups % 64 == 0"):
+        kk.conv2d_fwd_planes(xp, wf, 3, 3, 1, 1, 1)
+    dyp = kk.planes_split(torch.randn(QB, QH, QH, 64, device="cuda", generator=gen), 3)
+    wd = torch.zeros(3, 9, 96, 64, device="cuda", dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="Cin/groups % 64 == 0"):
+        kk.conv2d_dgrad_planes(dyp, wd, (QB, QH, QH, 96), 3, 3, 1, 1, 1)

@@ -33,7 +33,9 @@ for H, cin, cout, nbn, n in [(56, 256, 64, 2, 1), (56, 256, 64, 1, 1), (56, 256,
     old = K._table_choice(key, lambda t, dry=False: True)
     res = {}
     for t in (0, 1, 2, 3, 4):
-        if not (K._tile_legal(cin, t) if t < 4 else (cin % 128 == 0 and cout in (64, 128, 256, 512))): continue
+        # (every tensor of the launch is stored as bf16: dy, dx, the addend, the BatchNorm inputs)
+        if not K.ask("dgrad_bf16_tile_ok", B, H, H, cin, cout, 1, 1, 1, 0, 1, t, K._epi(addend=add, post=K.BnBwdFuse(mask, list(zip(xs, saved)))),
+                     K.DGRAD_IO_DY | K.DGRAD_IO_DX | K.DGRAD_IO_ADDEND | (3 if nbn > 1 else 1), 0): continue
         K._tile_cache[key] = t
         def run():
             post = K.BnBwdFuse(mask, list(zip(xs, saved)))
