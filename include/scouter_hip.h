@@ -13,6 +13,11 @@
  *   - return 0 on success, <0 on error (SC_ERR_* below); the message is in scouter_last_error() (thread-local);
  *   - tensors are caller-owned, dense, 16-byte aligned fp32 unless stated;
  *   - activations are NHWC ("[M = B*H*W][C]"), convolution weights are HWIO ([kh][kw][Cin/groups][Cout]).
+ *
+ * Beyond the training path the library holds what an explanation is drawn and scored with, each in a section of its own below:
+ * the input pipeline, Grad-CAM, RISE, insertion / deletion scores, Score-CAM, path and noise batches (Integrated Gradients,
+ * SmoothGrad), Grad-CAM++ and the infidelity / max-sensitivity scores.  The reference computes none of the scores itself; where
+ * no program exists to copy, the section's comment is the specification.
  */
 #ifndef SCOUTER_HIP_H
 #define SCOUTER_HIP_H
@@ -433,6 +438,70 @@ int scouter_grad_powers_accumulate(const float* grads, double* acc2, double* acc
  * SC_ERR_ARG. */
 int scouter_gradcampp_smooth_f32(const float* feat, const double* acc2, const double* acc3, const float* glast, float* out,
                                  int n_samples, int B, int N, int C, long out_stride, int relu, void* stream);
+
+/* ---- Infidelity and max-sensitivity of an explanation (Yeh et al., NeurIPS 2019, "On the (In)fidelity and Sensitivity of
+ * Explanations"; captum's infidelity and sensitivity_max, two columns of the SCOUTER paper's comparison of explanations;
+ * csrc/fidelity.hip, tools/attribution.py infidelity / sensitivity_max).  No reference program computes either here: the
+ * definitions below are the specification.  One image x of E = C * H * W elements, e the flat index, HW = H * W; a stream of N
+ * perturbed copies of x goes through the model (or the explanation method) in chunks [first, first + n), every forward with the
+ * clean image in row 0, and the chunks fill per-sample fp64 arrays [K][N].  One fixed order per output element and no atomics:
+ * bit-identical run to run, and no value depends on the chunking.  A null or misaligned pointer (fp32 / i32: 4 bytes, fp64: 8),
+ * a size below 1 or a chunk outside [0, N) is SC_ERR_ARG; sizes past 32-bit offsets or the grid are SC_ERR_UNSUPPORTED; nothing
+ * is launched after an error.
+ *
+ * INFIDELITY of K attributions a_k for the class columns c_k: z_j[e] = the standard normal of scouter_noise_images_f32 (the key
+ * (seed_lo, seed_hi), the counter (e / 4, j, 0, 0)), the perturbed image x_j = fmaf(sigma, z_j[e], x[e]) written by that call, the
+ * perturbation DEFINED as I_j[e] = -sigma * z_j[e] (the exact product of the two fp32 values: x - x_j up to the fma's rounding),
+ * dot[k][j] = sum_e a_k[e] * I_j[e] in fp64, delta[k][j] = F(out[0][c_k]) - F(out[1 + i][c_k]) for the sample j in row 1 + i of a
+ * forward (F the identity on the log-probabilities, or exp), and over ascending j in fp64
+ *   raw[k] = (1 / N) sum_j (dot - delta)^2,  beta[k] = sum_j dot * delta / sum_j dot^2 (0 when the denominator is 0),
+ *   normalized[k] = (1 / N) sum_j (beta * dot - delta)^2   (captum's normalize = True).
+ *
+ * dots fp64 [K][N], dots[k][first + j] = sum_e a_k[e] * I_{first + j}[e] for j < n.  attrs fp32 [K][A]: A == E is the FULL form
+ * (a_k = attrs[k]), A < E with E % A == 0 is the MAP form, A = HW, a map that counts for every channel (a_k[e] = attrs[k][e % A]);
+ * anything else is SC_ERR_ARG.  z is regenerated from Philox, no image buffer is read.  A thread owns groups of four elements
+ * 4q .. 4q + 3 (ascending q); per group it loads a tile of 4 attributions once and, per sample of a tile of 4 samples, forms the four
+ * p = -(double)sigma * (double)z and adds fma((double)a_k[e], p, .) in e order; then a butterfly over the wave, the waves of the
+ * workgroup in order through LDS, and a second launch that adds the workgroups' partial sums in workgroup order.  The grid
+ * along the elements is min(ceil(ceil(E / 4) / 256), 256) workgroups, a function of E alone.  16-byte loads when A is a multiple
+ * of 4 and attrs is 16-byte aligned, one element per load otherwise: the same bits.  sigma >= 0 and finite (0: every dot is 0).
+ * ws: at least scouter_perturb_dots_workspace_bytes(n, K, E) bytes, 8-byte aligned (less: SC_ERR_WORKSPACE). */
+size_t scouter_perturb_dots_workspace_bytes(int n, int K, long E);
+int scouter_perturb_dots_f64(const float* attrs, double* dots, float sigma, int seed_lo, int seed_hi, int first, int n, int N,
+                             int K, long E, long A, void* ws, size_t ws_bytes, void* stream);
+/* deltas fp64 [K][N], deltas[k][first + j] = F((double)out[0][cols[k]]) - F((double)out[1 + j][cols[k]]) for j < n: out fp32
+ * [1 + n][n_classes] is ONE forward's output with the clean image in row 0, cols i32 [K] in [0, n_classes) (checked by the caller;
+ * clamped here), of = SCOUTER_DELTA_LOG_PROB 0: F the identity, SCOUTER_DELTA_PROB 1: F = exp in fp64; another value is
+ * SC_ERR_ARG. */
+#define SCOUTER_DELTA_LOG_PROB 0
+#define SCOUTER_DELTA_PROB 1
+int scouter_output_deltas_f64(const float* out, const int* cols, double* deltas, int first, int n, int N, int K, int n_classes,
+                              int of, void* stream);
+/* One thread per row r < R of dots / deltas fp64 [R][N], the samples in ascending j, every product-and-add one fp64 fma:
+ * raw[r] = sum_j (dot - delta)^2 / N, beta[r] = sum_j dot * delta / sum_j dot^2 (0 when sum_j dot^2 == 0),
+ * normalized[r] = sum_j (fma(beta, dot, -delta))^2 / N.  raw, beta, normalized fp64 [R]. */
+int scouter_infidelity_finish_f64(const double* dots, const double* deltas, double* raw, double* beta, double* normalized,
+                                  long R, int N, void* stream);
+/* MAX-SENSITIVITY of an explanation method: d_j[e] = 2 * u - 1 with u = (float)(2 * (r >> 9) + 1) * 2^-24 from the Philox word
+ * r = word e % 4 of the counter (e / 4, j, 1, 0) under the same key -- the third counter word sets this stream apart from the
+ * noise -- so d_j[e] = ((2 * (r >> 9) + 1) - 2^23) * 2^-23 exactly, never 0 and inside (-1, 1); x_j = fmaf(radius, d_j[e], x[e]);
+ * the method explains [x, x_first, ...] as A fp32 [1 + n][K][M]; term[k][j] = sqrt(sum_m (A_j[k][m] - A_0[k][m])^2 / den_k) with
+ * den_k = sum_m A_0[k][m]^2, or 1 when that sum is 0 (captum's choice for a zero explanation); score[k] = max_j term[k][j], NaN if
+ * any term is NaN.
+ *
+ * out fp32 [n][E], out[j][e] = fmaf(radius, d_{first + j}[e], image[e]), radius >= 0 and finite: the twin of
+ * scouter_noise_images_f32 with its forms, its refusals and its rule that an element's value depends on (seed, first + j, e) alone.
+ * A thread writes a tile of 8 samples of its four elements; n above 65535 * 8: SC_ERR_UNSUPPORTED. */
+int scouter_uniform_images_f32(const float* image, float* out, float radius, int seed_lo, int seed_hi, int first, int n, long E,
+                               void* stream);
+/* terms fp64 [K][N], terms[k][first + j] = the term above for j < n, from maps fp32 [1 + n][K][M] of ONE call of the method (den_k
+ * comes from row 0 of the same call).  One workgroup of 256 threads per (j, k): a thread adds (A_j[m] - A_0[m])^2, the difference
+ * formed in fp64, and A_0[m]^2, one fma each, for m = t, t + 256, ... in ascending m; then a butterfly over the wave and the waves
+ * in order.  K above 65535: SC_ERR_UNSUPPORTED. */
+int scouter_map_distances_f64(const float* maps, double* terms, int first, int n, int N, int K, long M, void* stream);
+/* score fp64 [R], score[r] = max_j terms[r][j] over terms fp64 [R][N], one thread per row in ascending j; a NaN term makes the
+ * score NaN. */
+int scouter_sensitivity_finish_f64(const double* terms, double* score, long R, int N, void* stream);
 
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats

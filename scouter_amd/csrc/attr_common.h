@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
+// pathgrad.hip, fidelity.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
 // scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
 // same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
 #pragma once
@@ -51,6 +51,21 @@ __device__ __forceinline__ void at_block_minmax(float& lo, float& hi, float* s_l
     for (int k = 1; k < WAVES; ++k) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); }
 }
 
+// sum of v over a workgroup of WAVES waves in a fixed order (lanes by butterfly, then the waves in order through s_part [WAVES]);
+// the result is valid in thread 0.  Ends after one barrier: a second sum takes an s_part of its own.
+template <int WAVES>
+__device__ __forceinline__ double at_block_sum(double v, double* s_part) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) s_part[wv] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < WAVES; ++i) t += s_part[i];
+    return t;
+}
+
 // The two min-max scalings of a heat map as one affine map of v: ((v - lo) / span1 raised to lo2, minus lo2) / span2, to a byte.
 // After the first scaling the minimum is exactly 0 and the maximum exactly 1, so the extrema of max(., min_level) are
 // lo2 = max(0, min_level) and max(1, min_level).  A map that is constant at either step (or has a NaN / infinity in it) is flat.
@@ -72,6 +87,36 @@ struct AtHeatScale {
         return (unsigned char)(int)(255.f * c);
     }
 };
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The random streams of pathgrad.hip (noise_images) and fidelity.hip (perturb_dots, uniform_images), one copy for both.
+// Philox4x32-10 (Salmon et al., SC 2011): ten rounds, the key bumped between them
+__device__ __forceinline__ void pg_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                          unsigned (&r)[4]) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// a random word -> (2 (r >> 9) + 1) 2^-24, exact in fp32 and inside (0, 1)
+__device__ __forceinline__ float pg_uniform(unsigned r) { return (float)(2u * (r >> 9) + 1u) * 0x1p-24f; }
+
+// one Box-Muller pair from two words, with the accurate library functions
+__device__ __forceinline__ void pg_normal_pair(unsigned ra, unsigned rb, float& za, float& zb) {
+    const float rad = sqrtf(-2.f * logf(pg_uniform(ra)));
+    const float ang = 6.283185307179586f * pg_uniform(rb);
+    za = rad * cosf(ang);
+    zb = rad * sinf(ang);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // V = 1 or 4 consecutive elements with the widest access V allows (at most 16 bytes each); NT: streamed once, non-temporal

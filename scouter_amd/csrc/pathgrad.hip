@@ -88,34 +88,6 @@ extern "C" int scouter_path_images_f32(const float* image, const float* base, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC 2011): ten rounds, the key bumped between them
-__device__ __forceinline__ void pg_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                          unsigned (&r)[4]) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
-// a random word -> (2 (r >> 9) + 1) 2^-24, exact in fp32 and inside (0, 1)
-__device__ __forceinline__ float pg_uniform(unsigned r) { return (float)(2u * (r >> 9) + 1u) * 0x1p-24f; }
-
-// one Box-Muller pair from two words, with the accurate library functions
-__device__ __forceinline__ void pg_normal_pair(unsigned ra, unsigned rb, float& za, float& zb) {
-    const float rad = sqrtf(-2.f * logf(pg_uniform(ra)));
-    const float ang = 6.283185307179586f * pg_uniform(rb);
-    za = rad * cosf(ang);
-    zb = rad * sinf(ang);
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(PG_THREADS) void noise_images_kernel(const float* __restrict__ image, float* __restrict__ out,
                                                                   float sigma, unsigned seed_lo, unsigned seed_hi, int first,
@@ -264,19 +236,6 @@ __device__ __forceinline__ float pg_finish(int mode, double a, double s, float x
     }
 }
 
-// sum of v over the workgroup in a fixed order (lanes by butterfly, then the waves in order); the result is valid in thread 0
-__device__ __forceinline__ double pg_block_sum(double v, double* s_part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) s_part[wv] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < PG_THREADS / 64; ++i) t += s_part[i];
-    return t;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(PG_THREADS) void attr_finish_kernel(int mode, const double* __restrict__ acc,
                                                                  const double* __restrict__ acc_sq,
@@ -322,7 +281,7 @@ __global__ __launch_bounds__(PG_THREADS) void attr_finish_kernel(int mode, const
         else out[e] = r[0];
     }
     if (partial) {                                             // (uniform over the launch)
-        const double t = pg_block_sum(sum, s_part);
+        const double t = at_block_sum<PG_THREADS / 64>(sum, s_part);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
     }
 }
@@ -333,7 +292,7 @@ __global__ __launch_bounds__(PG_THREADS) void attr_total_kernel(const double* __
     __shared__ double s_part[PG_THREADS / 64];
     double v = 0.0;
     for (int i = threadIdx.x; i < count; i += PG_THREADS) v += partial[i];
-    const double t = pg_block_sum(v, s_part);
+    const double t = at_block_sum<PG_THREADS / 64>(v, s_part);
     if (threadIdx.x == 0) total[0] = t;
 }
 

@@ -2125,3 +2125,129 @@ def channel_mean(x, absolute=False, out=None):
     _native.check(_native.lib().scouter_channel_mean_f32(_p(x), _p(out), M, int(C), int(H) * int(W), 1 if absolute else 0,
                                                          _stream()), "channel_mean")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# infidelity and max-sensitivity (csrc/fidelity.hip; tools/attribution.py infidelity / sensitivity_max)
+# ---------------------------------------------------------------------------------------------------------------
+DELTA_LOG_PROB, DELTA_PROB = 0, 1                               # (include/scouter_hip.h SCOUTER_DELTA_*)
+_DELTA_MODES = {"log_prob": DELTA_LOG_PROB, "prob": DELTA_PROB}
+PERTURB_DOTS_CLASS_TILE, PERTURB_DOTS_SAMPLE_TILE = 4, 4        # (csrc/fidelity.hip FD_KT / FD_JT: the register tiles of perturb_dots)
+UNIFORM_IMAGES_SAMPLE_TILE = 8                                  # (csrc/fidelity.hip FD_IMG_JT: samples per thread of uniform_images)
+
+
+def _per_sample_chk(what, name, t, K):
+    """an fp64 per-sample array [K, N] on the device -> N"""
+    _chk(t, "%s: %s" % (what, name), torch.float64)
+    if t.dim() != 2 or t.shape[0] != K:
+        raise RuntimeError("%s: %s must be fp64 [K = %d, N], got shape %s" % (what, name, K, tuple(t.shape)))
+    return int(t.shape[1])
+
+
+def perturb_dots(attrs, dots, sigma, seed, first, n, channels=None):
+    """dots[k, first + j] = sum_e a_k[e] * (-sigma * z(seed, first + j, e)) for j < n, in fp64: the attribution-times-perturbation
+    sums of `infidelity` for the samples kernels.noise_images writes with the same sigma, seed and first -- z is regenerated, no
+    image is read.  attrs fp32 [K, C, H, W]: the full form, a_k = attrs[k] (channels, when given, must be C); attrs fp32 [K, H, W]:
+    maps that count for each of the `channels` channels, a_k[e] = attrs[k, e mod H W].  dots fp64 [K, N] with first + n <= N.
+    Partial sums go through the stream's workspace in a fixed order; the grid depends on the image's size alone, so chunks
+    filled by separate calls equal one call bit for bit.  sigma >= 0.  Two launches."""
+    _chk(attrs, "perturb_dots: attrs")
+    if attrs.dim() not in (3, 4) or attrs.shape[0] < 1 or (attrs.dim() == 3 and channels is None) or \
+            (attrs.dim() == 4 and channels is not None and int(channels) != attrs.shape[1]):
+        raise RuntimeError("perturb_dots: attrs must be [K, C, H, W], or [K, H, W] with channels=C (got shape %s, channels %r)"
+                           % (tuple(attrs.shape), channels))
+    K, A = int(attrs.shape[0]), int(attrs[0].numel())
+    E = A if attrs.dim() == 4 else A * int(channels)
+    N = _per_sample_chk("perturb_dots", "dots", dots, K)
+    lo, hi = _seed_words(seed)
+    lib = _native.lib()
+    nbytes = lib.scouter_perturb_dots_workspace_bytes(int(n), K, E)
+    ws = workspace(nbytes, attrs.device)
+    _native.check(lib.scouter_perturb_dots_f64(_p(attrs), _p(dots), float(sigma), lo, hi, int(first), int(n), N, K, E, A, _p(ws),
+                                               nbytes, _stream()), "perturb_dots")
+    return dots
+
+
+def uniform_images(image, out, radius, seed, first):
+    """out[j] = image + radius * d(seed, first + j) for fp32 image [C, H, W] and fp32 out [n, C, H, W] (a dense leading slice of a
+    longer buffer is fine): d uniform on (-1, 1), d = 2 u - 1 = ((2 (r >> 9) + 1) - 2^23) 2^-23 exactly (never 0) from the
+    Philox4x32-10 words of the counter (e / 4, first + j, 1, 0) under the 64-bit `seed` -- the stream beside noise_images', whose
+    third counter word is 0.  An element's value depends on (seed, first + j, e) alone, so chunks written by separate calls equal
+    one call.  radius >= 0.  One launch."""
+    _chk(image, "uniform_images: image"); _chk(out, "uniform_images: out")
+    n, E = _batch_of("uniform_images", image, out)
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_uniform_images_f32(_p(image), _p(out), float(radius), lo, hi, int(first), n, E, _stream()),
+                  "uniform_images")
+    return out
+
+
+def output_deltas(out, cols, deltas, first, of="log_prob"):
+    """deltas[k, first + j] = F(out[0, cols[k]]) - F(out[1 + j, cols[k]]) in fp64 for ONE forward's fp32 output [1 + n, n_classes]
+    with the clean image in row 0, cols int32 [K] on the device (the caller keeps them inside [0, n_classes)) and fp64 deltas
+    [K, N], first + n <= N.  of="log_prob": F is the identity (the model's output); of="prob": F = exp in fp64.  One launch;
+    nothing is read on the host."""
+    if of not in _DELTA_MODES:
+        raise ValueError("output_deltas: of must be 'log_prob' or 'prob', got %r" % (of,))
+    _chk(out, "output_deltas: out"); _chk(cols, "output_deltas: cols", torch.int32)
+    if out.dim() != 2 or cols.dim() != 1 or cols.shape[0] < 1:
+        raise RuntimeError("output_deltas: out must be [1 + n, n_classes] and cols [K] (got %s and %s)"
+                           % (tuple(out.shape), tuple(cols.shape)))
+    K = int(cols.shape[0])
+    N = _per_sample_chk("output_deltas", "deltas", deltas, K)
+    _native.check(_native.lib().scouter_output_deltas_f64(_p(out), _p(cols), _p(deltas), int(first), int(out.shape[0]) - 1, N, K,
+                                                          int(out.shape[1]), _DELTA_MODES[of], _stream()), "output_deltas")
+    return deltas
+
+
+def map_distances(maps, terms, first):
+    """terms[k, first + j] = sqrt(sum_m (maps[1 + j, k, m] - maps[0, k, m])^2 / den_k) in fp64 for the fp32 explanations
+    [1 + n, K, ...] of ONE call of an explanation method with the clean image in row 0: den_k = sum_m maps[0, k, m]^2, or 1 when
+    that is 0.  fp64 terms [K, N], first + n <= N.  One workgroup per (j, k) with a fixed summation order.  One launch."""
+    _chk(maps, "map_distances: maps")
+    if maps.dim() < 2 or maps.shape[1] < 1:
+        raise RuntimeError("map_distances: maps must be [1 + n, K, ...], got shape %s" % (tuple(maps.shape),))
+    K = int(maps.shape[1])
+    M = int(maps[0, 0].numel()) if maps.shape[0] else 0
+    N = _per_sample_chk("map_distances", "terms", terms, K)
+    _native.check(_native.lib().scouter_map_distances_f64(_p(maps), _p(terms), int(first), int(maps.shape[0]) - 1, N, K, M,
+                                                          _stream()), "map_distances")
+    return terms
+
+
+def infidelity_finish(dots, deltas, out=None):
+    """fp64 dots / deltas [..., N] -> (raw, normalized, beta), fp64 [...] each: raw = mean_j (dot - delta)^2,
+    beta = sum_j dot * delta / sum_j dot^2 (0 when the denominator is 0), normalized = mean_j (beta * dot - delta)^2, summed in
+    ascending j by one thread per row.  out: None, or the three tensors to fill.  One launch."""
+    _chk(dots, "infidelity_finish: dots", torch.float64); _chk(deltas, "infidelity_finish: deltas", torch.float64)
+    if dots.dim() < 1 or deltas.shape != dots.shape:
+        raise RuntimeError("infidelity_finish: dots and deltas must be the same [..., N] shape (got %s and %s)"
+                           % (tuple(dots.shape), tuple(deltas.shape)))
+    (lead, R), N = _lead(dots.shape, 1), int(dots.shape[-1])
+    if out is None:
+        out = tuple(torch.empty(lead, dtype=torch.float64, device=dots.device) for _ in range(3))
+    if len(out) != 3:
+        raise RuntimeError("infidelity_finish: out must be three tensors (raw, normalized, beta)")
+    for t in out:
+        _chk(t, "infidelity_finish: out", torch.float64)
+        if tuple(t.shape) != lead:
+            raise RuntimeError("infidelity_finish: out must be %s, got shape %s" % (lead, tuple(t.shape)))
+    raw, normalized, beta = out
+    _native.check(_native.lib().scouter_infidelity_finish_f64(_p(dots), _p(deltas), _p(raw), _p(beta), _p(normalized), R, N,
+                                                              _stream()), "infidelity_finish")
+    return raw, normalized, beta
+
+
+def sensitivity_finish(terms, out=None):
+    """fp64 terms [..., N] -> fp64 [...]: the largest term of each row, NaN when any of its terms is NaN.  One launch."""
+    _chk(terms, "sensitivity_finish: terms", torch.float64)
+    if terms.dim() < 1:
+        raise RuntimeError("sensitivity_finish: terms must be [..., N], got shape %s" % (tuple(terms.shape),))
+    (lead, R), N = _lead(terms.shape, 1), int(terms.shape[-1])
+    if out is None:
+        out = torch.empty(lead, dtype=torch.float64, device=terms.device)
+    _chk(out, "sensitivity_finish: out", torch.float64)
+    if tuple(out.shape) != lead:
+        raise RuntimeError("sensitivity_finish: out must be %s, got shape %s" % (lead, tuple(out.shape)))
+    _native.check(_native.lib().scouter_sensitivity_finish_f64(_p(terms), _p(out), R, N, _stream()), "sensitivity_finish")
+    return out

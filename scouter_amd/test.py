@@ -22,8 +22,13 @@ heat maps `<out>/smoothcampp_{c}.png` (tools/attribution.py smooth_gradcampp: --
 --smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--causal true` prints, for every family of maps
 drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
-`causal <family> class <c>: deletion <d> insertion <i>`.  The jet-colormap overlay of test.py:33-38 is matplotlib
-post-processing of these PNGs and is not reproduced.
+`causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
+the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
+--infidelity_sigma, --infidelity_batch rows per forward; grad, ig and smoothgrad with their full attribution, the others with their
+map) as `infidelity <family> class <c>: raw <r> normalized <n> beta <b>` and its max-sensitivity (tools/attribution.py
+sensitivity_max: --sensitivity_samples points within --sensitivity_radius, --sensitivity_batch rows per call) as
+`sensitivity <family> class <c>: max <s>` -- the infidelity and sensitivity columns of the paper, after Yeh et al. 2019.  The
+jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNGs and is not reproduced.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
@@ -32,7 +37,9 @@ post-processing of these PNGs and is not reproduced.
         [--scorecam true --scorecam_batch 250] [--ig true --ig_steps 50 --ig_batch 50] \
         [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
         [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
-        [--causal true --causal_step 224]"""
+        [--causal true --causal_step 224] \
+        [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
+        [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
 import argparse
 import functools
 import os
@@ -178,39 +185,92 @@ def run_smoothgrad(args, model, image, out_dir):
     return _run_gradient_family(args, model, image, out_dir, _smoothgrad, "smoothgrad")
 
 
+def _family_attribution(args, model, x, pred, family, slot_map=None, full=False):
+    """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
+    given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
+    rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
+    smoothcampp: smooth_gradcampp).  full: grad, ig and smoothgrad keep their attribution [n, 1, C, H, W] instead."""
+    from . import kernels as K
+    from .tools.attribution import gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
+    if family == "slot":
+        return slot_map
+    if family == "grad":
+        g = input_gradients(model, x, classes=[pred])
+        return g if full else g.mean(dim=2)
+    if family == "cam":
+        return gradcam(model, x, classes=[pred])
+    if family == "scorecam":
+        return scorecam(model, x, classes=[pred], batch=int(getattr(args, "scorecam_batch", 250)))
+    if family == "ig":
+        g = _ig(args, model, x, classes=[pred])
+        return g if full else K.channel_mean(g)
+    if family == "smoothgrad":
+        g = _smoothgrad(args, model, x, classes=[pred])
+        return g if full else K.channel_mean(g)
+    if family == "campp":
+        return gradcampp(model, x, classes=[pred])
+    if family == "smoothcampp":
+        return smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
+    return rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)),
+                batch=int(getattr(args, "rise_batch", 250)))
+
+
 def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
     integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp), one printed line each; returns
     {family: (deletion, insertion)}."""
-    from . import kernels as K
-    from .tools.attribution import causal_metrics, gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
+    from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
     step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
     scores = {}
     for family in families:
-        if family == "slot":
-            maps = slot_map
-        elif family == "grad":
-            maps = input_gradients(model, x, classes=[pred]).mean(dim=2)
-        elif family == "cam":
-            maps = gradcam(model, x, classes=[pred])
-        elif family == "scorecam":
-            maps = scorecam(model, x, classes=[pred], batch=int(getattr(args, "scorecam_batch", 250)))
-        elif family == "ig":
-            maps = K.channel_mean(_ig(args, model, x, classes=[pred]))
-        elif family == "smoothgrad":
-            maps = K.channel_mean(_smoothgrad(args, model, x, classes=[pred]))
-        elif family == "campp":
-            maps = gradcampp(model, x, classes=[pred])
-        elif family == "smoothcampp":
-            maps = smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
-        else:
-            maps = rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)), batch=batch)
+        maps = _family_attribution(args, model, x, pred, family, slot_map)
         r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
         scores[family] = (float(r.deletion[0, 0]), float(r.insertion[0, 0]))
         print("causal %s class %d: deletion %.6f insertion %.6f" % ((family, pred) + scores[family]))
+    return scores
+
+
+def run_infidelity(args, model, image, pred, families, slot_map=None):
+    """--infidelity true: the infidelity (tools/attribution.py infidelity: --infidelity_samples noisy copies at --infidelity_sigma,
+    --infidelity_batch rows per forward) of the predicted class's explanation of every family in `families` -- grad, ig and
+    smoothgrad with their full [C, H, W] attribution, the other families with their map, which counts for every channel -- one
+    printed line each; returns {family: (raw, normalized, beta)}."""
+    from .tools.attribution import infidelity
+    x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
+    scores = {}
+    for family in families:
+        attr = _family_attribution(args, model, x, pred, family, slot_map, full=True)
+        r = infidelity(model, x, attr, classes=[pred], n_samples=int(getattr(args, "infidelity_samples", 50)),
+                       sigma=float(getattr(args, "infidelity_sigma", 0.003)), batch=int(getattr(args, "infidelity_batch", 50)))
+        scores[family] = (float(r.raw[0, 0]), float(r.normalized[0, 0]), float(r.beta[0, 0]))
+        print("infidelity %s class %d: raw %.6e normalized %.6e beta %.6e" % ((family, pred) + scores[family]))
+    return scores
+
+
+def run_sensitivity(args, model, image, pred, families):
+    """--sensitivity true: the max-sensitivity (tools/attribution.py sensitivity_max: --sensitivity_samples points of the box of
+    half-width --sensitivity_radius, --sensitivity_batch rows per call) of the predicted class's FLOAT map of every family in
+    `families`, each family explaining the perturbed images as it explained the image (slot: an eval forward, then
+    slot_saliency), one printed line each; returns {family: score}."""
+    from .tools.attribution import _eval_mode, sensitivity_max, slot_saliency
+    x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
+
+    def slot_maps(images):
+        with _eval_mode(model), torch.no_grad():
+            model(images)
+        return slot_saliency(model)[:, pred:pred + 1].contiguous()
+
+    scores = {}
+    for family in families:
+        explain = slot_maps if family == "slot" else functools.partial(_family_attribution, args, model, pred=pred, family=family)
+        r = sensitivity_max(explain, x, n_samples=int(getattr(args, "sensitivity_samples", 10)),
+                            radius=float(getattr(args, "sensitivity_radius", 0.02)),
+                            batch=int(getattr(args, "sensitivity_batch", 11)))
+        scores[family] = float(r.score[0, 0])
+        print("sensitivity %s class %d: max %.6e" % (family, pred, scores[family]))
     return scores
 
 
@@ -250,6 +310,18 @@ def get_test_parser():
     parser.add_argument("--smoothcampp_samples", default=4, type=int, help="noisy copies per class of --smoothcampp")
     parser.add_argument("--smoothcampp_sigma", default=0.3, type=float, help="standard deviation of the noise of --smoothcampp")
     parser.add_argument("--smoothcampp_batch", default=4, type=int, help="noisy copies per feature pass of --smoothcampp")
+    parser.add_argument("--infidelity", default=False, type=_flag,
+                        help="true: print the infidelity of the predicted class's explanation of every family drawn")
+    parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
+    parser.add_argument("--infidelity_sigma", default=0.003, type=float, help="standard deviation of the noise of --infidelity")
+    parser.add_argument("--infidelity_batch", default=50, type=int,
+                        help="rows per forward of --infidelity, the clean image included")
+    parser.add_argument("--sensitivity", default=False, type=_flag,
+                        help="true: print the max-sensitivity of the predicted class's map of every family drawn")
+    parser.add_argument("--sensitivity_samples", default=10, type=int, help="perturbed copies of --sensitivity")
+    parser.add_argument("--sensitivity_radius", default=0.02, type=float, help="half-width of the box of --sensitivity")
+    parser.add_argument("--sensitivity_batch", default=11, type=int,
+                        help="rows per call of the explanation method of --sensitivity, the clean image included")
     return parser
 
 
@@ -277,7 +349,7 @@ def main():
         image = torch.from_numpy(np.random.default_rng(0).standard_normal((channels, size, size), dtype=np.float32))
     out, pred, maps, ratio = run(args, model, image, args.vis_dir, args.label)
     slot_map = None
-    if args.causal and model.use_slot:
+    if (args.causal or args.infidelity) and model.use_slot:
         from .tools.attribution import slot_saliency
         slot_map = slot_saliency(model)[:, pred:pred + 1].contiguous()       # (before another forward replaces last_attn)
     if want_grad:
@@ -296,11 +368,15 @@ def main():
         run_campp(args, model, image, args.vis_dir)
     if args.smoothcampp:
         run_smoothcampp(args, model, image, args.vis_dir)
+    families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
+                                ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
+                                ("campp", args.campp), ("smoothcampp", args.smoothcampp)) if on]
     if args.causal:
-        families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
-                                    ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
-                                    ("campp", args.campp), ("smoothcampp", args.smoothcampp)) if on]
         run_causal(args, model, image, pred, families, slot_map)
+    if args.infidelity:
+        run_infidelity(args, model, image, pred, families, slot_map)
+    if args.sensitivity:
+        run_sensitivity(args, model, image, pred, families)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:

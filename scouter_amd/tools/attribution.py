@@ -52,7 +52,19 @@ alpha = g^2 / (2 g^2 + sum_p g^3 A) before the rectified gradient is summed; the
 copies of the image (kernels.noise_images, float64 sums in sample order by kernels.grad_powers_accumulate, so the chunking does
 not change a bit) and rectifies the last sample's gradient, as the reference does.  The weighting and the contraction are HIP
 kernels (kernels.gradcampp, kernels.gradcampp_smooth); alpha is 0 where the reference divides 0 / 0.  Nothing comes to the host
-in between."""
+in between.
+
+Two more scores for any of these explanations (`infidelity`, `sensitivity_max`): the infidelity and the max-sensitivity of Yeh et
+al. 2019 ("On the (In)fidelity and Sensitivity of Explanations"), the last two columns of the SCOUTER paper's comparison, which its
+authors took from captum.  Infidelity adds Gaussian noise to the image and compares the change of the model's output with what
+the attribution predicts for that perturbation; max-sensitivity moves the image inside a small box and measures how far the
+explanation moves.  Like `causal_metrics` they cost eval forwards (or calls of the explanation method) over a stream of
+perturbed copies written straight into one reused batch buffer (kernels.noise_images, kernels.uniform_images), the clean image
+riding in row 0 of every batch; the attribution-times-perturbation sums regenerate the noise instead of reading it
+(kernels.perturb_dots), and the output differences, the map distances and the final sums are float64 in one fixed order
+(kernels.output_deltas, kernels.map_distances, kernels.infidelity_finish, kernels.sensitivity_finish), so the chunking does not
+change a bit of the per-sample sums.  No reference program computes either score here: the definitions in the two docstrings
+(and include/scouter_hip.h) are the specification."""
 import collections
 import contextlib
 import functools
@@ -758,3 +770,161 @@ def gradient_maps(attr, min_level=0.0, absolute=False):
         raise ValueError("attr must be a tensor [B, K, C, H, W], got %s"
                          % (tuple(attr.shape) if torch.is_tensor(attr) else type(attr).__name__,))
     return K.heat_maps(K.channel_mean(attr.detach().contiguous(), absolute=absolute), min_level)
+
+
+InfidelityScores = collections.namedtuple("InfidelityScores", "raw normalized beta dots deltas")
+InfidelityScores.__doc__ = """The result of `infidelity`, float64 on the images' device: raw / normalized / beta [B, K] (low
+infidelity means a faithful attribution; `normalized` is the one that means something for maps of arbitrary scale, `beta` the
+scale it chose), and the per-sample dots / deltas [B, K, N] they were summed from."""
+
+SensitivityScores = collections.namedtuple("SensitivityScores", "score terms")
+SensitivityScores.__doc__ = """The result of `sensitivity_max`, float64 on the images' device: score [B, K] (the largest relative
+change of the explanation; low means a stable explanation) and the per-sample terms [B, K, N]."""
+
+
+def _check_samples(n_samples, spread, name, batch):
+    n_samples, spread = int(n_samples), float(spread)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    if not 0.0 <= spread < float("inf"):
+        raise ValueError("%s must be finite and not negative, got %r" % (name, spread))
+    if batch < 2:
+        raise ValueError("batch must be at least 2 (the clean image and one sample), got %d" % batch)
+    return n_samples, spread
+
+
+def infidelity(model, images, attributions, classes=None, n_samples=50, sigma=0.003, batch=50, seed=0, of="log_prob"):
+    """Infidelity (Yeh et al., NeurIPS 2019; captum.metrics.infidelity with additive Gaussian noise) of `attributions` for
+    `images` [B, C, H, W] -> InfidelityScores, float64 on the device.  Per image x, attribution a_k and class c_k, with E = C H W:
+
+    noise        z_j[e], j < N = n_samples: the standard normal of kernels.noise_images for (seed, j, e); the perturbed image
+                 x_j = fma(sigma, z_j, x) is written by that kernel.
+    perturbation I_j[e] = -sigma z_j[e], the exact product (x - x_j up to the one rounding of the fma, not re-derived from x_j).
+    dots         dot[k, j] = sum_e a_k[e] I_j[e] in float64 (kernels.perturb_dots, which regenerates z).
+    deltas       delta[k, j] = F(out[0, c_k]) - F(out[1 + i, c_k]) in float64 from the fp32 eval-mode output of the forward that
+                 carried sample j in row 1 + i and the clean image in row 0 -- both sides of the difference come from the same
+                 kernel instances.  of="log_prob": F is the identity, the quantity `input_gradients` differentiates; of="prob":
+                 F = exp.
+    scores       raw = mean_j (dot - delta)^2, beta = sum_j dot delta / sum_j dot^2 (0 when the denominator is 0),
+                 normalized = mean_j (beta dot - delta)^2 -- captum's normalize=True, the only form that means anything for CAM,
+                 RISE and slot maps, whose scale is arbitrary.  Summed in ascending j (kernels.infidelity_finish).
+
+    attributions: [B, K, C, H, W] fp32, the full form (`input_gradients`, `integrated_gradients`, `smoothgrad`), or maps
+    [B, K, h, w], fp32 or uint8, that count for every channel (a_k[e] = m_k[e mod H W]); maps are resized with
+    kernels.resize_bilinear when (h, w) != (H, W), as in `causal_metrics`.  classes as in `causal_metrics`: None -- attribution k
+    belongs to class k and K must be the number of outputs; a list of K ints; a LongTensor [B] (each image its own class) with
+    K = 1.  `batch` is the number of rows per forward, the clean row included (at least 2).
+
+    Per image: row 0 of one reused buffer is written once; then chunks of up to batch - 1 samples: kernels.noise_images into the
+    rows behind it, the model under torch.no_grad() in eval mode (folded when the model's inference fold is on; the caller's
+    mode is restored), kernels.output_deltas and kernels.perturb_dots.  kernels.infidelity_finish once at the end.  No BatchNorm
+    buffer moves, no `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop; two calls give the
+    same bits, and `dots` has the same bits for every `batch`.  Any module whose eval forward returns [n, n_outputs] will do.
+
+    The defaults n_samples = 50 and sigma = 0.003 are remembered from captum's infidelity tutorial and could not be checked when
+    this was written; they are parameters and nothing else depends on them."""
+    if of not in ("log_prob", "prob"):
+        raise ValueError("of must be 'log_prob' or 'prob', got %r" % (of,))
+    B, C, H, W = _check_images(images).shape
+    x, batch = _check_images_batch(images, batch)
+    N, sigma = _check_samples(n_samples, sigma, "sigma", batch)
+    a = attributions
+    if not torch.is_tensor(a) or a.dim() not in (4, 5) or a.shape[0] != B or a.shape[1] < 1 or a[0, 0].numel() < 1:
+        raise ValueError("attributions must be a tensor [B = %d, K, h, w] or [B, K, %d, %d, %d], got %s"
+                         % (B, C, H, W, tuple(a.shape) if torch.is_tensor(a) else type(a).__name__))
+    full = a.dim() == 5
+    if full and (a.dtype != torch.float32 or tuple(a.shape[2:]) != (C, H, W)):
+        raise ValueError("full attributions must be fp32 [B, K, %d, %d, %d], got %s %s" % (C, H, W, a.dtype, tuple(a.shape)))
+    if not full and a.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("attribution maps must be fp32 or uint8, got %s" % a.dtype)
+    Kc = int(a.shape[1])
+    n = _num_outputs(model, images)
+    per_image, cols = _class_list(classes, B, n)
+    if per_image and Kc != 1:
+        raise ValueError("a tensor of classes (each image its own class) needs K = 1 attribution per image, got K = %d" % Kc)
+    if not per_image and len(cols) != Kc:
+        raise ValueError("%d attributions per image for %d classes%s" % (Kc, len(cols), "" if classes is not None else
+                                                                       " (classes=None: one attribution per model output)"))
+    _check_class_range(cols, n)
+    dev = images.device
+    a = a.detach().to(dev)
+    a = (a.float() if a.dtype != torch.float32 else a).contiguous()
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    dots = torch.empty((B, Kc, N), dtype=torch.float64, device=dev)
+    deltas = torch.empty_like(dots)
+    buf = torch.empty((min(batch, N + 1), C, H, W), dtype=torch.float32, device=dev)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            ab = a[b] if full or tuple(a.shape[2:]) == (H, W) else K.resize_bilinear(a[b], H, W)
+            buf[0].copy_(x[b])
+            for first in range(0, N, batch - 1):
+                m = min(batch - 1, N - first)
+                K.noise_images(x[b], buf[1:1 + m], sigma, seed, first)
+                out = model(buf[:1 + m])
+                out = out if out.dtype == torch.float32 and out.is_contiguous() else out.float().contiguous()
+                K.output_deltas(out, cb, deltas[b], first, of)
+                K.perturb_dots(ab, dots[b], sigma, seed, first, m, channels=C)
+    raw, normalized, beta = K.infidelity_finish(dots, deltas)
+    return InfidelityScores(raw, normalized, beta, dots, deltas)
+
+
+def sensitivity_max(explain, images, n_samples=10, radius=0.02, batch=11, seed=0):
+    """Max-sensitivity (Yeh et al., NeurIPS 2019; captum.metrics.sensitivity_max) of the explanation method `explain` at `images`
+    [B, C, H, W] -> SensitivityScores, float64 on the device.  Per image x:
+
+    perturbation d_j[e] = 2 u - 1, j < N = n_samples, uniform on (-1, 1) and never 0, from the Philox stream beside the noise of
+                 `smoothgrad` / `infidelity` (kernels.uniform_images: a value per (seed, j, e)); x_j = fma(radius, d_j, x), a point
+                 of the box of half-width `radius` around x.
+    explanations explain(images [n, C, H, W] on the device) -> an fp32 device tensor [n, K, ...] with M elements per map; every
+                 call carries the clean image in row 0 and perturbed samples in the rows behind it.
+    terms        term[k, j] = sqrt(sum_m (A_j[k, m] - A_0[k, m])^2 / den_k), den_k = sum_m A_0[k, m]^2, or 1 when that is 0
+                 (captum's choice for a zero explanation); float64, A_0 from the same call as A_j (kernels.map_distances).
+    score        score[k] = max_j term[k, j], NaN if any term is NaN (kernels.sensitivity_finish).
+
+    `explain` is any callable; for the families of this module, with a class list `cs` (a LongTensor of per-image classes would
+    have to follow the batch it is given):
+        grad         lambda im: input_gradients(model, im, classes=cs)
+        cam          lambda im: gradcam(model, im, classes=cs)
+        campp        lambda im: gradcampp(model, im, classes=cs)
+        smoothcampp  lambda im: smooth_gradcampp(model, im, classes=cs)
+        rise         lambda im: rise(model, im, classes=cs, masks=masks)
+        scorecam     lambda im: scorecam(model, im, classes=cs)
+        ig           lambda im: integrated_gradients(model, im, classes=cs)
+        smoothgrad   lambda im: smoothgrad(model, im, classes=cs)
+        slot         lambda im: (model(im), slot_saliency(model)[:, cs].contiguous())[1]        (model in eval mode, no_grad)
+    `batch` is the number of rows per call, the clean row included (at least 2).  Per image: row 0 of one reused buffer is
+    written once, then chunks of up to batch - 1 samples: kernels.uniform_images into the rows behind it, explain, and
+    kernels.map_distances.  A result that is not an fp32 device tensor [n, K, ...], or whose shape behind the first dimension
+    changes between calls, raises ValueError.  Nothing is copied to the host and nothing synchronises here; what `explain` does
+    to the model (its mode, `.grad`) is its own.
+
+    The defaults n_samples = 10 and radius = 0.02 are remembered from captum's sensitivity_max and could not be checked when this
+    was written; they are parameters and nothing else depends on them."""
+    if not callable(explain):
+        raise ValueError("explain must be callable: images [n, C, H, W] -> explanations [n, K, ...]")
+    x, batch = _check_images_batch(images, batch)
+    B, C, H, W = x.shape
+    N, radius = _check_samples(n_samples, radius, "radius", batch)
+    dev = x.device
+    buf = torch.empty((min(batch, N + 1), C, H, W), dtype=torch.float32, device=dev)
+    terms, shape = None, None
+    for b in range(B):
+        buf[0].copy_(x[b])
+        for first in range(0, N, batch - 1):
+            m = min(batch - 1, N - first)
+            K.uniform_images(x[b], buf[1:1 + m], radius, seed, first)
+            maps = explain(buf[:1 + m])
+            if not torch.is_tensor(maps) or maps.dtype != torch.float32 or not maps.is_cuda or maps.dim() < 2 or \
+                    maps.shape[0] != 1 + m or maps.shape[1] < 1 or maps[0, 0].numel() < 1:
+                raise ValueError("explain must return an fp32 device tensor [n = %d, K, ...], got %s"
+                                 % (1 + m, "%s %s" % (maps.dtype, tuple(maps.shape)) if torch.is_tensor(maps)
+                                    else type(maps).__name__))
+            if shape is None:
+                shape = tuple(maps.shape[1:])
+                terms = torch.empty((B, shape[0], N), dtype=torch.float64, device=dev)
+            elif tuple(maps.shape[1:]) != shape:
+                raise ValueError("explain returned maps of shape %s after %s: the shape of an explanation must not change"
+                                 % (tuple(maps.shape[1:]), shape))
+            K.map_distances(maps.detach().contiguous(), terms[b], first)
+    return SensitivityScores(K.sensitivity_finish(terms), terms)
