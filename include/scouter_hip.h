@@ -16,7 +16,8 @@
  *
  * Beyond the training path the library holds what an explanation is drawn and scored with, each in a section of its own below:
  * the input pipeline, Grad-CAM, RISE, insertion / deletion scores, Score-CAM, path and noise batches (Integrated Gradients,
- * SmoothGrad), Grad-CAM++ and the infidelity / max-sensitivity scores.  The reference computes none of the scores itself; where
+ * SmoothGrad), Grad-CAM++, the infidelity / max-sensitivity scores and the mask side of Extremal Perturbation.  The reference
+ * computes none of the scores itself; where
  * no program exists to copy, the section's comment is the specification.
  */
 #ifndef SCOUTER_HIP_H
@@ -502,6 +503,52 @@ int scouter_map_distances_f64(const float* maps, double* terms, int first, int n
 /* score fp64 [R], score[r] = max_j terms[r][j] over terms fp64 [R][N], one thread per row in ascending j; a NaN term makes the
  * score NaN. */
 int scouter_sensitivity_finish_f64(const double* terms, double* score, long R, int N, void* stream);
+
+/* ---- Extremal perturbation (Fong, Patrick, Vedaldi, ICCV 2019; torchray.attribution.extremal_perturbation, which the
+ * reference's torchcam_vis.py runs after RISE; csrc/extremal.hip, tools/attribution.py extremal_perturbation): the mask side of
+ * one step of the optimisation.  No reference program runs here: the definitions below are the specification.  n coarse masks
+ * pmask fp32 [n][hm][wm] in [0, 1] on a grid of `step` pixels, hm = ceil(H / step), wm = ceil(W / step); full masks [n][H][W];
+ * one image's blur pyramid P fp32 [L][C][H][W] (level L - 1 the image, level 0 the most blurred).  One launch each, no atomics,
+ * every cross-thread sum in one fixed order: bit-identical run to run, and a mask's values do not depend on n.  A null or
+ * misaligned (4 bytes) pointer, a size below 1, L < 2, a variant or flag outside {0, 1} is SC_ERR_ARG; sizes past 32-bit
+ * offsets, n above 65535 or a kernel table above 16384 floats are SC_ERR_UNSUPPORTED; nothing is launched after an error.
+ *
+ * SMOOTH-MAX UPSAMPLING.  r = 1 + ceil(sigma / step), D = 2 r + 1, beta = 20.  Cell (i, j) has its centre at pixel coordinates
+ * ((i + 0.5) step - 0.5, (j + 0.5) step - 0.5).  Pixel u = (y, x) sees the D * D cells c = (y / step + a, x / step + b), a, b in
+ * [-r, r]: v_c = k_c * p_c with k_c = exp(-2 * max(|u - centre_c| / sigma - 0.5, 0)^2), v_c = 0 for a cell outside the grid;
+ * out[u] = sum_c v_c * e_c / sum_c e_c, e_c = exp(beta * (v_c - vmax)), vmax = max_c v_c, the window in (a, b) order.  k depends on
+ * (y % step, x % step, a, b) alone: a table of step^2 * D^2 floats per workgroup in LDS.  stats (may be NULL) fp32 [n][H * W][2]
+ * receives (vmax, sum_c e_c) per pixel, what scouter_extremal_step_f32 reads. */
+int scouter_extremal_mask_f32(const float* pmask, float* out, float* stats, int n, int H, int W, int step, float sigma,
+                              void* stream);
+/* THE BLEND.  m' = mask (variant 0, preserve) or 1 - mask (variant 1, delete), t = m' * (L - 1), k = min(floor(t), L - 2),
+ * w = t - k: out[j][c][y][x] = fma(w, P[k + 1][c][q], (1 - w) * P[k][c][q]) with q = (y, x), or (y, W - 1 - x) when flip is set -- the
+ * mirrored image.  Exact at the ends: w = 0 gives P[k], m' = 1 gives the image.  At an interior knot the right-hand piece is
+ * used.  16-byte accesses when W is a multiple of 4 and every pointer is 16-byte aligned, one element otherwise: the same
+ * bits.  out may be a leading slice of a longer buffer. */
+int scouter_extremal_blend_f32(const float* pyramid, const float* mask, float* out, int n, int L, int C, int H, int W, int variant,
+                               int flip, void* stream);
+/* THE SEED of the backward and the reward: p_j = exp(logp[j][cols[j]]) for logp fp32 [n][n_out] and cols i32 [n] in [0, n_out)
+ * (checked by the caller; clamped here); seed[j][cols[j]] = -p_j (variant 0: the loss is -p) or +p_j (variant 1), every other
+ * entry of seed fp32 [n][n_out] is written 0; rewards fp32 [n_iters][n]: rewards[it][j] = p_j, 0 <= it < n_iters. */
+int scouter_extremal_seed_f32(const float* logp, const int* cols, float* seed, float* rewards, int n, int n_out, int n_iters,
+                              int it, int variant, void* stream);
+/* THE MASK GRADIENT.  dmask[j][q] = fma(+-(L - 1), sum_c dx[j][c][q'] * (P[k + 1][c][q] - P[k][c][q]), c2 * (mask[j][q] - tau)), + for
+ * variant 0 and - for variant 1, the sum one fma per channel in ascending c, k from mask[j][q] by the expression of the blend
+ * (the same bits), q' = q mirrored in x when flip is set (dx fp32 [n][C][H][W] is the gradient of the loss at the image the blend
+ * wrote), tau = 1 where ranks[j][q] < targets[j] and 0 elsewhere (ranks i32 [n][H * W] of scouter_saliency_ranks_i32 on the
+ * mask, targets i32 [n] the number of pixels of each mask's area), c2 = (float)(2 * lam / (H * W)) formed in fp64: the gradient of
+ * lam * mean_q (mask - tau)^2.  lam >= 0 and finite. */
+int scouter_extremal_mask_grad_f32(const float* pyramid, const float* mask, const float* dx, const int* ranks, const int* targets,
+                                   float* dmask, float lam, int n, int L, int C, int H, int W, int variant, int flip, void* stream);
+/* THE STEP, in place.  Per cell c of mask j: g = sum_u dmask[j][u] * k_uc * w_uc * (1 + beta * (v_uc - mask[j][u])) over the at most
+ * (D * step)^2 pixels u that see the cell, v_uc = k_uc * pmask[j][c], w_uc = exp(beta * (v_uc - vmax_u)) / den_u with (vmax_u, den_u)
+ * from stats as scouter_extremal_mask_f32 wrote them for THIS pmask (g is then d sum_u dmask * out / d pmask[j][c]); mom = g
+ * (first) or fma(momentum, mom, (1 - momentum) * g) -- SGD with dampening = momentum --; pmask = clamp(fma(-lr, mom, pmask), 0, 1).
+ * One wave per cell: a lane adds the pixels lane, lane + 64, ... of the cell's window (row-major) by one fma each, then a
+ * butterfly.  A cell's terms read its own pmask value and per-pixel arrays nothing here writes: no race. */
+int scouter_extremal_step_f32(float* pmask, float* mom, const float* mask, const float* dmask, const float* stats, int n, int H,
+                              int W, int step, float sigma, float lr, float momentum, int first, void* stream);
 
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats

@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
+// pathgrad.hip, fidelity.hip, extremal.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
 // scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
 // same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
 #pragma once
@@ -295,3 +295,45 @@ __device__ __forceinline__ void at_store_acc(float* __restrict__ acc, long plane
     for (int k = 0; k < KT; ++k)
         if (k < kt) acc[(long)(k0 + k) * plane + p] = a[k];
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Extremal perturbation (extremal.hip): what its kernels must agree on bit for bit.  The smooth-max upsampler's window and
+// kernel values -- extremal_mask forms them, extremal_step differentiates them -- and the knot of the blur pyramid, which
+// extremal_blend uses and extremal_mask_grad recomputes.
+constexpr float EX_BETA = 20.f;                 // the sharpness of the smooth max
+
+// the window's radius in cells: a pixel sees the (2 r + 1)^2 cells around its own
+static inline int ex_radius(int step, float sigma) { return 1 + (int)ceil((double)sigma / (double)step); }
+
+// k(|u - centre| / sigma), k(z) = exp(-2 max(z - 0.5, 0)^2), for the pixel at (ym, xm) inside its own cell and the cell (a, b)
+// cells away from it: u - centre = (ym - a step - (step - 1) / 2, xm - b step - (step - 1) / 2), half-integers that are exact
+__device__ __forceinline__ float ex_kernel_value(int ym, int xm, int a, int b, int step, float sigma) {
+    const float half = 0.5f * (float)(step - 1);
+    const float dy = (float)(ym - a * step) - half, dx = (float)(xm - b * step) - half;
+    const float d = fmaxf(sqrtf(fmaf(dy, dy, dx * dx)) / sigma - 0.5f, 0.f);
+    return expf(-2.f * d * d);
+}
+
+// tab[((ym step + xm) D + a + r) D + b + r] = ex_kernel_value(ym, xm, a, b), D = 2 r + 1: step^2 D^2 floats, once per workgroup
+// (the caller's barrier follows)
+template <int THREADS>
+__device__ __forceinline__ void ex_fill_table(float* __restrict__ tab, int step, int r, float sigma) {
+    const int D = 2 * r + 1, DD = D * D, T = step * step * DD;
+    for (int t = threadIdx.x; t < T; t += THREADS) {
+        const int pm = t / DD, ab = t - pm * DD, ia = ab / D, ib = ab - ia * D;
+        tab[t] = ex_kernel_value(pm / step, pm % step, ia - r, ib - r, step, sigma);
+    }
+}
+
+// the piece of the blur pyramid a mask value m selects: m' = m (variant 0, preserve) or 1 - m (variant 1, delete),
+// t = m' (L - 1) clamped to [0, L - 1] (a NaN goes to 0, so no value moves an address), k = min(floor(t), L - 2), w = t - k:
+// the right-hand piece at an interior knot, the last piece with w = 1 at m' = 1
+__device__ __forceinline__ void ex_knot(float m, int variant, int L, int& k, float& w) {
+    const float mp = variant ? 1.f - m : m;
+    const float t = fminf(fmaxf(mp * (float)(L - 1), 0.f), (float)(L - 1));
+    k = min((int)t, L - 2);
+    w = t - (float)k;
+}
+
+// (1 - w) p0 + w p1, exact at both ends: p0 at w = 0 and p1 at w = 1
+__device__ __forceinline__ float ex_mix(float p0, float p1, float w) { return fmaf(w, p1, (1.f - w) * p0); }

@@ -2251,3 +2251,135 @@ def sensitivity_finish(terms, out=None):
         raise RuntimeError("sensitivity_finish: out must be %s, got shape %s" % (lead, tuple(out.shape)))
     _native.check(_native.lib().scouter_sensitivity_finish_f64(_p(terms), _p(out), R, N, _stream()), "sensitivity_finish")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# extremal perturbation (csrc/extremal.hip; tools/attribution.py extremal_perturbation / extremal_maps)
+# ---------------------------------------------------------------------------------------------------------------
+EXTREMAL_PRESERVE, EXTREMAL_DELETE = 0, 1                       # (include/scouter_hip.h: the variant of the extremal kernels)
+_EXTREMAL_VARIANTS = {"preserve": EXTREMAL_PRESERVE, "delete": EXTREMAL_DELETE}
+EXTREMAL_BETA = 20.0                                            # (csrc/attr_common.h EX_BETA: the sharpness of the smooth max)
+
+
+def extremal_grid(H, W, step, sigma):
+    """(hm, wm, r) of the smooth-max upsampler: the coarse grid ceil(H / step) x ceil(W / step) and the window's radius in cells
+    r = 1 + ceil(sigma / step), sigma rounded to fp32 as the library receives it (csrc/attr_common.h ex_radius)."""
+    H, W, step = int(H), int(W), int(step)
+    if H < 1 or W < 1 or step < 1 or not float(sigma) > 0.0:
+        raise ValueError("extremal_grid: H = %d, W = %d, step = %d, sigma = %r (sizes at least 1, sigma positive)" % (H, W, step, sigma))
+    sigma32 = float(torch.tensor(float(sigma), dtype=F32))
+    return -(-H // step), -(-W // step), 1 + int(-(-sigma32 // step))
+
+
+def _extremal_variant(what, variant):
+    if variant not in _EXTREMAL_VARIANTS:
+        raise ValueError("%s: variant must be 'preserve' or 'delete', got %r" % (what, variant))
+    return _EXTREMAL_VARIANTS[variant]
+
+
+def _extremal_masks_chk(what, pmask, mask, step, sigma, stats):
+    """pmask fp32 [n, hm, wm] and mask fp32 [n, H, W] (and stats fp32 [n, H, W, 2] when given) of one grid -> (n, H, W)"""
+    _chk(pmask, what + ": pmask"); _chk(mask, what + ": mask"); _chk(stats, what + ": stats")
+    if mask.dim() != 3 or pmask.dim() != 3 or mask.shape[0] != pmask.shape[0] or mask.shape[0] < 1 or mask[0].numel() < 1:
+        raise RuntimeError("%s: pmask must be [n, hm, wm] and the mask [n, H, W] (got %s and %s)"
+                           % (what, tuple(pmask.shape), tuple(mask.shape)))
+    n, H, W = mask.shape
+    hm, wm, _ = extremal_grid(H, W, step, sigma)
+    if tuple(pmask.shape) != (n, hm, wm):
+        raise RuntimeError("%s: pmask must be [n = %d, %d, %d] for %d x %d pixels at step %d, got shape %s"
+                           % (what, n, hm, wm, H, W, int(step), tuple(pmask.shape)))
+    if stats is not None and tuple(stats.shape) != (n, H, W, 2):
+        raise RuntimeError("%s: stats must be [%d, %d, %d, 2], got shape %s" % (what, n, H, W, tuple(stats.shape)))
+    return n, H, W
+
+
+def extremal_mask(pmask, out, step, sigma, stats=None):
+    """out[j] = the smooth-max upsampling of pmask[j]: fp32 pmask [n, hm, wm] in [0, 1] on a grid of `step` pixels -> fp32 out
+    [n, H, W], hm = ceil(H / step), wm = ceil(W / step).  Cell (i, j) sits at pixel ((i + 0.5) step - 0.5, (j + 0.5) step - 0.5); pixel
+    u sees the (2 r + 1)^2 cells around its own, r = 1 + ceil(sigma / step); v_c = k(|u - centre_c| / sigma) p_c with
+    k(z) = exp(-2 max(z - 0.5, 0)^2), 0 for a cell outside the grid; out[u] = sum_c v_c softmax_c(20 v) -- inside [0, 1] by
+    construction.  stats: None, or fp32 [n, H, W, 2] that receives each pixel's softmax statistics (the window's maximum and the
+    sum of exp(20 (v - max))) for `extremal_step`.  One launch; the k table lives in LDS."""
+    n, H, W = _extremal_masks_chk("extremal_mask", pmask, out, step, sigma, stats)
+    _native.check(_native.lib().scouter_extremal_mask_f32(_p(pmask), _p(out), _p(stats), n, H, W, int(step), float(sigma),
+                                                          _stream()), "extremal_mask")
+    return out
+
+
+def _extremal_pyramid_chk(what, pyramid, mask, batch, name):
+    """pyramid fp32 [L, C, H, W], mask fp32 [n, H, W] and a batch fp32 [n, C, H, W] -> (n, L, C, H, W)"""
+    _chk(pyramid, what + ": pyramid"); _chk(mask, what + ": mask"); _chk(batch, "%s: %s" % (what, name))
+    if pyramid.dim() != 4 or mask.dim() != 3 or tuple(mask.shape[1:]) != tuple(pyramid.shape[2:]) or mask.shape[0] < 1:
+        raise RuntimeError("%s: pyramid must be [L, C, H, W] and mask [n, H, W] (got %s and %s)"
+                           % (what, tuple(pyramid.shape), tuple(mask.shape)))
+    L, C, H, W = pyramid.shape
+    n = int(mask.shape[0])
+    if tuple(batch.shape) != (n, C, H, W):
+        raise RuntimeError("%s: %s must be [%d, %d, %d, %d], got shape %s" % (what, name, n, C, H, W, tuple(batch.shape)))
+    return n, int(L), int(C), int(H), int(W)
+
+
+def extremal_blend(pyramid, mask, out, variant="preserve", flip=False):
+    """out[j, c] = the blur pyramid read at mask[j]: fp32 pyramid [L, C, H, W] (level L - 1 the image, level 0 the most blurred),
+    fp32 mask [n, H, W], fp32 out [n, C, H, W] (a dense leading slice of a longer buffer is fine).  m' = mask ("preserve") or
+    1 - mask ("delete"), t = m' (L - 1), k = min(floor(t), L - 2), w = t - k, out = (1 - w) P[k] + w P[k + 1]: exactly the image at
+    m' = 1 and exactly level 0 at m' = 0.  flip: the horizontally mirrored result.  One launch."""
+    v = _extremal_variant("extremal_blend", variant)
+    n, L, C, H, W = _extremal_pyramid_chk("extremal_blend", pyramid, mask, out, "out")
+    _native.check(_native.lib().scouter_extremal_blend_f32(_p(pyramid), _p(mask), _p(out), n, L, C, H, W, v, 1 if flip else 0,
+                                                           _stream()), "extremal_blend")
+    return out
+
+
+def extremal_seed(logp, cols, seed, rewards, it, variant="preserve"):
+    """seed[j, cols[j]] = -exp(logp[j, cols[j]]) ("preserve": the loss is minus the probability) or +exp(.) ("delete"), every other
+    entry of seed 0, and rewards[it, j] = exp(logp[j, cols[j]]): fp32 logp / seed [n, n_out], cols int32 [n] on the device (the
+    caller keeps them inside [0, n_out)), fp32 rewards [n_iters, n].  One launch; nothing is read on the host."""
+    v = _extremal_variant("extremal_seed", variant)
+    _chk(logp, "extremal_seed: logp"); _chk(cols, "extremal_seed: cols", torch.int32); _chk(seed, "extremal_seed: seed")
+    _chk(rewards, "extremal_seed: rewards")
+    if logp.dim() != 2 or seed.shape != logp.shape or tuple(cols.shape) != (logp.shape[0],) or rewards.dim() != 2 or \
+            rewards.shape[1] != logp.shape[0]:
+        raise RuntimeError("extremal_seed: logp and seed must be [n, n_out], cols [n] and rewards [n_iters, n] (got %s, %s, %s and "
+                           "%s)" % (tuple(logp.shape), tuple(seed.shape), tuple(cols.shape), tuple(rewards.shape)))
+    _native.check(_native.lib().scouter_extremal_seed_f32(_p(logp), _p(cols), _p(seed), _p(rewards), int(logp.shape[0]),
+                                                          int(logp.shape[1]), int(rewards.shape[0]), int(it), v, _stream()),
+                  "extremal_seed")
+    return seed
+
+
+def extremal_mask_grad(pyramid, mask, dx, ranks, targets, dmask, lam, variant="preserve", flip=False):
+    """dmask[j, q] = +-(L - 1) sum_c dx[j, c, q'] (P[k + 1] - P[k])[c, q] + (2 lam / (H W)) (mask[j, q] - tau[j, q]): the gradient of
+    loss_j + lam mean_q (mask - tau)^2 with respect to mask[j], for dx fp32 [n, C, H, W] = d loss / d (the image `extremal_blend`
+    wrote with the same variant and flip).  + for "preserve", - for "delete"; k from mask[j, q] by the blend's own expression; q'
+    is q mirrored when flip is set; tau = 1 where ranks[j, q] < targets[j], ranks int32 [n, H W] (or [n, H, W]) from
+    `saliency_ranks(mask)`, targets int32 [n] on the device.  lam >= 0.  One launch."""
+    v = _extremal_variant("extremal_mask_grad", variant)
+    n, L, C, H, W = _extremal_pyramid_chk("extremal_mask_grad", pyramid, mask, dx, "dx")
+    _chk(ranks, "extremal_mask_grad: ranks", torch.int32); _chk(targets, "extremal_mask_grad: targets", torch.int32)
+    _chk(dmask, "extremal_mask_grad: dmask")
+    if ranks.dim() not in (2, 3) or ranks.shape[0] != n or ranks[0].numel() != H * W or tuple(targets.shape) != (n,) or \
+            dmask.shape != mask.shape:
+        raise RuntimeError("extremal_mask_grad: ranks must be int32 [%d, %d], targets int32 [%d] and dmask %s (got %s, %s and %s)"
+                           % (n, H * W, n, tuple(mask.shape), tuple(ranks.shape), tuple(targets.shape), tuple(dmask.shape)))
+    _native.check(_native.lib().scouter_extremal_mask_grad_f32(_p(pyramid), _p(mask), _p(dx), _p(ranks), _p(targets), _p(dmask),
+                                                               float(lam), n, L, C, H, W, v, 1 if flip else 0, _stream()),
+                  "extremal_mask_grad")
+    return dmask
+
+
+def extremal_step(pmask, mom, mask, dmask, stats, step, sigma, lr, momentum, first):
+    """One SGD step on pmask fp32 [n, hm, wm], IN PLACE: g[c] = sum_u dmask[u] d mask[u] / d pmask[c] over the pixels that see
+    cell c (the derivative of `extremal_mask`: k w (1 + 20 (v - mask[u])), the softmax weight w rebuilt from `stats`), then
+    mom = g (first) or momentum * mom + (1 - momentum) * g, pmask = clamp(pmask - lr * mom, 0, 1).  mask, dmask fp32 [n, H, W] and
+    stats fp32 [n, H, W, 2] as `extremal_mask(pmask, mask, step, sigma, stats)` left them for THIS pmask; mom fp32 like pmask.  One
+    launch, one wave per cell, a fixed summation order."""
+    n, H, W = _extremal_masks_chk("extremal_step", pmask, mask, step, sigma, stats)
+    _chk(mom, "extremal_step: mom"); _chk(dmask, "extremal_step: dmask")
+    if stats is None or mom.shape != pmask.shape or dmask.shape != mask.shape:
+        raise RuntimeError("extremal_step: stats must be given, mom must be like pmask and dmask like mask (got %s and %s)"
+                           % (tuple(mom.shape), tuple(dmask.shape)))
+    _native.check(_native.lib().scouter_extremal_step_f32(_p(pmask), _p(mom), _p(mask), _p(dmask), _p(stats), n, H, W, int(step),
+                                                          float(sigma), float(lr), float(momentum), 1 if first else 0, _stream()),
+                  "extremal_step")
+    return pmask

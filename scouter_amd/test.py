@@ -19,8 +19,11 @@ SmoothGrad maps `<out>/smoothgrad_{c}.png` (tools/attribution.py smoothgrad: --s
 `<out>/campp_{c}.png` (tools/attribution.py gradcampp_maps: one backbone forward, floored at --grad_min_level, BatchNorm-folded
 under --eval_fold; torchcam's GradCAMpp of the reference's torchcam_vis.py); `--smoothcampp true` the per-class Smooth Grad-CAM++
 heat maps `<out>/smoothcampp_{c}.png` (tools/attribution.py smooth_gradcampp: --smoothcampp_samples noisy copies at
---smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp), the deletion and insertion scores of
+--smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--extremal true` the per-class Extremal
+Perturbation maps `<out>/extremal_{c}.png` (tools/attribution.py extremal_maps: --extremal_iters SGD steps on a smooth mask of
+--extremal_area of the image, variant --extremal_variant, the classes in groups of --extremal_batch, floored at --grad_min_level;
+torchray's extremal_perturbation of the reference's torchcam_vis.py); `--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
 the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
@@ -37,6 +40,7 @@ jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNG
         [--scorecam true --scorecam_batch 250] [--ig true --ig_steps 50 --ig_batch 50] \
         [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
         [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
+        [--extremal true --extremal_area 0.1 --extremal_iters 800 --extremal_variant preserve --extremal_batch 50] \
         [--causal true --causal_step 224] \
         [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
         [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
@@ -153,6 +157,20 @@ def run_smoothcampp(args, model, image, out_dir):
                      functools.partial(smooth_gradcampp_maps, model, **_smoothcampp_kwargs(args)))
 
 
+def _extremal_kwargs(args):
+    return dict(areas=(float(getattr(args, "extremal_area", 0.1)),), n_iters=int(getattr(args, "extremal_iters", 800)),
+                variant=str(getattr(args, "extremal_variant", "preserve")), batch=int(getattr(args, "extremal_batch", 50)))
+
+
+def run_extremal(args, model, image, out_dir):
+    """--extremal true: the Extremal Perturbation map of every class for the one image (torchray's extremal_perturbation of the
+    reference's torchcam_vis.py: --extremal_iters steps on a mask of --extremal_area of the image, variant --extremal_variant, the
+    classes in groups of --extremal_batch) -> `<out>/extremal_{c}.png`, uint8 maps at the input resolution; returns them
+    [C, H, W]."""
+    from .tools.attribution import extremal_maps
+    return _run_maps(args, model, image, out_dir, "extremal", functools.partial(extremal_maps, model, **_extremal_kwargs(args)))
+
+
 def _ig(args, model, x, classes=None):
     from .tools.attribution import integrated_gradients
     return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
@@ -189,9 +207,10 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
     """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
     given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
     rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
-    smoothcampp: smooth_gradcampp).  full: grad, ig and smoothgrad keep their attribution [n, 1, C, H, W] instead."""
+    smoothcampp: smooth_gradcampp; extremal: extremal_saliency).  full: grad, ig and smoothgrad keep their attribution
+    [n, 1, C, H, W] instead."""
     from . import kernels as K
-    from .tools.attribution import gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
+    from .tools.attribution import extremal_saliency, gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
     if family == "slot":
         return slot_map
     if family == "grad":
@@ -211,6 +230,8 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
         return gradcampp(model, x, classes=[pred])
     if family == "smoothcampp":
         return smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
+    if family == "extremal":
+        return extremal_saliency(model, x, classes=[pred], **_extremal_kwargs(args))
     return rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)),
                 batch=int(getattr(args, "rise_batch", 250)))
 
@@ -219,8 +240,8 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
-    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp), one printed line each; returns
-    {family: (deletion, insertion)}."""
+    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency), one printed
+    line each; returns {family: (deletion, insertion)}."""
     from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
     step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
@@ -310,6 +331,13 @@ def get_test_parser():
     parser.add_argument("--smoothcampp_samples", default=4, type=int, help="noisy copies per class of --smoothcampp")
     parser.add_argument("--smoothcampp_sigma", default=0.3, type=float, help="standard deviation of the noise of --smoothcampp")
     parser.add_argument("--smoothcampp_batch", default=4, type=int, help="noisy copies per feature pass of --smoothcampp")
+    parser.add_argument("--extremal", default=False, type=_flag,
+                        help="true: write the Extremal Perturbation map of every class as extremal_{c}.png into --vis_dir")
+    parser.add_argument("--extremal_area", default=0.1, type=float, help="fraction of the image the mask of --extremal covers")
+    parser.add_argument("--extremal_iters", default=800, type=int, help="SGD steps of --extremal")
+    parser.add_argument("--extremal_variant", default="preserve", choices=("preserve", "delete"),
+                        help="--extremal keeps (preserve) or removes (delete) the evidence under the mask")
+    parser.add_argument("--extremal_batch", default=50, type=int, help="masks per forward and backward of --extremal")
     parser.add_argument("--infidelity", default=False, type=_flag,
                         help="true: print the infidelity of the predicted class's explanation of every family drawn")
     parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
@@ -368,9 +396,11 @@ def main():
         run_campp(args, model, image, args.vis_dir)
     if args.smoothcampp:
         run_smoothcampp(args, model, image, args.vis_dir)
+    if args.extremal:
+        run_extremal(args, model, image, args.vis_dir)
     families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
                                 ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
-                                ("campp", args.campp), ("smoothcampp", args.smoothcampp)) if on]
+                                ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal)) if on]
     if args.causal:
         run_causal(args, model, image, pred, families, slot_map)
     if args.infidelity:

@@ -64,7 +64,19 @@ riding in row 0 of every batch; the attribution-times-perturbation sums regenera
 (kernels.perturb_dots), and the output differences, the map distances and the final sums are float64 in one fixed order
 (kernels.output_deltas, kernels.map_distances, kernels.infidelity_finish, kernels.sensitivity_finish), so the chunking does not
 change a bit of the per-sample sums.  No reference program computes either score here: the definitions in the two docstrings
-(and include/scouter_hip.h) are the specification."""
+(and include/scouter_hip.h) are the specification.
+
+An optimised mask (`extremal_perturbation`, `extremal_saliency`, `extremal_maps`, `perturbation_pyramid`, `pyramid_pass_plan`,
+`extremal_schedule`): Extremal Perturbation (Fong, Patrick, Vedaldi, ICCV 2019), what the reference's torchcam_vis.py runs with
+torchray.attribution.extremal_perturbation right after RISE.  Per image, class and area a coarse mask is upsampled by a smooth
+maximum, reads a blur pyramid of the image, and is moved by hundreds of SGD steps towards the mask of that area which keeps (or
+deletes) the most class probability.  It is the one method here whose cost is not model passes alone: every iteration pushes
+the batch of masks through the upsampler, the pyramid blend, an eval forward and input backward, a ranked area penalty, the
+upsampler's backward and the update.  The mask side is five HIP kernels and the ranking of `causal_metrics`
+(kernels.extremal_mask, extremal_blend, extremal_seed, saliency_ranks, extremal_mask_grad, extremal_step); the seed of the
+backward is written on the device from the forward's own output, so nothing comes to the host for the whole run.  No reference
+program runs here (torchray is not a dependency): the docstring of `extremal_perturbation` is the specification, and it lists
+what departs from TorchRay."""
 import collections
 import contextlib
 import functools
@@ -928,3 +940,209 @@ def sensitivity_max(explain, images, n_samples=10, radius=0.02, batch=11, seed=0
                                  % (tuple(maps.shape[1:]), shape))
             K.map_distances(maps.detach().contiguous(), terms[b], first)
     return SensitivityScores(K.sensitivity_finish(terms), terms)
+
+
+ExtremalMasks = collections.namedtuple("ExtremalMasks", "masks pmasks rewards")
+ExtremalMasks.__doc__ = """The result of `extremal_perturbation`, fp32 on the images' device: masks [B, K, A, H, W] in [0, 1] (the
+smooth-max upsampling of the final coarse masks), pmasks [B, K, A, hm, wm] (the coarse masks themselves) and rewards
+[B, K, A, n_iters] (the class probability of the perturbed image at every iteration, before that iteration's update)."""
+
+
+def pyramid_pass_plan(levels=8, max_blur=20.0):
+    """The blur passes of `perturbation_pyramid` (host arithmetic only): a list of levels - 1 entries, entry l for level l, each
+    (passes, sd, klen).  Level l has sigma_l = max_blur (1 - l / (levels - 1)) and comes from level l + 1 by the variance
+    increment sigma_l^2 - sigma_{l+1}^2, split into passes = ceil(increment / 25) equal Gaussian passes of standard deviation
+    sd = sqrt(increment / passes) <= 5 with klen = 2 ceil(3 sd) + 1 <= 31 taps -- 19 passes at the defaults."""
+    levels, max_blur = int(levels), float(max_blur)
+    if levels < 2:
+        raise ValueError("levels must be at least 2, got %d" % levels)
+    if not 0.0 < max_blur < float("inf"):
+        raise ValueError("max_blur must be positive and finite, got %r" % (max_blur,))
+    plan = []
+    for l in range(levels - 1):
+        hi, lo = max_blur * (1.0 - l / (levels - 1.0)), max_blur * (1.0 - (l + 1) / (levels - 1.0))
+        inc = hi * hi - lo * lo
+        passes = max(1, int(np.ceil(inc / 25.0)))
+        sd = float(np.sqrt(inc / passes))
+        plan.append((passes, sd, 2 * int(np.ceil(3.0 * sd)) + 1))
+    return plan
+
+
+def perturbation_pyramid(image, levels=8, max_blur=20.0):
+    """The blur pyramid of Extremal Perturbation for ONE `image` [C, H, W] -> fp32 [levels, C, H, W] on its device: level
+    levels - 1 is the image and level l the image blurred to sigma_l = max_blur (1 - l / (levels - 1)), so level 0 carries
+    max_blur.  Built with kernels.separable_filter alone, downwards: level l is level l + 1 after the passes of
+    `pyramid_pass_plan` (variances add), each with the taps of `gaussian_taps(klen, sd)`.  Zeros outside the image, as in
+    `causal_metrics`: this DEPARTS from TorchRay, whose Gaussian blur pads by replication, so the borders of the blurred levels
+    are darker here."""
+    if not torch.is_tensor(image) or image.dim() != 3:
+        raise ValueError("image must be a tensor [C, H, W], got %s"
+                         % (tuple(image.shape) if torch.is_tensor(image) else type(image).__name__,))
+    plan = pyramid_pass_plan(levels, max_blur)
+    x = image.detach().contiguous()
+    x = x.float() if x.dtype != torch.float32 else x
+    L = len(plan) + 1
+    pyr = torch.empty((L,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    pyr[L - 1].copy_(x)
+    tmp = torch.empty_like(x) if any(p[0] > 1 for p in plan) else None
+    for l in range(L - 2, -1, -1):
+        passes, sd, klen = plan[l]
+        taps = gaussian_taps(klen, sd).to(x.device)
+        src = pyr[l + 1]
+        for i in range(passes):
+            dst = pyr[l] if (passes - 1 - i) % 2 == 0 else tmp            # (the last pass lands in the level)
+            K.separable_filter(src, taps, out=dst)
+            src = dst
+    return pyr
+
+
+def extremal_schedule(n_iters, area_weight=300.0, area_growth=1.0035):
+    """lambda_it = area_weight * area_growth^it for it < n_iters, formed in float64 on the host (a list of floats); each is handed
+    to kernels.extremal_mask_grad as an fp32 scalar."""
+    return [float(area_weight) * float(area_growth) ** it for it in range(int(n_iters))]
+
+
+def _extremal_area_pixels(areas, HW):
+    """the areas of `extremal_perturbation` as pixel counts A = floor(a H W + 0.5), each inside [1, H W - 1]"""
+    try:
+        areas = [float(a) for a in areas]
+    except TypeError:
+        raise ValueError("areas must be a sequence of fractions of the image, got %r" % (areas,))
+    if not areas:
+        raise ValueError("areas must name at least one area")
+    counts = []
+    for a in areas:
+        A = int(np.floor(a * HW + 0.5)) if a == a and abs(a) < float("inf") else -1
+        if not 1 <= A <= HW - 1:
+            raise ValueError("area %r of %d pixels is %d pixels: an area must cover between 1 and H W - 1 pixels" % (a, HW, A))
+        counts.append(A)
+    return counts
+
+
+def extremal_perturbation(model, images, classes=None, areas=(0.1,), n_iters=800, step=7, sigma=21.0, levels=8, max_blur=20.0,
+                          variant="preserve", lr=0.01, momentum=0.9, area_weight=300.0, area_growth=1.0035, jitter=True, batch=50,
+                          init=None):
+    """Extremal Perturbation (Fong, Patrick, Vedaldi, ICCV 2019; torchray.attribution.extremal_perturbation, which the reference's
+    torchcam_vis.py runs after RISE) of `images` [B, C, H, W] -> ExtremalMasks: for every image, class c_k and area a, the smooth
+    mask of area a H W whose perturbed image keeps ("preserve") or loses ("delete") the most probability of class c_k, found by
+    n_iters steps of SGD.  No reference program runs here; this docstring (and include/scouter_hip.h) is the specification.
+
+    mask         a coarse mask p [hm, wm] in [0, 1], hm = ceil(H / step), wm = ceil(W / step), starts at 0.5 (or `init`) and is
+                 upsampled by kernels.extremal_mask: cell (i, j) sits at pixel ((i + 0.5) step - 0.5, (j + 0.5) step - 0.5), a pixel
+                 sees the (2 r + 1)^2 cells around its own, r = 1 + ceil(sigma / step), v_c = k(|u - centre_c| / sigma) p_c with
+                 k(z) = exp(-2 max(z - 0.5, 0)^2) (0 for a cell outside the grid) and m(u) = sum_c v_c softmax_c(20 v).
+    perturbation `perturbation_pyramid(image, levels, max_blur)` P [L, C, H, W]; m' = m ("preserve") or 1 - m ("delete"),
+                 t = m' (L - 1), k = min(floor(t), L - 2), w = t - k, x~ = (1 - w) P[k] + w P[k + 1] (kernels.extremal_blend).  With
+                 `jitter`, odd iterations hand the model the horizontally mirrored x~ and mirror the gradient back.
+    objective    p = exp(log_prob[c_k]) of the eval-mode output for x~ (recorded in `rewards`); loss = -p (preserve) or +p
+                 (delete) + lambda_it mean_q (m(q) - tau(q))^2, tau = 1 for the A = floor(a H W + 0.5) pixels
+                 kernels.saliency_ranks(m) ranks first (most salient first, ties by ascending index) and 0 for the rest -- the
+                 value of TorchRay's |sort(m) - template|^2 whatever the tie order; lambda_it = `extremal_schedule`.
+    update       g = d loss / d p (kernels.extremal_mask_grad, kernels.extremal_step); buf = g at the first iteration, then
+                 momentum buf + (1 - momentum) g (SGD with dampening = momentum); p = clamp(p - lr buf, 0, 1).
+
+    classes as in `gradcam`: None (every output), a list of ints (K = len), or a LongTensor [B] (each image its own class,
+    K = 1).  areas: fractions of the image, each with 1 <= A <= H W - 1.  init: None, fp32 [hm, wm] (every mask) or
+    [B, K, A, hm, wm].  Per image the K A masks form one batch, split into groups of at most `batch` rows; masks are independent,
+    so the grouping does not change a bit.  Every group runs the whole loop, per iteration: kernels.extremal_mask,
+    kernels.extremal_blend into one reused buffer, which becomes the leaf of an eval-mode forward and of one backward whose seed
+    kernels.extremal_seed writes from the output itself, kernels.saliency_ranks, kernels.extremal_mask_grad,
+    kernels.extremal_step.  The model is in eval mode (no BatchNorm buffer moves; the caller's mode is restored) and runs its
+    plain eval backward, as in `integrated_gradients` -- the inference fold is not involved; SlotModel's backward overwrites
+    the `.grad` of its parameters that require grad, as in any backward of it, while a plain torch module, differentiated by
+    torch.autograd.grad with respect to the input alone, has no `.grad` touched.  Nothing is copied to the host and nothing synchronises inside the loop; two calls give the same
+    bits.  Any module whose eval forward returns log-probabilities [n, n_outputs] and is differentiable to its input will do.
+
+    This DEPARTS from TorchRay in what it leaves out -- the `dual` variant, the contrastive reward, the `resize` / `smooth`
+    post-processing and the `margin` offset of the upsampler's grid -- in the zero padding of the blur (`perturbation_pyramid`),
+    and in the pyramid's piecewise-linear blend being differentiated by its right-hand piece at a knot."""
+    if variant not in ("preserve", "delete"):
+        raise ValueError("variant must be 'preserve' or 'delete', got %r" % (variant,))
+    n_iters, step, levels = int(n_iters), int(step), int(levels)
+    if n_iters < 1:
+        raise ValueError("n_iters must be at least 1, got %d" % n_iters)
+    if step < 1 or not 0.0 < float(sigma) < float("inf"):
+        raise ValueError("step must be at least 1 and sigma positive and finite, got %d and %r" % (step, sigma))
+    pyramid_pass_plan(levels, max_blur)                                      # (levels < 2: ValueError)
+    if not (0.0 <= float(lr) < float("inf") and 0.0 <= float(momentum) <= 1.0):
+        raise ValueError("lr must be finite and not negative and 0 <= momentum <= 1, got %r and %r" % (lr, momentum))
+    x, batch = _check_images_batch(images, batch)
+    B, C, H, W = x.shape
+    if H * W > 1 << 20:
+        raise ValueError("images of %d x %d pixels: the ranking covers at most 2^20" % (H, W))
+    counts = _extremal_area_pixels(areas, H * W)
+    hm, wm, _ = K.extremal_grid(H, W, step, sigma)
+    if init is not None:
+        if not torch.is_tensor(init) or not (tuple(init.shape) == (hm, wm) or
+                                             (init.dim() == 5 and tuple(init.shape[3:]) == (hm, wm) and init.shape[0] == B)):
+            raise ValueError("init must be None, [%d, %d] or [B = %d, K, A, %d, %d], got %s"
+                             % (hm, wm, B, hm, wm, tuple(init.shape) if torch.is_tensor(init) else type(init).__name__))
+    lams = extremal_schedule(n_iters, area_weight, area_growth)
+    n_out = _num_outputs(model, x)
+    per_image, cols = _class_columns(classes, B, n_out)
+    Kc, A = (1 if per_image else len(cols)), len(counts)
+    if init is not None and init.dim() == 5 and tuple(init.shape[:3]) != (B, Kc, A):
+        raise ValueError("init must be None, [%d, %d] or [B = %d, K = %d, A = %d, %d, %d], got %s"
+                         % (hm, wm, B, Kc, A, hm, wm, tuple(init.shape)))
+    dev = x.device
+    pmasks = torch.full((B, Kc * A, hm, wm), 0.5, dtype=torch.float32, device=dev)
+    if init is not None:
+        pmasks.copy_(init.detach().to(dev, dtype=torch.float32).reshape((-1, Kc * A, hm, wm) if init.dim() == 5 else (1, 1, hm, wm))
+                     .expand(B, Kc * A, hm, wm))
+    masks = torch.empty((B, Kc * A, H, W), dtype=torch.float32, device=dev)
+    rewards = torch.empty((B, Kc * A, n_iters), dtype=torch.float32, device=dev)
+    R = Kc * A
+    if R == 0:
+        return ExtremalMasks(masks.view(B, Kc, A, H, W), pmasks.view(B, Kc, A, hm, wm), rewards.view(B, Kc, A, n_iters))
+    rows = min(batch, R)
+    buf = torch.empty((rows, C, H, W), dtype=torch.float32, device=dev)
+    seed = torch.empty((rows, n_out), dtype=torch.float32, device=dev)
+    mask = torch.empty((rows, H, W), dtype=torch.float32, device=dev)
+    dmask = torch.empty_like(mask)
+    stats = torch.empty((rows, H, W, 2), dtype=torch.float32, device=dev)
+    ranks = torch.empty((rows, H * W), dtype=torch.int32, device=dev)
+    mom = torch.empty((rows, hm, wm), dtype=torch.float32, device=dev)
+    targets_all = torch.tensor(counts * Kc, dtype=torch.int32).to(dev)       # row k A + a: area a
+    with _eval_mode(model), torch.enable_grad():
+        for b in range(B):
+            cb = cols[b:b + 1] if per_image else cols
+            cols_all = torch.tensor([c for c in cb for _ in range(A)], dtype=torch.int32).to(dev)
+            pyr = perturbation_pyramid(x[b], levels, max_blur)
+            for r0 in range(0, R, batch):
+                n = min(batch, R - r0)
+                pm = pmasks[b, r0:r0 + n]
+                cg, tg = cols_all[r0:r0 + n], targets_all[r0:r0 + n]
+                mk, dm, st, rk = mask[:n], dmask[:n], stats[:n], ranks[:n]
+                rw = torch.empty((n_iters, n), dtype=torch.float32, device=dev)
+                for it in range(n_iters):
+                    flip = bool(jitter) and it % 2 == 1
+                    K.extremal_mask(pm, mk, step, sigma, st)
+                    leaf = K.extremal_blend(pyr, mk, buf[:n], variant, flip).detach().requires_grad_(True)
+                    out = model(leaf)
+                    logp = out.detach()
+                    logp = logp if logp.dtype == torch.float32 and logp.is_contiguous() else logp.float().contiguous()
+                    K.extremal_seed(logp, cg, seed[:n], rw, it, variant)
+                    g = torch.autograd.grad(out, leaf, seed[:n].to(out.dtype))[0]
+                    g = g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()
+                    K.saliency_ranks(mk.view(n, H * W), out=rk)
+                    K.extremal_mask_grad(pyr, mk, g, rk, tg, dm, lams[it], variant, flip)
+                    K.extremal_step(pm, mom[:n], mk, dm, st, step, sigma, lr, momentum, it == 0)
+                    del out, leaf, g
+                K.extremal_mask(pm, masks[b, r0:r0 + n], step, sigma)
+                rewards[b, r0:r0 + n].copy_(rw.t())
+    return ExtremalMasks(masks.view(B, Kc, A, H, W), pmasks.view(B, Kc, A, hm, wm), rewards.view(B, Kc, A, n_iters))
+
+
+def extremal_saliency(model, images, classes=None, variant="preserve", **kwargs):
+    """The masks of `extremal_perturbation` (its other keyword arguments pass through) as one FLOAT saliency map per class, fp32
+    [B, K, H, W] on the device: the mean of the masks over the areas (kernels.channel_mean, the area axis playing the channel),
+    and 1 - that mean for variant "delete", whose masks are small where the evidence is."""
+    r = extremal_perturbation(model, images, classes, variant=variant, **kwargs)
+    m = K.channel_mean(r.masks)
+    return 1.0 - m if variant == "delete" else m
+
+
+def extremal_maps(model, images, classes=None, min_level=0.0, **kwargs):
+    """uint8 Extremal Perturbation heat maps [B, K, H, W] on the device: `extremal_saliency` (the mean of the masks over the
+    areas; 1 - the mean for "delete"), then the drawing steps of `rise_maps` at the maps' own size (kernels.heat_maps)."""
+    return K.heat_maps(extremal_saliency(model, images, classes, **kwargs), min_level)
