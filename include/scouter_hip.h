@@ -694,7 +694,8 @@ int scouter_slot_loss_bwd_f32(const float* logp, const long* labels, const float
                               void* stream);
 
 /* ---- FC baseline head (`use_slot=False`): global average pool = scouter_avgpool_*_f32 with k = H, then
- * nn.Linear (weight [C][K], sloter/slot_model.py:116-125, timm/models/resnet.py:503-509).  dx / dw / db may be NULL. */
+ * nn.Linear (weight [C][K], sloter/slot_model.py:116-125, timm/models/resnet.py:503-509).  Each of dx, dw, db may be NULL
+ * independently of the other two: an output that is given is written, whichever of the others are left out. */
 int scouter_linear_small_fwd_f32(const float* x, const float* w, const float* bias, float* y, int B, int K, int C,
                                  void* stream);
 int scouter_linear_small_bwd_f32(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,

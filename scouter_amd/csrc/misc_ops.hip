@@ -696,12 +696,12 @@ __global__ __launch_bounds__(256) void linear_small_dgrad_kernel(const float* __
     for (int c = 0; c < C; ++c) s += dy[(long)b * C + c] * w[(long)c * K + k];
     dx[i] = s;
 }
-// dw[c][k] = sum_b dy[b][c] x[b][k] ; db[c] = sum_b dy[b][c]   (fixed summation order -> deterministic)
+// dw[c][k] = sum_b dy[b][c] x[b][k] ; db[c] = sum_b dy[b][c]   (fixed summation order -> deterministic); dw or db may be NULL
 __global__ __launch_bounds__(256) void linear_small_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                  float* __restrict__ dw, float* __restrict__ db, int B,
                                                                  int K, int C) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long)C * K) {
+    if (dw && i < (long)C * K) {
         const int c = (int)(i / K), k = (int)(i % K);
         float s = 0.f;
         for (int b = 0; b < B; ++b) s += dy[(long)b * C + c] * x[(long)b * K + k];
@@ -724,7 +724,9 @@ extern "C" int scouter_linear_small_bwd_f32(const float* dy, const float* x, con
     SC_REQUIRE(dy && x && w && B > 0 && K > 0 && C > 0, "linear_small_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (dx) hipLaunchKernelGGL(linear_small_dgrad_kernel, dim3(sc_cdiv((long)B * K, 256)), dim3(256), 0, st, dy, w, dx, B, K, C);
-    if (dw) hipLaunchKernelGGL(linear_small_wgrad_kernel, dim3(sc_cdiv((long)C * K, 256)), dim3(256), 0, st, dy, x, dw, db, B, K, C);
+    // (db is formed by the first C threads of the weight-gradient grid, cdiv(C*K, 256) workgroups >= C threads: the kernel
+    // runs when either output is asked for)
+    if (dw || db) hipLaunchKernelGGL(linear_small_wgrad_kernel, dim3(sc_cdiv((long)C * K, 256)), dim3(256), 0, st, dy, x, dw, db, B, K, C);
     return sc_check_launch("linear_small_bwd");
 }
 
