@@ -16,7 +16,8 @@
  *
  * Beyond the training path the library holds what an explanation is drawn and scored with, each in a section of its own below:
  * the input pipeline, Grad-CAM, RISE, insertion / deletion scores, Score-CAM, path and noise batches (Integrated Gradients,
- * SmoothGrad), Grad-CAM++, the infidelity / max-sensitivity scores and the mask side of Extremal Perturbation.  The reference
+ * SmoothGrad), Grad-CAM++, the infidelity / max-sensitivity scores and the mask sides of Extremal Perturbation and of
+ * information-bottleneck attribution.  The reference
  * computes none of the scores itself; where
  * no program exists to copy, the section's comment is the specification.
  */
@@ -549,6 +550,45 @@ int scouter_extremal_mask_grad_f32(const float* pyramid, const float* mask, cons
  * butterfly.  A cell's terms read its own pmask value and per-pixel arrays nothing here writes: no race. */
 int scouter_extremal_step_f32(float* pmask, float* mom, const float* mask, const float* dmask, const float* stats, int n, int H,
                               int W, int step, float sigma, float lr, float momentum, int first, void* stream);
+
+/* ---- Information-bottleneck attribution (Schulz, Sixt, Tombari, Landgraf, ICLR 2020; the reference's torchcam/IBA/pytorch.py,
+ * attached to model.layer4 by torchcam_vis.py; csrc/iba.hip, tools/attribution.py information_bottleneck): the mask side of one
+ * Adam step and the estimator of the feature distribution.  x, mean, std, active fp32 [h][w][C] (one image's features NHWC, the
+ * fitted mean, std and 0 / 1 activity); alpha fp32 [K][h][w][C], one mask per class; rows j = k * S + s; N = h * w, E = N * C.
+ * One launch each, no atomics, fixed summation orders: bit-identical run to run, and a class's values do not depend on K.
+ * A null or misaligned (4 bytes; 8 for fp64) pointer, a size below 1, a window radius not below h and w, a flag outside {0, 1}
+ * is SC_ERR_ARG; sigma above 3.25, h * w above 120, K above 65535 or sizes past 32-bit offsets are SC_ERR_UNSUPPORTED.
+ *
+ * SMOOTHING G: the depthwise window of side D = 2 * r + 1, r = round(2 * sigma) (to even at a tie), values
+ * exp(-d^2 / (2 * sigma^2)) normalised to sum 1 (formed in fp64, rounded once), over (h, w) with reflection padding that does
+ * not repeat the edge; sigma = 0: no smoothing.  lambda = G(sigmoid(alpha)), kappa = G(sigmoid(-alpha)) = 1 - lambda without the
+ * cancellation.  sd = max(std, min_std), r = (x - mean) / sd.
+ * NOISE: eps[j][e] is the stream of scouter_noise_images_f32: Philox4x32-10 under the key (seed_lo, seed_hi) and the counter
+ * (e / 4, first + j, 0, 0), e = p * C + c, Box-Muller on the word pairs.  The caller passes first = t * (all rows of the image) +
+ * the first row of this call.
+ * SAMPLE: z_out[j] = active ? fma(lambda_k, x, kappa_k * fma(sd, eps[j], mean)) : 0, clamped at 0 when relu is set;
+ * cap_out (may be NULL) fp32 [K][h][w][C] = active ? -0.5 * (1 + 2 * ln(kappa) - (r * lambda)^2 - kappa^2) : 0, in nats. */
+int scouter_iba_sample_f32(const float* x, const float* mean, const float* std, const float* active, const float* alpha,
+                           float* z_out, float* cap_out, int K, int S, int h, int w, int C, float sigma, float min_std, int seed_lo,
+                           int seed_hi, int first, int relu, void* stream);
+/* THE STEP, in place.  dz fp32 [K * S][h][w][C] = d loss / d z_out.  G_lambda[k] = active ? sum_s dz[k * S + s] * (x - fma(sd, eps, mean))
+ * * [z > 0 if relu] + (beta / E) * (1 / kappa + r^2 * lambda - kappa) : 0, one fma per sample in ascending s, eps and z regenerated by
+ * the expressions of the sample; G_alpha[k] = sigmoid(alpha) * sigmoid(-alpha) * G^T(G_lambda[k]), G^T the adjoint of the reflecting
+ * window; then Adam as torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no weight decay) at iteration t >= 0 on alpha, adam_m, adam_v
+ * (zeros before t = 0): m = fma(0.9, m, 0.1 * g), v = fma(0.999, v, 0.001 * g * g), alpha -= lr / (1 - 0.9^(t + 1)) * m /
+ * (sqrt(v) / sqrt(1 - 0.999^(t + 1)) + 1e-8), the two corrections formed in fp64. */
+int scouter_iba_step_f32(const float* x, const float* mean, const float* std, const float* active, float* alpha, const float* dz,
+                         float* adam_m, float* adam_v, int K, int S, int h, int w, int C, float sigma, float min_std, int seed_lo,
+                         int seed_hi, int first, float beta, float lr, int t, int relu, void* stream);
+/* THE ESTIMATOR.  Welford per element over the B rows of feat fp32 [B][E] in order, continuing from n0 earlier rows:
+ * d = x - mean; mean += d / n; m2 += d * (x - mean); nonzero += (x != 0); mean, m2 fp64 [E] and nonzero i32 [E] start at 0.  Any
+ * chunking of the same rows gives the same bits. */
+int scouter_iba_estimate_f64(const float* feat, double* mean, double* m2, int* nonzero, long n0, int B, long E, void* stream);
+/* mean_out = mean, std_out = sqrt(m2 / (n - 1)), active_out = (nonzero / n > threshold) ? 1 : 0, fp32 [E]; n < 2: SC_ERR_ARG. */
+int scouter_iba_estimate_finish_f32(const double* mean, const double* m2, const int* nonzero, float* mean_out, float* std_out,
+                                    float* active_out, long n, double threshold, long E, void* stream);
+/* out[i] = (sum_c cap[i][c]) / ln 2 for cap fp32 [rows][C]: fp64, ascending c, one thread per row. */
+int scouter_iba_bits_f32(const float* cap, float* out, long rows, int C, void* stream);
 
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats

@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
 // scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
 // same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
 #pragma once
@@ -337,3 +337,58 @@ __device__ __forceinline__ void ex_knot(float m, int variant, int L, int& k, flo
 
 // (1 - w) p0 + w p1, exact at both ends: p0 at w = 0 and p1 at w = 1
 __device__ __forceinline__ float ex_mix(float p0, float p1, float w) { return fmaf(w, p1, (1.f - w) * p0); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Information-bottleneck attribution (iba.hip): what iba_sample and iba_step must agree on bit for bit.  The smoothing window's
+// values, the reflecting index map with its adjoint, and the counter layout of the noise -- the stream of noise_images.
+constexpr int IB_MAX_R = 6, IB_MAX_D = 2 * IB_MAX_R + 1;       // sigma up to 3.25
+
+// the window's radius: round(2 sigma) to even at a tie, as Python's round; no smoothing (radius 0) for sigma <= 0
+static inline int ib_radius(float sigma) { return sigma > 0.f ? (int)nearbyint(2.0 * (double)sigma) : 0; }
+
+// w[a D + b] = exp(-((a - r)^2 + (b - r)^2) / (2 sigma^2)) / the sum of all of them, D = 2 r + 1: formed in fp64 and rounded once;
+// the one value 1 at radius 0
+struct IbWindow {
+    int r;
+    float w[IB_MAX_D * IB_MAX_D];
+};
+static inline void ib_window(float sigma, IbWindow& win) {      // (the caller has refused a radius above IB_MAX_R)
+    const int r = win.r = ib_radius(sigma), D = 2 * r + 1;
+    double g[IB_MAX_D], tot = 0.0;
+    for (int d = 0; d < D; ++d) {
+        g[d] = r ? exp(-(double)((d - r) * (d - r)) / (2.0 * (double)sigma * (double)sigma)) : 1.0;
+        tot += g[d];
+    }
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b) win.w[a * D + b] = (float)(g[a] * g[b] / (tot * tot));
+}
+
+// index i of an axis of n cells padded by reflection without the edge (ReflectionPad2d), -(n - 1) <= i <= 2 (n - 1)
+__device__ __forceinline__ int ib_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+
+// the adjoint of ib_reflect: the padded indices u in [-r, n - 1 + r] that map to cell c -- c itself, its mirror below 0 and its
+// mirror above n - 1 -- into u[3]; returns how many (r <= n - 1: a cell is mirrored at most once per side)
+__device__ __forceinline__ int ib_sources(int c, int n, int r, int (&u)[3]) {
+    int cnt = 1;
+    u[0] = c; u[1] = c; u[2] = c;
+    if (c > 0 && c <= r) u[cnt++] = -c;
+    if (c < n - 1 && n - 1 - c <= r) u[cnt++] = 2 * (n - 1) - c;
+    return cnt;
+}
+
+// eps of the V = 4 elements e .. e + 3 (e a multiple of 4) or of the one element e of sample `sample`: the Philox words of the
+// counter (e / 4, sample, 0, 0) through two Box-Muller pairs, as noise_images_kernel forms them
+template <int V>
+__device__ __forceinline__ void ib_noise(long e, unsigned sample, unsigned seed_lo, unsigned seed_hi, float (&z)[V]) {
+    unsigned r[4];
+    pg_philox((unsigned)(e >> 2), sample, 0u, 0u, seed_lo, seed_hi, r);
+    if constexpr (V == 4) {
+        pg_normal_pair(r[0], r[1], z[0], z[1]);
+        pg_normal_pair(r[2], r[3], z[2], z[3]);
+    } else {
+        const int i = (int)(e & 3);
+        float za, zb;
+        pg_normal_pair((i & 2) ? r[2] : r[0], (i & 2) ? r[3] : r[1], za, zb);
+        z[0] = (i & 1) ? zb : za;
+    }
+}

@@ -2383,3 +2383,142 @@ def extremal_step(pmask, mom, mask, dmask, stats, step, sigma, lr, momentum, fir
                                                           float(sigma), float(lr), float(momentum), 1 if first else 0, _stream()),
                   "extremal_step")
     return pmask
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# information-bottleneck attribution (csrc/iba.hip; tools/attribution.py information_bottleneck / iba_estimate)
+# ---------------------------------------------------------------------------------------------------------------
+def iba_radius(sigma):
+    """The radius of IBA's smoothing window: round(2 sigma) with sigma rounded to fp32 as the library receives it (to even at a
+    tie; csrc/attr_common.h ib_radius), 0 for sigma None or 0 -- no smoothing."""
+    if sigma is None:
+        return 0
+    s = float(torch.tensor(float(sigma), dtype=F32))
+    if not 0.0 <= s < float("inf"):
+        raise ValueError("iba: sigma = %r (positive and finite, or None / 0 for no smoothing)" % (sigma,))
+    return int(round(2.0 * s))
+
+
+class IbaState:
+    """The running state of `iba_estimate` for neurons of one shape: n rows seen, fp64 mean and M2, int32 non-zero counts."""
+
+    def __init__(self, shape, device):
+        self.shape, self.n = tuple(int(v) for v in shape), 0
+        self.mean = torch.zeros(self.shape, dtype=torch.float64, device=device)
+        self.m2 = torch.zeros(self.shape, dtype=torch.float64, device=device)
+        self.nonzero = torch.zeros(self.shape, dtype=torch.int32, device=device)
+
+
+def iba_estimate(features, state=None):
+    """Feeds the rows of features fp32 [B, ...] to the streaming Welford estimator `state` (None: a new IbaState of the rows'
+    shape) and returns it: per neuron, rows in order, fp64 d = x - mean; mean += d / n; M2 += d (x - mean), and an int32 count of
+    non-zero values.  Any chunking of the same rows gives the same bits.  One launch."""
+    _chk(features, "iba_estimate: features")
+    if features.dim() < 2 or features.shape[0] < 1 or features[0].numel() < 1:
+        raise RuntimeError("iba_estimate: features must be [B, ...] with B >= 1, got shape %s" % (tuple(features.shape),))
+    if state is None:
+        state = IbaState(features.shape[1:], features.device)
+    if not isinstance(state, IbaState) or state.shape != tuple(features.shape[1:]) or state.mean.device != features.device:
+        raise RuntimeError("iba_estimate: the state is for neurons of shape %s, the features are %s"
+                           % (getattr(state, "shape", None), tuple(features.shape[1:])))
+    B = int(features.shape[0])
+    _native.check(_native.lib().scouter_iba_estimate_f64(_p(features), _p(state.mean), _p(state.m2), _p(state.nonzero), state.n, B,
+                                                         int(state.mean.numel()), _stream()), "iba_estimate")
+    state.n += B
+    return state
+
+
+def iba_estimate_finish(state, threshold=0.01):
+    """(mean, std, active) of an IbaState as fp32 tensors of the neurons' shape: std = sqrt(M2 / (n - 1)), active = 1 where
+    nonzero / n > threshold and 0 elsewhere.  Fewer than 2 rows: RuntimeError (no NaN std).  One launch."""
+    if not isinstance(state, IbaState):
+        raise RuntimeError("iba_estimate_finish: state must be an IbaState, got %s" % type(state).__name__)
+    if state.n < 2:
+        raise RuntimeError("iba_estimate_finish: %d rows seen -- a standard deviation needs at least 2" % state.n)
+    mean = torch.empty(state.shape, dtype=F32, device=state.mean.device)
+    std, active = torch.empty_like(mean), torch.empty_like(mean)
+    _native.check(_native.lib().scouter_iba_estimate_finish_f32(_p(state.mean), _p(state.m2), _p(state.nonzero), _p(mean), _p(std),
+                                                                _p(active), state.n, float(threshold), int(mean.numel()),
+                                                                _stream()), "iba_estimate_finish")
+    return mean, std, active
+
+
+def _iba_chk(what, x, mean, std, active, alpha, rows_t, rows_name, sigma, t, row0, rows):
+    """x, mean, std, active fp32 [h, w, C], alpha fp32 [K, h, w, C] and a row tensor fp32 [K S, h, w, C] -> (K, S, h, w, C, first)"""
+    for t_, n_ in ((x, "x"), (mean, "mean"), (std, "std"), (active, "active"), (alpha, "alpha"), (rows_t, rows_name)):
+        if t_ is None:
+            raise RuntimeError("%s: %s is None" % (what, n_))
+        _chk(t_, "%s: %s" % (what, n_))
+    if x.dim() != 3 or x.numel() < 1 or any(tuple(v.shape) != tuple(x.shape) for v in (mean, std, active)):
+        raise RuntimeError("%s: x, mean, std and active must share one shape [h, w, C] (got %s, %s, %s and %s)"
+                           % (what, tuple(x.shape), tuple(mean.shape), tuple(std.shape), tuple(active.shape)))
+    if alpha.dim() != 4 or alpha.shape[0] < 1 or tuple(alpha.shape[1:]) != tuple(x.shape):
+        raise RuntimeError("%s: alpha must be [K, %s], got shape %s" % (what, ", ".join(str(v) for v in x.shape), tuple(alpha.shape)))
+    K_ = int(alpha.shape[0])
+    if rows_t.dim() != 4 or tuple(rows_t.shape[1:]) != tuple(x.shape) or rows_t.shape[0] < K_ or rows_t.shape[0] % K_:
+        raise RuntimeError("%s: %s must be [K S, %s] with K = %d, got shape %s"
+                           % (what, rows_name, ", ".join(str(v) for v in x.shape), K_, tuple(rows_t.shape)))
+    S = int(rows_t.shape[0]) // K_
+    h, w, C = (int(v) for v in x.shape)
+    r = iba_radius(sigma)
+    if r >= h or r >= w:
+        raise ValueError("%s: sigma = %r gives a window of radius %d; h = %d and w = %d must both exceed it" % (what, sigma, r, h, w))
+    rows = K_ * S if rows is None else int(rows)
+    t, row0 = int(t), int(row0)
+    if t < 0 or row0 < 0 or row0 + K_ * S > rows:
+        raise ValueError("%s: t = %d, rows [%d, %d) of %d (t and row0 not negative, the call's rows inside the image's)"
+                         % (what, t, row0, row0 + K_ * S, rows))
+    first = t * rows + row0
+    if first + K_ * S >= 1 << 31:
+        raise ValueError("%s: sample %d is past 2^31" % (what, first + K_ * S))
+    return K_, S, h, w, C, first
+
+
+def iba_sample(x, mean, std, active, alpha, z_out, cap_out, sigma, seed, t, relu, min_std=0.01, row0=0, rows=None):
+    """The bottleneck's samples of one image: z_out[k S + s] = active (lambda_k x + kappa_k (max(std, min_std) eps + mean)) for fp32 x,
+    mean, std, active [h, w, C] (NHWC features, the fitted distribution, the 0 / 1 activity), fp32 alpha [K, h, w, C] and fp32
+    z_out [K S, h, w, C]: lambda = G(sigmoid(alpha)), kappa = G(sigmoid(-alpha)) with G the Gaussian window of radius
+    `iba_radius(sigma)` under reflection padding (sigma None: no smoothing); clamped at 0 with `relu`.  eps is the stream of
+    `noise_images` for sample t * rows + row0 + k S + s under `seed` (rows: the rows of the whole image, default K S; row0: the
+    first row of this call) -- generated, never stored.  cap_out: None, or fp32 [K, h, w, C] that receives the capacity in nats,
+    -0.5 (1 + 2 ln kappa - (r lambda)^2 - kappa^2) with r = (x - mean) / max(std, min_std), 0 where inactive.  One launch."""
+    K_, S, h, w, C, first = _iba_chk("iba_sample", x, mean, std, active, alpha, z_out, "z_out", sigma, t, row0, rows)
+    _chk(cap_out, "iba_sample: cap_out")
+    if cap_out is not None and tuple(cap_out.shape) != tuple(alpha.shape):
+        raise RuntimeError("iba_sample: cap_out must be like alpha %s, got shape %s" % (tuple(alpha.shape), tuple(cap_out.shape)))
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_iba_sample_f32(_p(x), _p(mean), _p(std), _p(active), _p(alpha), _p(z_out), _p(cap_out), K_, S,
+                                                       h, w, C, float(sigma or 0.0), float(min_std), lo, hi, first,
+                                                       1 if relu else 0, _stream()), "iba_sample")
+    return z_out
+
+
+def iba_step(x, mean, std, active, alpha, dz, adam_m, adam_v, sigma, seed, t, beta, lr, relu, min_std=0.01, row0=0, rows=None):
+    """One Adam step on alpha fp32 [K, h, w, C], IN PLACE, for dz fp32 [K S, h, w, C] = d loss / d (the z_out `iba_sample` wrote with
+    the same arguments): G_lambda[k] = active (sum_s dz[k S + s] (x - (sd eps + mean)) [z > 0 if relu] + beta / (h w C) (1 / kappa +
+    r^2 lambda - kappa)), the noise regenerated; G_alpha = sigmoid'(alpha) G^T(G_lambda) with G^T the adjoint of the reflecting
+    window; Adam as torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8) at iteration t on adam_m, adam_v fp32 like alpha (zeros before
+    t = 0).  Nothing of size [K S, ...] is written.  One launch."""
+    K_, S, h, w, C, first = _iba_chk("iba_step", x, mean, std, active, alpha, dz, "dz", sigma, t, row0, rows)
+    _chk(adam_m, "iba_step: adam_m"); _chk(adam_v, "iba_step: adam_v")
+    if adam_m is None or adam_v is None or adam_m.shape != alpha.shape or adam_v.shape != alpha.shape:
+        raise RuntimeError("iba_step: adam_m and adam_v must be like alpha %s" % (tuple(alpha.shape),))
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_iba_step_f32(_p(x), _p(mean), _p(std), _p(active), _p(alpha), _p(dz), _p(adam_m), _p(adam_v),
+                                                     K_, S, h, w, C, float(sigma or 0.0), float(min_std), lo, hi, first, float(beta),
+                                                     float(lr), int(t), 1 if relu else 0, _stream()), "iba_step")
+    return alpha
+
+
+def iba_bits(cap, out=None):
+    """fp32 [..., C] capacities in nats -> fp32 [...] bits: the channels summed in ascending order in fp64, divided by ln 2.  One
+    launch, one thread per position."""
+    _chk(cap, "iba_bits: cap"); _chk(out, "iba_bits: out")
+    if cap.dim() < 2 or cap.numel() < 1:
+        raise RuntimeError("iba_bits: cap must be [..., C], got shape %s" % (tuple(cap.shape),))
+    if out is None:
+        out = torch.empty(cap.shape[:-1], dtype=F32, device=cap.device)
+    elif tuple(out.shape) != tuple(cap.shape[:-1]):
+        raise RuntimeError("iba_bits: out must be %s, got shape %s" % (tuple(cap.shape[:-1]), tuple(out.shape)))
+    _native.check(_native.lib().scouter_iba_bits_f32(_p(cap), _p(out), int(out.numel()), int(cap.shape[-1]), _stream()), "iba_bits")
+    return out

@@ -416,6 +416,28 @@ class SlotModel(nn.Module):
                 self.train(True)
         return FeaturePass(self, feat, logp, hstate)
 
+    def head_pass(self, features):
+        """`feature_pass` without the backbone: NHWC fp32 `features` [n, h, w, channel] on the device -- the backbone's output, or
+        anything of its shape, such as the noisy samples of tools/attribution.py information_bottleneck -- go through one
+        eval-mode head forward.  Returns a FeaturePass whose `.features` are the tensor given and whose `.grad(seed)` is the
+        gradient with respect to it, any number of times.  Works with use_slot on and off; the caller's mode is restored."""
+        if not torch.is_tensor(features) or not features.is_cuda:
+            raise RuntimeError("scouter_amd.SlotModel runs on a HIP device (got %s); there is no CPU fallback"
+                               % (features.device if torch.is_tensor(features) else type(features).__name__,))
+        if features.dim() != 4 or features.dtype != torch.float32:
+            raise ValueError("features must be fp32 NHWC [n, h, w, channel], got %s %s" % (features.dtype, tuple(features.shape)))
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad():
+                feat = features.detach().contiguous()
+                logp, _, hstate = self._head_forward(feat, None, True)
+        finally:
+            if was_training:
+                self.train(True)
+        return FeaturePass(self, feat, logp, hstate)
+
     def loss_seed(self, loss):
         """A cached tensor of ones shaped like the scalar loss: `loss.backward(model.loss_seed(loss))` spares autograd the
         `ones_like` fill it launches for a bare `loss.backward()` (the last ATen kernel of the step; engine.py, bench.py)."""

@@ -22,8 +22,12 @@ heat maps `<out>/smoothcampp_{c}.png` (tools/attribution.py smooth_gradcampp: --
 --smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--extremal true` the per-class Extremal
 Perturbation maps `<out>/extremal_{c}.png` (tools/attribution.py extremal_maps: --extremal_iters SGD steps on a smooth mask of
 --extremal_area of the image, variant --extremal_variant, the classes in groups of --extremal_batch, floored at --grad_min_level;
-torchray's extremal_perturbation of the reference's torchcam_vis.py); `--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal), the deletion and insertion scores of
+torchray's extremal_perturbation of the reference's torchcam_vis.py); `--iba true` the per-class information-bottleneck maps
+`<out>/iba_{c}.png` (tools/attribution.py iba_maps: --iba_steps Adam steps on a feature-space mask with --iba_samples_per_step noisy
+samples each, information weight --iba_beta, window --iba_sigma, the feature distribution fitted on --iba_fit images of the
+validation loader -- synthetic ones under --synthetic_data true --, at most --iba_batch head rows per pass, 0 = all; the IBA of
+the reference's torchcam_vis.py); `--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
 the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
@@ -41,6 +45,7 @@ jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNG
         [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
         [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
         [--extremal true --extremal_area 0.1 --extremal_iters 800 --extremal_variant preserve --extremal_batch 50] \
+        [--iba true --iba_beta 10 --iba_steps 10 --iba_samples_per_step 10 --iba_sigma 1.0 --iba_fit 5000 --iba_batch 0] \
         [--causal true --causal_step 224] \
         [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
         [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
@@ -171,6 +176,43 @@ def run_extremal(args, model, image, out_dir):
     return _run_maps(args, model, image, out_dir, "extremal", functools.partial(extremal_maps, model, **_extremal_kwargs(args)))
 
 
+def _iba_kwargs(args):
+    sigma = float(getattr(args, "iba_sigma", 1.0))
+    return dict(beta=float(getattr(args, "iba_beta", 10.0)), steps=int(getattr(args, "iba_steps", 10)),
+                samples=int(getattr(args, "iba_samples_per_step", 10)), sigma=sigma if sigma > 0.0 else None,
+                batch=int(getattr(args, "iba_batch", 0)) or None)
+
+
+def iba_fit(args, model):
+    """the feature distribution --iba needs (tools/attribution.py iba_estimate), fitted once per run on --iba_fit images of the
+    validation loader -- seeded synthetic images under --synthetic_data true -- and kept on `args`"""
+    est = getattr(args, "_iba_estimate", None)
+    if est is None:
+        from .tools.attribution import iba_estimate
+        from .train import _build_loaders
+        args.distributed = bool(getattr(args, "distributed", False))
+        _, loader, _ = _build_loaders(args)
+        transform = getattr(loader, "gpu_transform", None)
+
+        def batches():
+            for batch in loader:
+                images = batch["image"]
+                raw = not torch.is_tensor(images)
+                yield transform(images, args.device) if raw else images.to(args.device, dtype=torch.float32)
+
+        est = args._iba_estimate = iba_estimate(model, batches(), n_samples=int(getattr(args, "iba_fit", 5000)))
+    return est
+
+
+def run_iba(args, model, image, out_dir):
+    """--iba true: the information-bottleneck map of every class for the one image (the IBA the reference's torchcam_vis.py attaches
+    to layer4: --iba_steps Adam steps, --iba_samples_per_step samples, weight --iba_beta, window --iba_sigma) ->
+    `<out>/iba_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from .tools.attribution import iba_maps
+    return _run_maps(args, model, image, out_dir, "iba", functools.partial(iba_maps, model, estimate=iba_fit(args, model),
+                                                                          **_iba_kwargs(args)))
+
+
 def _ig(args, model, x, classes=None):
     from .tools.attribution import integrated_gradients
     return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
@@ -207,10 +249,11 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
     """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
     given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
     rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
-    smoothcampp: smooth_gradcampp; extremal: extremal_saliency).  full: grad, ig and smoothgrad keep their attribution
+    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck).  full: grad, ig and smoothgrad keep their attribution
     [n, 1, C, H, W] instead."""
     from . import kernels as K
-    from .tools.attribution import extremal_saliency, gradcam, gradcampp, input_gradients, rise, scorecam, smooth_gradcampp
+    from .tools.attribution import extremal_saliency, gradcam, gradcampp, information_bottleneck, input_gradients, rise, scorecam
+    from .tools.attribution import smooth_gradcampp
     if family == "slot":
         return slot_map
     if family == "grad":
@@ -232,6 +275,8 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
         return smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
     if family == "extremal":
         return extremal_saliency(model, x, classes=[pred], **_extremal_kwargs(args))
+    if family == "iba":
+        return information_bottleneck(model, x, iba_fit(args, model), classes=[pred], **_iba_kwargs(args))
     return rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)),
                 batch=int(getattr(args, "rise_batch", 250)))
 
@@ -240,7 +285,8 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
-    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency), one printed
+    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba:
+    information_bottleneck), one printed
     line each; returns {family: (deletion, insertion)}."""
     from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
@@ -338,6 +384,14 @@ def get_test_parser():
     parser.add_argument("--extremal_variant", default="preserve", choices=("preserve", "delete"),
                         help="--extremal keeps (preserve) or removes (delete) the evidence under the mask")
     parser.add_argument("--extremal_batch", default=50, type=int, help="masks per forward and backward of --extremal")
+    parser.add_argument("--iba", default=False, type=_flag,
+                        help="true: write the information-bottleneck map of every class as iba_{c}.png into --vis_dir")
+    parser.add_argument("--iba_beta", default=10.0, type=float, help="weight of the information term of --iba")
+    parser.add_argument("--iba_steps", default=10, type=int, help="Adam steps of --iba")
+    parser.add_argument("--iba_samples_per_step", default=10, type=int, help="noisy samples per class and step of --iba")
+    parser.add_argument("--iba_sigma", default=1.0, type=float, help="standard deviation of the smoothing window of --iba (0: none)")
+    parser.add_argument("--iba_fit", default=5000, type=int, help="images the feature distribution of --iba is fitted on")
+    parser.add_argument("--iba_batch", default=0, type=int, help="head rows per pass of --iba (0: all classes at once)")
     parser.add_argument("--infidelity", default=False, type=_flag,
                         help="true: print the infidelity of the predicted class's explanation of every family drawn")
     parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
@@ -398,9 +452,12 @@ def main():
         run_smoothcampp(args, model, image, args.vis_dir)
     if args.extremal:
         run_extremal(args, model, image, args.vis_dir)
+    if args.iba:
+        run_iba(args, model, image, args.vis_dir)
     families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
                                 ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
-                                ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal)) if on]
+                                ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal),
+                                ("iba", args.iba)) if on]
     if args.causal:
         run_causal(args, model, image, pred, families, slot_map)
     if args.infidelity:

@@ -76,7 +76,17 @@ upsampler's backward and the update.  The mask side is five HIP kernels and the 
 (kernels.extremal_mask, extremal_blend, extremal_seed, saliency_ranks, extremal_mask_grad, extremal_step); the seed of the
 backward is written on the device from the forward's own output, so nothing comes to the host for the whole run.  No reference
 program runs here (torchray is not a dependency): the docstring of `extremal_perturbation` is the specification, and it lists
-what departs from TorchRay."""
+what departs from TorchRay.
+
+An optimised mask in feature space (`iba_estimate`, `information_bottleneck`, `iba_saliency`, `iba_maps`): information-bottleneck
+attribution (Schulz, Sixt, Tombari, Landgraf, ICLR 2020), the IBA the reference's torchcam_vis.py attaches to model.layer4.  Noise
+replaces the backbone's output neuron by neuron, as much as a per-class mask allows, and ten Adam steps trade the class
+log-probability against the information the mask lets through; the map is that information in bits per cell.  The layer is the
+one `gradcam` reads, so the loop never enters the backbone: the samples go through SlotModel.head_pass and its head backward.
+The mask side of an iteration is two HIP kernels (kernels.iba_sample, kernels.iba_step: sigmoid, reflecting Gaussian window, noise
+from the stream of kernels.noise_images, blend and capacity; then the analytic gradient, the window's adjoint and Adam in place),
+the fitted feature distribution comes from a streaming float64 Welford kernel (kernels.iba_estimate), and nothing comes to the
+host in between.  The docstring of `information_bottleneck` is the definition and lists what departs from the reference."""
 import collections
 import contextlib
 import functools
@@ -904,7 +914,8 @@ def sensitivity_max(explain, images, n_samples=10, radius=0.02, batch=11, seed=0
         scorecam     lambda im: scorecam(model, im, classes=cs)
         ig           lambda im: integrated_gradients(model, im, classes=cs)
         smoothgrad   lambda im: smoothgrad(model, im, classes=cs)
-        slot         lambda im: (model(im), slot_saliency(model)[:, cs].contiguous())[1]        (model in eval mode, no_grad)
+        iba          lambda im: information_bottleneck(model, im, estimate, classes=cs)
+        slot       lambda im: (model(im), slot_saliency(model)[:, cs].contiguous())[1]        (model in eval mode, no_grad)
     `batch` is the number of rows per call, the clean row included (at least 2).  Per image: row 0 of one reused buffer is
     written once, then chunks of up to batch - 1 samples: kernels.uniform_images into the rows behind it, explain, and
     kernels.map_distances.  A result that is not an fp32 device tensor [n, K, ...], or whose shape behind the first dimension
@@ -1146,3 +1157,146 @@ def extremal_maps(model, images, classes=None, min_level=0.0, **kwargs):
     """uint8 Extremal Perturbation heat maps [B, K, H, W] on the device: `extremal_saliency` (the mean of the masks over the
     areas; 1 - the mean for "delete"), then the drawing steps of `rise_maps` at the maps' own size (kernels.heat_maps)."""
     return K.heat_maps(extremal_saliency(model, images, classes, **kwargs), min_level)
+
+
+IbaEstimate = collections.namedtuple("IbaEstimate", "mean std active n")
+IbaEstimate.__doc__ = """The fitted feature distribution `information_bottleneck` needs, from `iba_estimate`: fp32 mean, std and 0 / 1
+activity [h, w, channel] of the backbone's output (NHWC, on the device) and the number of images n they were fitted on."""
+
+
+def iba_estimate(model, batches, n_samples=5000, threshold=0.01):
+    """Fits the per-neuron distribution of the backbone's output over `batches`, any iterable of image batches [b, C, H, W] (or of
+    tuples whose first entry is one, as a data loader yields) -> IbaEstimate.  Each batch takes one SlotModel.feature_pass and one
+    kernels.iba_estimate launch (streaming Welford in float64, rows in order, so the batching does not change a bit); whole
+    batches are taken until at least `n_samples` images are in.  std = sqrt(M2 / (n - 1)); a neuron is active where it was
+    non-zero in more than `threshold` of the images (the reference's TorchWelfordEstimator).  Fewer than 2 images: ValueError."""
+    state = None
+    for batch in batches:
+        if state is not None and state.n >= int(n_samples):
+            break
+        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        feat = model.feature_pass(_check_images(images)).features
+        state = K.iba_estimate(feat, state)
+    if state is None or state.n < 2:
+        raise ValueError("iba_estimate needs at least 2 images, got %d" % (0 if state is None else state.n))
+    mean, std, active = K.iba_estimate_finish(state, threshold)
+    return IbaEstimate(mean, std, active, state.n)
+
+
+def _check_iba(images, estimate, steps, samples, sigma, batch):
+    """the refusals of information_bottleneck that need no launch -> (steps, samples, rows per group or None)"""
+    steps, samples = int(steps), int(samples)
+    if steps < 1 or samples < 1:
+        raise ValueError("steps and samples must be at least 1, got %d and %d" % (steps, samples))
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be at least 1, got %d" % int(batch))
+    if not isinstance(estimate, IbaEstimate) or not all(torch.is_tensor(v) for v in estimate[:3]):
+        raise ValueError("estimate must be an IbaEstimate (from iba_estimate), got %s" % type(estimate).__name__)
+    shape = tuple(estimate.mean.shape)
+    if len(shape) != 3 or tuple(estimate.std.shape) != shape or tuple(estimate.active.shape) != shape:
+        raise ValueError("estimate.mean, .std and .active must share one shape [h, w, channel], got %s, %s and %s"
+                         % (shape, tuple(estimate.std.shape), tuple(estimate.active.shape)))
+    r = K.iba_radius(sigma)
+    if r >= shape[0] or r >= shape[1]:
+        raise ValueError("sigma = %r smooths with a window of radius %d: the %d x %d features must exceed it in both directions "
+                         "(sigma=None: no smoothing)" % (sigma, r, shape[0], shape[1]))
+    _check_images(images)
+    if not images.is_cuda or not estimate.mean.is_cuda:
+        raise RuntimeError("information_bottleneck runs on a HIP device (images on %s, estimate on %s); there is no CPU fallback"
+                           % (images.device, estimate.mean.device))
+    return steps, samples, (None if batch is None else int(batch))
+
+
+def information_bottleneck(model, images, estimate, classes=None, beta=10.0, steps=10, samples=10, sigma=1.0, lr=1.0, min_std=0.01,
+                           relu=False, batch=None, seed=0):
+    """Information-bottleneck attribution (Schulz, Sixt, Tombari, Landgraf, ICLR 2020, "Restricting the Flow"; the per-sample
+    bottleneck of the reference's torchcam/IBA/pytorch.py, which torchcam_vis.py attaches to model.layer4) of `images` [B, C, H, W]
+    at the backbone's output -> fp32 [B, K, h, w] on the device, in bits per cell.  This docstring (and include/scouter_hip.h) is the
+    definition; tests/test_iba_cpu.py restates it in float64.
+
+    x is one image's feature tensor [h, w, C] (NHWC), m, s, a = `estimate` (`iba_estimate`), alpha [K, h, w, C] one mask per
+    explained class, S = samples, E = h w C.
+    smoothing G  the depthwise Gaussian window of side 2 round(2 sigma) + 1 (5 at sigma = 1), values exp(-d^2 / (2 sigma^2))
+                 normalised to sum 1, over (h, w) with reflection padding that does not repeat the edge (ReflectionPad2d);
+                 sigma=None: none.  h and w must both exceed the radius (ValueError; the reference raises from the pad).
+    mask         lambda = G(sigmoid(alpha)), kappa = 1 - lambda formed as G(sigmoid(-alpha)).
+    noise        eps[j], row j = k S + s, at iteration t: the stream of kernels.noise_images for sample t K S + j under `seed`.
+    sample       z[j] = a (lambda_k x + kappa_k (max(s, min_std) eps[j] + m)), clamped at 0 with `relu`.
+    capacity     cap_k = -0.5 (1 + 2 ln kappa - r^2 lambda^2 - kappa^2) nats where a = 1, r = (x - m) / max(s, min_std); exactly 0
+                 where a = 0.
+    loss_k       -mean_s log_probs[k S + s, class_k] + beta mean_{p, c} cap_k; the head runs on z (SlotModel.head_pass).
+    update       Adam as torch.optim.Adam (lr, betas (0.9, 0.999), eps 1e-8) on alpha from 5, by the analytic gradient
+                 sigmoid'(alpha) G^T(a (sum_s dz (x - (s eps + m)) [z > 0 if relu] + beta / E (1 / kappa + r^2 lambda - kappa))).
+    result       sum_c cap / ln 2 of the LAST forward, that is of alpha after steps - 1 updates -- what the reference returns.
+
+    classes as in `gradcam`: None (every output), a list of ints (K = len), or a LongTensor [B] (each image its own class,
+    K = 1).  `batch` caps the head rows per pass: the classes of an image run in groups of max(1, batch // samples) whole classes
+    (None: all at once); masks are independent and the noise of a row depends on (seed, t, row) alone, so the grouping does not
+    change a bit.  One SlotModel.feature_pass for the batch, then per image, group and iteration: kernels.iba_sample,
+    model.head_pass, its .grad with a seed of -1 / S built once, kernels.iba_step; the last iteration stops after the sample,
+    which writes the capacity, and kernels.iba_bits sums it.  Nothing is copied to the host and nothing synchronises; two calls
+    give the same bits.  Head parameters that require grad get their `.grad` overwritten by each backward.
+
+    This DEPARTS from the reference in four ways: kappa avoids the cancellation of fp32 1 - lambda at alpha around 5 to 17; an
+    inactive neuron's capacity is selected as 0 where the reference multiplies and drops the NaN with nansum (the same map); the
+    noise is the Philox stream, not torch's generator; and alpha past about 88 (never reached from 5 in tens of steps) gives
+    kappa = 0 and an infinite capacity."""
+    steps, S, batch = _check_iba(images, estimate, steps, samples, sigma, batch)
+    x, _ = _check_images_batch(images, 1)
+    B = x.shape[0]
+    fp = model.feature_pass(x)
+    feat, n_out = fp.features, int(fp.log_probs.shape[1])
+    del fp
+    _, h, w, C = feat.shape
+    if tuple(estimate.mean.shape) != (h, w, C):
+        raise ValueError("the estimate is for features %s, these images give %s" % (tuple(estimate.mean.shape), (h, w, C)))
+    per_image, cols = _class_columns(classes, B, n_out)
+    Kc = 1 if per_image else len(cols)
+    dev = feat.device
+    out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    kg = Kc if batch is None else min(Kc, max(1, batch // S))
+    mean, std, active = (v.detach().to(dev, dtype=torch.float32).contiguous() for v in estimate[:3])
+    z = torch.empty((kg * S, h, w, C), dtype=torch.float32, device=dev)
+    cap = torch.empty((kg, h, w, C), dtype=torch.float32, device=dev)
+    alpha, adam_m, adam_v = torch.empty_like(cap), torch.empty_like(cap), torch.empty_like(cap)
+    for b in range(B):
+        cb = cols[b:b + 1] if per_image else cols
+        for k0 in range(0, Kc, kg):
+            kn = min(kg, Kc - k0)
+            al, am, av = alpha[:kn], adam_m[:kn], adam_v[:kn]
+            al.fill_(5.0); am.zero_(); av.zero_()
+            hseed = torch.zeros((kn * S, n_out), dtype=torch.float32, device=dev)
+            hcols = torch.tensor([c for c in cb[k0:k0 + kn] for _ in range(S)], dtype=torch.int64).to(dev)
+            hseed[torch.arange(kn * S, device=dev), hcols] = -1.0 / S
+            for t in range(steps):
+                last = t == steps - 1
+                K.iba_sample(feat[b], mean, std, active, al, z[:kn * S], cap[:kn] if last else None, sigma, seed, t, relu, min_std,
+                             row0=k0 * S, rows=Kc * S)
+                if last:
+                    break
+                dz = model.head_pass(z[:kn * S]).grad(hseed)
+                K.iba_step(feat[b], mean, std, active, al, dz, am, av, sigma, seed, t, beta, lr, relu, min_std, row0=k0 * S,
+                           rows=Kc * S)
+                del dz
+            K.iba_bits(cap[:kn], out=out[b, k0:k0 + kn])
+    return out
+
+
+def iba_saliency(model, images, estimate, classes=None, size=None, **kwargs):
+    """The maps of `information_bottleneck` (its other keyword arguments pass through) brought to the image: fp32 [B, K, H, W] on
+    the device, `size` = (H, W) (None: the images' H x W).  The bits of a cell are spread over its pixels -- times h w / (H W) --
+    and resized by kernels.resize_bilinear, the clamped half-pixel bilinear.  The reference resizes with skimage's
+    resize(order=1), whose reflecting edge mode equals the clamped one when upsampling; skimage was not available to check
+    that when this was written."""
+    H, W = _out_size(size, images)
+    bits = information_bottleneck(model, images, estimate, classes, **kwargs)
+    h, w = bits.shape[-2:]
+    return K.resize_bilinear(bits * (float(h * w) / float(H * W)), H, W)
+
+
+def iba_maps(model, images, estimate, classes=None, size=None, min_level=0.0, **kwargs):
+    """uint8 information-bottleneck heat maps [B, K, H, W] on the device: `iba_saliency`, then the drawing steps of `rise_maps`
+    (kernels.heat_maps)."""
+    return K.heat_maps(iba_saliency(model, images, estimate, classes, size, **kwargs), min_level)
