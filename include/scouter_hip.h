@@ -590,6 +590,61 @@ int scouter_iba_estimate_finish_f32(const double* mean, const double* m2, const 
 /* out[i] = (sum_c cap[i][c]) / ln 2 for cap fp32 [rows][C]: fp64, ascending c, one thread per row. */
 int scouter_iba_bits_f32(const float* cap, float* out, long rows, int C, void* stream);
 
+/* ---- I-GOS (Qi, Khorram, Fuxin, AAAI 2020: integrated-gradient optimised saliency, which the reference's torchcam_vis.py runs
+ * first of all; csrc/igos.hip, tools/attribution.py igos): the mask side of one iteration.  No reference program runs here: the
+ * definitions below are the specification.  R coarse masks pmask fp32 [R][hm][wm] in [0, 1] of ONE image fp32 [C][H][W] and its
+ * baseline `base` of the same shape (NULL: zeros), one mask per class; d = image - base, the fp32 difference.  S = n_steps points
+ * on the path, T1 = T + 1 entries of the step ladder.  No atomics, every sum in one fixed order that depends on the shapes
+ * alone: bit-identical run to run, and a mask's values do not depend on R.  A null or misaligned (4 bytes; 8 for fp64) pointer,
+ * R, C, n or n_steps below 1, H or W below 2, hm outside [2, H], wm outside [2, W], a chunk outside its stream, T1 < 2, tv_beta
+ * outside [1, 64], a negative or non-finite sigma, tv_coeff or alpha, a flag outside {0, 1} is SC_ERR_ARG; hm * wm above 16384,
+ * T1 above 64, R, n_steps or the rows of a trial chunk above 65535 or sizes past 32-bit offsets are SC_ERR_UNSUPPORTED; nothing
+ * is launched after an error.
+ *
+ * THE UPSAMPLER U (torch.nn.UpsamplingBilinear2d, align_corners = True): sy = (float)(hm - 1) / (float)(H - 1); for pixel row y:
+ * s = (float)y * sy, i0 = min((int)s, hm - 1), i1 = min(i0 + 1, hm - 1), t = s - i0; the columns likewise; U(p)[y][x] =
+ * fma(ty, bot - top, top) with top = fma(tx, p[i0][j1] - p[i0][j0], p[i0][j0]) and bot the same on row i1.  16-byte stores when W
+ * is a multiple of 4 and the image-sized pointers are 16-byte aligned, one element otherwise, in every kernel below: the same
+ * bits. */
+int scouter_igos_upsample_f32(const float* pmask, float* out, int R, int H, int W, int hm, int wm, void* stream);
+/* THE PATH.  Stream row g = r * S + j, a = (float)(j + 1) / (float)S: out[g - first][c][q] = fma(sigma, z, fma(a * U(p_r)[q], d[c][q],
+ * base[c][q])) for the n rows from `first`, z the value scouter_noise_images_f32 gives for (seed, sample0 + j, e = c * H * W + q):
+ * Philox4x32-10 under the key (seed_lo, seed_hi) and the counter (e / 4, sample0 + j, 0, 0), Box-Muller on the word pairs.  Every
+ * mask row sees the same noise.  sigma == 0: no noise is formed and out = fma(a * U, d, base).  out may be a leading slice of a
+ * longer buffer. */
+int scouter_igos_path_images_f32(const float* image, const float* base, const float* pmask, float* out, int first, int n, int R,
+                                 int n_steps, int C, int H, int W, int hm, int wm, float sigma, int seed_lo, int seed_hi, int sample0,
+                                 void* stream);
+/* THE CONTRACTION.  dx fp32 [n][C][H][W], the input gradients of stream rows first .. first + n - 1; acc fp64 [R][H][W]:
+ * acc[r][q] = fma(w_j, sum_c (double)dx[g][c][q] * (double)d[c][q], acc[r][q]) for the rows g = r * S + j of the chunk in ascending j,
+ * the channel sum from 0 in ascending c, w_j = ((j + 1) / S) / S in fp64: calls over consecutive pieces give the bits of one. */
+int scouter_igos_accumulate_f64(const float* image, const float* base, const float* dx, double* acc, int first, int n, int R,
+                                int n_steps, int C, int H, int W, void* stream);
+/* THE MASK GRADIENT.  loss1(p) = l1 * mean|1 - p| + tv_coeff * (mean_{i < hm - 1, j} |p[i][j] - p[i + 1][j]|^beta +
+ * mean_{i, j < wm - 1} |p[i][j] - p[i][j + 1]|^beta), l1 = l1[r] (fp32 [R] on the device), beta = tv_beta; the derivative of |.| and of
+ * |.|^beta at 0 is 0.  dmask[r][cell] = (float)(sum_u acc[r][u] * wy_u * wx_u + d loss1 / d p[cell]) in fp64: the adjoint of U as a gather
+ * over the pixels u whose i0 / i1 (weights 1 - t / t) and j0 / j1 touch the cell, one wave per cell, a lane adding the pixels
+ * lane, lane + 64, ... of the cell's window in row-major order by one fma each, then a butterfly.  stats fp64 [R][2] =
+ * (loss1(p_r), sum over the cells of (double)dmask^2, the stored fp32 values), one workgroup of 1024 threads per row: a thread adds
+ * its cells t, t + 1024, ... in order, the lanes meet by a butterfly and the waves in order.  Two launches. */
+int scouter_igos_mask_grad_f32(const float* pmask, const double* acc, const float* l1, float* dmask, double* stats, float tv_coeff,
+                               float tv_beta, int R, int H, int W, int hm, int wm, void* stream);
+/* THE TRIALS of the line search.  steps fp32 [T1] on the device, steps[0] = 0.  Stream row g = r * T1 + k: cand_k[cell] =
+ * min(max(fma(-steps[k], dmask[r][cell], p_r[cell]), 0), 1) (a NaN goes to 0), out[g - first][c][q] = fma(U(cand_k)[q], d[c][q],
+ * base[c][q]).  No noise. */
+int scouter_igos_trial_images_f32(const float* image, const float* base, const float* pmask, const float* dmask, const float* steps,
+                                  float* out, int first, int n, int R, int T1, int C, int H, int W, int hm, int wm, void* stream);
+/* THE STEP, in place.  logp fp32 [R * T1][n_out], the outputs for the trial stream; cols i32 [R] in [0, n_out) (checked by the
+ * caller; clamped here).  Per row r in fp64: tot_k = loss1(cand_k) + exp(logp[r * T1 + k][cols[r]]), thr_k = tot_0 - alpha * steps[k] *
+ * stats[r][1]; chosen = the first k in 1 .. T with NOT (tot_k > thr_k) -- a NaN accepts -- and T when none passes; p_r = cand_chosen,
+ * the bits of the trial stream.  curves fp64 [R][n_iters][4]: curves[r][it] = (loss1(p_r) before, exp(logp[r * T1][cols[r]]),
+ * steps[chosen], chosen).  adapt = 1 and n_iters > 3: at it == n_iters / 2, l1[r] /= 10 when |curves[r][it][1] - curves[r][0][1]| <=
+ * 1e-3; otherwise at it == (int)(n_iters / 1.25), l1[r] /= 5 when that difference is <= 1e-2 (fp32 divisions, after this
+ * iteration's totals).  One workgroup of 1024 threads per row, the sums of loss1 as in scouter_igos_mask_grad_f32. */
+int scouter_igos_step_f32(float* pmask, const float* dmask, const float* steps, const float* logp, const int* cols, const double* stats,
+                          float* l1, double* curves, int R, int T1, int n_out, int hm, int wm, int it, int n_iters, double alpha,
+                          float tv_coeff, float tv_beta, int adapt, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

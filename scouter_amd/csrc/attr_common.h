@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
 // scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
 // same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
 #pragma once
@@ -391,4 +391,35 @@ __device__ __forceinline__ void ib_noise(long e, unsigned sample, unsigned seed_
         pg_normal_pair((i & 2) ? r[2] : r[0], (i & 2) ? r[3] : r[1], za, zb);
         z[0] = (i & 1) ? zb : za;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// I-GOS (igos.hip): what its kernels must agree on bit for bit.  The align-corners upsampler (torch.nn.UpsamplingBilinear2d) --
+// igos_upsample, igos_path_images and igos_trial_images form it, igos_mask_grad gathers its adjoint through the same source
+// coordinates -- and the candidate cell of the line search, which igos_trial_images evaluates and igos_step stores.
+
+// the scale of an axis of n_in cells upsampled to n_out >= 2 pixels: the ends of the two grids coincide
+static inline float ig_scale(int n_in, int n_out) { return (float)(n_in - 1) / (float)(n_out - 1); }
+
+// source coordinate of destination index d, align_corners = True: s = d scale, the lower index clamped to n - 1, the upper one
+// min(lower + 1, n - 1), t = s - lower.  Every index is clamped, so no value moves an address.  s is the ROUNDED product:
+// contraction is switched off here, or the compiler fuses the product into the difference and t = fma(d, scale, -lower) carries
+// the bits the rounding of s drops (seen on gfx950: t off by up to 6e-8 at 3 cells -> 13 pixels).
+__device__ __forceinline__ void ig_source(int d, float scale, int n, int& i0, int& i1, float& t) {
+#pragma clang fp contract(off)
+    const float s = (float)d * scale;
+    i0 = min((int)s, n - 1);
+    i1 = min(i0 + 1, n - 1);
+    t = s - (float)i0;
+}
+
+// the cell the line search tries at step size `step` along -dm: clamp(p - step dm, 0, 1); a NaN goes to 0
+__device__ __forceinline__ float ig_candidate(float p, float dm, float step) {
+    return fminf(fmaxf(fmaf(-step, dm, p), 0.f), 1.f);
+}
+
+// the upsampled value of a pixel from its four cells, cell(i) the value of cell i of the row-major hm x wm grid
+template <typename Cell>
+__device__ __forceinline__ float ig_upsample_at(Cell cell, int wm, int y0, int y1, float ty, int x0, int x1, float tx) {
+    return at_bilerp(cell(y0 * wm + x0), cell(y0 * wm + x1), cell(y1 * wm + x0), cell(y1 * wm + x1), tx, ty);
 }

@@ -2522,3 +2522,190 @@ def iba_bits(cap, out=None):
         raise RuntimeError("iba_bits: out must be %s, got shape %s" % (tuple(cap.shape[:-1]), tuple(out.shape)))
     _native.check(_native.lib().scouter_iba_bits_f32(_p(cap), _p(out), int(out.numel()), int(cap.shape[-1]), _stream()), "iba_bits")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# I-GOS (csrc/igos.hip; tools/attribution.py igos / igos_maps)
+# ---------------------------------------------------------------------------------------------------------------
+IGOS_MAX_CELLS, IGOS_MAX_LADDER = 16384, 64                      # (csrc/igos.hip IG_MAX_CELLS, IG_MAX_LADDER)
+
+
+def _igos_grid_chk(what, pmask, H, W):
+    """pmask fp32 [R, hm, wm] for images of H x W pixels -> (R, hm, wm)"""
+    if pmask is None:
+        raise RuntimeError("%s: pmask is None" % what)
+    _chk(pmask, what + ": pmask")
+    if pmask.dim() != 3 or pmask.shape[0] < 1:
+        raise RuntimeError("%s: pmask must be [R, hm, wm], got shape %s" % (what, tuple(pmask.shape)))
+    R, hm, wm = (int(v) for v in pmask.shape)
+    if H < 2 or W < 2:
+        raise ValueError("%s: an image of %d x %d pixels (each side at least 2)" % (what, H, W))
+    if not (2 <= hm <= H and 2 <= wm <= W):
+        raise ValueError("%s: a mask of %d x %d cells for %d x %d pixels (2 <= hm <= H, 2 <= wm <= W)" % (what, hm, wm, H, W))
+    if hm * wm > IGOS_MAX_CELLS:
+        raise ValueError("%s: a mask of %d x %d cells (at most %d cells)" % (what, hm, wm, IGOS_MAX_CELLS))
+    return R, hm, wm
+
+
+def _igos_image_chk(what, image, base):
+    """image fp32 [C, H, W] and base of the same shape (None: zeros) -> (C, H, W)"""
+    if image is None:
+        raise RuntimeError("%s: image is None" % what)
+    _chk(image, what + ": image"); _chk(base, what + ": base")
+    if image.dim() != 3 or image.numel() < 1:
+        raise RuntimeError("%s: image must be [C, H, W], got shape %s" % (what, tuple(image.shape)))
+    if base is not None and tuple(base.shape) != tuple(image.shape):
+        raise RuntimeError("%s: base must have the image's shape %s, got %s" % (what, tuple(image.shape), tuple(base.shape)))
+    return tuple(int(v) for v in image.shape)
+
+
+def _igos_chunk_chk(what, batch, name, C, H, W, first, total, stream):
+    """a batch fp32 [n, C, H, W] that holds rows first .. first + n - 1 of a stream of `total` rows -> n"""
+    if batch is None:
+        raise RuntimeError("%s: %s is None" % (what, name))
+    _chk(batch, "%s: %s" % (what, name))
+    if batch.dim() != 4 or batch.shape[0] < 1 or tuple(batch.shape[1:]) != (C, H, W):
+        raise RuntimeError("%s: %s must be [n, %d, %d, %d], got shape %s" % (what, name, C, H, W, tuple(batch.shape)))
+    n, first = int(batch.shape[0]), int(first)
+    if first < 0 or first + n > total:
+        raise ValueError("%s: rows [%d, %d) lie outside the %s of %d rows" % (what, first, first + n, stream, total))
+    return n
+
+
+def igos_upsample(pmask, out):
+    """out[r] = U(pmask[r]): fp32 pmask [R, hm, wm] -> fp32 out [R, H, W] by torch.nn.UpsamplingBilinear2d's rule (align_corners =
+    True): sy = (float)(hm - 1) / (float)(H - 1), s = (float)y sy, i0 = min((int)s, hm - 1), i1 = min(i0 + 1, hm - 1), t = s - i0, the
+    columns likewise, three fmas per pixel (include/scouter_hip.h).  2 <= hm <= H, 2 <= wm <= W, hm wm <= 16384.  One launch."""
+    _chk(out, "igos_upsample: out")
+    if out is None or out.dim() != 3:
+        raise RuntimeError("igos_upsample: out must be [R, H, W], got %s" % (None if out is None else tuple(out.shape),))
+    H, W = int(out.shape[1]), int(out.shape[2])
+    R, hm, wm = _igos_grid_chk("igos_upsample", pmask, H, W)
+    if out.shape[0] != R:
+        raise RuntimeError("igos_upsample: out must be [R = %d, H, W], got shape %s" % (R, tuple(out.shape)))
+    _native.check(_native.lib().scouter_igos_upsample_f32(_p(pmask), _p(out), R, H, W, hm, wm, _stream()), "igos_upsample")
+    return out
+
+
+def igos_path_images(image, base, pmask, out, first, n_steps, sigma, seed, sample0):
+    """Rows first .. first + n - 1 of one image's path stream -> fp32 out [n, C, H, W] (a dense leading slice of a longer buffer is
+    fine).  Stream row g is mask row r = g // S and point j = g % S, S = n_steps, a = (float)(j + 1) / (float)S; per element
+    d = image - base, m = a U(pmask[r]), x = fma(m, d, base), out = fma(sigma, z, x) with z the value `noise_images` gives for (seed,
+    sample0 + j, element): every mask row sees the same noise.  sigma == 0: no noise is formed and out = x bit for bit.  image fp32
+    [C, H, W], base like it (None: zeros), pmask fp32 [R, hm, wm].  An element depends on (g, seed, sample0) alone, so chunks
+    written by separate calls equal one call.  One launch."""
+    C, H, W = _igos_image_chk("igos_path_images", image, base)
+    R, hm, wm = _igos_grid_chk("igos_path_images", pmask, H, W)
+    S = int(n_steps)
+    if S < 1:
+        raise ValueError("igos_path_images: n_steps = %d (at least 1)" % S)
+    n = _igos_chunk_chk("igos_path_images", out, "out", C, H, W, first, R * S, "path stream R n_steps")
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_igos_path_images_f32(_p(image), _p(base), _p(pmask), _p(out), int(first), n, R, S, C, H, W, hm,
+                                                             wm, float(sigma), lo, hi, int(sample0), _stream()), "igos_path_images")
+    return out
+
+
+def igos_accumulate(image, base, dx, acc, first, n_steps):
+    """acc[r] += sum_j w_j sum_c (double)dx[g, c] (double)d[c] for fp32 dx [n, C, H, W], the input gradients of stream rows first ..
+    first + n - 1 of `igos_path_images` (g = r S + j), and fp64 acc [R, H, W]: d = image - base in fp32, w_j = ((j + 1) / S) / S in
+    fp64, the channel sum from 0 in ascending c, the rows in ascending j by one fma each onto the values in acc -- calls over
+    consecutive pieces give the bits of one call.  One launch."""
+    C, H, W = _igos_image_chk("igos_accumulate", image, base)
+    _chk(acc, "igos_accumulate: acc", torch.float64)
+    if acc is None or acc.dim() != 3 or acc.shape[0] < 1 or tuple(acc.shape[1:]) != (H, W):
+        raise RuntimeError("igos_accumulate: acc must be fp64 [R, %d, %d], got %s" % (H, W, None if acc is None else tuple(acc.shape)))
+    if H < 2 or W < 2:
+        raise ValueError("igos_accumulate: an image of %d x %d pixels (each side at least 2)" % (H, W))
+    R, S = int(acc.shape[0]), int(n_steps)
+    if S < 1:
+        raise ValueError("igos_accumulate: n_steps = %d (at least 1)" % S)
+    n = _igos_chunk_chk("igos_accumulate", dx, "dx", C, H, W, first, R * S, "path stream R n_steps")
+    _native.check(_native.lib().scouter_igos_accumulate_f64(_p(image), _p(base), _p(dx), _p(acc), int(first), n, R, S, C, H, W,
+                                                            _stream()), "igos_accumulate")
+    return acc
+
+
+def igos_mask_grad(pmask, acc, l1, dmask, stats, tv_coeff, tv_beta):
+    """dmask[r] = U^T(acc[r]) + d loss1 / d pmask[r] for fp32 pmask / dmask [R, hm, wm], fp64 acc [R, H, W] from `igos_accumulate` and
+    fp32 l1 [R] on the device: loss1(p) = l1_r mean|1 - p| + tv_coeff (mean|p[i, :] - p[i + 1, :]|^tv_beta + mean|p[:, j] -
+    p[:, j + 1]|^tv_beta), the derivative of |.| and |.|^beta at 0 taken as 0; U^T the adjoint of `igos_upsample`, gathered per cell in
+    fp64 over the pixels whose source rows and columns touch it; one rounding to fp32 at the end.  stats fp64 [R, 2] receives
+    (loss1(p_r), sum dmask_r^2 over the stored fp32 values).  tv_coeff >= 0, 1 <= tv_beta <= 64.  Two launches (the gather, one wave
+    per cell; the sums, one workgroup per row), fixed orders."""
+    _chk(acc, "igos_mask_grad: acc", torch.float64); _chk(l1, "igos_mask_grad: l1"); _chk(dmask, "igos_mask_grad: dmask")
+    _chk(stats, "igos_mask_grad: stats", torch.float64)
+    if acc is None or acc.dim() != 3:
+        raise RuntimeError("igos_mask_grad: acc must be fp64 [R, H, W], got %s" % (None if acc is None else tuple(acc.shape),))
+    H, W = int(acc.shape[1]), int(acc.shape[2])
+    R, hm, wm = _igos_grid_chk("igos_mask_grad", pmask, H, W)
+    if acc.shape[0] != R or l1 is None or tuple(l1.shape) != (R,) or dmask is None or dmask.shape != pmask.shape or stats is None or \
+            tuple(stats.shape) != (R, 2):
+        raise RuntimeError("igos_mask_grad: acc must be [R = %d, H, W], l1 fp32 [R], dmask like pmask and stats fp64 [R, 2] (got %s, %s, "
+                           "%s and %s)" % (R, tuple(acc.shape), None if l1 is None else tuple(l1.shape),
+                                           None if dmask is None else tuple(dmask.shape), None if stats is None else tuple(stats.shape)))
+    _native.check(_native.lib().scouter_igos_mask_grad_f32(_p(pmask), _p(acc), _p(l1), _p(dmask), _p(stats), float(tv_coeff),
+                                                           float(tv_beta), R, H, W, hm, wm, _stream()), "igos_mask_grad")
+    return dmask
+
+
+def _igos_ladder_chk(what, steps):
+    _chk(steps, what + ": steps")
+    if steps is None or steps.dim() != 1 or steps.shape[0] < 2:
+        raise RuntimeError("%s: steps must be fp32 [T + 1] with steps[0] = 0 and at least one trial step, got %s"
+                           % (what, None if steps is None else tuple(steps.shape)))
+    if steps.shape[0] > IGOS_MAX_LADDER:
+        raise ValueError("%s: a ladder of %d steps (at most %d)" % (what, steps.shape[0], IGOS_MAX_LADDER))
+    return int(steps.shape[0])
+
+
+def igos_trial_images(image, base, pmask, dmask, steps, out, first):
+    """Rows first .. first + n - 1 of one image's trial stream -> fp32 out [n, C, H, W] (a dense leading slice of a longer buffer
+    is fine).  steps fp32 [T1] on the device with steps[0] = 0; stream row g is mask row r = g // T1 and step k = g % T1; the
+    candidate cell is clamp(fma(-steps[k], dmask[r], pmask[r]), 0, 1) and out = fma(U(candidate), image - base, base).  No noise.
+    One launch."""
+    C, H, W = _igos_image_chk("igos_trial_images", image, base)
+    R, hm, wm = _igos_grid_chk("igos_trial_images", pmask, H, W)
+    _chk(dmask, "igos_trial_images: dmask")
+    if dmask is None or dmask.shape != pmask.shape:
+        raise RuntimeError("igos_trial_images: dmask must be like pmask %s, got %s"
+                           % (tuple(pmask.shape), None if dmask is None else tuple(dmask.shape)))
+    T1 = _igos_ladder_chk("igos_trial_images", steps)
+    n = _igos_chunk_chk("igos_trial_images", out, "out", C, H, W, first, R * T1, "trial stream R (T + 1)")
+    _native.check(_native.lib().scouter_igos_trial_images_f32(_p(image), _p(base), _p(pmask), _p(dmask), _p(steps), _p(out), int(first),
+                                                              n, R, T1, C, H, W, hm, wm, _stream()), "igos_trial_images")
+    return out
+
+
+def igos_step(pmask, dmask, steps, logp, cols, stats, l1, curves, it, n_iters, alpha, tv_coeff, tv_beta, adapt):
+    """The line search of one iteration, on the device, pmask fp32 [R, hm, wm] IN PLACE.  logp fp32 [R T1, n_out]: the eval outputs
+    of the whole trial stream of `igos_trial_images`; cols int32 [R] (the caller keeps them inside [0, n_out)); stats fp64 [R, 2]
+    from `igos_mask_grad` for THIS pmask.  Per row in fp64: tot_k = loss1(cand_k) + exp(logp[r T1 + k, cols[r]]), thr_k = tot_0 -
+    alpha steps[k] stats[r, 1]; chosen = the first k in 1 .. T with not (tot_k > thr_k) -- a NaN accepts -- or T when none passes;
+    pmask[r] = cand_chosen, the bits the trial stream was formed from.  curves fp64 [R, n_iters, 4]: curves[r, it] = (loss1 before,
+    probability before, steps[chosen], chosen).  adapt (and n_iters > 3): at it == n_iters // 2, l1[r] /= 10 when |prob(it) -
+    prob(0)| <= 1e-3; otherwise at it == int(n_iters / 1.25), l1[r] /= 5 when it is <= 1e-2 -- l1 fp32 [R] is the per-row state.  One
+    launch, one workgroup per row."""
+    _chk(dmask, "igos_step: dmask"); _chk(logp, "igos_step: logp"); _chk(cols, "igos_step: cols", torch.int32)
+    _chk(stats, "igos_step: stats", torch.float64); _chk(l1, "igos_step: l1"); _chk(curves, "igos_step: curves", torch.float64)
+    if pmask is None:
+        raise RuntimeError("igos_step: pmask is None")
+    _chk(pmask, "igos_step: pmask")
+    if pmask.dim() != 3 or pmask.shape[0] < 1 or pmask.shape[1] < 2 or pmask.shape[2] < 2:
+        raise RuntimeError("igos_step: pmask must be [R, hm, wm] with hm, wm >= 2, got shape %s" % (tuple(pmask.shape),))
+    R, hm, wm = (int(v) for v in pmask.shape)
+    if hm * wm > IGOS_MAX_CELLS:
+        raise ValueError("igos_step: a mask of %d x %d cells (at most %d cells)" % (hm, wm, IGOS_MAX_CELLS))
+    T1 = _igos_ladder_chk("igos_step", steps)
+    n_iters, it = int(n_iters), int(it)
+    if any(t is None for t in (dmask, logp, cols, stats, l1, curves)) or dmask.shape != pmask.shape or logp.dim() != 2 or \
+            logp.shape[0] != R * T1 or logp.shape[1] < 1 or tuple(cols.shape) != (R,) or tuple(stats.shape) != (R, 2) or \
+            tuple(l1.shape) != (R,) or tuple(curves.shape) != (R, n_iters, 4):
+        raise RuntimeError("igos_step: dmask must be like pmask, logp [R (T + 1) = %d, n_out], cols int32 [R], stats fp64 [R, 2], l1 "
+                           "fp32 [R] and curves fp64 [R, n_iters, 4]" % (R * T1))
+    if not 0 <= it < n_iters:
+        raise ValueError("igos_step: iteration %d lies outside [0, n_iters = %d)" % (it, n_iters))
+    _native.check(_native.lib().scouter_igos_step_f32(_p(pmask), _p(dmask), _p(steps), _p(logp), _p(cols), _p(stats), _p(l1), _p(curves),
+                                                      R, T1, int(logp.shape[1]), hm, wm, it, n_iters, float(alpha), float(tv_coeff),
+                                                      float(tv_beta), 1 if adapt else 0, _stream()), "igos_step")
+    return pmask

@@ -26,8 +26,11 @@ torchray's extremal_perturbation of the reference's torchcam_vis.py); `--iba tru
 `<out>/iba_{c}.png` (tools/attribution.py iba_maps: --iba_steps Adam steps on a feature-space mask with --iba_samples_per_step noisy
 samples each, information weight --iba_beta, window --iba_sigma, the feature distribution fitted on --iba_fit images of the
 validation loader -- synthetic ones under --synthetic_data true --, at most --iba_batch head rows per pass, 0 = all; the IBA of
-the reference's torchcam_vis.py); `--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba), the deletion and insertion scores of
+the reference's torchcam_vis.py); `--igos true` the per-class I-GOS maps `<out>/igos_{c}.png` (tools/attribution.py igos_maps:
+--igos_iters iterations of --igos_steps noisy path images each on a mask of --igos_size x --igos_size cells, L1 weight --igos_l1,
+total-variation weight --igos_tv, at most --igos_batch rows per pass, floored at --grad_min_level; the Integrated_Mask the
+reference's torchcam_vis.py runs first); `--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba, igos), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
 the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
@@ -46,6 +49,7 @@ jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNG
         [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
         [--extremal true --extremal_area 0.1 --extremal_iters 800 --extremal_variant preserve --extremal_batch 50] \
         [--iba true --iba_beta 10 --iba_steps 10 --iba_samples_per_step 10 --iba_sigma 1.0 --iba_fit 5000 --iba_batch 0] \
+        [--igos true --igos_size 8 --igos_iters 15 --igos_steps 20 --igos_l1 1.0 --igos_tv 20.0 --igos_batch 50] \
         [--causal true --causal_step 224] \
         [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
         [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
@@ -213,6 +217,20 @@ def run_iba(args, model, image, out_dir):
                                                                           **_iba_kwargs(args)))
 
 
+def _igos_kwargs(args):
+    return dict(size=int(getattr(args, "igos_size", 8)), n_iters=int(getattr(args, "igos_iters", 15)),
+                n_steps=int(getattr(args, "igos_steps", 20)), l1_coeff=float(getattr(args, "igos_l1", 1.0)),
+                tv_coeff=float(getattr(args, "igos_tv", 20.0)), batch=int(getattr(args, "igos_batch", 50)))
+
+
+def run_igos(args, model, image, out_dir):
+    """--igos true: the I-GOS map of every class for the one image (the Integrated_Mask of the reference's torchcam_vis.py:
+    --igos_iters iterations of --igos_steps path images on a mask of --igos_size cells a side, weights --igos_l1 and --igos_tv, at
+    most --igos_batch rows per pass) -> `<out>/igos_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from .tools.attribution import igos_maps
+    return _run_maps(args, model, image, out_dir, "igos", functools.partial(igos_maps, model, **_igos_kwargs(args)))
+
+
 def _ig(args, model, x, classes=None):
     from .tools.attribution import integrated_gradients
     return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
@@ -249,11 +267,11 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
     """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
     given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
     rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
-    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck).  full: grad, ig and smoothgrad keep their attribution
+    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck; igos: igos_saliency).  full: grad, ig and smoothgrad keep their attribution
     [n, 1, C, H, W] instead."""
     from . import kernels as K
     from .tools.attribution import extremal_saliency, gradcam, gradcampp, information_bottleneck, input_gradients, rise, scorecam
-    from .tools.attribution import smooth_gradcampp
+    from .tools.attribution import igos_saliency, smooth_gradcampp
     if family == "slot":
         return slot_map
     if family == "grad":
@@ -277,6 +295,8 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
         return extremal_saliency(model, x, classes=[pred], **_extremal_kwargs(args))
     if family == "iba":
         return information_bottleneck(model, x, iba_fit(args, model), classes=[pred], **_iba_kwargs(args))
+    if family == "igos":
+        return igos_saliency(model, x, classes=[pred], **_igos_kwargs(args))
     return rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)),
                 batch=int(getattr(args, "rise_batch", 250)))
 
@@ -286,7 +306,7 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
     integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba:
-    information_bottleneck), one printed
+    information_bottleneck; igos: igos_saliency), one printed
     line each; returns {family: (deletion, insertion)}."""
     from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
@@ -392,6 +412,14 @@ def get_test_parser():
     parser.add_argument("--iba_sigma", default=1.0, type=float, help="standard deviation of the smoothing window of --iba (0: none)")
     parser.add_argument("--iba_fit", default=5000, type=int, help="images the feature distribution of --iba is fitted on")
     parser.add_argument("--iba_batch", default=0, type=int, help="head rows per pass of --iba (0: all classes at once)")
+    parser.add_argument("--igos", default=False, type=_flag,
+                        help="true: write the I-GOS map of every class as igos_{c}.png into --vis_dir")
+    parser.add_argument("--igos_size", default=8, type=int, help="cells a side of the mask of --igos")
+    parser.add_argument("--igos_iters", default=15, type=int, help="iterations of --igos")
+    parser.add_argument("--igos_steps", default=20, type=int, help="noisy path images per class and iteration of --igos")
+    parser.add_argument("--igos_l1", default=1.0, type=float, help="weight of the L1 term of --igos")
+    parser.add_argument("--igos_tv", default=20.0, type=float, help="weight of the total-variation term of --igos")
+    parser.add_argument("--igos_batch", default=50, type=int, help="images per forward (and backward) of --igos")
     parser.add_argument("--infidelity", default=False, type=_flag,
                         help="true: print the infidelity of the predicted class's explanation of every family drawn")
     parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
@@ -454,10 +482,12 @@ def main():
         run_extremal(args, model, image, args.vis_dir)
     if args.iba:
         run_iba(args, model, image, args.vis_dir)
+    if args.igos:
+        run_igos(args, model, image, args.vis_dir)
     families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
                                 ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
                                 ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal),
-                                ("iba", args.iba)) if on]
+                                ("iba", args.iba), ("igos", args.igos)) if on]
     if args.causal:
         run_causal(args, model, image, pred, families, slot_map)
     if args.infidelity:

@@ -86,7 +86,18 @@ one `gradcam` reads, so the loop never enters the backbone: the samples go throu
 The mask side of an iteration is two HIP kernels (kernels.iba_sample, kernels.iba_step: sigmoid, reflecting Gaussian window, noise
 from the stream of kernels.noise_images, blend and capacity; then the analytic gradient, the window's adjoint and Adam in place),
 the fitted feature distribution comes from a streaming float64 Welford kernel (kernels.iba_estimate), and nothing comes to the
-host in between.  The docstring of `information_bottleneck` is the definition and lists what departs from the reference."""
+host in between.  The docstring of `information_bottleneck` is the definition and lists what departs from the reference.
+
+A mask found along integrated gradients (`igos`, `igos_saliency`, `igos_maps`, `igos_ladder`): I-GOS (Qi, Khorram, Fuxin, AAAI
+2020), the Integrated_Mask the reference's torchcam_vis.py runs first of all.  Per image and class a coarse mask blends the image
+with a blurred copy; every iteration sends twenty noisy images on the path from the blurred copy to the masked image through an
+eval forward and input backward, contracts their gradients into the mask's descent direction, and chooses the step by a
+backtracking line search.  The reference does this one image and one pass at a time, with host noise and a host read per trial
+step; here the classes of an image are the rows of one stream, the path images, the contraction, the upsampler's adjoint with
+the L1 / total-variation terms and the trial images are HIP kernels (kernels.igos_path_images, igos_accumulate, igos_mask_grad,
+igos_trial_images, igos_upsample), every trial step goes through the model in one batch, and the selection itself runs on the
+device (kernels.igos_step), so nothing comes to the host for the whole run.  The docstring of `igos` is the specification and
+lists what departs from the reference."""
 import collections
 import contextlib
 import functools
@@ -1300,3 +1311,193 @@ def iba_maps(model, images, estimate, classes=None, size=None, min_level=0.0, **
     """uint8 information-bottleneck heat maps [B, K, H, W] on the device: `iba_saliency`, then the drawing steps of `rise_maps`
     (kernels.heat_maps)."""
     return K.heat_maps(iba_saliency(model, images, estimate, classes, size, **kwargs), min_level)
+
+
+IgosMasks = collections.namedtuple("IgosMasks", "masks pmasks curves")
+IgosMasks.__doc__ = """The result of `igos`, on the images' device: fp32 masks [B, K, H, W] in [0, 1] (the upsampled final masks, small
+where the evidence is), fp32 pmasks [B, K, hm, wm] (the coarse masks themselves) and fp64 curves [B, K, n_iters, 4]: per iteration
+the regulariser before the update, the class probability of the masked image before the update, the step size the line search
+took and its index in `igos_ladder`."""
+
+
+def igos_ladder(step0=200.0, shrink=0.2, min_step=1e-5):
+    """The step sizes the line search of `igos` tries, as a list of floats (host, float64): [0, step0, step0 shrink, step0 shrink^2,
+    ...] up to and including the first value below min_step, each formed from the one before by one multiplication.  Entry 0 is
+    the step of size 0 -- the mask as it stands.  The defaults give 12 trial steps, 200 down to 4.096e-6."""
+    step0, shrink, min_step = float(step0), float(shrink), float(min_step)
+    if not 0.0 < step0 < float("inf") or not 0.0 < shrink < 1.0 or not 0.0 < min_step < float("inf"):
+        raise ValueError("igos_ladder: step0 = %r, shrink = %r, min_step = %r (step0 and min_step positive and finite, 0 < shrink < 1)"
+                         % (step0, shrink, min_step))
+    ladder, s = [0.0, step0], step0
+    while s >= min_step:
+        s *= shrink
+        ladder.append(s)
+        if len(ladder) > K.IGOS_MAX_LADDER:
+            raise ValueError("igos_ladder: step0 = %r, shrink = %r, min_step = %r give more than %d steps"
+                             % (step0, shrink, min_step, K.IGOS_MAX_LADDER - 1))
+    return ladder
+
+
+def _igos_size(size, H, W):
+    """the `size` argument of `igos` -> (hm, wm), checked against the image"""
+    try:
+        hm, wm = (int(size), int(size)) if not isinstance(size, (tuple, list)) else (int(size[0]), int(size[1]))
+        ok = not isinstance(size, (tuple, list)) or len(size) == 2
+    except (TypeError, ValueError, IndexError):
+        ok, hm, wm = False, 0, 0
+    if not ok:
+        raise ValueError("size must be an int or (hm, wm), got %r" % (size,))
+    if H < 2 or W < 2:
+        raise ValueError("images of %d x %d pixels: each side must be at least 2" % (H, W))
+    if not (2 <= hm <= H and 2 <= wm <= W):
+        raise ValueError("a mask of %d x %d cells for images of %d x %d pixels (2 <= hm <= H, 2 <= wm <= W)" % (hm, wm, H, W))
+    if hm * wm > K.IGOS_MAX_CELLS:
+        raise ValueError("a mask of %d x %d cells: at most %d cells" % (hm, wm, K.IGOS_MAX_CELLS))
+    return hm, wm
+
+
+def igos(model, images, classes=None, size=8, n_iters=15, n_steps=20, l1_coeff=1.0, tv_coeff=20.0, tv_beta=2.0, sigma=0.2,
+         baseline=None, blur_klen=31, blur_sigma=30.0, step0=200.0, shrink=0.2, min_step=1e-5, alpha=1e-4, adapt_l1=True, batch=50,
+         seed=0, init=None):
+    """I-GOS (Qi, Khorram, Fuxin, AAAI 2020; the Integrated_Mask the reference's torchcam_vis.py runs first of all) of `images`
+    [B, C, H, W] -> IgosMasks: for every image and class c_k the small, smooth mask whose masked image loses the most probability
+    of class c_k, found by n_iters steps along the integrated gradient with a backtracking line search.  The reference program
+    cannot run here; this docstring (and include/scouter_hip.h) is the specification.  The defaults are the reference's call.
+
+    mask         a coarse mask p [hm, wm] in [0, 1], (hm, wm) = `size` (an int: both), starts at 1 (or `init`) and is upsampled by
+                 U = torch.nn.UpsamplingBilinear2d's rule, align_corners = True (kernels.igos_upsample).  1 keeps the image, 0
+                 replaces it: the masked image is x' + U(p) (x - x'), x' the `baseline`: None (the image blurred by
+                 kernels.separable_filter with `gaussian_taps(blur_klen, blur_sigma)`), [C, H, W] (one for the batch) or [B, C, H, W].
+    regulariser  loss1(p) = l1 mean|1 - p| + tv_coeff (mean|p[i, :] - p[i + 1, :]|^tv_beta + mean|p[:, j] - p[:, j + 1]|^tv_beta); l1
+                 starts at l1_coeff and is a per-class state (below).
+    direction    at iteration `it` the n_steps = S path points x_j = x' + (j + 1) / S U(p) (x - x') + sigma z_j, z_j the noise of
+                 kernels.noise_images for (seed, it S + j, element) -- the same for every class -- go through the model, and
+                 g = d (loss1 + (1 / S) sum_j prob_j) / d p, prob = exp(log_prob[c_k]): the input gradients are contracted with
+                 (j + 1) / S (x - x') in float64 (kernels.igos_accumulate), pulled back through U and joined by the regulariser's
+                 derivative (kernels.igos_mask_grad; the derivative of |.| at 0 is 0).
+    line search  the candidates cand_k = clamp(p - steps[k] g, 0, 1) for EVERY k of `igos_ladder(step0, shrink, min_step)` (k = 0:
+                 the mask as it stands) form one batched stream (kernels.igos_trial_images) that goes through the model without
+                 noise; tot_k = loss1(cand_k) + prob(cand_k); the first k >= 1 with not (tot_k > tot_0 - alpha steps[k] sum g^2) is
+                 taken, the last one when none passes (kernels.igos_step), and p = cand_k.
+    adapt_l1     (n_iters > 3) after iteration n_iters // 2, l1 /= 10 for a class whose probability has moved by at most 1e-3 since
+                 iteration 0; otherwise after iteration int(n_iters / 1.25), l1 /= 5 when it has moved by at most 1e-2.
+
+    classes as in `gradcam` / `extremal_perturbation`: None (every output), a list of ints (K = len), or a LongTensor [B] (each
+    image its own class, K = 1).  init: None, fp32 [hm, wm] (every mask) or [B, K, hm, wm].  Per image the K masks are the rows of
+    one stream: per iteration the K S path images in chunks of at most `batch` rows -- kernels.igos_path_images into one reused
+    buffer, which becomes the leaf of an eval-mode forward and of one backward whose seed kernels.extremal_seed (variant
+    "delete") writes from the output itself, kernels.igos_accumulate -- then kernels.igos_mask_grad, the K T1 trial images in
+    chunks under no_grad, kernels.igos_step; kernels.igos_upsample at the end.  Rows are independent and every sum has one fixed
+    order, so neither `batch` nor the set of classes in the call changes a bit of a class's result, and two calls give the same
+    bits.  Nothing is copied to the host and nothing synchronises inside the loop.  The model is in eval mode (no BatchNorm buffer
+    moves; the caller's mode is restored) and runs its plain eval backward, as in `extremal_perturbation`: SlotModel's backward
+    overwrites the `.grad` of its parameters that require grad, a plain torch module has no `.grad` touched.  Any module whose
+    eval forward returns log-probabilities [n, n_outputs] and is differentiable to its input will do.
+
+    This DEPARTS from the reference in: the path term's weight 1 / n_steps (the reference hard-codes / 20, the same at the
+    default); the probability, which is exp of the model's log-probability (the reference applies a softmax to its model's
+    output); the blur, zero-padded with at most 31 taps (the reference: cv2.GaussianBlur(51, 50), reflecting border); the noise,
+    Philox and Box-Muller on the device (the reference: cv2.randn on the host); the per-iteration top-40-pixel curve, left out;
+    adapt_l1, which compares with iteration 0 (the reference's curve starts with a doubled entry, so it compares with the
+    iteration before); and the line search, which evaluates every candidate in one batch -- more forwards, no host round trip,
+    the same choice."""
+    n_iters, S = int(n_iters), int(n_steps)
+    if n_iters < 1 or S < 1:
+        raise ValueError("n_iters and n_steps must be at least 1, got %d and %d" % (n_iters, S))
+    if not (0.0 <= float(l1_coeff) < float("inf") and 0.0 <= float(tv_coeff) < float("inf")):
+        raise ValueError("l1_coeff and tv_coeff must be finite and not negative, got %r and %r" % (l1_coeff, tv_coeff))
+    if not 1.0 <= float(tv_beta) <= 64.0:
+        raise ValueError("tv_beta must lie inside [1, 64], got %r" % (tv_beta,))
+    if not 0.0 <= float(sigma) < float("inf"):
+        raise ValueError("sigma must be finite and not negative, got %r" % (sigma,))
+    if not 0.0 <= float(alpha) < float("inf"):
+        raise ValueError("alpha must be finite and not negative, got %r" % (alpha,))
+    ladder = igos_ladder(step0, shrink, min_step)
+    T1 = len(ladder)
+    if (n_iters + 1) * S >= 1 << 31:
+        raise ValueError("n_iters * n_steps = %d noise samples are past 2^31" % (n_iters * S))
+    x, batch = _check_images_batch(images, batch)
+    B, C, H, W = x.shape
+    hm, wm = _igos_size(size, H, W)
+    if baseline is not None:
+        if not torch.is_tensor(baseline) or tuple(baseline.shape) not in ((C, H, W), (B, C, H, W)):
+            raise ValueError("baseline must be None, [%d, %d, %d] or [%d, %d, %d, %d], got %s"
+                             % (C, H, W, B, C, H, W, tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__))
+    else:
+        taps = gaussian_taps(blur_klen, blur_sigma)
+    if init is not None:
+        if not torch.is_tensor(init) or not (tuple(init.shape) == (hm, wm) or
+                                             (init.dim() == 4 and tuple(init.shape[2:]) == (hm, wm) and init.shape[0] == B)):
+            raise ValueError("init must be None, [%d, %d] or [B = %d, K, %d, %d], got %s"
+                             % (hm, wm, B, hm, wm, tuple(init.shape) if torch.is_tensor(init) else type(init).__name__))
+    n_out = _num_outputs(model, x)
+    per_image, cols = _class_columns(classes, B, n_out)
+    R = 1 if per_image else len(cols)
+    if init is not None and init.dim() == 4 and init.shape[1] != R:
+        raise ValueError("init must be None, [%d, %d] or [B = %d, K = %d, %d, %d], got %s" % (hm, wm, B, R, hm, wm, tuple(init.shape)))
+    dev = x.device
+    pmasks = torch.ones((B, R, hm, wm), dtype=torch.float32, device=dev)
+    if init is not None:
+        pmasks.copy_(init.detach().to(dev, dtype=torch.float32).reshape((B, R, hm, wm) if init.dim() == 4 else (1, 1, hm, wm))
+                     .expand(B, R, hm, wm))
+    masks = torch.empty((B, R, H, W), dtype=torch.float32, device=dev)
+    curves = torch.zeros((B, R, n_iters, 4), dtype=torch.float64, device=dev)
+    if R == 0:
+        return IgosMasks(masks, pmasks, curves)
+    if baseline is not None:
+        baseline = baseline.detach().to(dev, dtype=torch.float32).contiguous()
+    else:
+        taps = taps.to(dev)
+    rows = min(batch, R * max(S, T1))
+    buf = torch.empty((rows, C, H, W), dtype=torch.float32, device=dev)
+    seed_rows = torch.empty((min(rows, R * S), n_out), dtype=torch.float32, device=dev)
+    probs = torch.empty((1, seed_rows.shape[0]), dtype=torch.float32, device=dev)     # (extremal_seed's rewards: not kept)
+    acc = torch.empty((R, H, W), dtype=torch.float64, device=dev)
+    dmask = torch.empty((R, hm, wm), dtype=torch.float32, device=dev)
+    stats = torch.empty((R, 2), dtype=torch.float64, device=dev)
+    logp_all = torch.empty((R * T1, n_out), dtype=torch.float32, device=dev)
+    l1 = torch.empty((R,), dtype=torch.float32, device=dev)
+    steps = torch.tensor(ladder, dtype=torch.float64).to(torch.float32).to(dev)
+    with _eval_mode(model), torch.enable_grad():
+        for b in range(B):
+            cb = cols[b:b + 1] if per_image else cols
+            cols_rows = torch.tensor(cb, dtype=torch.int32).to(dev)
+            cols_path = torch.tensor([c for c in cb for _ in range(S)], dtype=torch.int32).to(dev)
+            base = K.separable_filter(x[b], taps) if baseline is None else baseline if baseline.dim() == 3 else baseline[b]
+            pm = pmasks[b]
+            l1.fill_(float(l1_coeff))
+            for it in range(n_iters):
+                acc.zero_()
+                for first in range(0, R * S, batch):
+                    n = min(batch, R * S - first)
+                    leaf = K.igos_path_images(x[b], base, pm, buf[:n], first, S, sigma, seed, it * S).detach().requires_grad_(True)
+                    out = model(leaf)
+                    logp = out.detach()
+                    logp = logp if logp.dtype == torch.float32 and logp.is_contiguous() else logp.float().contiguous()
+                    K.extremal_seed(logp, cols_path[first:first + n], seed_rows[:n], probs[:, :n], 0, "delete")
+                    g = torch.autograd.grad(out, leaf, seed_rows[:n].to(out.dtype))[0]
+                    g = g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()
+                    K.igos_accumulate(x[b], base, g, acc, first, S)
+                    del out, leaf, g
+                K.igos_mask_grad(pm, acc, l1, dmask, stats, tv_coeff, tv_beta)
+                with torch.no_grad():
+                    for first in range(0, R * T1, batch):
+                        n = min(batch, R * T1 - first)
+                        logp_all[first:first + n].copy_(model(K.igos_trial_images(x[b], base, pm, dmask, steps, buf[:n], first)))
+                K.igos_step(pm, dmask, steps, logp_all, cols_rows, stats, l1, curves[b], it, n_iters, alpha, tv_coeff, tv_beta,
+                            adapt_l1)
+            K.igos_upsample(pm, masks[b])
+    return IgosMasks(masks, pmasks, curves)
+
+
+def igos_saliency(model, images, classes=None, **kwargs):
+    """The masks of `igos` (its other keyword arguments pass through) as one FLOAT saliency map per class, fp32 [B, K, H, W] on
+    the device: 1 - masks, large where the evidence is.  The reference draws -mask + 2 max(mask), which the min-max scaling of
+    the drawing steps reduces to the same map."""
+    return 1.0 - igos(model, images, classes, **kwargs).masks
+
+
+def igos_maps(model, images, classes=None, min_level=0.0, **kwargs):
+    """uint8 I-GOS heat maps [B, K, H, W] on the device: `igos_saliency`, then the drawing steps of `rise_maps` at the maps' own
+    size (kernels.heat_maps)."""
+    return K.heat_maps(igos_saliency(model, images, classes, **kwargs), min_level)
