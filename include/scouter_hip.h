@@ -365,6 +365,37 @@ int scouter_scorecam_mask_images_f32(const float* image, const float* feat, cons
 int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges, float* acc,
                                     int first, int n, int n_classes, int K, int h, int w, int C, void* stream);
 
+/* ---- SS-CAM (Wang et al. 2020) and IS-CAM (Naidu et al. 2020), the SSCAM / ISSCAM of the reference's torchcam_vis.py: loops over
+ * Score-CAM (csrc/sscam.hip, tools/attribution.py sscam / iscam).  feat, ranges, mask_c, live and dead are Score-CAM's, with its
+ * limits and error codes.  Every channel's mask goes through the model n_samples = N times; the N * C rows of an image form ONE
+ * flat stream, row r = sample j = r / C, channel c = r % C, and a call takes n <= C consecutive rows from first_row, which may
+ * straddle a sample boundary but never hold a channel twice.  One fixed order per output element and no atomics: bit-identical
+ * run to run and for any split of the stream into chunks.
+ *
+ * out fp32 [n][Cin][H][W], row first_row + i: out[i][ch][y][x] = image[ch][y][x] * g, g = a + nz, a = scale_j * mask_c(y, x),
+ * nz = sigma * z(seed, j, e), e = ch * H * W + y * W + x -- two products, then ONE sum fused with neither, then the product with
+ * the image, all fp32 with no contraction.  scale_j = 1, or with ramp != 0 (IS-CAM) (float)((double)(j + 1) * (j + 2) / (2 * N)),
+ * the partial sum of (t + 1) / N over t <= j.  z is the standard normal scouter_noise_images_f32 gives for (seed, sample j,
+ * element e): it depends on the sample and the image element, not on the channel c.  sigma == 0: no noise is formed and
+ * out = image * a, which with ramp == 0 is scouter_scorecam_mask_images_f32 bit for bit.  A dead channel writes zeros, noise or
+ * not.  16-byte accesses when W is a multiple of 4 and image / out are 16-byte aligned, one pixel per thread otherwise; both
+ * give the same bits.  n < 1, n > C, n_samples < 1, rows outside [0, N * C), sigma negative, NaN or infinite: SC_ERR_ARG;
+ * N * C of 2^31 or more: SC_ERR_UNSUPPORTED. */
+int scouter_sscam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out, int first_row, int n,
+                                  int n_samples, int ramp, float sigma, int seed_lo, int seed_hi, int Cin, int H, int W, int h,
+                                  int w, int C, void* stream);
+/* wsum fp64 [C][K], wsum[c][k] += (double)expf(logp[i][cols[k]]) with c = (first_row + i) % C, for logp fp32 [n][n_classes] (the
+ * model's output for the n rows scouter_sscam_mask_images_f32 wrote at the same first_row) and cols i32 [K] in [0, n_classes)
+ * (checked by the caller, who holds them on the host; clamped here).  One thread per (i, k) and n <= C (above: SC_ERR_ARG), so
+ * no two threads meet: the sum of a (channel, class) runs in stream order whatever the chunking.  wsum is 8-byte aligned. */
+int scouter_sscam_weights_f64(const float* logp, const int* cols, double* wsum, int first_row, int n, int n_classes, int K, int C,
+                              void* stream);
+/* out fp32 [K][h][w] = sum_c live_c * (float)(wsum[c][k] * norm) * feat[p][c]: the weight is rounded from fp64 ONCE, then the fma
+ * chain of scouter_scorecam_accumulate_f32 runs from 0 over the live channels in ascending order -- after one sample and with
+ * norm = 1 the bits of that call onto a zero acc.  out is overwritten.  norm must be finite. */
+int scouter_sscam_contract_f32(const double* wsum, const float* feat, const float* ranges, float* out, double norm, int K, int h,
+                               int w, int C, void* stream);
+
 /* ---- Path and noise batches for the gradient methods that need many gradients per image: Integrated Gradients (Sundararajan
  * et al., ICML 2017) and SmoothGrad / VarGrad (Smilkov et al. 2017; Adebayo et al. 2018), captum's IntegratedGradients and
  * NoiseTunnel of the reference's captum_vis.py (csrc/pathgrad.hip, tools/attribution.py integrated_gradients / smoothgrad).

@@ -27,25 +27,9 @@
 //   of one call.  The weights of SC_NP channels at a time are staged in LDS, so n is unbounded.
 #include "attr_common.h"
 
-constexpr int SC_MAX_SRC = 1024;              // source positions h w per channel (they live in LDS)
+// (SC_MAX_SRC, SC_THREADS, SC_KT, SC_NP, sc_value, sc_scale, sc_live, sc_mask, sc_add_live and sc_check_geometry live in
+// attr_common.h: sscam.hip forms the same masks and the same fma chain)
 constexpr int SC_TC = 8, SC_RANGE_THREADS = SC_TC * 64;      // channels per workgroup of the range kernel, one wave each
-constexpr int SC_THREADS = 256;
-constexpr int SC_KT = 16;                     // classes per thread (accumulators in registers)
-constexpr int SC_NP = 32;                     // channels whose weights are staged in LDS at a time
-
-// bilinear value at column (x0, x1, tx) of the two source rows r0 / r1 (LDS) with row weight ty
-__device__ __forceinline__ float sc_value(const float* __restrict__ r0, const float* __restrict__ r1, float ty, int x0, int x1,
-                                          float tx) {
-    return at_bilerp(r0[x0], r0[x1], r1[x0], r1[x1], tx, ty);
-}
-
-// in / out of one axis: the scale every kernel hands to at_source
-__device__ __forceinline__ float sc_scale(int in, int out) { return (float)in / (float)out; }
-
-__device__ __forceinline__ bool sc_live(float lo, float hi) { return hi - lo > 0.f; }      // (false with a NaN / infinity)
-
-// the mask value of a live channel: (U - lo) / span, span = hi - lo
-__device__ __forceinline__ float sc_mask(float u, float lo, float span) { return (u - lo) / span; }
 
 __global__ __launch_bounds__(SC_RANGE_THREADS) void scorecam_ranges_kernel(const float* __restrict__ feat,
                                                                            float* __restrict__ ranges, int h, int w, int C,
@@ -84,15 +68,6 @@ __global__ __launch_bounds__(SC_RANGE_THREADS) void scorecam_ranges_kernel(const
         ranges[2 * (long)c] = lo;
         ranges[2 * (long)c + 1] = hi;
     }
-}
-
-static int sc_check_geometry(const char* what, int h, int w, int C) {
-    SC_REQUIRE(h > 0 && w > 0 && C > 0, "%s: bad arguments (h %d, w %d, C %d: each must be at least 1)", what, h, w, C);
-    SC_UNSUPPORTED((long)h * w <= SC_MAX_SRC, "%s: source map %d x %d (a channel lives in LDS: at most %d positions)", what, h, w,
-                   SC_MAX_SRC);
-    SC_UNSUPPORTED((long)h * w * C < (1L << 31), "%s: features of %d x %d x %d elements are past the 32-bit offsets", what, h, w,
-                   C);
-    return SC_OK;
 }
 
 extern "C" int scouter_scorecam_ranges_f32(const float* feat, float* ranges, int h, int w, int C, int H, int W, void* stream) {
@@ -212,14 +187,7 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_accumulate_kernel(const f
             s_live[tid] = sc_live(ranges[2 * c], ranges[2 * c + 1]) ? 1 : 0;
         }
         __syncthreads();
-        if (mine) {
-            for (int j = 0; j < np; ++j) {
-                if (!s_live[j]) continue;                       // (uniform over the workgroup)
-                const float v = f[n0 + j];
-#pragma unroll
-                for (int k = 0; k < SC_KT; ++k) a[k] = fmaf(s_w[j][k], v, a[k]);
-            }
-        }
+        if (mine) sc_add_live(f + n0, s_w, s_live, np, a);
     }
     if (mine) at_store_acc<SC_KT>(acc, hw, p, k0, kt, a);
 }

@@ -2015,6 +2015,61 @@ def scorecam_accumulate(logp, cols, feat, ranges, acc, first):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# SS-CAM and IS-CAM (csrc/sscam.hip; tools/attribution.py sscam / iscam): loops over Score-CAM
+# ---------------------------------------------------------------------------------------------------------------
+def sscam_mask_images(image, feat, ranges, out, first_row, n_samples, sigma=0.0, seed=0, ramp=False):
+    """Rows first_row .. first_row + n - 1 of the flat stream of n_samples * C rows (row r = sample j = r // C, channel c = r % C)
+    for fp32 image [Cin, H, W], feat [h, w, C], ranges [C, 2] of scorecam_ranges at the same H x W and fp32 out [n, Cin, H, W] (a
+    dense leading slice of a longer buffer is fine), n <= C: out[i, ch, y, x] = image[ch, y, x] * (scale_j * mask_c(y, x) +
+    sigma * z(seed, j, e)), e = ch * H * W + y * W + x, two fp32 products, one sum fused with neither, one product with the
+    image.  mask_c is scorecam_mask_images'; z the value noise_images gives for (seed, sample j, element e), the same for every
+    channel; scale_j = 1, or with `ramp` (IS-CAM) float32((j + 1) * (j + 2) / (2 * n_samples)).  sigma == 0: no noise is formed;
+    with ramp False that is scorecam_mask_images bit for bit.  A dead channel gives zeros, noise or not.  One launch."""
+    _chk(image, "sscam_mask_images: image"); _chk(out, "sscam_mask_images: out")
+    if image.dim() != 3:
+        raise RuntimeError("sscam_mask_images: image must be [Cin, H, W], got shape %s" % (tuple(image.shape),))
+    Cin, H, W = image.shape
+    h, w, C = _scorecam_feat_chk("sscam_mask_images", feat, ranges)
+    if out.dim() != 4 or tuple(out.shape[1:]) != (Cin, H, W):
+        raise RuntimeError("sscam_mask_images: out must be [n, %d, %d, %d], got shape %s" % (Cin, H, W, tuple(out.shape)))
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_sscam_mask_images_f32(_p(image), _p(feat), _p(ranges), _p(out), int(first_row),
+                                                              int(out.shape[0]), int(n_samples), 1 if ramp else 0, float(sigma),
+                                                              lo, hi, Cin, H, W, h, w, C, _stream()), "sscam_mask_images")
+    return out
+
+
+def sscam_weights(logp, cols, wsum, first_row):
+    """wsum[c, k] += float64(exp(logp[i, cols[k]])) (the fp32 exp of scorecam_accumulate), c = (first_row + i) % C, for fp32 logp
+    [n, n_classes] (the model's output for the n rows of sscam_mask_images at the same first_row), cols int32 [K] on the device
+    (the caller keeps them inside [0, n_classes)) and float64 wsum [C, K], n <= C.  One thread per (i, k): chunks that cut the
+    stream anywhere give the bits of any other cut.  One launch; nothing is read on the host."""
+    _chk(logp, "sscam_weights: logp"); _chk(cols, "sscam_weights: cols", torch.int32)
+    _chk(wsum, "sscam_weights: wsum", torch.float64)
+    if logp.dim() != 2 or cols.dim() != 1 or wsum.dim() != 2 or wsum.shape[1] != cols.shape[0]:
+        raise RuntimeError("sscam_weights: logp must be [n, n_classes], cols [K] and wsum [C, K] (got %s, %s and %s)"
+                           % (tuple(logp.shape), tuple(cols.shape), tuple(wsum.shape)))
+    _native.check(_native.lib().scouter_sscam_weights_f64(_p(logp), _p(cols), _p(wsum), int(first_row), int(logp.shape[0]),
+                                                          int(logp.shape[1]), int(cols.shape[0]), int(wsum.shape[0]),
+                                                          _stream()), "sscam_weights")
+    return wsum
+
+
+def sscam_contract(wsum, feat, ranges, out, norm=1.0):
+    """out[k, p] = sum_c live_c * float32(wsum[c, k] * norm) * feat[p, c] for float64 wsum [C, K] of sscam_weights, feat
+    [h, w, C], ranges [C, 2] and fp32 out [K, h, w], which is overwritten: the weight is rounded from float64 once, then one fma per
+    live channel in ascending order from 0 -- the chain of scorecam_accumulate.  One launch."""
+    _chk(wsum, "sscam_contract: wsum", torch.float64); _chk(out, "sscam_contract: out")
+    h, w, C = _scorecam_feat_chk("sscam_contract", feat, ranges)
+    if wsum.dim() != 2 or wsum.shape[0] != C or tuple(out.shape) != (wsum.shape[1], h, w):
+        raise RuntimeError("sscam_contract: wsum must be [C = %d, K] and out [K, h = %d, w = %d] (got %s and %s)"
+                           % (C, h, w, tuple(wsum.shape), tuple(out.shape)))
+    _native.check(_native.lib().scouter_sscam_contract_f32(_p(wsum), _p(feat), _p(ranges), _p(out), float(norm),
+                                                           int(wsum.shape[1]), h, w, C, _stream()), "sscam_contract")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # path and noise batches (csrc/pathgrad.hip; tools/attribution.py integrated_gradients / smoothgrad / gradient_maps)
 # ---------------------------------------------------------------------------------------------------------------
 ATTR_IG, ATTR_MEAN, ATTR_MEAN_SQ, ATTR_VAR = 0, 1, 2, 3         # (include/scouter_hip.h SCOUTER_ATTR_*)

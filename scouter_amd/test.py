@@ -29,8 +29,13 @@ validation loader -- synthetic ones under --synthetic_data true --, at most --ib
 the reference's torchcam_vis.py); `--igos true` the per-class I-GOS maps `<out>/igos_{c}.png` (tools/attribution.py igos_maps:
 --igos_iters iterations of --igos_steps noisy path images each on a mask of --igos_size x --igos_size cells, L1 weight --igos_l1,
 total-variation weight --igos_tv, at most --igos_batch rows per pass, floored at --grad_min_level; the Integrated_Mask the
-reference's torchcam_vis.py runs first); `--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba, igos), the deletion and insertion scores of
+reference's torchcam_vis.py runs first); `--sscam true` the per-class SS-CAM heat maps `<out>/sscam_{c}.png` (tools/attribution.py
+sscam_maps: --sscam_samples noisy copies of every channel's Score-CAM mask at --sscam_sigma, --sscam_batch masked images per
+forward, floored at --grad_min_level, BatchNorm-folded under --eval_fold; torchcam's SSCAM of the reference's torchcam_vis.py);
+`--iscam true` the per-class IS-CAM heat maps `<out>/iscam_{c}.png` (tools/attribution.py iscam_maps: every mask at
+--iscam_samples scales along a ramp, --iscam_batch masked images per forward; torchcam's ISCAM, the ISSCAM that file lists);
+`--causal true` prints, for every family of maps
+drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba, igos, sscam, iscam), the deletion and insertion scores of
 the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
 `causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
 the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
@@ -50,6 +55,8 @@ jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNG
         [--extremal true --extremal_area 0.1 --extremal_iters 800 --extremal_variant preserve --extremal_batch 50] \
         [--iba true --iba_beta 10 --iba_steps 10 --iba_samples_per_step 10 --iba_sigma 1.0 --iba_fit 5000 --iba_batch 0] \
         [--igos true --igos_size 8 --igos_iters 15 --igos_steps 20 --igos_l1 1.0 --igos_tv 20.0 --igos_batch 50] \
+        [--sscam true --sscam_samples 35 --sscam_sigma 2.0 --sscam_batch 250] \
+        [--iscam true --iscam_samples 10 --iscam_batch 250] \
         [--causal true --causal_step 224] \
         [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
         [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
@@ -143,6 +150,31 @@ def run_scorecam(args, model, image, out_dir):
     from .tools.attribution import scorecam_maps
     return _run_maps(args, model, image, out_dir, "scorecam",
                      functools.partial(scorecam_maps, model, batch=int(getattr(args, "scorecam_batch", 250))))
+
+
+def _sscam_kwargs(args):
+    return dict(n_samples=int(getattr(args, "sscam_samples", 35)), sigma=float(getattr(args, "sscam_sigma", 2.0)),
+                batch=int(getattr(args, "sscam_batch", 250)))
+
+
+def _iscam_kwargs(args):
+    return dict(n_samples=int(getattr(args, "iscam_samples", 10)), batch=int(getattr(args, "iscam_batch", 250)))
+
+
+def run_sscam(args, model, image, out_dir):
+    """--sscam true: the SS-CAM heat map of every class for the one image at the backbone's output (torchcam's SSCAM of the
+    reference's torchcam_vis.py: --sscam_samples noisy copies of every channel's mask at --sscam_sigma, --sscam_batch masked
+    images per forward) -> `<out>/sscam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from .tools.attribution import sscam_maps
+    return _run_maps(args, model, image, out_dir, "sscam", functools.partial(sscam_maps, model, **_sscam_kwargs(args)))
+
+
+def run_iscam(args, model, image, out_dir):
+    """--iscam true: the IS-CAM heat map of every class for the one image at the backbone's output (torchcam's ISCAM, the ISSCAM
+    of the reference's torchcam_vis.py: every channel's mask at --iscam_samples scales along a ramp, --iscam_batch masked images
+    per forward) -> `<out>/iscam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
+    from .tools.attribution import iscam_maps
+    return _run_maps(args, model, image, out_dir, "iscam", functools.partial(iscam_maps, model, **_iscam_kwargs(args)))
 
 
 def run_campp(args, model, image, out_dir):
@@ -267,11 +299,16 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
     """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
     given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
     rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
-    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck; igos: igos_saliency).  full: grad, ig and smoothgrad keep their attribution
+    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck; igos: igos_saliency; sscam: sscam;
+    iscam: iscam).  full: grad, ig and smoothgrad keep their attribution
     [n, 1, C, H, W] instead."""
     from . import kernels as K
     from .tools.attribution import extremal_saliency, gradcam, gradcampp, information_bottleneck, input_gradients, rise, scorecam
-    from .tools.attribution import igos_saliency, smooth_gradcampp
+    from .tools.attribution import igos_saliency, iscam, smooth_gradcampp, sscam
+    if family == "sscam":
+        return sscam(model, x, classes=[pred], **_sscam_kwargs(args))
+    if family == "iscam":
+        return iscam(model, x, classes=[pred], **_iscam_kwargs(args))
     if family == "slot":
         return slot_map
     if family == "grad":
@@ -306,7 +343,7 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
     mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
     integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba:
-    information_bottleneck; igos: igos_saliency), one printed
+    information_bottleneck; igos: igos_saliency; sscam: sscam; iscam: iscam), one printed
     line each; returns {family: (deletion, insertion)}."""
     from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
@@ -420,6 +457,15 @@ def get_test_parser():
     parser.add_argument("--igos_l1", default=1.0, type=float, help="weight of the L1 term of --igos")
     parser.add_argument("--igos_tv", default=20.0, type=float, help="weight of the total-variation term of --igos")
     parser.add_argument("--igos_batch", default=50, type=int, help="images per forward (and backward) of --igos")
+    parser.add_argument("--sscam", default=False, type=_flag,
+                        help="true: write the SS-CAM heat map of every class as sscam_{c}.png into --vis_dir")
+    parser.add_argument("--sscam_samples", default=35, type=int, help="noisy copies of every channel's mask of --sscam")
+    parser.add_argument("--sscam_sigma", default=2.0, type=float, help="standard deviation of the noise of --sscam")
+    parser.add_argument("--sscam_batch", default=250, type=int, help="masked images per forward of --sscam")
+    parser.add_argument("--iscam", default=False, type=_flag,
+                        help="true: write the IS-CAM heat map of every class as iscam_{c}.png into --vis_dir")
+    parser.add_argument("--iscam_samples", default=10, type=int, help="scales of every channel's mask of --iscam")
+    parser.add_argument("--iscam_batch", default=250, type=int, help="masked images per forward of --iscam")
     parser.add_argument("--infidelity", default=False, type=_flag,
                         help="true: print the infidelity of the predicted class's explanation of every family drawn")
     parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
@@ -484,10 +530,14 @@ def main():
         run_iba(args, model, image, args.vis_dir)
     if args.igos:
         run_igos(args, model, image, args.vis_dir)
+    if args.sscam:
+        run_sscam(args, model, image, args.vis_dir)
+    if args.iscam:
+        run_iscam(args, model, image, args.vis_dir)
     families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
                                 ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
                                 ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal),
-                                ("iba", args.iba), ("igos", args.igos)) if on]
+                                ("iba", args.iba), ("igos", args.igos), ("sscam", args.sscam), ("iscam", args.iscam)) if on]
     if args.causal:
         run_causal(args, model, image, pred, families, slot_map)
     if args.infidelity:

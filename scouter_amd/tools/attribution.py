@@ -33,6 +33,19 @@ on).  A mask exists only as its channel's h x w source values and its range; the
 are three HIP kernels (kernels.scorecam_ranges, kernels.scorecam_mask_images, kernels.scorecam_accumulate) and nothing comes
 to the host in between.
 
+Smoothed and integrated Score-CAM (`sscam`, `sscam_maps`, `iscam`, `iscam_maps`, `iscam_ramp`): SS-CAM (Wang et al. 2020) and
+IS-CAM (Naidu et al. 2020), the SSCAM and ISSCAM of the reference's torchcam_vis.py.  Every channel's mask goes through the model
+N times -- with Gaussian noise added to the mask (SS-CAM, 35 times at torchcam's defaults), or scaled along a ramp (IS-CAM, 10
+times) -- and the channel is weighted by the mean, or the sum, of the class probabilities: N C eval forwards per image, 71 680
+for SS-CAM on resnest26d.  The N C rows of an image form one flat stream cut into chunks that may straddle a sample boundary;
+the masked noisy batch is written straight into one reused buffer (kernels.sscam_mask_images: Score-CAM's mask expression and
+the stream of kernels.noise_images, one noise field per sample shared by all channels), the weights of every class are summed
+in float64 per (channel, class) from the one stream (kernels.sscam_weights) and contracted with the features once
+(kernels.sscam_contract, the fma chain of kernels.scorecam_accumulate), and nothing comes to the host in between.  With one
+sample and no noise both are `scorecam` bit for bit.  The docstrings of `sscam` and `iscam` are the definition and list what
+departs from torchcam: our random stream, one noise field for all images of a batch, every class from one stream, dead channels
+weighted 0, no final ReLU and no normalisation.
+
 Gradient methods that need many gradients per image (`integrated_gradients`, `smoothgrad`, `gradient_maps`, `ig_quadrature`):
 Integrated Gradients (Sundararajan et al. 2017) and SmoothGrad / SmoothGrad-squared / VarGrad (Smilkov et al. 2017), what the
 reference's captum_vis.py runs with captum's IntegratedGradients and NoiseTunnel.  The images on the path from a baseline to
@@ -469,6 +482,115 @@ def scorecam_maps(model, images, classes=None, size=None, min_level=0.0, batch=2
     all zeros."""
     H, W = _out_size(size, images)
     return K.cam_maps(scorecam(model, images, classes, batch=batch), H, W, min_level)
+
+
+def iscam_ramp(n_samples):
+    """The scales of `iscam` as fp32 [n_samples] (host): scale_j = float32((j + 1) (j + 2) / (2 N)), the partial sum of
+    (t + 1) / N over t <= j in closed form -- the reference accumulates fmap += (i + 1) / N * input * mask, so the image of step i
+    carries that partial sum.  kernels.sscam_mask_images forms the same value on the device."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    j = np.arange(n_samples, dtype=np.float64)
+    return ((j + 1.0) * (j + 2.0) / (2.0 * n_samples)).astype(np.float32)
+
+
+def _scorecam_stream(model, images, classes, n_samples, sigma, batch, seed, ramp, norm):
+    """the loop shared by sscam and iscam: per image the n_samples * C rows as one flat stream cut into chunks of min(batch, C)
+    rows, float64 weight sums per (channel, class), one contraction at the end"""
+    B, Cin, H, W = _check_images(images).shape
+    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
+    x, batch = _check_images_batch(images, batch)
+    dev = images.device
+    feat = model.feature_pass(x).features.detach()          # (the FeaturePass and its head state are dropped here)
+    feat = (feat.float() if feat.dtype != torch.float32 else feat).contiguous()
+    _, h, w, C = feat.shape
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    out = torch.zeros((B, Kc, h, w), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    rows, step = n_samples * C, min(batch, C)
+    buf = torch.empty((step, Cin, H, W), dtype=torch.float32, device=dev)
+    ranges = torch.empty((C, 2), dtype=torch.float32, device=dev)
+    wsum = torch.empty((C, Kc), dtype=torch.float64, device=dev)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            K.scorecam_ranges(feat[b], H, W, out=ranges)
+            wsum.zero_()
+            for first in range(0, rows, step):
+                chunk = K.sscam_mask_images(x[b], feat[b], ranges, buf[:min(step, rows - first)], first, n_samples, sigma, seed,
+                                            ramp)
+                K.sscam_weights(model(chunk), cb, wsum, first)
+            K.sscam_contract(wsum, feat[b], ranges, out[b], norm)
+    return out
+
+
+def sscam(model, images, classes=None, n_samples=35, sigma=2.0, batch=250, seed=0):
+    """SS-CAM (Wang et al. 2020; torchcam's SSCAM, whose defaults these are) of `images` [B, Cin, H, W] at the backbone's output
+    -> fp32 [B, K, h, w] on the images' device: `scorecam` with every channel's weight averaged over n_samples noisy copies of its
+    mask, S[b, k, p] = sum_c live_c * w[c, k] * A[b, p, c], w[c, k] = (1 / N) sum_j exp(log_prob_{j,c}[classes[k]]), log_prob_{j,c}
+    the eval-mode output for images[b] * (mask_c + sigma * z_j).  A, mask_c, live and dead are `scorecam`'s.  z_j is standard
+    normal, a function of (seed, j, image element) alone (kernels.noise_images' stream): it has the image's shape [Cin, H, W] and is
+    the same for every channel c, as in torchcam, where one draw is broadcast over all masks.  In fp32: sigma * z is one product,
+    added to the mask in one sum, times the image.  sigma is absolute (>= 0); sigma = 0 forms no noise.
+
+    The weight sums are float64 per (channel, class) in sample order and are rounded to fp32 once, w32 = float32(sum / N); then
+    the live channels are added in ascending order, one fma each, as in `scorecam`.  So sscam(n_samples=1, sigma=0) equals
+    `scorecam` bit for bit.
+
+    Per image the N * C rows form one flat stream, row r = sample r // C, channel r % C, cut into chunks of min(batch, C) rows
+    that may straddle a sample boundary (no short chunk at the end of every sample) but never hold a channel twice:
+    kernels.scorecam_ranges once, then per chunk kernels.sscam_mask_images into one reused buffer, the model under
+    torch.no_grad() in eval mode (folded when the model's inference fold is on; the caller's mode is restored) and
+    kernels.sscam_weights; kernels.sscam_contract at the end.  The same bits for any two runs.  No BatchNorm buffer moves, no
+    `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop.  classes as in `scorecam`.
+
+    What departs from torchcam: the noise comes from our Philox stream, not torch's host generator; one noise field serves all
+    images of the batch (sample j of every image); every class is weighted from the ONE stream of forwards, where the reference
+    repeats the loop, and redraws the noise, per class; a dead channel is weighted 0, where the reference divides 0 / 0 in
+    _normalize; and, as in `scorecam`, there is no final ReLU and no normalisation -- `sscam_maps` / kernels.cam_maps do both."""
+    n_samples, sigma = int(n_samples), float(sigma)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    if not 0.0 <= sigma < float("inf"):
+        raise ValueError("sigma must be finite and not negative, got %r" % (sigma,))
+    return _scorecam_stream(model, images, classes, n_samples, sigma, batch, seed, False, 1.0 / n_samples)
+
+
+def sscam_maps(model, images, classes=None, size=None, min_level=0.0, n_samples=35, sigma=2.0, batch=250, seed=0):
+    """uint8 SS-CAM heat maps [B, K, H, W] on the device: `sscam`, then the drawing steps of `scorecam_maps` in one launch
+    (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(sscam(model, images, classes, n_samples=n_samples, sigma=sigma, batch=batch, seed=seed), H, W, min_level)
+
+
+def iscam(model, images, classes=None, n_samples=10, batch=250):
+    """IS-CAM (Naidu et al. 2020; torchcam's ISCAM, whose default this is) of `images` [B, Cin, H, W] at the backbone's output ->
+    fp32 [B, K, h, w] on the images' device: `scorecam` with every channel's mask sent through the model n_samples times along
+    a ramp, S[b, k, p] = sum_c live_c * w[c, k] * A[b, p, c], w[c, k] = sum_j exp(log_prob_{j,c}[classes[k]]) -- a SUM, with no
+    division by N, as in the reference -- and log_prob_{j,c} the eval-mode output for images[b] * (scale_j * mask_c), scale_j =
+    `iscam_ramp(n_samples)[j]` (one fp32 product with the mask).  No noise and no seed.
+
+    The float64 weight sums, the flat stream of N * C rows, the kernels and the guarantees are `sscam`'s; iscam(n_samples=1)
+    equals `scorecam` bit for bit (scale_0 = 1).  classes as in `scorecam`.
+
+    What departs from torchcam: every class is weighted from the one stream of forwards (the reference repeats the loop per
+    class); a dead channel is weighted 0, where the reference divides 0 / 0 in _normalize; no final ReLU and no normalisation
+    -- `iscam_maps` / kernels.cam_maps do both.  There is no random stream to differ in, and nothing is shared between the
+    images of a batch."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    return _scorecam_stream(model, images, classes, n_samples, 0.0, batch, 0, True, 1.0)
+
+
+def iscam_maps(model, images, classes=None, size=None, min_level=0.0, n_samples=10, batch=250):
+    """uint8 IS-CAM heat maps [B, K, H, W] on the device: `iscam`, then the drawing steps of `scorecam_maps` in one launch
+    (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(iscam(model, images, classes, n_samples=n_samples, batch=batch), H, W, min_level)
 
 
 CausalScores = collections.namedtuple("CausalScores", "deletion insertion deletion_curve insertion_curve step")
