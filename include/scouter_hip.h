@@ -336,51 +336,36 @@ int scouter_causal_curve_f32(const float* logp, const int* cols, float* curve_fl
  * two ends halved, and divides by n_points - 1.  n_points < 2: SC_ERR_ARG; R above 65535 * 256: SC_ERR_UNSUPPORTED. */
 int scouter_causal_auc_f32(const float* curves, float* scores, long R, int n_points, void* stream);
 
-/* ---- Score-CAM (Wang et al., CVPR-W 2020; the gradient-free CAMs of the reference's torchcam_vis.py; csrc/scorecam.hip,
- * tools/attribution.py scorecam).  For ONE image's backbone output feat NHWC fp32 [h][w][C] and channel c:
+/* ---- The Score-CAM family: Score-CAM (Wang et al., CVPR-W 2020), SS-CAM (Wang et al. 2020) and IS-CAM (Naidu et al. 2020), the
+ * gradient-free CAMs of the reference's torchcam_vis.py (csrc/scorecam.hip, tools/attribution.py scorecam / sscam / iscam).  For
+ * ONE image's backbone output feat NHWC fp32 [h][w][C] and channel c:
  * U_c = the bilinear resize of feat[:, :, c] to H x W (F.interpolate align_corners=False, the source coordinate and the three
  * fmas of scouter_resize_bilinear_f32), lo_c / hi_c = the minimum / maximum of the fp32 values U_c(y, x) over the H * W pixels
  * (NOT the extrema of the h * w source values), span_c = hi_c - lo_c.  The channel is LIVE when span_c > 0 and its mask is
  * mask_c(y, x) = (U_c(y, x) - lo_c) / span_c -- one subtraction, then one correctly rounded division -- which attains exactly
  * 0 and exactly 1; otherwise (a constant channel, or a NaN / infinity in its range) it is DEAD: its mask is 0 everywhere and its
- * weight 0.  U and the mask are formed by the same inlined expressions in all three calls and never stored; every index is
+ * weight 0.  U and the mask are formed by the same inlined expressions wherever they are needed and never stored; every index is
  * clamped, so no feature value moves an address.  A channel's h * w source values live in LDS: h * w <= 1024, above that (or
- * features past 32-bit offsets) SC_ERR_UNSUPPORTED.  A null or misaligned (4-byte) pointer, a count below 1 or a channel range
- * outside [0, C) is SC_ERR_ARG; nothing is launched after an error.  One fixed order per output element and no atomics:
- * bit-identical run to run.
+ * features past 32-bit offsets) SC_ERR_UNSUPPORTED.  A null or misaligned (4-byte) pointer or a count below 1 is SC_ERR_ARG;
+ * nothing is launched after an error.
+ *
+ * Every channel's mask goes through the model n_samples = N times (Score-CAM: N = 1, no noise, no ramp); the N * C rows of an
+ * image form ONE flat stream, row r = sample j = r / C, channel c = r % C, and a call takes n <= C consecutive rows from
+ * first_row, which may straddle a sample boundary but never hold a channel twice.  One fixed order per output element and no
+ * atomics: bit-identical run to run and for any split of the stream into chunks.
  *
  * ranges fp32 [C][2] = (lo_c, hi_c) for every channel, one launch: a workgroup reads 8 channels for all positions coalesced along
  * C into LDS, each wave walks the H * W pixels of one channel and ends in a butterfly min / max. */
 int scouter_scorecam_ranges_f32(const float* feat, float* ranges, int h, int w, int C, int H, int W, void* stream);
-/* out fp32 [n][Cin][H][W], out[i] = image [Cin][H][W] * mask_{first + i}, 0 <= first and first + n <= C; the mask value is formed
- * once per pixel for all Cin channels; a dead channel writes zeros.  16-byte accesses when W is a multiple of 4 and image / out
- * are 16-byte aligned, one pixel per thread otherwise.  Any n >= 1. */
-int scouter_scorecam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out, int first, int n,
-                                     int Cin, int H, int W, int h, int w, int C, void* stream);
-/* acc fp32 [K][h][w] += sum_i live_{first + i} * expf(logp[i][cols[k]]) * feat[p][first + i], logp fp32 [n][n_classes] (the model's
- * output for the n images of scouter_scorecam_mask_images_f32 with the same `first`), cols i32 [K] in [0, n_classes) (checked by
- * the caller; clamped here).  Every output element belongs to one thread, which starts from the value in acc and adds one fma
- * per live channel in i order (a dead channel is skipped): no atomics, no partial sums -- splitting the channels over several
- * calls at any point gives the bits of one call.  Any n >= 1 (the weights are staged through LDS in pieces), any K >= 1. */
-int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges, float* acc,
-                                    int first, int n, int n_classes, int K, int h, int w, int C, void* stream);
-
-/* ---- SS-CAM (Wang et al. 2020) and IS-CAM (Naidu et al. 2020), the SSCAM / ISSCAM of the reference's torchcam_vis.py: loops over
- * Score-CAM (csrc/sscam.hip, tools/attribution.py sscam / iscam).  feat, ranges, mask_c, live and dead are Score-CAM's, with its
- * limits and error codes.  Every channel's mask goes through the model n_samples = N times; the N * C rows of an image form ONE
- * flat stream, row r = sample j = r / C, channel c = r % C, and a call takes n <= C consecutive rows from first_row, which may
- * straddle a sample boundary but never hold a channel twice.  One fixed order per output element and no atomics: bit-identical
- * run to run and for any split of the stream into chunks.
- *
- * out fp32 [n][Cin][H][W], row first_row + i: out[i][ch][y][x] = image[ch][y][x] * g, g = a + nz, a = scale_j * mask_c(y, x),
+/* out fp32 [n][Cin][H][W], row first_row + i: out[i][ch][y][x] = image[ch][y][x] * g, g = a + nz, a = scale_j * mask_c(y, x),
  * nz = sigma * z(seed, j, e), e = ch * H * W + y * W + x -- two products, then ONE sum fused with neither, then the product with
  * the image, all fp32 with no contraction.  scale_j = 1, or with ramp != 0 (IS-CAM) (float)((double)(j + 1) * (j + 2) / (2 * N)),
  * the partial sum of (t + 1) / N over t <= j.  z is the standard normal scouter_noise_images_f32 gives for (seed, sample j,
  * element e): it depends on the sample and the image element, not on the channel c.  sigma == 0: no noise is formed and
- * out = image * a, which with ramp == 0 is scouter_scorecam_mask_images_f32 bit for bit.  A dead channel writes zeros, noise or
- * not.  16-byte accesses when W is a multiple of 4 and image / out are 16-byte aligned, one pixel per thread otherwise; both
- * give the same bits.  n < 1, n > C, n_samples < 1, rows outside [0, N * C), sigma negative, NaN or infinite: SC_ERR_ARG;
- * N * C of 2^31 or more: SC_ERR_UNSUPPORTED. */
+ * out = image * a, which with ramp == 0 is image * mask_c exactly (Score-CAM's masked image).  The mask value is formed once
+ * per pixel for all Cin channels; a dead channel writes zeros, noise or not.  16-byte accesses when W is a multiple of 4 and
+ * image / out are 16-byte aligned, one pixel per thread otherwise; both give the same bits.  n < 1, n > C, n_samples < 1, rows
+ * outside [0, N * C), sigma negative, NaN or infinite: SC_ERR_ARG; N * C of 2^31 or more: SC_ERR_UNSUPPORTED. */
 int scouter_sscam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out, int first_row, int n,
                                   int n_samples, int ramp, float sigma, int seed_lo, int seed_hi, int Cin, int H, int W, int h,
                                   int w, int C, void* stream);
@@ -390,9 +375,10 @@ int scouter_sscam_mask_images_f32(const float* image, const float* feat, const f
  * no two threads meet: the sum of a (channel, class) runs in stream order whatever the chunking.  wsum is 8-byte aligned. */
 int scouter_sscam_weights_f64(const float* logp, const int* cols, double* wsum, int first_row, int n, int n_classes, int K, int C,
                               void* stream);
-/* out fp32 [K][h][w] = sum_c live_c * (float)(wsum[c][k] * norm) * feat[p][c]: the weight is rounded from fp64 ONCE, then the fma
- * chain of scouter_scorecam_accumulate_f32 runs from 0 over the live channels in ascending order -- after one sample and with
- * norm = 1 the bits of that call onto a zero acc.  out is overwritten.  norm must be finite. */
+/* out fp32 [K][h][w] = sum_c live_c * (float)(wsum[c][k] * norm) * feat[p][c]: the weight is rounded from fp64 ONCE (after one
+ * sample and with norm = 1 it is expf(logp) exactly), then every output element belongs to one thread, which starts from 0 and
+ * adds one fma per live channel in ascending order (a dead channel is skipped): no atomics, no partial sums.  The weights are
+ * staged through LDS in pieces: any C, any K >= 1.  out is overwritten.  norm must be finite. */
 int scouter_sscam_contract_f32(const double* wsum, const float* feat, const float* ranges, float* out, double norm, int K, int h,
                                int w, int C, void* stream);
 

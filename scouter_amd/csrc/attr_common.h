@@ -1,7 +1,8 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, sscam.hip), each defined ONCE: where two kernels promise the same bits -- heat_maps and cam_maps at the map's own size,
-// scorecam_ranges and the masks scorecam_mask_images forms, resize_bilinear and the resize inside cam_maps -- they call the
-// same inlined function here on the same operands.  Inlined functions and templates only: no kernel, no entry point, no state.
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip), each defined ONCE: where two kernels promise the same bits --
+// heat_maps and cam_maps at the map's own size, resize_bilinear and the resize inside cam_maps and scorecam_ranges -- they call
+// the same inlined function here on the same operands.  (The mask and the fma chain of the Score-CAM family have one file,
+// scorecam.hip, and are defined there.)  Inlined functions and templates only: no kernel, no entry point, no state.
 #pragma once
 #include "common.h"
 
@@ -257,38 +258,8 @@ static inline AtPixelGrid at_pixel_grid(int H, int W, int threads, uintptr_t poi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The halves the accumulate kernels share (rise_accumulate_kernel, scorecam_accumulate_kernel): KT class accumulators in
-// registers per thread that START from acc, the weights of a piece of terms staged in LDS, the class columns clamped.
-
-// s_col[k] = the clamped column of class k0 + k, k < kt (the host refuses an index outside [0, n_classes))
-template <int KT>
-__device__ __forceinline__ void at_stage_columns(const int* __restrict__ cols, int k0, int kt, int n_classes, int* s_col) {
-    const int tid = threadIdx.x;
-    if (tid < KT) {
-        int c = tid < kt ? cols[k0 + tid] : 0;
-        s_col[tid] = min(max(c, 0), n_classes - 1);
-    }
-}
-
-// s_w[j][k] = factor(expf(logp[n0 + j][s_col[k]])) for the np terms of a piece, 0 for k >= kt
-template <int KT, int THREADS, typename Factor>
-__device__ __forceinline__ void at_stage_weights(const float* __restrict__ logp, int n0, int np, int kt, int n_classes,
-                                                 const int* s_col, float (*s_w)[KT], Factor factor) {
-    for (int i = threadIdx.x; i < np * KT; i += THREADS) {
-        const int j = i / KT, k = i - j * KT;
-        s_w[j][k] = k < kt ? factor(expf(logp[(long)(n0 + j) * n_classes + s_col[k]])) : 0.f;
-    }
-}
-
-// a[k] = acc[k0 + k][p] for the kt classes of a thread that owns element p of the plane (mine), else 0 ...
-template <int KT>
-__device__ __forceinline__ void at_load_acc(const float* __restrict__ acc, long plane, long p, int k0, int kt, bool mine,
-                                            float (&a)[KT]) {
-#pragma unroll
-    for (int k = 0; k < KT; ++k) a[k] = (mine && k < kt) ? acc[(long)(k0 + k) * plane + p] : 0.f;
-}
-
-// ... and back
+// The end the class-tiled kernels share (rise_accumulate_kernel, sscam_contract_kernel): acc[k0 + k][p] = a[k] for the kt
+// classes a thread holds in registers for element p of the plane
 template <int KT>
 __device__ __forceinline__ void at_store_acc(float* __restrict__ acc, long plane, long p, int k0, int kt, const float (&a)[KT]) {
 #pragma unroll
@@ -424,47 +395,3 @@ __device__ __forceinline__ float ig_upsample_at(Cell cell, int wm, int y0, int y
     return at_bilerp(cell(y0 * wm + x0), cell(y0 * wm + x1), cell(y1 * wm + x0), cell(y1 * wm + x1), tx, ty);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Score-CAM and the loops over it (scorecam.hip, sscam.hip): what their kernels must agree on bit for bit.  The resized value of
-// a channel and its mask -- scorecam_ranges takes their extrema, scorecam_mask_images and sscam_mask_images form them -- and
-// the fma chain over the live channels, which scorecam_accumulate and sscam_contract both run.
-constexpr int SC_MAX_SRC = 1024;              // source positions h w per channel (they live in LDS)
-constexpr int SC_THREADS = 256;
-constexpr int SC_KT = 16;                     // classes per thread (accumulators in registers)
-constexpr int SC_NP = 32;                     // channels whose weights are staged in LDS at a time
-
-// bilinear value at column (x0, x1, tx) of the two source rows r0 / r1 (LDS) with row weight ty
-__device__ __forceinline__ float sc_value(const float* __restrict__ r0, const float* __restrict__ r1, float ty, int x0, int x1,
-                                          float tx) {
-    return at_bilerp(r0[x0], r0[x1], r1[x0], r1[x1], tx, ty);
-}
-
-// in / out of one axis: the scale every kernel hands to at_source
-__device__ __forceinline__ float sc_scale(int in, int out) { return (float)in / (float)out; }
-
-__device__ __forceinline__ bool sc_live(float lo, float hi) { return hi - lo > 0.f; }      // (false with a NaN / infinity)
-
-// the mask value of a live channel: (U - lo) / span, span = hi - lo
-__device__ __forceinline__ float sc_mask(float u, float lo, float span) { return (u - lo) / span; }
-
-// a[k] = fmaf(s_w[j][k], f[j], a[k]) for the np staged channels in j order, a dead one skipped (s_live: uniform over the
-// workgroup); f points at the thread's position, channel of s_w[0]
-__device__ __forceinline__ void sc_add_live(const float* __restrict__ f, const float (*s_w)[SC_KT], const int* s_live, int np,
-                                            float (&a)[SC_KT]) {
-    for (int j = 0; j < np; ++j) {
-        if (!s_live[j]) continue;
-        const float v = f[j];
-#pragma unroll
-        for (int k = 0; k < SC_KT; ++k) a[k] = fmaf(s_w[j][k], v, a[k]);
-    }
-}
-
-// the geometry every call of the family refuses: a channel's h w source values live in LDS, offsets are 32-bit
-static inline int sc_check_geometry(const char* what, int h, int w, int C) {
-    SC_REQUIRE(h > 0 && w > 0 && C > 0, "%s: bad arguments (h %d, w %d, C %d: each must be at least 1)", what, h, w, C);
-    SC_UNSUPPORTED((long)h * w <= SC_MAX_SRC, "%s: source map %d x %d (a channel lives in LDS: at most %d positions)", what, h, w,
-                   SC_MAX_SRC);
-    SC_UNSUPPORTED((long)h * w * C < (1L << 31), "%s: features of %d x %d x %d elements are past the 32-bit offsets", what, h, w,
-                   C);
-    return SC_OK;
-}

@@ -101,6 +101,37 @@ extern "C" int scouter_rise_mask_images_f32(const float* image, const unsigned c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The staging of rise_accumulate_kernel: the class columns clamped, the weights of a piece of masks in LDS, KT class
+// accumulators in registers per thread that START from acc (at_store_acc of attr_common.h writes them back).
+
+// s_col[k] = the clamped column of class k0 + k, k < kt (the host refuses an index outside [0, n_classes))
+template <int KT>
+__device__ __forceinline__ void rs_stage_columns(const int* __restrict__ cols, int k0, int kt, int n_classes, int* s_col) {
+    const int tid = threadIdx.x;
+    if (tid < KT) {
+        int c = tid < kt ? cols[k0 + tid] : 0;
+        s_col[tid] = min(max(c, 0), n_classes - 1);
+    }
+}
+
+// s_w[j][k] = factor(expf(logp[n0 + j][s_col[k]])) for the np terms of a piece, 0 for k >= kt
+template <int KT, int THREADS, typename Factor>
+__device__ __forceinline__ void rs_stage_weights(const float* __restrict__ logp, int n0, int np, int kt, int n_classes,
+                                                 const int* s_col, float (*s_w)[KT], Factor factor) {
+    for (int i = threadIdx.x; i < np * KT; i += THREADS) {
+        const int j = i / KT, k = i - j * KT;
+        s_w[j][k] = k < kt ? factor(expf(logp[(long)(n0 + j) * n_classes + s_col[k]])) : 0.f;
+    }
+}
+
+// a[k] = acc[k0 + k][p] for the kt classes of a thread that owns element p of the plane (mine), else 0
+template <int KT>
+__device__ __forceinline__ void rs_load_acc(const float* __restrict__ acc, long plane, long p, int k0, int kt, bool mine,
+                                            float (&a)[KT]) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k) a[k] = (mine && k < kt) ? acc[(long)(k0 + k) * plane + p] : 0.f;
+}
+
 __global__ __launch_bounds__(RS_THREADS) void rise_accumulate_kernel(const float* __restrict__ logp, const int* __restrict__ cols,
                                                                      const unsigned char* __restrict__ grids,
                                                                      const int* __restrict__ shifts, float* __restrict__ acc,
@@ -112,19 +143,19 @@ __global__ __launch_bounds__(RS_THREADS) void rise_accumulate_kernel(const float
     __shared__ int s_col[RS_KT];
     const int tid = threadIdx.x;
     const int k0 = blockIdx.y * RS_KT, kt = min(RS_KT, K - k0), ss = s * s;
-    at_stage_columns<RS_KT>(cols, k0, kt, n_classes, s_col);
+    rs_stage_columns<RS_KT>(cols, k0, kt, n_classes, s_col);
     const long plane = (long)H * W;
     const long p = (long)blockIdx.x * RS_THREADS + tid;
     const bool live = p < plane;
     const int y = live ? (int)(p / W) : 0, x = live ? (int)(p - (long)y * W) : 0;
     const float sy = rs_scale(H, s), sx = rs_scale(W, s);
     float a[RS_KT];
-    at_load_acc<RS_KT>(acc, plane, p, k0, kt, live, a);
+    rs_load_acc<RS_KT>(acc, plane, p, k0, kt, live, a);
 
     for (int n0 = 0; n0 < N; n0 += RS_NP) {
         const int np = min(RS_NP, N - n0);
         __syncthreads();                                        // (s_col is written; the previous piece is consumed)
-        at_stage_weights<RS_KT, RS_THREADS>(logp, n0, np, kt, n_classes, s_col, s_w, [scale](float e) { return scale * e; });
+        rs_stage_weights<RS_KT, RS_THREADS>(logp, n0, np, kt, n_classes, s_col, s_w, [scale](float e) { return scale * e; });
         for (int i = tid; i < np * ss; i += RS_THREADS) {
             const int j = i / ss;
             s_g[j][i - j * ss] = grids[(long)n0 * ss + i];

@@ -1,7 +1,9 @@
-// Score-CAM (Wang et al., CVPR-W 2020; the gradient-free CAM family of the reference's torchcam_vis.py): every channel of the
-// backbone's output, upsampled and min-max scaled, masks the image; the masked images go through the model and every channel
-// is weighted by the class probability its mask produced.  Three kernels, each with one fixed order per output element and no
-// atomics, so two calls give the same bits.
+// The Score-CAM family (the gradient-free CAMs of the reference's torchcam_vis.py): Score-CAM (Wang et al., CVPR-W 2020), SS-CAM
+// (Wang et al. 2020, "SS-CAM: Smoothed Score-CAM") and IS-CAM (Naidu et al. 2020, "IS-CAM: Integrated Score-CAM").  Every channel
+// of the backbone's output, upsampled and min-max scaled, masks the image; the masked images go through the model N times -- as
+// they are (Score-CAM, N = 1), with Gaussian noise added to the mask (SS-CAM) or scaled along a ramp (IS-CAM) -- and every channel
+// is weighted by the sum (the mean) of the class probabilities its masks produced.  Four kernels, each with one fixed order per
+// output element and no atomics, so two calls give the same bits.
 //
 // For one image's features feat NHWC [h][w][C] and channel c,
 //   U_c(y, x) = bilinear(feat[:, :, c], H x W, align_corners = False)
@@ -14,23 +16,92 @@
 // formed by ONE inlined expression (at_source / sc_value) and the mask by one more (sc_mask) wherever they are needed; neither
 // is ever stored: C full-resolution masks never exist.  Every index is clamped, so no feature value moves an address.
 //
+// The N C rows of an image form ONE flat stream, row r = sample j = r / C, channel c = r % C; a chunk of at most C consecutive
+// rows may straddle a sample boundary, and no two of its rows share a channel.  For row r the masked image is, in fp32 and in
+// this order with no contraction,
+//   a = scale_j mask_c(y, x)                  scale_j = 1, or with `ramp` (float)((double)(j + 1) (j + 2) / (2 N))
+//   nz = sigma z(seed, j, e)                  e = ch H W + y W + x, z the value of noise_images for (seed, sample j, element e)
+//   g = a + nz                                (one sum, fused with neither product)
+//   out[ch][y][x] = image[ch][y][x] g         (sigma == 0: no noise is formed, out = image a; without the ramp a = mask_c exactly)
+// A dead channel writes zeros, noise or not.  The noise depends on the sample and the image element, not on the channel.
+//
 // scorecam_ranges_kernel: ranges[c] = (lo_c, hi_c).  A workgroup takes SC_TC consecutive channels: it reads them for all h w
 //   positions coalesced along C into LDS (transposed, odd stride), then each wave owns a channel and walks the H W destination
 //   pixels, a butterfly min / max at the end.
-// scorecam_mask_images_kernel: out[i][ch][y][x] = image[ch][y][x] mask_{first + i}(y, x).  A workgroup belongs to ONE channel
-//   (blockIdx.x) and holds its h w source values and (lo, span) in LDS / registers; the mask value of a pixel is formed once and
-//   multiplies all Cin image channels.  W a multiple of 4 and 16-byte aligned pointers: four pixels of a row per thread, 16-byte
-//   loads and stores; anything else: one pixel per thread.  A dead channel writes zeros.
-// scorecam_accumulate_kernel: acc[k][p] += sum_i live_{first + i} expf(logp[i][cols[k]]) feat[p][first + i].  One thread per
-//   position and per tile of SC_KT classes (blockIdx.y), SC_KT accumulators in registers that START from acc and take one fma per
-//   live channel in i order (a dead channel is skipped): splitting the channels over several calls at any point gives the bits
-//   of one call.  The weights of SC_NP channels at a time are staged in LDS, so n is unbounded.
+// sscam_mask_images_kernel: a workgroup belongs to ONE row (blockIdx.x) and holds its channel's h w source values and (lo, span)
+//   in LDS / registers; the mask value of a pixel is formed once and multiplies all Cin image channels, the noise is formed once
+//   per image channel.  W a multiple of 4 and 16-byte aligned pointers: four pixels of a row per thread, 16-byte loads and stores
+//   (e is a multiple of 4 there, so the four words of one Philox counter serve them); anything else: one pixel per thread.  Both
+//   go through ss_gain, so they give the same bits.
+// sscam_weights_kernel: wsum[c][k] += (double)expf(logp[i][cols[k]]), c = (first_row + i) % C, one thread per (i, k): a chunk
+//   holds a channel at most once, so no two threads meet, and any split of the stream gives the same bits.
+// sscam_contract_kernel: out[k][p] = sum_c live_c (float)(wsum[c][k] norm) feat[p][c].  One thread per position and per tile of
+//   SC_KT classes (blockIdx.y), SC_KT accumulators in registers that start at 0 and take one fma per live channel in ascending
+//   order (sc_add_live; a dead channel is skipped), the weight rounded from fp64 once.  The weights of SC_NP channels at a time
+//   are staged in LDS, so C is unbounded.
 #include "attr_common.h"
 
-// (SC_MAX_SRC, SC_THREADS, SC_KT, SC_NP, sc_value, sc_scale, sc_live, sc_mask, sc_add_live and sc_check_geometry live in
-// attr_common.h: sscam.hip forms the same masks and the same fma chain)
+constexpr int SC_MAX_SRC = 1024;              // source positions h w per channel (they live in LDS)
+constexpr int SC_THREADS = 256;
+constexpr int SC_KT = 16;                     // classes per thread (accumulators in registers)
+constexpr int SC_NP = 32;                     // channels whose weights are staged in LDS at a time
 constexpr int SC_TC = 8, SC_RANGE_THREADS = SC_TC * 64;      // channels per workgroup of the range kernel, one wave each
 
+// bilinear value at column (x0, x1, tx) of the two source rows r0 / r1 (LDS) with row weight ty
+__device__ __forceinline__ float sc_value(const float* __restrict__ r0, const float* __restrict__ r1, float ty, int x0, int x1,
+                                          float tx) {
+    return at_bilerp(r0[x0], r0[x1], r1[x0], r1[x1], tx, ty);
+}
+
+// in / out of one axis: the scale every kernel hands to at_source
+__device__ __forceinline__ float sc_scale(int in, int out) { return (float)in / (float)out; }
+
+__device__ __forceinline__ bool sc_live(float lo, float hi) { return hi - lo > 0.f; }      // (false with a NaN / infinity)
+
+// the mask value of a live channel: (U - lo) / span, span = hi - lo
+__device__ __forceinline__ float sc_mask(float u, float lo, float span) { return (u - lo) / span; }
+
+// a[k] = fmaf(s_w[j][k], f[j], a[k]) for the np staged channels in j order, a dead one skipped (s_live: uniform over the
+// workgroup); f points at the thread's position, channel of s_w[0]
+__device__ __forceinline__ void sc_add_live(const float* __restrict__ f, const float (*s_w)[SC_KT], const int* s_live, int np,
+                                            float (&a)[SC_KT]) {
+    for (int j = 0; j < np; ++j) {
+        if (!s_live[j]) continue;
+        const float v = f[j];
+#pragma unroll
+        for (int k = 0; k < SC_KT; ++k) a[k] = fmaf(s_w[j][k], v, a[k]);
+    }
+}
+
+// the geometry every call of the family refuses: a channel's h w source values live in LDS, offsets are 32-bit
+static inline int sc_check_geometry(const char* what, int h, int w, int C) {
+    SC_REQUIRE(h > 0 && w > 0 && C > 0, "%s: bad arguments (h %d, w %d, C %d: each must be at least 1)", what, h, w, C);
+    SC_UNSUPPORTED((long)h * w <= SC_MAX_SRC, "%s: source map %d x %d (a channel lives in LDS: at most %d positions)", what, h, w,
+                   SC_MAX_SRC);
+    SC_UNSUPPORTED((long)h * w * C < (1L << 31), "%s: features of %d x %d x %d elements are past the 32-bit offsets", what, h, w,
+                   C);
+    return SC_OK;
+}
+
+// the scale of sample j of n_samples on IS-CAM's ramp: the partial sum of (t + 1) / N over t <= j, in closed form
+__device__ __forceinline__ float ss_ramp(int j, int n_samples) {
+    return (float)((double)(j + 1) * (double)(j + 2) / (2.0 * (double)n_samples));
+}
+
+// a = scale m: one product
+__device__ __forceinline__ float ss_scaled(float scale, float m) {
+#pragma clang fp contract(off)
+    return scale * m;
+}
+
+// g = a + sigma z: one product, then one sum; contraction is switched off here, or the compiler fuses the two
+__device__ __forceinline__ float ss_gain(float a, float sigma, float z) {
+#pragma clang fp contract(off)
+    const float nz = sigma * z;
+    return a + nz;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SC_RANGE_THREADS) void scorecam_ranges_kernel(const float* __restrict__ feat,
                                                                            float* __restrict__ ranges, int h, int w, int C,
                                                                            int H, int W) {
@@ -84,19 +155,22 @@ extern "C" int scouter_scorecam_ranges_f32(const float* feat, float* ranges, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool VEC>
-__global__ __launch_bounds__(SC_THREADS) void scorecam_mask_images_kernel(const float* __restrict__ image,
-                                                                          const float* __restrict__ feat,
-                                                                          const float* __restrict__ ranges,
-                                                                          float* __restrict__ out, int first, int Cin, int H,
-                                                                          int W, int h, int w, int C) {
+template <bool VEC, bool NOISE>
+__global__ __launch_bounds__(SC_THREADS) void sscam_mask_images_kernel(const float* __restrict__ image,
+                                                                       const float* __restrict__ feat,
+                                                                       const float* __restrict__ ranges, float* __restrict__ out,
+                                                                       int first_row, int n_samples, int ramp, float sigma,
+                                                                       unsigned seed_lo, unsigned seed_hi, int Cin, int H, int W,
+                                                                       int h, int w, int C) {
     __shared__ float s_src[SC_MAX_SRC];
     const int tid = threadIdx.x;
-    const int c = first + blockIdx.x;                          // (the host keeps 0 <= first and first + n <= C)
+    const int r = first_row + blockIdx.x;                      // (the host keeps 0 <= first_row and first_row + n <= N C < 2^31)
+    const int j = r / C, c = r - j * C;
     for (int p = tid; p < h * w; p += SC_THREADS) s_src[p] = feat[(long)p * C + c];
     const float lo = ranges[2 * (long)c], hi = ranges[2 * (long)c + 1];
     const float span = hi - lo;
     const bool live = sc_live(lo, hi);
+    const float scale = ramp ? ss_ramp(j, n_samples) : 1.f;
     __syncthreads();
     const float sy = sc_scale(h, H), sx = sc_scale(w, W);
     const long plane = (long)H * W;
@@ -119,99 +193,152 @@ __global__ __launch_bounds__(SC_THREADS) void scorecam_mask_images_kernel(const 
         at_source(y, sy, h, y0, y1, ty);
         const float* r0 = s_src + y0 * w;
         const float* r1 = s_src + y1 * w;
-        float m[V];
+        float a[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             int x0, x1;
             float tx;
             at_source(x + k, sx, w, x0, x1, tx);
-            m[k] = sc_mask(sc_value(r0, r1, ty, x0, x1, tx), lo, span);
+            a[k] = ss_scaled(scale, sc_mask(sc_value(r0, r1, ty, x0, x1, tx), lo, span));
         }
-        at_scale_channels<VEC>(image, o, plane, p, Cin, m);
+        if constexpr (!NOISE) {
+            at_scale_channels<VEC>(image, o, plane, p, Cin, a);
+        } else {
+            for (int ch = 0; ch < Cin; ++ch) {
+                const long e = ch * plane + p;                 // (VEC: a multiple of 4, as plane and p are)
+                float z[V], g[V];
+                ib_noise<V>(e, (unsigned)j, seed_lo, seed_hi, z);
+#pragma unroll
+                for (int k = 0; k < V; ++k) g[k] = ss_gain(a[k], sigma, z[k]);
+                at_scale_channels<VEC>(image + ch * plane, o + ch * plane, plane, p, 1, g);
+            }
+        }
     }
 }
 
-extern "C" int scouter_scorecam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out, int first,
-                                                int n, int Cin, int H, int W, int h, int w, int C, void* stream) {
-    SC_REQUIRE(image && feat && ranges && out, "scorecam_mask_images: null pointer (image %p, feat %p, ranges %p, out %p)",
+extern "C" int scouter_sscam_mask_images_f32(const float* image, const float* feat, const float* ranges, float* out,
+                                             int first_row, int n, int n_samples, int ramp, float sigma, int seed_lo, int seed_hi,
+                                             int Cin, int H, int W, int h, int w, int C, void* stream) {
+    SC_REQUIRE(image && feat && ranges && out, "sscam_mask_images: null pointer (image %p, feat %p, ranges %p, out %p)",
                (const void*)image, (const void*)feat, (const void*)ranges, (void*)out);
-    if (int rc = sc_check_geometry("scorecam_mask_images", h, w, C)) return rc;
-    SC_REQUIRE(n > 0 && Cin > 0 && H > 0 && W > 0,
-               "scorecam_mask_images: bad arguments (n %d, Cin %d, H %d, W %d: each must be at least 1)", n, Cin, H, W);
-    SC_REQUIRE(first >= 0 && (long)first + n <= C, "scorecam_mask_images: channels [%d, %ld) lie outside [0, C = %d)", first,
-               (long)first + n, C);
+    if (int rc = sc_check_geometry("sscam_mask_images", h, w, C)) return rc;
+    SC_REQUIRE(n > 0 && n_samples > 0 && Cin > 0 && H > 0 && W > 0,
+               "sscam_mask_images: bad arguments (n %d, n_samples %d, Cin %d, H %d, W %d: each must be at least 1)", n, n_samples,
+               Cin, H, W);
+    SC_REQUIRE(n <= C, "sscam_mask_images: a chunk of n = %d rows holds a channel twice (at most C = %d)", n, C);
+    SC_UNSUPPORTED((long)n_samples * C < (1L << 31), "sscam_mask_images: a stream of %d x %d rows is past the 32-bit row index",
+                   n_samples, C);
+    SC_REQUIRE(first_row >= 0 && (long)first_row + n <= (long)n_samples * C,
+               "sscam_mask_images: rows [%d, %ld) lie outside [0, n_samples C = %ld)", first_row, (long)first_row + n,
+               (long)n_samples * C);
+    SC_REQUIRE(sigma >= 0.f && sigma < INFINITY, "sscam_mask_images: sigma %g must be finite and not negative", (double)sigma);
     SC_REQUIRE((((uintptr_t)image | (uintptr_t)feat | (uintptr_t)ranges | (uintptr_t)out) & 3) == 0,
-               "scorecam_mask_images: misaligned pointer (image, feat, ranges and out must be 4-byte aligned)");
-    SC_UNSUPPORTED((long)Cin * H * W < (1L << 31), "scorecam_mask_images: image of %d x %d x %d elements is past the 32-bit offsets",
+               "sscam_mask_images: misaligned pointer (image, feat, ranges and out must be 4-byte aligned)");
+    SC_UNSUPPORTED((long)Cin * H * W < (1L << 31), "sscam_mask_images: image of %d x %d x %d elements is past the 32-bit offsets",
                    Cin, H, W);
     hipStream_t st = (hipStream_t)stream;
     const AtPixelGrid px = at_pixel_grid(H, W, SC_THREADS, (uintptr_t)image | (uintptr_t)out);
     const double elems = (double)n * Cin * H * W;
-    ScProfScope prof("scorecam_mask_images", st, elems + 18.0 * n * (double)H * W,
+    const bool noise = sigma > 0.f;
+    ScProfScope prof(noise ? "sscam_mask_images<noise>" : "sscam_mask_images", st,
+                     (noise ? 100.0 : 1.0) * elems + 19.0 * n * (double)H * W,
                      4.0 * (elems + (double)Cin * H * W + (double)n * (h * w + 2)));
     const dim3 grid((unsigned)n, px.tiles);
-    if (px.vec)
-        hipLaunchKernelGGL(scorecam_mask_images_kernel<true>, grid, dim3(SC_THREADS), 0, st, image, feat, ranges, out, first, Cin,
-                           H, W, h, w, C);
-    else
-        hipLaunchKernelGGL(scorecam_mask_images_kernel<false>, grid, dim3(SC_THREADS), 0, st, image, feat, ranges, out, first,
-                           Cin, H, W, h, w, C);
-    return sc_check_launch("scorecam_mask_images");
+    const unsigned klo = (unsigned)seed_lo, khi = (unsigned)seed_hi;
+#define SS_LAUNCH(VEC, NOISE)                                                                                                   \
+    hipLaunchKernelGGL((sscam_mask_images_kernel<VEC, NOISE>), grid, dim3(SC_THREADS), 0, st, image, feat, ranges, out, first_row, \
+                       n_samples, ramp, sigma, klo, khi, Cin, H, W, h, w, C)
+    if (px.vec) {
+        if (noise) SS_LAUNCH(true, true);
+        else SS_LAUNCH(true, false);
+    } else {
+        if (noise) SS_LAUNCH(false, true);
+        else SS_LAUNCH(false, false);
+    }
+#undef SS_LAUNCH
+    return sc_check_launch("sscam_mask_images");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SC_THREADS) void scorecam_accumulate_kernel(const float* __restrict__ logp,
-                                                                         const int* __restrict__ cols,
-                                                                         const float* __restrict__ feat,
-                                                                         const float* __restrict__ ranges,
-                                                                         float* __restrict__ acc, int first, int n, int n_classes,
-                                                                         int K, int hw, int C) {
+__global__ __launch_bounds__(SC_THREADS) void sscam_weights_kernel(const float* __restrict__ logp, const int* __restrict__ cols,
+                                                                   double* __restrict__ wsum, int first_row, int n, int n_classes,
+                                                                   int K, int C) {
+    const int t = blockIdx.x * SC_THREADS + threadIdx.x;       // (the host keeps n K < 2^31)
+    if (t >= n * K) return;
+    const int i = t / K, k = t - i * K;
+    const int col = min(max(cols[k], 0), n_classes - 1);       // (the caller refuses an index outside [0, n_classes))
+    const int c = (int)(((long)first_row + i) % C);
+    wsum[(long)c * K + k] += (double)expf(logp[(long)i * n_classes + col]);
+}
+
+extern "C" int scouter_sscam_weights_f64(const float* logp, const int* cols, double* wsum, int first_row, int n, int n_classes,
+                                         int K, int C, void* stream) {
+    SC_REQUIRE(logp && cols && wsum, "sscam_weights: null pointer (logp %p, cols %p, wsum %p)", (const void*)logp,
+               (const void*)cols, (void*)wsum);
+    SC_REQUIRE(n > 0 && n_classes > 0 && K > 0 && C > 0,
+               "sscam_weights: bad arguments (n %d, n_classes %d, K %d, C %d: each must be at least 1)", n, n_classes, K, C);
+    SC_REQUIRE(n <= C, "sscam_weights: a chunk of n = %d rows holds a channel twice (at most C = %d)", n, C);
+    SC_REQUIRE(first_row >= 0, "sscam_weights: first_row %d is negative", first_row);
+    SC_REQUIRE((((uintptr_t)logp | (uintptr_t)cols) & 3) == 0 && ((uintptr_t)wsum & 7) == 0,
+               "sscam_weights: misaligned pointer (logp and cols must be 4-byte aligned, wsum 8-byte)");
+    SC_UNSUPPORTED((long)n * K < (1L << 31) && (long)n * n_classes < (1L << 31) && (long)C * K < (1L << 31),
+                   "sscam_weights: n %d x K %d, n x n_classes %d or C %d x K elements are past the 32-bit offsets", n, K,
+                   n_classes, C);
+    hipStream_t st = (hipStream_t)stream;
+    ScProfScope prof("sscam_weights", st, 2.0 * n * K, 20.0 * n * K + 4.0 * K);
+    hipLaunchKernelGGL(sscam_weights_kernel, dim3((unsigned)sc_cdiv((long)n * K, SC_THREADS)), dim3(SC_THREADS), 0, st, logp, cols,
+                       wsum, first_row, n, n_classes, K, C);
+    return sc_check_launch("sscam_weights");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SC_THREADS) void sscam_contract_kernel(const double* __restrict__ wsum, const float* __restrict__ feat,
+                                                                    const float* __restrict__ ranges, float* __restrict__ out,
+                                                                    double norm, int K, int hw, int C) {
     __shared__ __attribute__((aligned(16))) float s_w[SC_NP][SC_KT];
     __shared__ int s_live[SC_NP];
-    __shared__ int s_col[SC_KT];
     const int tid = threadIdx.x;
     const int k0 = blockIdx.y * SC_KT, kt = min(SC_KT, K - k0);
-    at_stage_columns<SC_KT>(cols, k0, kt, n_classes, s_col);
     const int p = blockIdx.x * SC_THREADS + tid;
     const bool mine = p < hw;
-    const float* __restrict__ f = feat + (long)(mine ? p : 0) * C + first;
+    const float* __restrict__ f = feat + (long)(mine ? p : 0) * C;
     float a[SC_KT];
-    at_load_acc<SC_KT>(acc, hw, p, k0, kt, mine, a);
+#pragma unroll
+    for (int k = 0; k < SC_KT; ++k) a[k] = 0.f;
 
-    for (int n0 = 0; n0 < n; n0 += SC_NP) {
-        const int np = min(SC_NP, n - n0);
-        __syncthreads();                                        // (s_col is written; the previous piece is consumed)
-        at_stage_weights<SC_KT, SC_THREADS>(logp, n0, np, kt, n_classes, s_col, s_w, [](float e) { return e; });
+    for (int c0 = 0; c0 < C; c0 += SC_NP) {
+        const int np = min(SC_NP, C - c0);
+        __syncthreads();                                        // (the previous piece is consumed)
+        for (int i = tid; i < np * SC_KT; i += SC_THREADS) {
+            const int j = i / SC_KT, k = i - j * SC_KT;
+            s_w[j][k] = k < kt ? (float)(wsum[(long)(c0 + j) * K + k0 + k] * norm) : 0.f;
+        }
         if (tid < np) {
-            const long c = (long)first + n0 + tid;
+            const long c = (long)c0 + tid;
             s_live[tid] = sc_live(ranges[2 * c], ranges[2 * c + 1]) ? 1 : 0;
         }
         __syncthreads();
-        if (mine) sc_add_live(f + n0, s_w, s_live, np, a);
+        if (mine) sc_add_live(f + c0, s_w, s_live, np, a);
     }
-    if (mine) at_store_acc<SC_KT>(acc, hw, p, k0, kt, a);
+    if (mine) at_store_acc<SC_KT>(out, hw, p, k0, kt, a);
 }
 
-extern "C" int scouter_scorecam_accumulate_f32(const float* logp, const int* cols, const float* feat, const float* ranges,
-                                               float* acc, int first, int n, int n_classes, int K, int h, int w, int C,
-                                               void* stream) {
-    SC_REQUIRE(logp && cols && feat && ranges && acc,
-               "scorecam_accumulate: null pointer (logp %p, cols %p, feat %p, ranges %p, acc %p)", (const void*)logp,
-               (const void*)cols, (const void*)feat, (const void*)ranges, (void*)acc);
-    if (int rc = sc_check_geometry("scorecam_accumulate", h, w, C)) return rc;
-    SC_REQUIRE(n > 0 && n_classes > 0 && K > 0,
-               "scorecam_accumulate: bad arguments (n %d, n_classes %d, K %d: each must be at least 1)", n, n_classes, K);
-    SC_REQUIRE(first >= 0 && (long)first + n <= C, "scorecam_accumulate: channels [%d, %ld) lie outside [0, C = %d)", first,
-               (long)first + n, C);
-    SC_REQUIRE((((uintptr_t)logp | (uintptr_t)cols | (uintptr_t)feat | (uintptr_t)ranges | (uintptr_t)acc) & 3) == 0,
-               "scorecam_accumulate: misaligned pointer (logp, cols, feat, ranges and acc must be 4-byte aligned)");
+extern "C" int scouter_sscam_contract_f32(const double* wsum, const float* feat, const float* ranges, float* out, double norm,
+                                          int K, int h, int w, int C, void* stream) {
+    SC_REQUIRE(wsum && feat && ranges && out, "sscam_contract: null pointer (wsum %p, feat %p, ranges %p, out %p)",
+               (const void*)wsum, (const void*)feat, (const void*)ranges, (void*)out);
+    if (int rc = sc_check_geometry("sscam_contract", h, w, C)) return rc;
+    SC_REQUIRE(K > 0, "sscam_contract: bad arguments (K %d must be at least 1)", K);
+    SC_REQUIRE(norm == norm && norm - norm == 0.0, "sscam_contract: norm %g must be finite", norm);
+    SC_REQUIRE((((uintptr_t)feat | (uintptr_t)ranges | (uintptr_t)out) & 3) == 0 && ((uintptr_t)wsum & 7) == 0,
+               "sscam_contract: misaligned pointer (feat, ranges and out must be 4-byte aligned, wsum 8-byte)");
     const int ktiles = sc_cdiv(K, SC_KT);
-    SC_UNSUPPORTED(ktiles <= 65535, "scorecam_accumulate: K = %d classes (at most %d)", K, 65535 * SC_KT);
+    SC_UNSUPPORTED(ktiles <= 65535, "sscam_contract: K = %d classes (at most %d)", K, 65535 * SC_KT);
+    SC_UNSUPPORTED((long)C * K < (1L << 31), "sscam_contract: weights of %d x %d elements are past the 32-bit offsets", C, K);
     hipStream_t st = (hipStream_t)stream;
     const double px = (double)h * w;
-    ScProfScope prof("scorecam_accumulate", st, 2.0 * n * px * ktiles * SC_KT,
-                     8.0 * K * px + 4.0 * n * ((double)n_classes + px + 2.0));
-    hipLaunchKernelGGL(scorecam_accumulate_kernel, dim3((unsigned)sc_cdiv((long)h * w, SC_THREADS), (unsigned)ktiles),
-                       dim3(SC_THREADS), 0, st, logp, cols, feat, ranges, acc, first, n, n_classes, K, h * w, C);
-    return sc_check_launch("scorecam_accumulate");
+    ScProfScope prof("sscam_contract", st, 2.0 * C * px * ktiles * SC_KT, 4.0 * K * px + 8.0 * C * K + 4.0 * C * (px + 2.0));
+    hipLaunchKernelGGL(sscam_contract_kernel, dim3((unsigned)sc_cdiv((long)h * w, SC_THREADS), (unsigned)ktiles), dim3(SC_THREADS),
+                       0, st, wsum, feat, ranges, out, norm, K, h * w, C);
+    return sc_check_launch("sscam_contract");
 }

@@ -1947,7 +1947,7 @@ def causal_auc(curves, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Score-CAM (csrc/scorecam.hip; tools/attribution.py scorecam / scorecam_maps)
+# The Score-CAM family: Score-CAM, SS-CAM and IS-CAM (csrc/scorecam.hip; tools/attribution.py scorecam / sscam / iscam)
 # ---------------------------------------------------------------------------------------------------------------
 def _scorecam_feat_chk(what, feat, ranges):
     """feat fp32 [h, w, C] (one image's NHWC features) and, when given, ranges fp32 [C, 2] -> (h, w, C)"""
@@ -1965,7 +1965,7 @@ def _scorecam_feat_chk(what, feat, ranges):
 def scorecam_ranges(feat, H, W, out=None):
     """fp32 feat [h, w, C] (one image's NHWC features) -> fp32 [C, 2] = (lo_c, hi_c): the minimum and maximum of channel c
     resized bilinearly to H x W (align_corners=False), taken over the H * W fp32 values of the resized channel -- the ones
-    scorecam_mask_images forms -- not over the h * w source values.  A channel is live when hi - lo > 0.  h * w <= 1024 (a
+    sscam_mask_images forms -- not over the h * w source values.  A channel is live when hi - lo > 0.  h * w <= 1024 (a
     channel's source lives in LDS).  One launch; the resized channel is never stored."""
     h, w, C = _scorecam_feat_chk("scorecam_ranges", feat, None)
     if out is None:
@@ -1978,53 +1978,16 @@ def scorecam_ranges(feat, H, W, out=None):
     return out
 
 
-def scorecam_mask_images(image, feat, ranges, out, first):
-    """out[i, ch] = image[ch] * mask_{first + i} for fp32 image [Cin, H, W], feat [h, w, C], ranges [C, 2] of scorecam_ranges at
-    the same H x W and fp32 out [n, Cin, H, W] (a dense leading slice of a longer buffer is fine), 0 <= first and
-    first + n <= C.  mask_c = (U_c - lo_c) / (hi_c - lo_c) with U_c the bilinear resize of channel c, formed in registers,
-    never stored; a dead channel (hi_c - lo_c > 0 is false) gives zeros.  One launch."""
-    _chk(image, "scorecam_mask_images: image"); _chk(out, "scorecam_mask_images: out")
-    if image.dim() != 3:
-        raise RuntimeError("scorecam_mask_images: image must be [Cin, H, W], got shape %s" % (tuple(image.shape),))
-    Cin, H, W = image.shape
-    h, w, C = _scorecam_feat_chk("scorecam_mask_images", feat, ranges)
-    if out.dim() != 4 or tuple(out.shape[1:]) != (Cin, H, W):
-        raise RuntimeError("scorecam_mask_images: out must be [n, %d, %d, %d], got shape %s" % (Cin, H, W, tuple(out.shape)))
-    _native.check(_native.lib().scouter_scorecam_mask_images_f32(_p(image), _p(feat), _p(ranges), _p(out), int(first),
-                                                                 int(out.shape[0]), Cin, H, W, h, w, C, _stream()),
-                  "scorecam_mask_images")
-    return out
-
-
-def scorecam_accumulate(logp, cols, feat, ranges, acc, first):
-    """acc[k, p] += sum_i live_{first + i} * exp(logp[i, cols[k]]) * feat[p, first + i] for fp32 logp [n, n_classes] (the model's
-    output for the n images of scorecam_mask_images at the same `first`), cols int32 [K] on the device (the caller keeps them
-    inside [0, n_classes)), feat [h, w, C], ranges [C, 2] and fp32 acc [K, h, w].  One thread per element adds the live channels
-    one fma at a time in i order onto the value in acc: calls over consecutive pieces of the channels give the bits of one
-    call.  One launch; nothing is read on the host."""
-    _chk(logp, "scorecam_accumulate: logp"); _chk(cols, "scorecam_accumulate: cols", torch.int32)
-    _chk(acc, "scorecam_accumulate: acc")
-    h, w, C = _scorecam_feat_chk("scorecam_accumulate", feat, ranges)
-    if logp.dim() != 2 or cols.dim() != 1 or tuple(acc.shape) != (cols.shape[0], h, w):
-        raise RuntimeError("scorecam_accumulate: logp must be [n, n_classes], cols [K] and acc [K, h = %d, w = %d] (got %s, %s "
-                           "and %s)" % (h, w, tuple(logp.shape), tuple(cols.shape), tuple(acc.shape)))
-    _native.check(_native.lib().scouter_scorecam_accumulate_f32(_p(logp), _p(cols), _p(feat), _p(ranges), _p(acc), int(first),
-                                                                int(logp.shape[0]), int(logp.shape[1]), int(cols.shape[0]),
-                                                                h, w, C, _stream()), "scorecam_accumulate")
-    return acc
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# SS-CAM and IS-CAM (csrc/sscam.hip; tools/attribution.py sscam / iscam): loops over Score-CAM
-# ---------------------------------------------------------------------------------------------------------------
 def sscam_mask_images(image, feat, ranges, out, first_row, n_samples, sigma=0.0, seed=0, ramp=False):
     """Rows first_row .. first_row + n - 1 of the flat stream of n_samples * C rows (row r = sample j = r // C, channel c = r % C)
     for fp32 image [Cin, H, W], feat [h, w, C], ranges [C, 2] of scorecam_ranges at the same H x W and fp32 out [n, Cin, H, W] (a
     dense leading slice of a longer buffer is fine), n <= C: out[i, ch, y, x] = image[ch, y, x] * (scale_j * mask_c(y, x) +
     sigma * z(seed, j, e)), e = ch * H * W + y * W + x, two fp32 products, one sum fused with neither, one product with the
-    image.  mask_c is scorecam_mask_images'; z the value noise_images gives for (seed, sample j, element e), the same for every
-    channel; scale_j = 1, or with `ramp` (IS-CAM) float32((j + 1) * (j + 2) / (2 * n_samples)).  sigma == 0: no noise is formed;
-    with ramp False that is scorecam_mask_images bit for bit.  A dead channel gives zeros, noise or not.  One launch."""
+    image.  mask_c = (U_c - lo_c) / (hi_c - lo_c) with U_c the bilinear resize of channel c (align_corners=False), formed in
+    registers, never stored; z the value noise_images gives for (seed, sample j, element e), the same for every channel;
+    scale_j = 1, or with `ramp` (IS-CAM) float32((j + 1) * (j + 2) / (2 * n_samples)).  sigma == 0: no noise is formed; with ramp
+    False that is image[ch] * mask_c exactly, Score-CAM's masked image (n_samples = 1: row r is channel r).  A dead channel
+    (hi_c - lo_c > 0 is false) gives zeros, noise or not.  One launch."""
     _chk(image, "sscam_mask_images: image"); _chk(out, "sscam_mask_images: out")
     if image.dim() != 3:
         raise RuntimeError("sscam_mask_images: image must be [Cin, H, W], got shape %s" % (tuple(image.shape),))
@@ -2040,7 +2003,7 @@ def sscam_mask_images(image, feat, ranges, out, first_row, n_samples, sigma=0.0,
 
 
 def sscam_weights(logp, cols, wsum, first_row):
-    """wsum[c, k] += float64(exp(logp[i, cols[k]])) (the fp32 exp of scorecam_accumulate), c = (first_row + i) % C, for fp32 logp
+    """wsum[c, k] += float64(exp(logp[i, cols[k]])) (the exp in fp32, then widened), c = (first_row + i) % C, for fp32 logp
     [n, n_classes] (the model's output for the n rows of sscam_mask_images at the same first_row), cols int32 [K] on the device
     (the caller keeps them inside [0, n_classes)) and float64 wsum [C, K], n <= C.  One thread per (i, k): chunks that cut the
     stream anywhere give the bits of any other cut.  One launch; nothing is read on the host."""
@@ -2057,8 +2020,8 @@ def sscam_weights(logp, cols, wsum, first_row):
 
 def sscam_contract(wsum, feat, ranges, out, norm=1.0):
     """out[k, p] = sum_c live_c * float32(wsum[c, k] * norm) * feat[p, c] for float64 wsum [C, K] of sscam_weights, feat
-    [h, w, C], ranges [C, 2] and fp32 out [K, h, w], which is overwritten: the weight is rounded from float64 once, then one fma per
-    live channel in ascending order from 0 -- the chain of scorecam_accumulate.  One launch."""
+    [h, w, C], ranges [C, 2] and fp32 out [K, h, w], which is overwritten: the weight is rounded from float64 once, then one
+    thread per element adds the live channels (hi_c - lo_c > 0) one fma at a time in ascending order from 0.  One launch."""
     _chk(wsum, "sscam_contract: wsum", torch.float64); _chk(out, "sscam_contract: out")
     h, w, C = _scorecam_feat_chk("sscam_contract", feat, ranges)
     if wsum.dim() != 2 or wsum.shape[0] != C or tuple(out.shape) != (wsum.shape[1], h, w):

@@ -29,9 +29,10 @@ the reference's torchcam_vis.py (SS-CAM, IS-CAM) are loops over.  Every channel 
 reads -- is resized to the image, min-max scaled to [0, 1] and multiplied onto the image; every masked image goes through the
 model, and every channel is weighted by the class probability its mask produced.  No gradient: one feature pass and one eval
 forward per channel (512 for resnet18, 2048 for resnest26d / resnest50d; BatchNorm-folded when the model's inference fold is
-on).  A mask exists only as its channel's h x w source values and its range; the ranges, the masked batch and the weighted sum
-are three HIP kernels (kernels.scorecam_ranges, kernels.scorecam_mask_images, kernels.scorecam_accumulate) and nothing comes
-to the host in between.
+on).  A mask exists only as its channel's h x w source values and its range; the ranges, the masked batch, the weights and the
+weighted sum are four HIP kernels (kernels.scorecam_ranges, kernels.sscam_mask_images, kernels.sscam_weights,
+kernels.sscam_contract) and nothing comes to the host in between.  It is the one-sample row of the stream SS-CAM and IS-CAM run
+on, below.
 
 Smoothed and integrated Score-CAM (`sscam`, `sscam_maps`, `iscam`, `iscam_maps`, `iscam_ramp`): SS-CAM (Wang et al. 2020) and
 IS-CAM (Naidu et al. 2020), the SSCAM and ISSCAM of the reference's torchcam_vis.py.  Every channel's mask goes through the model
@@ -41,10 +42,10 @@ for SS-CAM on resnest26d.  The N C rows of an image form one flat stream cut int
 the masked noisy batch is written straight into one reused buffer (kernels.sscam_mask_images: Score-CAM's mask expression and
 the stream of kernels.noise_images, one noise field per sample shared by all channels), the weights of every class are summed
 in float64 per (channel, class) from the one stream (kernels.sscam_weights) and contracted with the features once
-(kernels.sscam_contract, the fma chain of kernels.scorecam_accumulate), and nothing comes to the host in between.  With one
-sample and no noise both are `scorecam` bit for bit.  The docstrings of `sscam` and `iscam` are the definition and list what
-departs from torchcam: our random stream, one noise field for all images of a batch, every class from one stream, dead channels
-weighted 0, no final ReLU and no normalisation.
+(kernels.sscam_contract: one fma per live channel in ascending order), and nothing comes to the host in between.  `scorecam` is
+the same loop with one sample, no noise and no ramp, so with those arguments both are `scorecam` bit for bit.  The docstrings
+of `sscam` and `iscam` are the definition and list what departs from torchcam: our random stream, one noise field for all images
+of a batch, every class from one stream, dead channels weighted 0, no final ReLU and no normalisation.
 
 Gradient methods that need many gradients per image (`integrated_gradients`, `smoothgrad`, `gradient_maps`, `ig_quadrature`):
 Integrated Gradients (Sundararajan et al. 2017) and SmoothGrad / SmoothGrad-squared / VarGrad (Smilkov et al. 2017), what the
@@ -446,33 +447,14 @@ def scorecam(model, images, classes=None, batch=250):
     `gradcam`: bilinear resizing is linear, so resizing S (what `scorecam_maps` does) equals the official sum of upsampled maps.
 
     classes as in `gradcam` / `rise`: None (every class), a list of ints (K = len), or a LongTensor [B] (each image its own
-    class, K = 1).  Per image: kernels.scorecam_ranges once, then the C masked images go through the model in chunks of `batch`
-    (the last may be shorter): kernels.scorecam_mask_images into one reused buffer, the model under torch.no_grad() in eval
-    mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.scorecam_accumulate onto the
-    result in channel order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied
-    to the host and nothing synchronises inside the loop."""
-    B, Cin, H, W = _check_images(images).shape
-    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
-    x, batch = _check_images_batch(images, batch)
-    dev = images.device
-    feat = model.feature_pass(x).features.detach()          # (the FeaturePass and its head state are dropped here)
-    feat = (feat.float() if feat.dtype != torch.float32 else feat).contiguous()
-    _, h, w, C = feat.shape
-    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
-    Kc = 1 if per_image else len(cols)
-    out = torch.zeros((B, Kc, h, w), dtype=torch.float32, device=dev)
-    if Kc == 0:
-        return out
-    buf = torch.empty((min(batch, C), Cin, H, W), dtype=torch.float32, device=dev)
-    ranges = torch.empty((C, 2), dtype=torch.float32, device=dev)
-    with _eval_mode(model), torch.no_grad():
-        for b in range(B):
-            cb = cols_dev[b:b + 1] if per_image else cols_dev
-            K.scorecam_ranges(feat[b], H, W, out=ranges)
-            for first in range(0, C, batch):
-                chunk = K.scorecam_mask_images(x[b], feat[b], ranges, buf[:min(batch, C - first)], first)
-                K.scorecam_accumulate(model(chunk), cb, feat[b], ranges, out[b], first)
-    return out
+    class, K = 1).  It is the one-sample row of the stream `sscam` and `iscam` run on (`_scorecam_stream` with n_samples = 1, no
+    noise, no ramp, norm = 1).  Per image: kernels.scorecam_ranges once, then the C masked images go through the model in chunks
+    of `batch` (the last may be shorter): kernels.sscam_mask_images into one reused buffer, the model under torch.no_grad() in
+    eval mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.sscam_weights (each
+    channel's probabilities, held in float64, which holds an fp32 value exactly); kernels.sscam_contract at the end, one fma per
+    live channel in ascending order -- the same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is
+    copied to the host and nothing synchronises inside the loop."""
+    return _scorecam_stream(model, images, classes, 1, 0.0, batch, 0, False, 1.0)
 
 
 def scorecam_maps(model, images, classes=None, size=None, min_level=0.0, batch=250):
@@ -496,8 +478,8 @@ def iscam_ramp(n_samples):
 
 
 def _scorecam_stream(model, images, classes, n_samples, sigma, batch, seed, ramp, norm):
-    """the loop shared by sscam and iscam: per image the n_samples * C rows as one flat stream cut into chunks of min(batch, C)
-    rows, float64 weight sums per (channel, class), one contraction at the end"""
+    """the loop shared by scorecam, sscam and iscam: per image the n_samples * C rows as one flat stream cut into chunks of
+    min(batch, C) rows, float64 weight sums per (channel, class), one contraction at the end"""
     B, Cin, H, W = _check_images(images).shape
     per_image, cols = _class_columns(classes, B, _num_classes(model, images))
     x, batch = _check_images_batch(images, batch)

@@ -1,5 +1,6 @@
-"""Score-CAM without a GPU: the three entry points of csrc/scorecam.hip are declared in include/scouter_hip.h with their argument
-lists and exported by the built library, scouter_amd.test's parser knows --scorecam / --scorecam_batch, and scorecam /
+"""Score-CAM without a GPU: scouter_scorecam_ranges_f32 of csrc/scorecam.hip is declared in include/scouter_hip.h with its
+argument list and exported by the built library (the sscam_* entry points Score-CAM runs on: test_sscam_cpu.py), the two entry points
+Score-CAM once had for itself are gone from both, scouter_amd.test's parser knows --scorecam / --scorecam_batch, and scorecam /
 scorecam_maps can be imported from tools/attribution.py."""
 import ctypes
 import inspect
@@ -9,11 +10,9 @@ P, I = ctypes.c_void_p, ctypes.c_int
 DECLARED = {
     # feat, ranges, h, w, C, H, W, stream
     "scouter_scorecam_ranges_f32": [P, P, I, I, I, I, I, P],
-    # image, feat, ranges, out, first, n, Cin, H, W, h, w, C, stream
-    "scouter_scorecam_mask_images_f32": [P, P, P, P, I, I, I, I, I, I, I, I, P],
-    # logp, cols, feat, ranges, acc, first, n, n_classes, K, h, w, C, stream
-    "scouter_scorecam_accumulate_f32": [P, P, P, P, P, I, I, I, I, I, I, I, P],
 }
+# the mask writer and the accumulation Score-CAM had for itself: sscam_mask_images, sscam_weights and sscam_contract do their work
+REMOVED = ["scouter_scorecam_%s_f32" % part for part in ("mask_images", "accumulate")]
 
 
 def test_scorecam_symbols_are_declared_and_exported():
@@ -27,14 +26,15 @@ def test_scorecam_symbols_are_declared_and_exported():
         assert declared[name] == (ctypes.c_int, argtypes), (name, declared[name])
         assert hasattr(lib, name), name
         assert getattr(_native.lib(), name).argtypes == argtypes
+    for name in REMOVED:                          # (an object file left behind by an earlier build would still export them)
+        assert name not in declared, name
+        assert not hasattr(lib, name), name
 
 
 def test_scorecam_wrappers_and_host_functions_exist():
     from scouter_amd import kernels as K
     from scouter_amd.tools.attribution import scorecam, scorecam_maps
     assert list(inspect.signature(K.scorecam_ranges).parameters) == ["feat", "H", "W", "out"]
-    assert list(inspect.signature(K.scorecam_mask_images).parameters) == ["image", "feat", "ranges", "out", "first"]
-    assert list(inspect.signature(K.scorecam_accumulate).parameters) == ["logp", "cols", "feat", "ranges", "acc", "first"]
     sig = inspect.signature(scorecam)
     assert list(sig.parameters) == ["model", "images", "classes", "batch"]
     assert sig.parameters["classes"].default is None and sig.parameters["batch"].default == 250
@@ -67,8 +67,3 @@ def test_cpu_tensors_are_refused():
     feat = torch.zeros((2, 2, 4))
     with pytest.raises(RuntimeError, match="scorecam_ranges"):
         K.scorecam_ranges(feat, 8, 8)
-    with pytest.raises(RuntimeError, match="scorecam_mask_images"):
-        K.scorecam_mask_images(torch.zeros((1, 8, 8)), feat, torch.zeros((4, 2)), torch.zeros((4, 1, 8, 8)), 0)
-    with pytest.raises(RuntimeError, match="scorecam_accumulate"):
-        K.scorecam_accumulate(torch.zeros((4, 3)), torch.zeros(3, dtype=torch.int32), feat, torch.zeros((4, 2)),
-                              torch.zeros((3, 2, 2)), 0)

@@ -1,7 +1,8 @@
-"""Score-CAM (-m gpu): the three kernels of csrc/scorecam.hip against fp64 -- kernels.scorecam_ranges and
-kernels.scorecam_mask_images against channels resized with F.interpolate in float64 (no reference program is involved),
-kernels.scorecam_accumulate against the float64 einsum -- their refusals, tools/attribution.py scorecam on whole models against
-the same fp64 sum over the HIP path's own features and log-probabilities, and scorecam_maps / test.py run_scorecam / run_causal.
+"""Score-CAM (-m gpu): the kernels of csrc/scorecam.hip as Score-CAM runs them -- one sample, no noise, no ramp -- against fp64:
+kernels.scorecam_ranges and kernels.sscam_mask_images against channels resized with F.interpolate in float64 (no reference
+program is involved), kernels.sscam_weights followed by kernels.sscam_contract against the float64 einsum -- the refusals of
+scorecam_ranges (those of the sscam_* calls: test_sscam_gpu.py), tools/attribution.py scorecam on whole models against the same
+fp64 sum over the HIP path's own features and log-probabilities, and scorecam_maps / test.py run_scorecam / run_causal.
 
 Inputs.  Features are relu(randn) from a seeded CPU generator.  Every channel meant to be live gets its maximum at [0, 0] and a 0
 at [h - 1, w - 1]; the clamped interpolation reproduces the corners exactly when H >= h and W >= w, so the span of the resized
@@ -125,7 +126,7 @@ def test_scorecam_ranges_are_the_extrema_of_resize_bilinear(case):
     assert torch.equal(got[:, 0], U.amin(dim=(1, 2))) and torch.equal(got[:, 1], U.amax(dim=(1, 2)))
 
 
-# ------------------------------------------------------------------------------------------------ 2: K.scorecam_mask_images
+# ------------------------------------------------------------------------------------------------ 2: K.sscam_mask_images, one sample
 def _check_mask_images(case, seed=0):
     from scouter_amd import kernels as K
     Cin, H, W, h, w, C, first, n = case
@@ -138,14 +139,14 @@ def _check_mask_images(case, seed=0):
     coef = (4 * e_U / span + 8 * EPS)[sl]
     bound = coef[:, None, None, None] * image.double().abs()[None]
     out = torch.full((n + 1, Cin, H, W), SENTINEL, device="cuda")
-    got = K.scorecam_mask_images(image.cuda(), Ad, ranges, out[:n], first)
-    ones = K.scorecam_mask_images(torch.ones((Cin, H, W), device="cuda"), Ad, ranges, torch.empty((n, Cin, H, W), device="cuda"),
-                                  first)
+    got = K.sscam_mask_images(image.cuda(), Ad, ranges, out[:n], first, 1)
+    ones = K.sscam_mask_images(torch.ones((Cin, H, W), device="cuda"), Ad, ranges, torch.empty((n, Cin, H, W), device="cuda"),
+                               first, 1)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr() and bool((out[n] == SENTINEL).all())            # the extra image keeps the sentinel
     res = out[:n].cpu().double()
     err = (res - ref).abs()
-    print("scorecam_mask_images", case, "max err %.3e, max err / bound %.3f" %
+    print("sscam_mask_images, one sample", case, "max err %.3e, max err / bound %.3f" %
           (float(err.max()), float((err / bound.clamp_min(1e-300)).max())))
     assert bool((err <= bound).all()), (float(err.max()), float((err / bound.clamp_min(1e-300)).max()))
     lv = live64[sl]
@@ -159,15 +160,15 @@ def _check_mask_images(case, seed=0):
 
 
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
-def test_scorecam_mask_images_against_fp64(case):
+def test_scorecam_masked_images_against_fp64(case):
     _check_mask_images(case)
 
 
-# ------------------------------------------------------------------------------------------------ 3: K.scorecam_accumulate
-# (K, n_classes, h, w, C, the columns or None for 0 .. K - 1, acc starts from seeded non-zero values, signed features)
-ACC_CASES = [(10, 10, 7, 7, 64, None, True, False), (3, 200, 2, 2, 512, [150, 7, 150], False, False),
-             (200, 200, 9, 9, 20, None, False, False), (1, 1, 1, 1, 4, None, False, False),
-             (5, 12, 3, 5, 37, [11, 0, 3, 3, 7], False, True)]
+# ------------------------------------------------------------------------------------------------ 3: K.sscam_weights, K.sscam_contract
+# (K, n_classes, h, w, C, the columns or None for 0 .. K - 1, signed features)
+ACC_CASES = [(10, 10, 7, 7, 64, None, False), (3, 200, 2, 2, 512, [150, 7, 150], False),
+             (200, 200, 9, 9, 20, None, False), (1, 1, 1, 1, 4, None, False),
+             (5, 12, 3, 5, 37, [11, 0, 3, 3, 7], True)]
 
 
 def check_accumulated(got, ref, absref, start, C, what):
@@ -184,103 +185,69 @@ def check_accumulated(got, ref, absref, start, C, what):
     assert bool((err <= bound).all()), (what, float(err.max()), float((err / bound.clamp_min(1e-300))[~zero].max()))
 
 
-@pytest.mark.parametrize("case", ACC_CASES, ids=lambda c: "%dof%d_%dx%d_c%d%s" % (c[:5] + ("_signed" if c[7] else "",)))
-def test_scorecam_accumulate_against_fp64(case):
+@pytest.mark.parametrize("case", ACC_CASES, ids=lambda c: "%dof%d_%dx%d_c%d%s" % (c[:5] + ("_signed" if c[6] else "",)))
+def test_scorecam_weights_and_contract_against_fp64(case):
+    """one sample: kernels.sscam_weights (one call, and a call cut at C // 3) followed by kernels.sscam_contract(norm = 1)"""
     from scouter_amd import kernels as K
-    Kc, n_classes, h, w, C, cols, seeded, signed = case
+    Kc, n_classes, h, w, C, cols, signed = case
     H, W = 2 * h + 1, 2 * w + 3
     cols = torch.tensor(cols if cols is not None else list(range(Kc)), dtype=torch.int32)
     gen = torch.Generator().manual_seed(7200 + C)
     logp = F.log_softmax(torch.randn((C, n_classes), generator=gen), dim=1)
     dead = (1, C - 1)
     A = make_features(h, w, C, dead, 7300 + C, signed=signed)
-    acc0 = torch.rand((Kc, h, w), generator=gen) + 0.25 if seeded else torch.zeros((Kc, h, w))
     _, _, _, live64, _, _, _ = reference_fp64(A, H, W)
     assert int(live64.sum()) == (C - 2 if h * w > 1 else 0)
     wts = logp.double().exp()[:, cols.long()] * live64[:, None].double()                  # [C, K]
-    ref = acc0.double() + torch.einsum("ck,hwc->khw", wts, A.double())
+    ref = torch.einsum("ck,hwc->khw", wts, A.double())
     absref = torch.einsum("ck,hwc->khw", wts, A.double().abs())
     ld, cd, Ad = logp.cuda(), cols.cuda(), A.cuda()
     ranges = K.scorecam_ranges(Ad, H, W)
     assert torch.equal((ranges[:, 1] - ranges[:, 0] > 0).cpu(), live64)
-    one = K.scorecam_accumulate(ld, cd, Ad, ranges, acc0.cuda(), 0)
-    cut = C // 3
-    two = acc0.cuda()
-    K.scorecam_accumulate(ld[:cut], cd, Ad, ranges, two, 0)
-    K.scorecam_accumulate(ld[cut:], cd, Ad, ranges, two, cut)
-    again = K.scorecam_accumulate(ld, cd, Ad, ranges, acc0.cuda(), 0)
+
+    def run(lp, cuts):
+        wsum = torch.zeros((C, Kc), dtype=torch.float64, device="cuda")
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            K.sscam_weights(lp[a:b], cd, wsum, a)
+        return K.sscam_contract(wsum, Ad, ranges, torch.full((Kc, h, w), SENTINEL, device="cuda"), 1.0)
+
+    one = run(ld, [0, C])
+    two = run(ld, [0, C // 3, C])
+    again = run(ld, [0, C])
     torch.cuda.synchronize()
-    check_accumulated(one, ref, absref, acc0.double(), C, "scorecam_accumulate %s" % (case[:5],))
+    check_accumulated(one, ref, absref, torch.zeros_like(ref), C, "sscam_weights, sscam_contract %s" % (case[:5],))
     assert torch.equal(one, two) and torch.equal(one, again)      # split at any point, and a second call: the same bits
-    if seeded:
-        assert float((one.cpu() - acc0).min()) >= 0 and float((one.cpu() - acc0).max()) > 0
     # dead channels given a huge log-probability change nothing
     huge = ld.clone()
     huge[(~live64).nonzero().flatten().cuda()] = 1.0e4
-    same = K.scorecam_accumulate(huge, cd, Ad, ranges, acc0.cuda(), 0)
-    assert torch.equal(same, one)
+    assert torch.equal(run(huge, [0, C]), one)
 
 
 # ------------------------------------------------------------------------------------------------ 4: refusals
-BAD = {"scorecam_ranges": ["null", "hw_cap", "H0", "W0", "out_shape"],
-       "scorecam_mask_images": ["null", "first_low", "first_high", "ranges_shape", "hw_cap", "out_shape", "H0"],
-       "scorecam_accumulate": ["null", "first_low", "first_high", "ranges_shape", "hw_cap", "K0"]}
+BAD = {"scorecam_ranges": ["null", "hw_cap", "H0", "W0", "out_shape"]}
 
 
 @pytest.mark.parametrize("call,bad", [(c, b) for c in BAD for b in BAD[c]])
 def test_scorecam_kernels_refuse_bad_arguments(call, bad):
-    """a null pointer, a channel range outside [0, C), ranges that are not [C, 2], h w above 1024, K = 0, H or W below 1, an output
-    of the wrong shape: an error naming the call, the outputs untouched, and a valid call afterwards is right"""
+    """a null pointer, h w above 1024, H or W below 1, an output of the wrong shape: an error naming the call, the output
+    untouched, and a valid call afterwards is right"""
     from scouter_amd import _native
     from scouter_amd import kernels as K
-    Cin, H, W, h, w, C, n, Kc = 2, 20, 24, 3, 4, 6, 4, 3
+    H, W, h, w, C = 20, 24, 3, 4, 6
     if bad == "hw_cap":
         h, w = 33, 32                                                    # 1056 source positions: above the 1024 a channel may have
-    image = torch.ones((Cin, H, W), device="cuda")
     feat = torch.rand((h, w, C), generator=torch.Generator().manual_seed(5)).cuda()
     ranges = torch.full((C, 2), SENTINEL, device="cuda")
-    good_ranges = torch.tensor([[0.0, 1.0]] * C, device="cuda")
-    out = torch.full((n, Cin, H, W), SENTINEL, device="cuda")
-    acc = torch.full((Kc, h, w), SENTINEL, device="cuda")
-    logp = torch.zeros((n, 6), device="cuda")
-    cols = torch.tensor([0, 5, 2], dtype=torch.int32, device="cuda")
-    first = {"first_low": -1, "first_high": C - n + 1}.get(bad, 1)
-    rg = good_ranges[:C - 1] if bad == "ranges_shape" else good_ranges
     lib = _native.lib()
     with pytest.raises(RuntimeError, match=call):
-        if call == "scorecam_ranges":
-            if bad == "null":
-                _native.check(lib.scouter_scorecam_ranges_f32(feat.data_ptr(), None, h, w, C, H, W, None), call)
-            elif bad == "out_shape":
-                K.scorecam_ranges(feat, H, W, out=ranges[:C - 1])
-            else:
-                K.scorecam_ranges(feat, 0 if bad == "H0" else H, 0 if bad == "W0" else W, out=ranges)
-        elif call == "scorecam_mask_images":
-            if bad == "null":
-                _native.check(lib.scouter_scorecam_mask_images_f32(image.data_ptr(), None, good_ranges.data_ptr(), out.data_ptr(),
-                                                                   first, n, Cin, H, W, h, w, C, None), call)
-            elif bad == "out_shape":
-                K.scorecam_mask_images(image, feat, rg, out.view(n, Cin, W, H), first)
-            elif bad == "H0":
-                K.scorecam_mask_images(image[:, :0], feat, rg, out[:, :, :0], first)
-            else:
-                K.scorecam_mask_images(image, feat, rg, out, first)
+        if bad == "null":
+            _native.check(lib.scouter_scorecam_ranges_f32(feat.data_ptr(), None, h, w, C, H, W, None), call)
+        elif bad == "out_shape":
+            K.scorecam_ranges(feat, H, W, out=ranges[:C - 1])
         else:
-            if bad == "null":
-                _native.check(lib.scouter_scorecam_accumulate_f32(logp.data_ptr(), cols.data_ptr(), feat.data_ptr(),
-                                                                  good_ranges.data_ptr(), None, first, n, 6, Kc, h, w, C, None),
-                              call)
-            elif bad == "K0":
-                K.scorecam_accumulate(logp, cols[:0], feat, rg, acc[:0], first)
-            else:
-                K.scorecam_accumulate(logp, cols, feat, rg, acc, first)
-    if call == "scorecam_accumulate" and bad == "K0":                    # K = 0 at the library too, with every pointer valid
-        with pytest.raises(RuntimeError, match=call):
-            _native.check(lib.scouter_scorecam_accumulate_f32(logp.data_ptr(), cols.data_ptr(), feat.data_ptr(),
-                                                              good_ranges.data_ptr(), acc.data_ptr(), first, n, 6, 0, h, w, C,
-                                                              None), call)
+            K.scorecam_ranges(feat, 0 if bad == "H0" else H, 0 if bad == "W0" else W, out=ranges)
     torch.cuda.synchronize()
-    assert bool((out == SENTINEL).all()) and bool((acc == SENTINEL).all()) and bool((ranges == SENTINEL).all())
+    assert bool((ranges == SENTINEL).all())
     _check_ranges(CASES[0])
     _check_mask_images(CASES[3])
 
@@ -307,8 +274,8 @@ def bn_buffers(m):
 
 def expected_scorecam(m, images, batch):
     """fp64 (ref, absref) [B, n, h, w]: the definition's sum over the HIP path's own data -- the features of feature_pass, the
-    live flags of K.scorecam_ranges (checked against fp64 above), the same chunks built with K.scorecam_mask_images and the
-    model in eval mode under no_grad at the same batch"""
+    live flags of K.scorecam_ranges (checked against fp64 above), the same chunks built with K.sscam_mask_images (one sample)
+    and the model in eval mode under no_grad at the same batch"""
     from scouter_amd import kernels as K
     B, Cin, H, W = images.shape
     feat = m.feature_pass(images).features.detach().float().contiguous()
@@ -324,7 +291,7 @@ def expected_scorecam(m, images, batch):
                 logp = []
                 for first in range(0, C, batch):
                     n = min(batch, C - first)
-                    chunk = K.scorecam_mask_images(images[b], feat[b], ranges, torch.empty((n, Cin, H, W), device="cuda"), first)
+                    chunk = K.sscam_mask_images(images[b], feat[b], ranges, torch.empty((n, Cin, H, W), device="cuda"), first, 1)
                     logp.append(m(chunk).cpu().double())
                 wts = torch.cat(logp).exp() * live[:, None]
                 A = feat[b].cpu().double()

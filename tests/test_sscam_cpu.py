@@ -1,5 +1,5 @@
-"""SS-CAM and IS-CAM without a GPU: the three entry points of csrc/sscam.hip are declared in include/scouter_hip.h with their
-argument lists and exported by the built library, the wrappers and host functions have the specified signatures and defaults,
+"""SS-CAM and IS-CAM without a GPU: the three sscam_* entry points of csrc/scorecam.hip are declared in include/scouter_hip.h with
+their argument lists and exported by the built library, the wrappers and host functions have the specified signatures and defaults,
 scouter_amd.test's parser knows --sscam / --iscam and their options while train.py's does not, CPU tensors are refused with an
 error naming the call, and iscam_ramp is the fp32 rounding of the reference's own accumulation."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Cost of SS-CAM next to the bare forwards it is made of, next to Score-CAM in the same run, and its three kernels alone.
+"""Cost of SS-CAM next to the bare forwards it is made of, next to Score-CAM in the same run, and the family's four kernels alone.
 
     python tools_dev/sscam_bench.py [--model resnest26d] [--batch 250] [--samples 35] [--sigma 2.0] [--repeats 3] [--out FILE]
                                     [--iters N]
@@ -7,9 +7,9 @@
 (one feature pass, kernels.scorecam_ranges, then per chunk kernels.sscam_mask_images, the model, kernels.sscam_weights, and
 kernels.sscam_contract at the end) and ms of bare `model(x)` forwards under no_grad at the same batch sizes (N C // batch at
 `batch` and one at N C % batch), device events around whole calls, the two alternating; then the same pair for
-tools/attribution.scorecam.  The two ratios side by side are what the noise and the weights launch cost per chunk.  Then
-kernels.sscam_mask_images without and with noise next to kernels.scorecam_mask_images at the same output shape, alternating,
-with the byte floor at --hbm-tbs and the share of one forward of the same chunk, and kernels.sscam_weights /
+tools/attribution.scorecam, the same loop with one sample and no noise.  The two ratios side by side are what the noise costs
+per chunk.  Then kernels.sscam_mask_images without and with noise at the same output shape, alternating, with the byte floor at
+--hbm-tbs and the share of one forward of the same chunk, and kernels.scorecam_ranges / kernels.sscam_weights /
 kernels.sscam_contract once each.
 --iters N: instead, N chunks (mask writer with noise, forward, weights) and nothing else -- the body of a
 `rocprofv3 --kernel-trace --stats` run."""
@@ -102,36 +102,35 @@ def main():
         say("%s %s: sscam ratio %.3f against scorecam ratio %.3f from the same run: %+.3f"
             % (a.model, state, ratios["sscam"], ratios["scorecam"], ratios["sscam"] - ratios["scorecam"]))
 
-    # ---- the mask writer without and with noise next to Score-CAM's at the same output shape, alternating
+    # ---- the mask writer without and with noise at the same output shape, alternating
     m.set_inference_fold(False)
-    f_old = lambda: K.scorecam_mask_images(image[0], feat, ranges, buf, 0)
     f_new = lambda: K.sscam_mask_images(image[0], feat, ranges, buf, 0, N, 0.0, 0)
     f_noise = lambda: K.sscam_mask_images(image[0], feat, ranges, buf, 0, N, a.sigma, 0)
 
     def forward():
         with torch.no_grad():
             m(buf)
-    f_old(); f_new(); f_noise(); forward()
-    t_old, t_new, t_noise, t_fwd = [], [], [], []
+    f_new(); f_noise(); forward()
+    t_new, t_noise, t_fwd = [], [], []
     for _ in range(a.repeats):
-        t_old.append(window(f_old, 0.25) * 1e3)
         t_new.append(window(f_new, 0.25) * 1e3)
         t_noise.append(window(f_noise, 0.25) * 1e3)
         t_fwd.append(window(forward, 0.25) * 1e3)
     nbytes = 4.0 * (buf.numel() + image[0].numel())
     floor = nbytes / (a.hbm_tbs * 1e12) * 1e6
     us = lambda ts: " ".join("%.1f" % v for v in ts)
-    say("sscam_mask_images [%d, 3, 224, 224] sigma 0: us %s | scorecam_mask_images at the same shape: us %s | best / best = %.2f | "
-        "%.1f MB, floor %.1f us at %.1f TB/s, best / floor = %.2f"
-        % (n, us(t_new), us(t_old), min(t_new) / min(t_old), nbytes / 1e6, floor, a.hbm_tbs, min(t_new) / floor))
+    say("sscam_mask_images [%d, 3, 224, 224] sigma 0: us %s | %.1f MB, floor %.1f us at %.1f TB/s, best / floor = %.2f"
+        % (n, us(t_new), nbytes / 1e6, floor, a.hbm_tbs, min(t_new) / floor))
     say("sscam_mask_images [%d, 3, 224, 224] sigma %g: us %s | best / floor = %.2f | one unfolded forward of the chunk: us %s | "
         "share of the forward %.4f"
         % (n, a.sigma, us(t_noise), min(t_noise) / floor, us(t_fwd), min(t_noise) / min(t_fwd)))
 
-    # ---- the two small kernels
+    # ---- the three small kernels
     logp = torch.log_softmax(torch.randn(n, 10, device="cuda"), dim=1)
     out = torch.empty((10, h, w), device="cuda")
     for name, fn, nbytes in (
+            ("scorecam_ranges [%d, %d, %d] -> 224^2" % (h, w, C), lambda: K.scorecam_ranges(feat, 224, 224, out=ranges),
+             4.0 * (feat.numel() + ranges.numel())),
             ("sscam_weights [%d rows, 10 classes]" % n, lambda: K.sscam_weights(logp, cols, wsum, 0),
              4.0 * logp.numel() + 16.0 * n * 10),
             ("sscam_contract [10, %d, %d] x %d" % (h, w, C), lambda: K.sscam_contract(wsum, feat, ranges, out, 1.0 / N),
