@@ -1,66 +1,45 @@
 """Single-image inference + slot attention maps -- the `--vis` path of the reference (test.py:18-122 together with
 sloter/utils/slot_attention.py:68-85): eval-mode forward of ONE image on the HIP path, per-class uint8 attention
 maps written as `<out>/slot_{c}.png`, the input as `<out>/image.png`, and (optionally) the attention-area ratio the
-reference prints with --cal_area_size (test.py:40-44).  `--grad true` adds the per-class gradient attribution maps
-`<out>/grad_{c}.png` (d log-probability / d image through tools/attribution.py, floored at --grad_min_level; also for the
-`--use_slot false` baseline, the model the reference attributes); `--cam true` the per-class Grad-CAM heat maps at the last
-backbone stage, `<out>/cam_{c}.png` (tools/attribution.py gradcam_maps: one backbone forward, floored at --grad_min_level,
-BatchNorm-folded under --eval_fold; what the reference draws with captum's LayerGradCam on layer4); `--rise true` the per-class
-RISE perturbation maps `<out>/rise_{c}.png` (tools/attribution.py rise_maps: --rise_masks random masks through the model in
-chunks of --rise_batch, floored at --grad_min_level, BatchNorm-folded under --eval_fold; what the reference's torchcam_vis.py
-draws with torchray's rise); `--scorecam true` the per-class Score-CAM heat maps `<out>/scorecam_{c}.png`
-(tools/attribution.py scorecam_maps: one eval forward per channel of the last backbone stage, in chunks of --scorecam_batch,
-floored at --grad_min_level, BatchNorm-folded under --eval_fold; the gradient-free CAM family of the reference's
-torchcam_vis.py); `--ig true` the per-class Integrated Gradients maps `<out>/ig_{c}.png` (tools/attribution.py
-integrated_gradients: --ig_steps Gauss-Legendre steps from a zero baseline in chunks of --ig_batch, drawn by gradient_maps,
-floored at --grad_min_level; captum's IntegratedGradients of the reference's captum_vis.py); `--smoothgrad true` the per-class
-SmoothGrad maps `<out>/smoothgrad_{c}.png` (tools/attribution.py smoothgrad: --smoothgrad_samples noisy copies at
---smoothgrad_sigma in chunks of --smoothgrad_batch; captum's NoiseTunnel); `--campp true` the per-class Grad-CAM++ heat maps
-`<out>/campp_{c}.png` (tools/attribution.py gradcampp_maps: one backbone forward, floored at --grad_min_level, BatchNorm-folded
-under --eval_fold; torchcam's GradCAMpp of the reference's torchcam_vis.py); `--smoothcampp true` the per-class Smooth Grad-CAM++
-heat maps `<out>/smoothcampp_{c}.png` (tools/attribution.py smooth_gradcampp: --smoothcampp_samples noisy copies at
---smoothcampp_sigma in chunks of --smoothcampp_batch; torchcam's SmoothGradCAMpp); `--extremal true` the per-class Extremal
-Perturbation maps `<out>/extremal_{c}.png` (tools/attribution.py extremal_maps: --extremal_iters SGD steps on a smooth mask of
---extremal_area of the image, variant --extremal_variant, the classes in groups of --extremal_batch, floored at --grad_min_level;
-torchray's extremal_perturbation of the reference's torchcam_vis.py); `--iba true` the per-class information-bottleneck maps
-`<out>/iba_{c}.png` (tools/attribution.py iba_maps: --iba_steps Adam steps on a feature-space mask with --iba_samples_per_step noisy
-samples each, information weight --iba_beta, window --iba_sigma, the feature distribution fitted on --iba_fit images of the
-validation loader -- synthetic ones under --synthetic_data true --, at most --iba_batch head rows per pass, 0 = all; the IBA of
-the reference's torchcam_vis.py); `--igos true` the per-class I-GOS maps `<out>/igos_{c}.png` (tools/attribution.py igos_maps:
---igos_iters iterations of --igos_steps noisy path images each on a mask of --igos_size x --igos_size cells, L1 weight --igos_l1,
-total-variation weight --igos_tv, at most --igos_batch rows per pass, floored at --grad_min_level; the Integrated_Mask the
-reference's torchcam_vis.py runs first); `--sscam true` the per-class SS-CAM heat maps `<out>/sscam_{c}.png` (tools/attribution.py
-sscam_maps: --sscam_samples noisy copies of every channel's Score-CAM mask at --sscam_sigma, --sscam_batch masked images per
-forward, floored at --grad_min_level, BatchNorm-folded under --eval_fold; torchcam's SSCAM of the reference's torchcam_vis.py);
-`--iscam true` the per-class IS-CAM heat maps `<out>/iscam_{c}.png` (tools/attribution.py iscam_maps: every mask at
---iscam_samples scales along a ramp, --iscam_batch masked images per forward; torchcam's ISCAM, the ISSCAM that file lists);
-`--causal true` prints, for every family of maps
-drawn in the call (slot under --use_slot true, grad, cam, rise, scorecam, ig, smoothgrad, campp, smoothcampp, extremal, iba, igos, sscam, iscam), the deletion and insertion scores of
-the predicted class's map (tools/attribution.py causal_metrics on the float maps, --causal_step pixels per point, 0 = one image row; the DAUC / IAUC the paper compares explanations with) as
-`causal <family> class <c>: deletion <d> insertion <i>`; `--infidelity true` and `--sensitivity true` print, for the same families,
-the infidelity of the predicted class's explanation (tools/attribution.py infidelity: --infidelity_samples noisy copies at
---infidelity_sigma, --infidelity_batch rows per forward; grad, ig and smoothgrad with their full attribution, the others with their
-map) as `infidelity <family> class <c>: raw <r> normalized <n> beta <b>` and its max-sensitivity (tools/attribution.py
-sensitivity_max: --sensitivity_samples points within --sensitivity_radius, --sensitivity_batch rows per call) as
-`sensitivity <family> class <c>: max <s>` -- the infidelity and sensitivity columns of the paper, after Yeh et al. 2019.  The
-jet-colormap overlay of test.py:33-38 is matplotlib post-processing of these PNGs and is not reproduced.
+reference prints with --cal_area_size (test.py:40-44).  The jet-colormap overlay of test.py:33-38 is matplotlib
+post-processing of these PNGs and is not reproduced.
+
+Every other explanation family is one row of FAMILIES below and follows one pattern: `--<name> true` draws the family's map of
+every class for the image with tools/attribution.py, under the options `--<name>_<option>` of its row, and writes the uint8
+maps as `<out>/<name>_{c}.png` at the input resolution, floored at --grad_min_level and BatchNorm-folded under --eval_fold.
+
+    slot         the xSlot attention itself (--use_slot true; no flag)
+    grad         d log-probability / d image (the reference's train.py --grad / --grad_min_level, captum_vis.py; also for the
+                 --use_slot false baseline, the model the reference attributes)
+    cam          Grad-CAM at the last backbone stage (captum's LayerGradCam on layer4)
+    rise         RISE: random masks through the model (torchray's rise of the reference's torchcam_vis.py)
+    scorecam     Score-CAM: one eval forward per channel of the last backbone stage (the gradient-free CAMs of torchcam_vis.py)
+    ig           Integrated Gradients: zero baseline, Gauss-Legendre steps (captum's IntegratedGradients of captum_vis.py)
+    smoothgrad   SmoothGrad: the mean gradient over noisy copies (captum's NoiseTunnel)
+    campp        Grad-CAM++ (torchcam's GradCAMpp of torchcam_vis.py)
+    smoothcampp  Smooth Grad-CAM++ (torchcam's SmoothGradCAMpp)
+    extremal     Extremal Perturbation: SGD on a smooth mask of a fixed area (torchray's extremal_perturbation)
+    iba          information bottleneck at the backbone's output, its feature distribution fitted on --iba_fit images of the
+                 validation loader -- synthetic ones under --synthetic_data true (the IBA of torchcam_vis.py)
+    igos         I-GOS: a coarse mask moved along integrated gradients (the Integrated_Mask torchcam_vis.py runs first)
+    sscam        SS-CAM: Score-CAM over noisy copies of every mask (torchcam's SSCAM)
+    iscam        IS-CAM: Score-CAM with every mask at scales along a ramp (torchcam's ISCAM, the ISSCAM torchcam_vis.py lists)
+
+The three scores are the rows of SCORES; each scores the predicted class's explanation of every family drawn in the call, in
+the order above.  `--causal true` prints the deletion and insertion scores (tools/attribution.py causal_metrics on the float
+maps; the DAUC / IAUC the paper compares explanations with) as `causal <family> class <c>: deletion <d> insertion <i>`;
+`--infidelity true` the infidelity (tools/attribution.py infidelity; grad, ig and smoothgrad with their full attribution, the
+others with their map) as `infidelity <family> class <c>: raw <r> normalized <n> beta <b>`; `--sensitivity true` the
+max-sensitivity (tools/attribution.py sensitivity_max) as `sensitivity <family> class <c>: max <s>` -- the infidelity and
+sensitivity columns of the paper, after Yeh et al. 2019.  `--help` lists every option with its default.
 
     python -m scouter_amd.test --model resnest26d --dataset ImageNet --channel 2048 --num_classes 10 \
         --slots_per_class 1 --to_k_layer 3 --power 2 --use_slot true --vis true --pre_trained false \
         [--checkpoint saved_model/ImageNet_use_slot_checkpoint.pth] [--image some.jpg] --img_size 224 \
         [--grad true --grad_min_level 0.1] [--cam true] [--rise true --rise_masks 4000 --rise_batch 250] \
-        [--scorecam true --scorecam_batch 250] [--ig true --ig_steps 50 --ig_batch 50] \
-        [--smoothgrad true --smoothgrad_samples 50 --smoothgrad_sigma 1.0 --smoothgrad_batch 50] \
-        [--campp true] [--smoothcampp true --smoothcampp_samples 4 --smoothcampp_sigma 0.3 --smoothcampp_batch 4] \
-        [--extremal true --extremal_area 0.1 --extremal_iters 800 --extremal_variant preserve --extremal_batch 50] \
-        [--iba true --iba_beta 10 --iba_steps 10 --iba_samples_per_step 10 --iba_sigma 1.0 --iba_fit 5000 --iba_batch 0] \
-        [--igos true --igos_size 8 --igos_iters 15 --igos_steps 20 --igos_l1 1.0 --igos_tv 20.0 --igos_batch 50] \
-        [--sscam true --sscam_samples 35 --sscam_sigma 2.0 --sscam_batch 250] \
-        [--iscam true --iscam_samples 10 --iscam_batch 250] \
-        [--causal true --causal_step 224] \
-        [--infidelity true --infidelity_samples 50 --infidelity_sigma 0.003 --infidelity_batch 50] \
-        [--sensitivity true --sensitivity_samples 10 --sensitivity_radius 0.02 --sensitivity_batch 11]"""
+        [--causal true --causal_step 224] [--infidelity true] [--sensitivity true]"""
 import argparse
+import collections
 import functools
 import os
 
@@ -71,6 +50,126 @@ from .sloter.slot_model import SlotModel
 from .train import _flag, checkpoint_name, get_args_parser
 
 
+# ------------------------------------------------------------------------------------------------ the table
+# One option of a row: `--<row>_<suffix>` of the parser, read with `type` and `default`, handed to the row's library function
+# as `keyword` (None: to nothing; the tool reads it itself) after `convert` (None: as it is).
+Option = collections.namedtuple("Option", "suffix keyword type default help choices convert", defaults=(None, None))
+
+# One explanation family.  `name` is the flag `--<name>`, the PNG stem and the word of the score lines; `what` the phrase of the
+# flag's help.  `maps` and `explain` name functions of tools/attribution.py:
+#   explain(model, images, classes=, **options) -> the float explanation, maps [n, K, h, w];
+#   maps(model, images, min_level=, **options) -> the uint8 maps [n, K, H, W].
+# `reduce` marks the families whose explanation is a full attribution [n, K, C, H, W], the form --infidelity scores: it is the
+# step from there to the float map, and `maps` then draws that attribution, maps(attribution, min_level=).  `estimate`: both
+# functions also take estimate=iba_fit(args, model).  `flag` False: on by something else than a flag of this parser (main()).
+Family = collections.namedtuple("Family", "name what options maps explain reduce estimate flag",
+                                defaults=((), None, None, None, False, True))
+
+# One score of the families drawn: the flag `--<name>`, the word that opens its printed lines, the options of its
+# tools/attribution.py function.
+Score = collections.namedtuple("Score", "name what options")
+
+
+def _channel_mean(g):
+    from . import kernels as K
+    return K.channel_mean(g)
+
+
+_O = Option
+FAMILIES = (
+    # (its PNGs are written by run(); its float map is the `slot_map` main() captures right after the predicting forward)
+    Family("slot", "xSlot attention map", flag=False),
+    # (--grad / --grad_min_level belong to train.py's parser; drawn on the host)
+    Family("grad", "gradient attribution map", maps="attribution_maps", explain="input_gradients",
+           reduce=lambda g: g.mean(dim=2), flag=False),
+    Family("cam", "Grad-CAM heat map", maps="gradcam_maps", explain="gradcam"),
+    Family("rise", "RISE saliency map", maps="rise_maps", explain="rise", options=(
+        _O("masks", "n_masks", int, 4000, "number of random masks"),
+        _O("batch", "batch", int, 250, "masked images per forward"))),
+    Family("scorecam", "Score-CAM heat map", maps="scorecam_maps", explain="scorecam", options=(
+        _O("batch", "batch", int, 250, "masked images per forward"),)),
+    Family("ig", "Integrated Gradients map", maps="gradient_maps", explain="integrated_gradients", reduce=_channel_mean, options=(
+        _O("steps", "n_steps", int, 50, "Gauss-Legendre steps"),
+        _O("batch", "batch", int, 50, "path images per forward and backward"))),
+    Family("smoothgrad", "SmoothGrad map", maps="gradient_maps", explain="smoothgrad", reduce=_channel_mean, options=(
+        _O("samples", "n_samples", int, 50, "noisy copies per class"),
+        _O("sigma", "sigma", float, 1.0, "standard deviation of the noise"),
+        _O("batch", "batch", int, 50, "noisy copies per forward and backward"))),
+    Family("campp", "Grad-CAM++ heat map", maps="gradcampp_maps", explain="gradcampp"),
+    Family("smoothcampp", "Smooth Grad-CAM++ heat map", maps="smooth_gradcampp_maps", explain="smooth_gradcampp", options=(
+        _O("samples", "n_samples", int, 4, "noisy copies per class"),
+        _O("sigma", "sigma", float, 0.3, "standard deviation of the noise"),
+        _O("batch", "batch", int, 4, "noisy copies per feature pass"))),
+    Family("extremal", "Extremal Perturbation map", maps="extremal_maps", explain="extremal_saliency", options=(
+        _O("area", "areas", float, 0.1, "fraction of the image the mask covers", convert=lambda a: (a,)),
+        _O("iters", "n_iters", int, 800, "SGD steps"),
+        _O("variant", "variant", str, "preserve", "keep (preserve) or remove (delete) the evidence under the mask",
+           choices=("preserve", "delete")),
+        _O("batch", "batch", int, 50, "masks per forward and backward"))),
+    Family("iba", "information-bottleneck map", maps="iba_maps", explain="information_bottleneck", estimate=True, options=(
+        _O("beta", "beta", float, 10.0, "weight of the information term"),
+        _O("steps", "steps", int, 10, "Adam steps"),
+        _O("samples_per_step", "samples", int, 10, "noisy samples per class and step"),
+        _O("sigma", "sigma", float, 1.0, "standard deviation of the smoothing window (0: none)",
+           convert=lambda s: s if s > 0.0 else None),
+        _O("fit", None, int, 5000, "images the feature distribution is fitted on"),
+        _O("batch", "batch", int, 0, "head rows per pass (0: all classes at once)", convert=lambda b: b or None))),
+    Family("igos", "I-GOS map", maps="igos_maps", explain="igos_saliency", options=(
+        _O("size", "size", int, 8, "cells a side of the mask"),
+        _O("iters", "n_iters", int, 15, "iterations"),
+        _O("steps", "n_steps", int, 20, "noisy path images per class and iteration"),
+        _O("l1", "l1_coeff", float, 1.0, "weight of the L1 term"),
+        _O("tv", "tv_coeff", float, 20.0, "weight of the total-variation term"),
+        _O("batch", "batch", int, 50, "images per forward (and backward)"))),
+    Family("sscam", "SS-CAM heat map", maps="sscam_maps", explain="sscam", options=(
+        _O("samples", "n_samples", int, 35, "noisy copies of every channel's mask"),
+        _O("sigma", "sigma", float, 2.0, "standard deviation of the noise"),
+        _O("batch", "batch", int, 250, "masked images per forward"))),
+    Family("iscam", "IS-CAM heat map", maps="iscam_maps", explain="iscam", options=(
+        _O("samples", "n_samples", int, 10, "scales of every channel's mask"),
+        _O("batch", "batch", int, 250, "masked images per forward"))),
+)
+SCORES = (
+    Score("causal", "deletion / insertion scores of the predicted class's map", (
+        _O("step", "step", int, 0, "pixels changed per point (0: --img_size)", convert=lambda s: s or None),)),
+    Score("infidelity", "infidelity of the predicted class's explanation", (
+        _O("samples", "n_samples", int, 50, "noisy copies"),
+        _O("sigma", "sigma", float, 0.003, "standard deviation of the noise"),
+        _O("batch", "batch", int, 50, "rows per forward, the clean image included"))),
+    Score("sensitivity", "max-sensitivity of the predicted class's map", (
+        _O("samples", "n_samples", int, 10, "perturbed copies"),
+        _O("radius", "radius", float, 0.02, "half-width of the box"),
+        _O("batch", "batch", int, 11, "rows per call of the explanation method, the clean image included"))),
+)
+_ROWS = {row.name: row for row in FAMILIES + SCORES}
+
+
+def _row(name):
+    if name not in _ROWS:
+        raise ValueError("unknown explanation family or score %r (known: %s)" % (name, ", ".join(_ROWS)))
+    return _ROWS[name]
+
+
+def _options(args, name):
+    """{suffix: value} of every option of the row `name`, read from `args` and converted; a namespace without an option (the
+    tests build such) gets the table's default"""
+    values = {}
+    for o in _row(name).options:
+        v = o.type(getattr(args, "%s_%s" % (name, o.suffix), o.default))
+        values[o.suffix] = o.convert(v) if o.convert else v
+    return values
+
+
+def option_kwargs(args, name):
+    """the keyword arguments the options of the row `name` give its library functions"""
+    values = _options(args, name)
+    return {o.keyword: values[o.suffix] for o in _row(name).options if o.keyword}
+
+
+_igos_kwargs = functools.partial(option_kwargs, name="igos")           # (tests/test_igos_cpu.py reads the keywords by this name)
+
+
+# ------------------------------------------------------------------------------------------------ the image and the prediction
 def load_image(path, size, channels):
     """RGB (or grey) image -> normalised float tensor [c, size, size] (dataset/transform_func.py:101-124: resize to
     img_size, ToTensor, ImageNet mean/std)."""
@@ -103,122 +202,7 @@ def run(args, model, image, out_dir, label=None):
     return output[0].cpu(), pred, maps, ratio
 
 
-def run_grad(args, model, image, out_dir):
-    """--grad true: the gradient attribution of every class for the one image (reference train.py --grad /
-    --grad_min_level, captum_vis.py) -> `<out>/grad_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from PIL import Image
-    from .tools.attribution import attribution_maps, input_gradients
-    os.makedirs(out_dir, exist_ok=True)
-    grads = input_gradients(model, image.unsqueeze(0).to(args.device, dtype=torch.float32))
-    maps = attribution_maps(grads, min_level=float(args.grad_min_level))[0]
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "grad_%d.png" % c))
-    return maps
-
-
-def _run_maps(args, model, image, out_dir, stem, maps_fn):
-    """one attribution family for the one image: maps_fn(images [1, C, H, W] on the device, min_level=) -> uint8 maps [1, C, H, W]
-    on the device, saved as `<out>/<stem>_{c}.png`; returns them [C, H, W] (host)"""
-    from PIL import Image
-    os.makedirs(out_dir, exist_ok=True)
-    maps = maps_fn(image.unsqueeze(0).to(args.device, dtype=torch.float32), min_level=float(args.grad_min_level))[0].cpu().numpy()
-    for c, m in enumerate(maps):
-        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "%s_%d.png" % (stem, c)))
-    return maps
-
-
-def run_cam(args, model, image, out_dir):
-    """--cam true: the Grad-CAM heat map of every class for the one image at the backbone's output (reference captum_vis.py
-    LayerGradCam on layer4) -> `<out>/cam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import gradcam_maps
-    return _run_maps(args, model, image, out_dir, "cam", functools.partial(gradcam_maps, model))
-
-
-def run_rise(args, model, image, out_dir):
-    """--rise true: the RISE saliency map of every class for the one image (reference torchcam_vis.py, torchray.attribution.rise)
-    -> `<out>/rise_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import rise_maps
-    return _run_maps(args, model, image, out_dir, "rise",
-                     functools.partial(rise_maps, model, n_masks=int(getattr(args, "rise_masks", 4000)),
-                                       batch=int(getattr(args, "rise_batch", 250))))
-
-
-def run_scorecam(args, model, image, out_dir):
-    """--scorecam true: the Score-CAM heat map of every class for the one image at the backbone's output (Wang et al. 2020; the
-    gradient-free CAMs of the reference's torchcam_vis.py) -> `<out>/scorecam_{c}.png`, uint8 maps at the input resolution;
-    returns them [C, H, W]."""
-    from .tools.attribution import scorecam_maps
-    return _run_maps(args, model, image, out_dir, "scorecam",
-                     functools.partial(scorecam_maps, model, batch=int(getattr(args, "scorecam_batch", 250))))
-
-
-def _sscam_kwargs(args):
-    return dict(n_samples=int(getattr(args, "sscam_samples", 35)), sigma=float(getattr(args, "sscam_sigma", 2.0)),
-                batch=int(getattr(args, "sscam_batch", 250)))
-
-
-def _iscam_kwargs(args):
-    return dict(n_samples=int(getattr(args, "iscam_samples", 10)), batch=int(getattr(args, "iscam_batch", 250)))
-
-
-def run_sscam(args, model, image, out_dir):
-    """--sscam true: the SS-CAM heat map of every class for the one image at the backbone's output (torchcam's SSCAM of the
-    reference's torchcam_vis.py: --sscam_samples noisy copies of every channel's mask at --sscam_sigma, --sscam_batch masked
-    images per forward) -> `<out>/sscam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import sscam_maps
-    return _run_maps(args, model, image, out_dir, "sscam", functools.partial(sscam_maps, model, **_sscam_kwargs(args)))
-
-
-def run_iscam(args, model, image, out_dir):
-    """--iscam true: the IS-CAM heat map of every class for the one image at the backbone's output (torchcam's ISCAM, the ISSCAM
-    of the reference's torchcam_vis.py: every channel's mask at --iscam_samples scales along a ramp, --iscam_batch masked images
-    per forward) -> `<out>/iscam_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import iscam_maps
-    return _run_maps(args, model, image, out_dir, "iscam", functools.partial(iscam_maps, model, **_iscam_kwargs(args)))
-
-
-def run_campp(args, model, image, out_dir):
-    """--campp true: the Grad-CAM++ heat map of every class for the one image at the backbone's output (torchcam's GradCAMpp of
-    the reference's torchcam_vis.py) -> `<out>/campp_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import gradcampp_maps
-    return _run_maps(args, model, image, out_dir, "campp", functools.partial(gradcampp_maps, model))
-
-
-def _smoothcampp_kwargs(args):
-    return dict(n_samples=int(getattr(args, "smoothcampp_samples", 4)), sigma=float(getattr(args, "smoothcampp_sigma", 0.3)),
-                batch=int(getattr(args, "smoothcampp_batch", 4)))
-
-
-def run_smoothcampp(args, model, image, out_dir):
-    """--smoothcampp true: the Smooth Grad-CAM++ heat map of every class for the one image (torchcam's SmoothGradCAMpp:
-    --smoothcampp_samples noisy copies at --smoothcampp_sigma in chunks of --smoothcampp_batch) -> `<out>/smoothcampp_{c}.png`,
-    uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import smooth_gradcampp_maps
-    return _run_maps(args, model, image, out_dir, "smoothcampp",
-                     functools.partial(smooth_gradcampp_maps, model, **_smoothcampp_kwargs(args)))
-
-
-def _extremal_kwargs(args):
-    return dict(areas=(float(getattr(args, "extremal_area", 0.1)),), n_iters=int(getattr(args, "extremal_iters", 800)),
-                variant=str(getattr(args, "extremal_variant", "preserve")), batch=int(getattr(args, "extremal_batch", 50)))
-
-
-def run_extremal(args, model, image, out_dir):
-    """--extremal true: the Extremal Perturbation map of every class for the one image (torchray's extremal_perturbation of the
-    reference's torchcam_vis.py: --extremal_iters steps on a mask of --extremal_area of the image, variant --extremal_variant, the
-    classes in groups of --extremal_batch) -> `<out>/extremal_{c}.png`, uint8 maps at the input resolution; returns them
-    [C, H, W]."""
-    from .tools.attribution import extremal_maps
-    return _run_maps(args, model, image, out_dir, "extremal", functools.partial(extremal_maps, model, **_extremal_kwargs(args)))
-
-
-def _iba_kwargs(args):
-    sigma = float(getattr(args, "iba_sigma", 1.0))
-    return dict(beta=float(getattr(args, "iba_beta", 10.0)), steps=int(getattr(args, "iba_steps", 10)),
-                samples=int(getattr(args, "iba_samples_per_step", 10)), sigma=sigma if sigma > 0.0 else None,
-                batch=int(getattr(args, "iba_batch", 0)) or None)
-
-
+# ------------------------------------------------------------------------------------------------ the families
 def iba_fit(args, model):
     """the feature distribution --iba needs (tools/attribution.py iba_estimate), fitted once per run on --iba_fit images of the
     validation loader -- seeded synthetic images under --synthetic_data true -- and kept on `args`"""
@@ -236,122 +220,67 @@ def iba_fit(args, model):
                 raw = not torch.is_tensor(images)
                 yield transform(images, args.device) if raw else images.to(args.device, dtype=torch.float32)
 
-        est = args._iba_estimate = iba_estimate(model, batches(), n_samples=int(getattr(args, "iba_fit", 5000)))
+        est = args._iba_estimate = iba_estimate(model, batches(), n_samples=_options(args, "iba")["fit"])
     return est
 
 
-def run_iba(args, model, image, out_dir):
-    """--iba true: the information-bottleneck map of every class for the one image (the IBA the reference's torchcam_vis.py attaches
-    to layer4: --iba_steps Adam steps, --iba_samples_per_step samples, weight --iba_beta, window --iba_sigma) ->
-    `<out>/iba_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import iba_maps
-    return _run_maps(args, model, image, out_dir, "iba", functools.partial(iba_maps, model, estimate=iba_fit(args, model),
-                                                                          **_iba_kwargs(args)))
+def _call(args, model, x, family, function, **kwargs):
+    """function(model, x, **kwargs) of tools/attribution.py under the options of the row `family`"""
+    from .tools import attribution
+    kwargs.update(option_kwargs(args, family.name))
+    if family.estimate:
+        kwargs["estimate"] = iba_fit(args, model)
+    return getattr(attribution, function)(model, x, **kwargs)
 
 
-def _igos_kwargs(args):
-    return dict(size=int(getattr(args, "igos_size", 8)), n_iters=int(getattr(args, "igos_iters", 15)),
-                n_steps=int(getattr(args, "igos_steps", 20)), l1_coeff=float(getattr(args, "igos_l1", 1.0)),
-                tv_coeff=float(getattr(args, "igos_tv", 20.0)), batch=int(getattr(args, "igos_batch", 50)))
+def run_family(args, model, image, out_dir, name):
+    """`--<name> true`: the maps of every class of the family `name` for the one image -> `<out>/<name>_{c}.png`, uint8 maps at
+    the input resolution, floored at --grad_min_level; returns them [C, H, W] (host).  run_grad, run_cam, ... below are this
+    function for one name each."""
+    from PIL import Image
+    from .tools import attribution
+    family = _row(name)
+    os.makedirs(out_dir, exist_ok=True)
+    x, min_level = image.unsqueeze(0).to(args.device, dtype=torch.float32), float(args.grad_min_level)
+    if family.reduce is None:
+        maps = _call(args, model, x, family, family.maps, min_level=min_level)[0]
+    else:
+        maps = getattr(attribution, family.maps)(_call(args, model, x, family, family.explain), min_level=min_level)[0]
+    if torch.is_tensor(maps):                                             # (attribution_maps has drawn on the host already)
+        maps = maps.cpu().numpy()
+    for c, m in enumerate(maps):
+        Image.fromarray(m, mode="L").save(os.path.join(out_dir, "%s_%d.png" % (name, c)))
+    return maps
 
 
-def run_igos(args, model, image, out_dir):
-    """--igos true: the I-GOS map of every class for the one image (the Integrated_Mask of the reference's torchcam_vis.py:
-    --igos_iters iterations of --igos_steps path images on a mask of --igos_size cells a side, weights --igos_l1 and --igos_tv, at
-    most --igos_batch rows per pass) -> `<out>/igos_{c}.png`, uint8 maps at the input resolution; returns them [C, H, W]."""
-    from .tools.attribution import igos_maps
-    return _run_maps(args, model, image, out_dir, "igos", functools.partial(igos_maps, model, **_igos_kwargs(args)))
-
-
-def _ig(args, model, x, classes=None):
-    from .tools.attribution import integrated_gradients
-    return integrated_gradients(model, x, classes=classes, n_steps=int(getattr(args, "ig_steps", 50)),
-                                batch=int(getattr(args, "ig_batch", 50)))
-
-
-def _smoothgrad(args, model, x, classes=None):
-    from .tools.attribution import smoothgrad
-    return smoothgrad(model, x, classes=classes, n_samples=int(getattr(args, "smoothgrad_samples", 50)),
-                      sigma=float(getattr(args, "smoothgrad_sigma", 1.0)), batch=int(getattr(args, "smoothgrad_batch", 50)))
-
-
-def _run_gradient_family(args, model, image, out_dir, attribute, stem):
-    from .tools.attribution import gradient_maps
-    return _run_maps(args, model, image, out_dir, stem,
-                     lambda x, min_level: gradient_maps(attribute(args, model, x), min_level=min_level))
-
-
-def run_ig(args, model, image, out_dir):
-    """--ig true: the Integrated Gradients attribution of every class for the one image (captum's IntegratedGradients of the
-    reference's captum_vis.py: zero baseline, Gauss-Legendre, --ig_steps steps) -> `<out>/ig_{c}.png`, uint8 maps at the input
-    resolution drawn on the device (tools/attribution.py gradient_maps, floored at --grad_min_level); returns them [C, H, W]."""
-    return _run_gradient_family(args, model, image, out_dir, _ig, "ig")
-
-
-def run_smoothgrad(args, model, image, out_dir):
-    """--smoothgrad true: the SmoothGrad attribution of every class for the one image (captum's NoiseTunnel of the reference's
-    captum_vis.py: --smoothgrad_samples noisy copies at --smoothgrad_sigma) -> `<out>/smoothgrad_{c}.png`, drawn like run_ig;
-    returns the uint8 maps [C, H, W]."""
-    return _run_gradient_family(args, model, image, out_dir, _smoothgrad, "smoothgrad")
+# run_<name>(args, model, image, out_dir) of every family the tool draws: run_grad, run_cam, run_rise, ... in table order
+globals().update({"run_" + f.name: functools.partial(run_family, name=f.name) for f in FAMILIES if f.maps})
 
 
 def _family_attribution(args, model, x, pred, family, slot_map=None, full=False):
-    """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w] (slot: the
-    given `slot_map`, taken right after the forward that predicted; grad: the channel mean of input_gradients; cam: gradcam;
-    rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of integrated_gradients / smoothgrad; campp: gradcampp;
-    smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba: information_bottleneck; igos: igos_saliency; sscam: sscam;
-    iscam: iscam).  full: grad, ig and smoothgrad keep their attribution
-    [n, 1, C, H, W] instead."""
-    from . import kernels as K
-    from .tools.attribution import extremal_saliency, gradcam, gradcampp, information_bottleneck, input_gradients, rise, scorecam
-    from .tools.attribution import igos_saliency, iscam, smooth_gradcampp, sscam
-    if family == "sscam":
-        return sscam(model, x, classes=[pred], **_sscam_kwargs(args))
-    if family == "iscam":
-        return iscam(model, x, classes=[pred], **_iscam_kwargs(args))
-    if family == "slot":
+    """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w]: the
+    row's `explain`, brought to a map by its `reduce`; for the row without one (slot) the given `slot_map`, taken right after
+    the forward that predicted.  full: the families with a `reduce` keep their attribution [n, 1, C, H, W] instead."""
+    row = _row(family)
+    if row.explain is None:
         return slot_map
-    if family == "grad":
-        g = input_gradients(model, x, classes=[pred])
-        return g if full else g.mean(dim=2)
-    if family == "cam":
-        return gradcam(model, x, classes=[pred])
-    if family == "scorecam":
-        return scorecam(model, x, classes=[pred], batch=int(getattr(args, "scorecam_batch", 250)))
-    if family == "ig":
-        g = _ig(args, model, x, classes=[pred])
-        return g if full else K.channel_mean(g)
-    if family == "smoothgrad":
-        g = _smoothgrad(args, model, x, classes=[pred])
-        return g if full else K.channel_mean(g)
-    if family == "campp":
-        return gradcampp(model, x, classes=[pred])
-    if family == "smoothcampp":
-        return smooth_gradcampp(model, x, classes=[pred], **_smoothcampp_kwargs(args))
-    if family == "extremal":
-        return extremal_saliency(model, x, classes=[pred], **_extremal_kwargs(args))
-    if family == "iba":
-        return information_bottleneck(model, x, iba_fit(args, model), classes=[pred], **_iba_kwargs(args))
-    if family == "igos":
-        return igos_saliency(model, x, classes=[pred], **_igos_kwargs(args))
-    return rise(model, x, classes=[pred], n_masks=int(getattr(args, "rise_masks", 4000)),
-                batch=int(getattr(args, "rise_batch", 250)))
+    g = _call(args, model, x, row, row.explain, classes=[pred])
+    return g if full or row.reduce is None else row.reduce(g)
 
 
+# ------------------------------------------------------------------------------------------------ the scores
 def run_causal(args, model, image, pred, families, slot_map=None):
-    """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics) of the predicted class's FLOAT map of
-    every family in `families` (slot: `slot_map` [1, 1, h, w], taken right after the forward that predicted; grad: the channel
-    mean of input_gradients; cam: gradcam; rise: rise; scorecam: scorecam; ig / smoothgrad: kernels.channel_mean of
-    integrated_gradients / smoothgrad; campp: gradcampp; smoothcampp: smooth_gradcampp; extremal: extremal_saliency; iba:
-    information_bottleneck; igos: igos_saliency; sscam: sscam; iscam: iscam), one printed
-    line each; returns {family: (deletion, insertion)}."""
+    """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics: --causal_step pixels per point, 0 =
+    one image row) of the predicted class's FLOAT map (_family_attribution) of every family in `families`, one printed line
+    each; returns {family: (deletion, insertion)}."""
     from .tools.attribution import causal_metrics
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
-    step, batch = int(getattr(args, "causal_step", 0)) or None, int(getattr(args, "rise_batch", 250))
+    # (the forward batch of the metric is --rise_batch whatever the family: the flag it had when RISE was the one family scored)
+    kwargs = dict(option_kwargs(args, "causal"), batch=option_kwargs(args, "rise")["batch"])
     scores = {}
     for family in families:
         maps = _family_attribution(args, model, x, pred, family, slot_map)
-        r = causal_metrics(model, x, maps, classes=[pred], step=step, batch=batch)
+        r = causal_metrics(model, x, maps, classes=[pred], **kwargs)
         scores[family] = (float(r.deletion[0, 0]), float(r.insertion[0, 0]))
         print("causal %s class %d: deletion %.6f insertion %.6f" % ((family, pred) + scores[family]))
     return scores
@@ -364,11 +293,11 @@ def run_infidelity(args, model, image, pred, families, slot_map=None):
     printed line each; returns {family: (raw, normalized, beta)}."""
     from .tools.attribution import infidelity
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
+    kwargs = option_kwargs(args, "infidelity")
     scores = {}
     for family in families:
         attr = _family_attribution(args, model, x, pred, family, slot_map, full=True)
-        r = infidelity(model, x, attr, classes=[pred], n_samples=int(getattr(args, "infidelity_samples", 50)),
-                       sigma=float(getattr(args, "infidelity_sigma", 0.003)), batch=int(getattr(args, "infidelity_batch", 50)))
+        r = infidelity(model, x, attr, classes=[pred], **kwargs)
         scores[family] = (float(r.raw[0, 0]), float(r.normalized[0, 0]), float(r.beta[0, 0]))
         print("infidelity %s class %d: raw %.6e normalized %.6e beta %.6e" % ((family, pred) + scores[family]))
     return scores
@@ -381,6 +310,7 @@ def run_sensitivity(args, model, image, pred, families):
     slot_saliency), one printed line each; returns {family: score}."""
     from .tools.attribution import _eval_mode, sensitivity_max, slot_saliency
     x = image.unsqueeze(0).to(args.device, dtype=torch.float32)
+    kwargs = option_kwargs(args, "sensitivity")
 
     def slot_maps(images):
         with _eval_mode(model), torch.no_grad():
@@ -389,95 +319,32 @@ def run_sensitivity(args, model, image, pred, families):
 
     scores = {}
     for family in families:
-        explain = slot_maps if family == "slot" else functools.partial(_family_attribution, args, model, pred=pred, family=family)
-        r = sensitivity_max(explain, x, n_samples=int(getattr(args, "sensitivity_samples", 10)),
-                            radius=float(getattr(args, "sensitivity_radius", 0.02)),
-                            batch=int(getattr(args, "sensitivity_batch", 11)))
+        explain = slot_maps if _row(family).explain is None else \
+            functools.partial(_family_attribution, args, model, pred=pred, family=family)
+        r = sensitivity_max(explain, x, **kwargs)
         scores[family] = float(r.score[0, 0])
         print("sensitivity %s class %d: max %.6e" % (family, pred, scores[family]))
     return scores
 
 
+# ------------------------------------------------------------------------------------------------ the command line
 def get_test_parser():
-    """the training tool's arguments plus this tool's own"""
+    """the training tool's arguments plus this tool's own: a flag and the options of every row of FAMILIES and SCORES"""
     parser = argparse.ArgumentParser("single-image xSlot inference", parents=[get_args_parser()])
     parser.add_argument("--checkpoint", default="", help="checkpoint written by train.py (default: the standard name "
                                                          "under --output_dir, if it exists)")
     parser.add_argument("--image", default="", help="image file; a seeded synthetic image is used when empty")
     parser.add_argument("--label", default=None, type=int)
     parser.add_argument("--vis_dir", default="sloter/vis")
-    parser.add_argument("--cam", default=False, type=_flag,
-                        help="true: write the Grad-CAM heat map of every class as cam_{c}.png into --vis_dir")
-    parser.add_argument("--rise", default=False, type=_flag,
-                        help="true: write the RISE saliency map of every class as rise_{c}.png into --vis_dir")
-    parser.add_argument("--rise_masks", default=4000, type=int, help="number of random masks of --rise")
-    parser.add_argument("--rise_batch", default=250, type=int, help="masked images per forward of --rise")
-    parser.add_argument("--causal", default=False, type=_flag,
-                        help="true: print the deletion / insertion scores of the predicted class's map of every family drawn")
-    parser.add_argument("--causal_step", default=0, type=int, help="pixels changed per point of --causal (0: --img_size)")
-    parser.add_argument("--scorecam", default=False, type=_flag,
-                        help="true: write the Score-CAM heat map of every class as scorecam_{c}.png into --vis_dir")
-    parser.add_argument("--scorecam_batch", default=250, type=int, help="masked images per forward of --scorecam")
-    parser.add_argument("--ig", default=False, type=_flag,
-                        help="true: write the Integrated Gradients map of every class as ig_{c}.png into --vis_dir")
-    parser.add_argument("--ig_steps", default=50, type=int, help="Gauss-Legendre steps of --ig")
-    parser.add_argument("--ig_batch", default=50, type=int, help="path images per forward and backward of --ig")
-    parser.add_argument("--smoothgrad", default=False, type=_flag,
-                        help="true: write the SmoothGrad map of every class as smoothgrad_{c}.png into --vis_dir")
-    parser.add_argument("--smoothgrad_samples", default=50, type=int, help="noisy copies per class of --smoothgrad")
-    parser.add_argument("--smoothgrad_sigma", default=1.0, type=float, help="standard deviation of the noise of --smoothgrad")
-    parser.add_argument("--smoothgrad_batch", default=50, type=int, help="noisy copies per forward and backward of --smoothgrad")
-    parser.add_argument("--campp", default=False, type=_flag,
-                        help="true: write the Grad-CAM++ heat map of every class as campp_{c}.png into --vis_dir")
-    parser.add_argument("--smoothcampp", default=False, type=_flag,
-                        help="true: write the Smooth Grad-CAM++ heat map of every class as smoothcampp_{c}.png into --vis_dir")
-    parser.add_argument("--smoothcampp_samples", default=4, type=int, help="noisy copies per class of --smoothcampp")
-    parser.add_argument("--smoothcampp_sigma", default=0.3, type=float, help="standard deviation of the noise of --smoothcampp")
-    parser.add_argument("--smoothcampp_batch", default=4, type=int, help="noisy copies per feature pass of --smoothcampp")
-    parser.add_argument("--extremal", default=False, type=_flag,
-                        help="true: write the Extremal Perturbation map of every class as extremal_{c}.png into --vis_dir")
-    parser.add_argument("--extremal_area", default=0.1, type=float, help="fraction of the image the mask of --extremal covers")
-    parser.add_argument("--extremal_iters", default=800, type=int, help="SGD steps of --extremal")
-    parser.add_argument("--extremal_variant", default="preserve", choices=("preserve", "delete"),
-                        help="--extremal keeps (preserve) or removes (delete) the evidence under the mask")
-    parser.add_argument("--extremal_batch", default=50, type=int, help="masks per forward and backward of --extremal")
-    parser.add_argument("--iba", default=False, type=_flag,
-                        help="true: write the information-bottleneck map of every class as iba_{c}.png into --vis_dir")
-    parser.add_argument("--iba_beta", default=10.0, type=float, help="weight of the information term of --iba")
-    parser.add_argument("--iba_steps", default=10, type=int, help="Adam steps of --iba")
-    parser.add_argument("--iba_samples_per_step", default=10, type=int, help="noisy samples per class and step of --iba")
-    parser.add_argument("--iba_sigma", default=1.0, type=float, help="standard deviation of the smoothing window of --iba (0: none)")
-    parser.add_argument("--iba_fit", default=5000, type=int, help="images the feature distribution of --iba is fitted on")
-    parser.add_argument("--iba_batch", default=0, type=int, help="head rows per pass of --iba (0: all classes at once)")
-    parser.add_argument("--igos", default=False, type=_flag,
-                        help="true: write the I-GOS map of every class as igos_{c}.png into --vis_dir")
-    parser.add_argument("--igos_size", default=8, type=int, help="cells a side of the mask of --igos")
-    parser.add_argument("--igos_iters", default=15, type=int, help="iterations of --igos")
-    parser.add_argument("--igos_steps", default=20, type=int, help="noisy path images per class and iteration of --igos")
-    parser.add_argument("--igos_l1", default=1.0, type=float, help="weight of the L1 term of --igos")
-    parser.add_argument("--igos_tv", default=20.0, type=float, help="weight of the total-variation term of --igos")
-    parser.add_argument("--igos_batch", default=50, type=int, help="images per forward (and backward) of --igos")
-    parser.add_argument("--sscam", default=False, type=_flag,
-                        help="true: write the SS-CAM heat map of every class as sscam_{c}.png into --vis_dir")
-    parser.add_argument("--sscam_samples", default=35, type=int, help="noisy copies of every channel's mask of --sscam")
-    parser.add_argument("--sscam_sigma", default=2.0, type=float, help="standard deviation of the noise of --sscam")
-    parser.add_argument("--sscam_batch", default=250, type=int, help="masked images per forward of --sscam")
-    parser.add_argument("--iscam", default=False, type=_flag,
-                        help="true: write the IS-CAM heat map of every class as iscam_{c}.png into --vis_dir")
-    parser.add_argument("--iscam_samples", default=10, type=int, help="scales of every channel's mask of --iscam")
-    parser.add_argument("--iscam_batch", default=250, type=int, help="masked images per forward of --iscam")
-    parser.add_argument("--infidelity", default=False, type=_flag,
-                        help="true: print the infidelity of the predicted class's explanation of every family drawn")
-    parser.add_argument("--infidelity_samples", default=50, type=int, help="noisy copies of --infidelity")
-    parser.add_argument("--infidelity_sigma", default=0.003, type=float, help="standard deviation of the noise of --infidelity")
-    parser.add_argument("--infidelity_batch", default=50, type=int,
-                        help="rows per forward of --infidelity, the clean image included")
-    parser.add_argument("--sensitivity", default=False, type=_flag,
-                        help="true: print the max-sensitivity of the predicted class's map of every family drawn")
-    parser.add_argument("--sensitivity_samples", default=10, type=int, help="perturbed copies of --sensitivity")
-    parser.add_argument("--sensitivity_radius", default=0.02, type=float, help="half-width of the box of --sensitivity")
-    parser.add_argument("--sensitivity_batch", default=11, type=int,
-                        help="rows per call of the explanation method of --sensitivity, the clean image included")
+    for row in FAMILIES + SCORES:
+        if isinstance(row, Score):
+            parser.add_argument("--" + row.name, default=False, type=_flag, help="true: print the %s of every family drawn" % row.what)
+        elif row.flag:
+            parser.add_argument("--" + row.name, default=False, type=_flag,
+                                help="true: write the %s of every class as %s_{c}.png into --vis_dir" % (row.what, row.name))
+        for o in row.options:
+            parser.add_argument("--%s_%s" % (row.name, o.suffix), default=o.default, type=o.type, choices=o.choices,
+                                help="--%s: %s (default: %s)" % (row.name, o.help, o.default))
     return parser
 
 
@@ -508,36 +375,12 @@ def main():
     if (args.causal or args.infidelity) and model.use_slot:
         from .tools.attribution import slot_saliency
         slot_map = slot_saliency(model)[:, pred:pred + 1].contiguous()       # (before another forward replaces last_attn)
-    if want_grad:
-        run_grad(args, model, image, args.vis_dir)
-    if args.cam:
-        run_cam(args, model, image, args.vis_dir)
-    if args.rise:
-        run_rise(args, model, image, args.vis_dir)
-    if args.scorecam:
-        run_scorecam(args, model, image, args.vis_dir)
-    if args.ig:
-        run_ig(args, model, image, args.vis_dir)
-    if args.smoothgrad:
-        run_smoothgrad(args, model, image, args.vis_dir)
-    if args.campp:
-        run_campp(args, model, image, args.vis_dir)
-    if args.smoothcampp:
-        run_smoothcampp(args, model, image, args.vis_dir)
-    if args.extremal:
-        run_extremal(args, model, image, args.vis_dir)
-    if args.iba:
-        run_iba(args, model, image, args.vis_dir)
-    if args.igos:
-        run_igos(args, model, image, args.vis_dir)
-    if args.sscam:
-        run_sscam(args, model, image, args.vis_dir)
-    if args.iscam:
-        run_iscam(args, model, image, args.vis_dir)
-    families = [f for f, on in (("slot", model.use_slot), ("grad", want_grad), ("cam", args.cam), ("rise", args.rise),
-                                ("scorecam", args.scorecam), ("ig", args.ig), ("smoothgrad", args.smoothgrad),
-                                ("campp", args.campp), ("smoothcampp", args.smoothcampp), ("extremal", args.extremal),
-                                ("iba", args.iba), ("igos", args.igos), ("sscam", args.sscam), ("iscam", args.iscam)) if on]
+    unflagged = {"slot": model.use_slot, "grad": want_grad}                  # the rows with `flag` False
+    drawn = [f for f in FAMILIES if (getattr(args, f.name) if f.flag else unflagged[f.name])]
+    for f in drawn:
+        if f.maps:
+            run_family(args, model, image, args.vis_dir, f.name)
+    families = [f.name for f in drawn]
     if args.causal:
         run_causal(args, model, image, pred, families, slot_map)
     if args.infidelity:
