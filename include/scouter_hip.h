@@ -237,6 +237,19 @@ int scouter_conv2d_planes_partial_rows(long M, int tile);
 #define SCOUTER_WGRAD_ROWS32 5
 int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                    int kernel);
+/* the launch of the per-tap kernel (one workgroup per tap: kernel = SCOUTER_WGRAD_F32 / SCOUTER_WGRAD_BF16) for this shape and
+ * plan_hint, one integer per call: BM / BN -- the input / output channel edge of the block tile; SPLITS -- split-K slabs (above 1:
+ * the slab sum runs); PIX_PER_SPLIT -- pixels of one split (the last split holds the rest); MODE -- the addressing mode, 0 =
+ * general, 1 = same-size padded taps, 2 = pointwise.  Evaluated by the launchers' own plan and mode functions.  -1: the entry
+ * point refuses the shape (or an unknown kernel / field).  With plan_hint < 0 the entry points run a tap-fused kernel instead
+ * where scouter_conv2d_wgrad_kernel_ok says TAPS / XWT / BWT; this query describes the per-tap launch they fall back to. */
+#define SCOUTER_WGRAD_PLAN_BM 0
+#define SCOUTER_WGRAD_PLAN_BN 1
+#define SCOUTER_WGRAD_PLAN_SPLITS 2
+#define SCOUTER_WGRAD_PLAN_PIX_PER_SPLIT 3
+#define SCOUTER_WGRAD_PLAN_MODE 4
+long scouter_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                               int kernel, int plan_hint, int field);
 /* stem (Cin < 32): im2col of the NCHW image into [M][Kpad] rows so the stem runs as a 1x1 conv on the same path */
 int scouter_im2col_nchw_f32(const float* x, float* col, int B, int Cin, int H, int W, int k, int stride, int pad,
                             int Kpad, void* stream);

@@ -1030,12 +1030,37 @@ extern "C" int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int 
     }
 }
 
+// what the per-tap launch of scouter_conv2d_wgrad_f32 / _bf16_io is for this shape and plan_hint: the wgrad_plan() and
+// wgrad_same_mode() calls of the two launchers below, nothing of its own
+extern "C" long scouter_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
+                                          int kernel, int plan_hint, int field) {
+    if ((kernel != 0 && kernel != 1) || !sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return -1;
+    const ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+    if (kernel == 0 ? !wgrad_entry_ok(g) : !wgrad_bf16_geom_ok(g)) return -1;
+    const WgradPlan p = kernel == 0 ? wgrad_plan(g, plan_hint) : wgrad_plan(g, plan_hint, true, 64);
+    switch (field) {
+        case 0: return p.bm;
+        case 1: return p.bn;
+        case 2: return p.splits;
+        case 3: return p.pix_per_split;
+        case 4: return wgrad_same_mode(g, kernel == 0 ? BK : 64);
+        default: return -1;
+    }
+}
+
 extern "C" size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw,
                                                        int stride, int pad, int groups, int plan_hint) {
     if (groups <= 0 || Cin % groups || Cout % groups) return 0;
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     WgradPlan p = wgrad_plan(g, plan_hint);
     size_t need = p.splits <= 1 ? 0 : (size_t)p.splits * kh * kw * g.Cg * Cout * sizeof(float);
+    if (wgrad_bf16_geom_ok(g)) {
+        // the bf16 kernel's plan of the same hint: 96 / 160 channels per group are two / three ragged 64-wide tiles where the fp32
+        // kernel has three / five of 32, so its budget buys more splits
+        const WgradPlan pb = wgrad_plan(g, plan_hint, true, 64);
+        const size_t nb = pb.splits <= 1 ? 0 : (size_t)pb.splits * kh * kw * g.Cg * Cout * sizeof(float);
+        if (nb > need) need = nb;
+    }
     if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {                                           // tap-fused plan (see wgrad_f32)
         const long tiles = (long)(g.Ng / (g.Ng % 64 == 0 ? 64 : 32)) * groups;
         long want = 1024 / tiles;

@@ -327,6 +327,7 @@ def _fuse_wanted(post, kh, plane_kernel=False):
 # POLICY here: the switches, the measured thresholds and which legal kernel a layer is sent to.
 EPI_BIAS, EPI_ADDEND, EPI_RELU, EPI_BN_STATS, EPI_BN_BWD, EPI_BN_BWD2 = 1, 2, 4, 8, 16, 32          # (SCOUTER_EPI_*)
 WGRAD_F32, WGRAD_BF16, WGRAD_TAPS, WGRAD_XWT, WGRAD_BWT, WGRAD_ROWS32 = 0, 1, 2, 3, 4, 5             # (SCOUTER_WGRAD_*)
+WGRAD_PLAN_FIELDS = ("bm", "bn", "splits", "pix_per_split", "mode")                                  # (SCOUTER_WGRAD_PLAN_*)
 _asked = {}
 
 

@@ -4,8 +4,10 @@
 // Host side of the library and this file with the sanitizer, from the repository root:
 //   for f in scouter_amd/csrc/*.hip; do hipcc --offload-arch=gfx950 -O1 -std=c++17 -fPIC -Xarch_host -fsanitize=undefined \
 //       -Xarch_host -fno-sanitize-recover=undefined -c $f -o build_dev/ubsan/$(basename $f .hip).o; done
-//   hipcc --offload-arch=gfx950 -fsanitize=undefined -Iinclude tools_dev/route_queries_ubsan.cpp build_dev/ubsan/*.o \
-//       -o build_dev/ubsan/route_queries_ubsan && build_dev/ubsan/route_queries_ubsan
+//   hipcc -std=c++17 -fsanitize=undefined -fno-sanitize-recover=undefined -Iinclude -x c++ -c tools_dev/route_queries_ubsan.cpp \
+//       -o build_dev/ubsan/route_queries_main.o        (on its own: next to a .cpp, hipcc reads the object files as HIP source)
+//   hipcc --offload-arch=gfx950 -fsanitize=undefined build_dev/ubsan/*.o -o build_dev/ubsan/route_queries_ubsan && \
+//       build_dev/ubsan/route_queries_ubsan
 #include <initializer_list>
 #include <stdio.h>
 
@@ -48,6 +50,10 @@ int main() {
                             }
                         }
                     for (int k = 0; k <= 5; ++k, ++calls) yes += scouter_conv2d_wgrad_kernel_ok(B, H, W, Ci, Co, kh, kw, s, p, g, k);
+                    for (int plan : {-1, 0, 3, 51})
+                        for (int k = 0; k <= 1; ++k)
+                            for (int field = 0; field <= 4; ++field, ++calls)
+                                yes += scouter_conv2d_wgrad_plan(B, H, W, Ci, Co, kh, kw, s, p, g, k, plan, field) >= 0;
                     for (int plan : {-1, 0, 3, 51, 64, 67})
                         for (int np = 1; np <= 3; np += 2, ++calls)
                             yes += scouter_conv2d_wgrad_planes_plan_ok(B, H, W, Ci, Co, kh, kw, p, g, np, plan);
