@@ -471,6 +471,38 @@ int scouter_grad_powers_accumulate(const float* grads, double* acc2, double* acc
 int scouter_gradcampp_smooth_f32(const float* feat, const double* acc2, const double* acc3, const float* glast, float* out,
                                  int n_samples, int B, int N, int C, long out_stride, int relu, void* stream);
 
+/* ---- CAM of the FC baseline (Zhou et al., CVPR 2016; torchcam's CAM(model, 'layer4', 'fc'), the first extractor of the
+ * reference's torchcam_vis.py: CAM._get_weights followed by compute_cams; csrc/fccam.hip, tools/attribution.py fccam).
+ * feat NHWC fp32 [B][N = h*w][C], w fp32 [n_classes][C] (the fc weight as it is stored), both 16-byte aligned; cols i32 on the
+ * device -- per_image == 0: [K] columns shared by all images; per_image != 0: [B], each image its own class, K = 1 -- in
+ * [0, n_classes) (checked by the caller, clamped here); out fp32 [B][K][N]:
+ * out[b][k][p] = sum_c w[col][c] * feat[b][p][c] (relu != 0: clamped at 0).  No bias and no 1 / N.  One workgroup per image and
+ * tile of 8 positions, the tile staged in LDS 2048 channels at a time and walked by the K classes: the features cross HBM once
+ * (every class re-reads the tile from LDS, a wave per class: for large K the LDS traffic sets the time, not HBM).
+ * fp32, one fixed summation order per element that depends on C alone and no atomics: two calls, a per-image call and the
+ * matching columns of an all-classes call, and an image at another batch position give the same bits.  Any N, C, K >= 1.  A
+ * null or misaligned pointer, a count below 1, or per_image with K != 1: SC_ERR_ARG; a tensor past 32-bit offsets:
+ * SC_ERR_UNSUPPORTED; nothing is launched then. */
+int scouter_cam_fc_f32(const float* feat, const float* w, const int* cols, float* out, int B, int N, int C, int n_classes, int K,
+                       int per_image, int relu, void* stream);
+
+/* ---- Localisation scores of uint8 maps: the area size and the precision of the SCOUTER paper's comparison and the pointing
+ * game (Zhang et al., ECCV 2016) from one pass (csrc/localization.hip, tools/attribution.py localization).  maps u8
+ * [B][K][H][W] (what scouter_cam_maps_u8 / scouter_heat_maps_u8 write), boxes i32 [B][max_boxes][4] = (x0, y0, x1, y1), half-open
+ * pixel ranges of the map's own grid, n_boxes i32 [B] in [0, max_boxes] (clamped); boxes and n_boxes may both be null: no image
+ * has a box.  A pixel is inside when it lies in any of its image's first n_boxes[b] boxes (a union: a pixel under two boxes
+ * counts once); boxes are clipped to the map and a box with x1 <= x0 or y1 <= y0 holds nothing.  sums i64 [B][K][4] =
+ * (S, the sum of the map's bytes; S_in, the sum of the bytes inside; arg, the flat index y * W + x of the largest byte, the
+ * smallest index among equals; hit, 1 if that pixel is inside, else 0).  Integers only, so every value is exact.  One
+ * workgroup per map, no atomics.  1 <= max_boxes <= 32 and H * W < 2^31, else SC_ERR_UNSUPPORTED. */
+int scouter_map_localization_u8(const unsigned char* maps, const int* boxes, const int* n_boxes, long* sums, int B, int K, int H,
+                                int W, int max_boxes, void* stream);
+/* The bytes SlotAttention.vis_maps draws (reference slot_attention.py:74) for every image of a batch: maps fp32 [M][G][N] ->
+ * out u8 [M][G][N]; per group m, lo and hi over all G * N values, span = hi - lo,
+ * out = (unsigned char)((v - lo) / span * 255.f) -- these fp32 operations in this order, truncating; span == 0: all zeros.
+ * One workgroup per group.  G * N < 2^31. */
+int scouter_group_maps_u8(const float* maps, unsigned char* out, int M, int G, long N, void* stream);
+
 /* ---- Infidelity and max-sensitivity of an explanation (Yeh et al., NeurIPS 2019, "On the (In)fidelity and Sensitivity of
  * Explanations"; captum's infidelity and sensitivity_max, two columns of the SCOUTER paper's comparison of explanations;
  * csrc/fidelity.hip, tools/attribution.py infidelity / sensitivity_max).  No reference program computes either here: the

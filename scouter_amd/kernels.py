@@ -1723,6 +1723,31 @@ def cam_maps(cam, H, W, min_level=0.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# CAM of the FC baseline (csrc/fccam.hip; tools/attribution.py fccam / fccam_maps)
+# ---------------------------------------------------------------------------------------------------------------
+def cam_fc(feat, weight, cols, out, per_image=False, relu=False):
+    """out[b, k, p] = sum_c weight[cols[k], c] * feat[b, p, c] (relu: clamped at 0) for NHWC fp32 feat [B, h, w, C], the fc weight
+    fp32 [n_classes, C] as it is stored, and fp32 out [B, K, h, w] or [B, K, h * w].  cols int32 on the device (the caller keeps
+    them inside [0, n_classes)): [K] columns shared by all images, or with per_image [B] -- every image its own class -- and
+    K = 1.  No bias and no 1 / (h w).  One launch in which the features cross HBM once; one fixed summation order per element
+    that depends on C alone, so two calls, a per-image call and the matching columns of an all-classes call, and an image at
+    another batch position give the same bits."""
+    _chk(feat, "cam_fc: feat"); _chk(weight, "cam_fc: weight"); _chk(cols, "cam_fc: cols", torch.int32); _chk(out, "cam_fc: out")
+    if feat.dim() != 4 or weight.dim() != 2 or weight.shape[1] != feat.shape[3] or cols.dim() != 1:
+        raise RuntimeError("cam_fc: feat must be NHWC [B, h, w, C], weight [n_classes, C] and cols [K] or [B] (got %s, %s and %s)"
+                           % (tuple(feat.shape), tuple(weight.shape), tuple(cols.shape)))
+    B, h, w, C = feat.shape
+    N, Kc = h * w, 1 if per_image else int(cols.shape[0])
+    if cols.shape[0] != (B if per_image else Kc) or out.dim() not in (3, 4) or tuple(out.shape[:2]) != (B, Kc) or \
+            out.numel() != B * Kc * N:
+        raise RuntimeError("cam_fc: cols must be [%s] and out [B = %d, K = %d, h = %d, w = %d] or [B, K, h * w] (got %s and %s)"
+                           % ("B = %d" % B if per_image else "K", B, Kc, h, w, tuple(cols.shape), tuple(out.shape)))
+    _native.check(_native.lib().scouter_cam_fc_f32(_p(feat), _p(weight), _p(cols), _p(out), B, N, C, int(weight.shape[0]), Kc,
+                                                   int(bool(per_image)), int(bool(relu)), _stream()), "cam_fc")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Grad-CAM++ / Smooth Grad-CAM++ (csrc/gradcampp.hip; tools/attribution.py gradcampp / smooth_gradcampp)
 # ---------------------------------------------------------------------------------------------------------------
 def gradcampp(feat, dfeat, out, relu=True):
@@ -1833,6 +1858,48 @@ def heat_maps(maps, min_level=0.0):
     lead, M = _lead(maps.shape, 2)
     out = torch.empty(tuple(maps.shape), dtype=torch.uint8, device=maps.device)
     _native.check(_native.lib().scouter_heat_maps_u8(_p(maps), _p(out), M, H, W, float(min_level), _stream()), "heat_maps")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Localisation scores of byte maps (csrc/localization.hip; tools/attribution.py localization / slot_maps)
+# ---------------------------------------------------------------------------------------------------------------
+def map_localization(maps, boxes=None, n_boxes=None):
+    """uint8 maps [B, K, H, W] -> int64 [B, K, 4] on the device = (S, S_in, arg, hit) per map: the sum of its bytes, the sum of
+    the bytes inside the union of its image's boxes, the flat index y * W + x of its largest byte (the smallest index among
+    equals) and whether that pixel lies in a box.  boxes int32 [B, max_boxes, 4] = (x0, y0, x1, y1), half-open pixel ranges of
+    the map's own grid, clipped to the map (x1 <= x0 or y1 <= y0: an empty box), 1 <= max_boxes <= 32; n_boxes int32 [B] says how
+    many of an image's boxes count.  Both None: no image has a box.  Integers only, so every value is exact.  One launch."""
+    _chk(maps, "map_localization: maps", torch.uint8)
+    _chk(boxes, "map_localization: boxes", torch.int32); _chk(n_boxes, "map_localization: n_boxes", torch.int32)
+    if maps.dim() != 4:
+        raise RuntimeError("map_localization: maps must be uint8 [B, K, H, W], got shape %s" % (tuple(maps.shape),))
+    B, Kc, H, W = maps.shape
+    if (boxes is None) != (n_boxes is None):
+        raise RuntimeError("map_localization: boxes and n_boxes must both be given or both be None")
+    max_boxes = 1
+    if boxes is not None:
+        if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4 or tuple(n_boxes.shape) != (B,):
+            raise RuntimeError("map_localization: boxes must be int32 [B = %d, max_boxes, 4] and n_boxes int32 [B] (got %s and %s)"
+                               % (B, tuple(boxes.shape), tuple(n_boxes.shape)))
+        max_boxes = int(boxes.shape[1])
+    sums = torch.empty((B, Kc, 4), dtype=torch.int64, device=maps.device)
+    _native.check(_native.lib().scouter_map_localization_u8(_p(maps), _p(boxes), _p(n_boxes), _p(sums), B, Kc, H, W, max_boxes,
+                                                            _stream()), "map_localization")
+    return sums
+
+
+def group_maps(maps):
+    """fp32 maps [M, G, ...] -> uint8 of the same shape on the device, the G maps of a group scaled JOINTLY: lo and hi over all
+    values of the group, uint8((v - lo) / (hi - lo) * 255) in fp32, truncating -- what SlotAttention.vis_maps does on the host for
+    the classes of one image; a constant group is all zeros.  One launch."""
+    _chk(maps, "group_maps: maps")
+    if maps.dim() < 3:
+        raise RuntimeError("group_maps: maps must be [M, G, ...], got shape %s" % (tuple(maps.shape),))
+    M, G = int(maps.shape[0]), int(maps.shape[1])
+    N = maps[0, 0].numel() if M and G else 0
+    out = torch.empty(tuple(maps.shape), dtype=torch.uint8, device=maps.device)
+    _native.check(_native.lib().scouter_group_maps_u8(_p(maps), _p(out), M, G, N, _stream()), "group_maps")
     return out
 
 

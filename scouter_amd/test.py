@@ -144,26 +144,27 @@ SCORES = (
 _ROWS = {row.name: row for row in FAMILIES + SCORES}
 
 
-def _row(name):
-    if name not in _ROWS:
-        raise ValueError("unknown explanation family or score %r (known: %s)" % (name, ", ".join(_ROWS)))
-    return _ROWS[name]
+def _row(name, rows=_ROWS):
+    """the row `name` of the table `rows` {name: row}: this tool's own, or one that extends it (tools/explanation_table.py)"""
+    if name not in rows:
+        raise ValueError("unknown explanation family or score %r (known: %s)" % (name, ", ".join(rows)))
+    return rows[name]
 
 
-def _options(args, name):
+def _options(args, name, rows=_ROWS):
     """{suffix: value} of every option of the row `name`, read from `args` and converted; a namespace without an option (the
     tests build such) gets the table's default"""
     values = {}
-    for o in _row(name).options:
+    for o in _row(name, rows).options:
         v = o.type(getattr(args, "%s_%s" % (name, o.suffix), o.default))
         values[o.suffix] = o.convert(v) if o.convert else v
     return values
 
 
-def option_kwargs(args, name):
+def option_kwargs(args, name, rows=_ROWS):
     """the keyword arguments the options of the row `name` give its library functions"""
-    values = _options(args, name)
-    return {o.keyword: values[o.suffix] for o in _row(name).options if o.keyword}
+    values = _options(args, name, rows)
+    return {o.keyword: values[o.suffix] for o in _row(name, rows).options if o.keyword}
 
 
 _igos_kwargs = functools.partial(option_kwargs, name="igos")           # (tests/test_igos_cpu.py reads the keywords by this name)
@@ -225,9 +226,9 @@ def iba_fit(args, model):
 
 
 def _call(args, model, x, family, function, **kwargs):
-    """function(model, x, **kwargs) of tools/attribution.py under the options of the row `family`"""
+    """function(model, x, **kwargs) of tools/attribution.py under the options of the row `family` (its own: read from the row)"""
     from .tools import attribution
-    kwargs.update(option_kwargs(args, family.name))
+    kwargs.update(option_kwargs(args, family.name, {family.name: family}))
     if family.estimate:
         kwargs["estimate"] = iba_fit(args, model)
     return getattr(attribution, function)(model, x, **kwargs)
@@ -348,8 +349,9 @@ def get_test_parser():
     return parser
 
 
-def main():
-    args = get_test_parser().parse_args()
+def build_model(args):
+    """the model of a parsed command line on --device, folded under --eval_fold, with --checkpoint (or the standard name under
+    --output_dir) loaded where it exists -> (model, whether --grad was given); shared with tools/explanation_table.py"""
     for name, typ in (("num_classes", int), ("lambda_value", float), ("power", int), ("slots_per_class", int)):
         setattr(args, name, typ(getattr(args, name)))
     args.vis, args.vis_id = False, 0                  # maps are taken from model.slot.last_attn, image index 0
@@ -363,6 +365,12 @@ def main():
         print("load", ckpt)
     else:
         print("no checkpoint found (%s): random weights" % ckpt)
+    return model, want_grad
+
+
+def main():
+    args = get_test_parser().parse_args()
+    model, want_grad = build_model(args)
     channels, size = (1 if args.dataset == "MNIST" else 3), int(args.img_size)
     if args.image:
         raw, image = load_image(args.image, size, channels)

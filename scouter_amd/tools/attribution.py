@@ -111,7 +111,20 @@ step; here the classes of an image are the rows of one stream, the path images, 
 the L1 / total-variation terms and the trial images are HIP kernels (kernels.igos_path_images, igos_accumulate, igos_mask_grad,
 igos_trial_images, igos_upsample), every trial step goes through the model in one batch, and the selection itself runs on the
 device (kernels.igos_step), so nothing comes to the host for the whole run.  The docstring of `igos` is the specification and
-lists what departs from the reference."""
+lists what departs from the reference.
+
+The class activation map itself (`fccam`, `fccam_maps`): CAM (Zhou et al. 2016), the first extractor the reference's
+torchcam_vis.py builds -- torchcam's CAM(model, 'layer4', 'fc') on the FC baseline (--use_slot false).  The fc weights of a class
+are contracted with the features `gradcam` reads: one feature pass and one HIP kernel (kernels.cam_fc) in which the features
+cross HBM once, no backward at all.  It exists for the baseline only; a model with a slot head has no fc layer and is refused.
+
+Where a map lies (`localization`, `slot_maps`): the area size and the precision of the SCOUTER paper's comparison and the strict
+pointing game, for the uint8 maps every *_maps function draws, against bounding boxes.  One HIP kernel forms the exact integer
+sums of a batch of maps (kernels.map_localization: the mass, the mass inside the union of an image's boxes, the largest byte's
+position and whether a box holds it) and the ratios are float64 divisions of them on the device; `slot_maps` gives the byte
+slot maps of a whole batch, each image scaled as SlotAttention.vis_maps scales one on the host (kernels.group_maps), the maps
+the reference's attention_ratio is taken from.  tools/explanation_table.py puts these scores, `causal_metrics` and `infidelity`
+into the paper's table: one row per family, every cell a mean over a validation set."""
 import collections
 import contextlib
 import functools
@@ -126,7 +139,11 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None):
     """Gradient of the model output with respect to `images` [B, C, H, W] -> fp32 [B, K, C, H, W] on the images' device.
 
     of="log_prob": K = len(classes) (None: every class); slice [:, k] is d(sum_b output[b, classes[k]]) / d images -- one
-    eval-mode forward + backward per class, with a one-hot gradient on the model output (the log-probabilities).
+    eval-mode forward + backward per class, with a one-hot gradient on the model output (the log-probabilities).  A LongTensor
+    [B] as `classes`: every image its own class, K = 1 and one backward with the seed 1 at (b, classes[b]), the convention of
+    `gradcam` and every other method here (any other tensor is a ValueError, a class outside the outputs an IndexError).  Before
+    this form existed a tensor was iterated like a list of ints -- K = len(classes) columns for every image; pass
+    `classes.tolist()` for that.
     of="loss": K = 1, the gradient of the training loss (losses[0]) for the labels `target`.
 
     The model is put in eval mode (BatchNorm uses its running statistics and no buffer moves) and the caller's mode is
@@ -143,6 +160,14 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None):
                 x = images.detach().float().clone().requires_grad_(True)
                 _, losses = model(x, target)
                 grads.append(torch.autograd.grad(losses[0], x)[0])
+            elif torch.is_tensor(classes):                     # a LongTensor [B]: every image its own class, one backward, K = 1
+                _, cols = _class_list(classes, images.shape[0], None)
+                x = images.detach().float().clone().requires_grad_(True)
+                out = model(x)
+                _check_class_range(cols, out.shape[1])
+                seed = torch.zeros_like(out)
+                seed[torch.arange(out.shape[0], device=out.device), classes.to(out.device)] = 1.0
+                grads.append(torch.autograd.grad(out, x, seed)[0])
             else:
                 seed = None
                 for c in (classes if classes is not None else range(_num_classes(model, images))):
@@ -242,6 +267,39 @@ def gradcam_maps(model, images, classes=None, size=None, min_level=0.0):
     either scaling step is all zeros, like attribution_maps."""
     H, W = _out_size(size, images)
     return K.cam_maps(gradcam(model, images, classes), H, W, min_level)
+
+
+def fccam(model, images, classes=None, relu=False):
+    """CAM (Zhou et al., CVPR 2016; torchcam's CAM(model, 'layer4', 'fc'), the first extractor of the reference's
+    torchcam_vis.py) of `images` [B, C, H, W] for the FC baseline (--use_slot false) -> fp32 [B, K, h, w] on the images' device:
+    cam[b, k, p] = sum_c fc.weight[classes[k], c] * features[b, p, c] (`relu`: clamped at 0) -- CAM._get_weights followed by
+    compute_cams: no bias and no 1 / (h w), so mean_p cam[b, k] + fc.bias[classes[k]] is the model's logit.
+
+    classes as in `gradcam`: None (every class), a list of K ints, or a LongTensor [B] (every image its own class, K = 1).  One
+    SlotModel.feature_pass for the batch -- eval mode, the caller's mode restored, BatchNorm-folded when the model's inference
+    fold is on -- and one launch (kernels.cam_fc); there is no backward at all, so no `.grad` appears.  RuntimeError for a model
+    with a slot head: it has no fc layer to read."""
+    B = _check_images(images).shape[0]
+    if getattr(model, "use_slot", True):
+        raise RuntimeError("fccam: the model has a slot head and no fc layer to read: CAM belongs to the --use_slot false "
+                           "baseline; gradcam is the method for the slot model")
+    weight = model.backbone.fc.weight.detach()
+    per_image, cols = _class_columns(classes, B, int(weight.shape[0]))
+    feat = model.feature_pass(images).features
+    _, h, w, _ = feat.shape
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.data_ptr() % 16:
+        weight = weight.float().contiguous().clone()
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(feat.device)
+    cam = torch.empty((B, 1 if per_image else len(cols), h, w), dtype=torch.float32, device=feat.device)
+    if cam.numel() == 0:
+        return cam
+    return K.cam_fc(feat, weight, cols_dev, cam, per_image=per_image, relu=relu)
+
+
+def fccam_maps(model, images, classes=None, size=None, min_level=0.0):
+    """uint8 CAM heat maps [B, K, H, W] on the device: `fccam`, then the drawing steps of `gradcam_maps` (kernels.cam_maps)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(fccam(model, images, classes), H, W, min_level)
 
 
 def gradcampp(model, images, classes=None, relu=True):
@@ -610,6 +668,50 @@ def slot_saliency(model):
         a = a.reshape(a.shape[0], slot.num_classes, slot.slots_per_class, a.shape[-1]).sum(2)
     side = int(a.size(2) ** 0.5)
     return a.reshape(a.shape[0], a.shape[1], side, side).contiguous()
+
+
+def slot_maps(model):
+    """The uint8 slot maps of EVERY image of the model's last forward, [B, num_classes, h, w] on the device: `slot_saliency`
+    with the maps of all classes of an image scaled jointly to bytes (kernels.group_maps: uint8((v - lo) / (hi - lo) * 255) in
+    fp32 over the image's num_classes h w values) -- image i holds the bytes SlotAttention.vis_maps draws on the host with
+    vis_id = i, the map the reference's attention_ratio (test.py:40-44) is taken from.  A constant image is all zeros."""
+    return K.group_maps(slot_saliency(model))
+
+
+LocalizationScores = collections.namedtuple("LocalizationScores", "area precision hit boxed empty sums")
+LocalizationScores.__doc__ = """The result of `localization`, all on the maps' device: area / precision / hit float64 [B, K], boxed
+bool [B] (the image has a box), empty bool [B, K] (the map is all zeros) and the integers they come from, sums int64 [B, K, 4] =
+(S, S_in, arg, hit) of kernels.map_localization."""
+
+
+def localization(maps, boxes=None, n_boxes=None):
+    """Area size, precision and pointing game of uint8 `maps` [B, K, H, W] (what every *_maps function, kernels.cam_maps and
+    kernels.heat_maps produce) against bounding boxes -> LocalizationScores.  The SCOUTER paper names the first two scores and no
+    reference program computes precision or pointing, so this docstring is their specification.
+
+    boxes int32 [B, max_boxes, 4] = (x0, y0, x1, y1), half-open pixel ranges of the map's own H x W grid, at most 32 an image;
+    n_boxes int32 [B] says how many of an image's boxes count.  Both None: no image has a box.  A pixel is inside when it lies
+    in any of its image's boxes -- a union, a pixel under two boxes counts once; boxes are clipped to the map, and a box with
+    x1 <= x0 or y1 <= y0 holds nothing.  With S the sum of a map's bytes and S_in the sum of those inside:
+
+    area = S / (255 H W): the reference's attention_ratio (test.py:40-44), for any map.
+    precision = S_in / S, and 0 where S == 0 (`empty`): the share of the map's mass inside the boxes, taken on the BYTE map, not
+        on the float map it was drawn from.
+    hit = 1 when the map's largest byte -- the smallest flat index y W + x among equals -- lies inside, else 0: the STRICT
+        pointing game; the customary 15-pixel tolerance is not applied.
+
+    kernels.map_localization forms the integers exactly, one launch; the two ratios are float64 divisions of them on the device.
+    An image without a box (`boxed` false) has precision and hit 0: a mean over a data set leaves it out (and the empty maps),
+    as tools/explanation_table.py does.  Nothing is read on the host."""
+    sums = K.map_localization(maps, boxes, n_boxes)
+    H, W = maps.shape[-2:]
+    S, S_in = sums[..., 0], sums[..., 1]
+    empty = S == 0
+    # (a tensor as the divisor: torch multiplies by the reciprocal of a Python scalar on the device, which is one rounding more)
+    area = S.double() / torch.full_like(S, 255 * H * W).double()
+    precision = torch.where(empty, torch.zeros_like(area), S_in.double() / torch.where(empty, torch.ones_like(S), S).double())
+    boxed = (n_boxes > 0) if n_boxes is not None else torch.zeros(maps.shape[0], dtype=torch.bool, device=maps.device)
+    return LocalizationScores(area, precision, sums[..., 3].double(), boxed, empty, sums)
 
 
 def _num_outputs(model, images):
