@@ -58,6 +58,32 @@ int scouter_get_switch(const char* name);
 int scouter_resize_normalize_u8_f32(const unsigned char* const* srcs, const int* hw, unsigned char* tmp,
                                     const long* tmp_off, const float* lut, float* out, int B, int C, int max_h, int max_w,
                                     int out_h, int out_w, void* stream);
+/* the same resize with the bytes stored as they are: out uint8 [B][C][out_h][out_w] -- the input of the augmentation
+ * stages below (the float entry point above is unchanged). */
+int scouter_resize_u8(const unsigned char* const* srcs, const int* hw, unsigned char* tmp, const long* tmp_off,
+                      unsigned char* out, int B, int C, int max_h, int max_w, int out_h, int out_w, void* stream);
+
+/* ---- training augmentation on the GPU (`--aug true`): the reference's tools/image_aug.py (imgaug Fliplr, Flipud, Affine,
+ * GaussianBlur in random order, per image on a CPU worker, dataset/transform_func.py:112-118) between the resize and the
+ * table lookup, on planar bytes [B][C][S][S] (C in {1, 3, 4}, 5 <= S <= 32768, B * C <= 65535).  No reference program runs
+ * here (imgaug / OpenCV are third-party), so the definition -- and its departures from them: own random stream, float
+ * bilinear warp, float blur, unrounded translation -- is the docstring of scouter_amd/dataset/augment.py, whose
+ * `augment_host` is the yardstick.  A drawn sequence reduces to blur, warp, blur; which of them an image takes is read by
+ * the kernels from per-image tables ON THE DEVICE (row b at table + b * stride, strides in 4-byte words), so a stage is
+ * one launch per batch.  src and dst must differ.
+ *   blur    klen[b] (0: copy; else odd, <= 9) and taps[b][0 .. klen) float32: row pass then column pass in float32, border
+ *           reflect-101, products summed in ascending tap order, no rounding between the passes (the intermediate stays
+ *           in LDS), one round-half-to-even to a byte.
+ *   warp    identity[b] != 0: copy; else minv[b][0 .. 6) = top two rows of the inverse matrix: output (x, y) reads
+ *           u = m0 x + m1 y + m2, v = m3 x + m4 y + m5 (float32: two rounded products, their rounded sum, plus the
+ *           constant, no fma), bilinear over the four taps around (floor u, floor v), a tap outside counts as 0, along x
+ *           then along y, round half to even, clamp, byte.
+ *   finish  out float32 [B][C][S][S] = lut[c][byte], lut the [C][256] table of scouter_resize_normalize_u8_f32. */
+int scouter_aug_blur_u8(const unsigned char* src, unsigned char* dst, const int* klen, int klen_stride, const float* taps,
+                        int taps_stride, int B, int C, int S, void* stream);
+int scouter_aug_warp_u8(const unsigned char* src, unsigned char* dst, const float* minv, int minv_stride,
+                        const int* identity, int identity_stride, int B, int C, int S, void* stream);
+int scouter_aug_finish_u8_f32(const unsigned char* src, const float* lut, float* out, int B, int C, int S, void* stream);
 
 /* optional per-kernel hipEvent timing used by bench.py's roofline leg: when enabled, every launch of the conv / BN /
  * xSlot kernels is bracketed by two hipEvents on ITS stream and aggregated by kernel-instance name.

@@ -77,10 +77,12 @@ __global__ __launch_bounds__(256) void img_resize_h_kernel(const unsigned char* 
 }
 
 // vertical pass + ToTensor/Normalize lookup: tmp [h][out_w][C] -> out [B][C][out_h][out_w] float
+// (BYTES: the resized bytes themselves, same planar layout, for the augmentation stages of augment.hip; `lut` unused)
 // grid (ceil(out_h / IMG_TILE), column chunks, B)
+template <bool BYTES>
 __global__ __launch_bounds__(256) void img_resize_v_kernel(const unsigned char* __restrict__ tmp,
                                                            const long* __restrict__ tmp_off, const int* __restrict__ hw,
-                                                           const float* __restrict__ lut, float* __restrict__ out, int C,
+                                                           const float* __restrict__ lut, void* __restrict__ out_, int C,
                                                            int out_h, int out_w, int cols_per_block) {
     __shared__ int kk[IMG_TILE][IMG_MAX_TAPS];
     __shared__ int ymin_s[IMG_TILE], cnt_s[IMG_TILE];
@@ -97,8 +99,26 @@ __global__ __launch_bounds__(256) void img_resize_v_kernel(const unsigned char* 
         int acc = 1 << (IMG_PRECISION_BITS - 1);
         const int n = cnt_s[yl];
         for (int y = 0; y < n; ++y) acc += (int)p[(long)y * out_w * C] * kk[yl][y];
-        out[(((long)b * C + c) * out_h + y0 + yl) * out_w + xx] = lut[c * 256 + img_clip8(acc)];
+        const long at = (((long)b * C + c) * out_h + y0 + yl) * out_w + xx;
+        if constexpr (BYTES) ((unsigned char*)out_)[at] = img_clip8(acc);
+        else ((float*)out_)[at] = lut[c * 256 + img_clip8(acc)];
     }
+}
+
+// both passes; `lut` == nullptr selects the byte output
+static int img_resize_launch(const char* what, const unsigned char* const* srcs, const int* hw, unsigned char* tmp,
+                             const long* tmp_off, const float* lut, void* out, int B, int C, int max_h, int max_w, int out_h,
+                             int out_w, hipStream_t st) {
+    const int rpb = 32;
+    hipLaunchKernelGGL(img_resize_h_kernel, dim3(sc_cdiv(out_w, IMG_TILE), sc_cdiv(max_h, rpb), B), dim3(256), 0, st, srcs,
+                       hw, tmp, tmp_off, C, out_w, rpb);
+    const int cpb = 64;
+    const dim3 grid(sc_cdiv(out_h, IMG_TILE), sc_cdiv(out_w, cpb), B);
+    if (lut)
+        hipLaunchKernelGGL(img_resize_v_kernel<false>, grid, dim3(256), 0, st, tmp, tmp_off, hw, lut, out, C, out_h, out_w, cpb);
+    else
+        hipLaunchKernelGGL(img_resize_v_kernel<true>, grid, dim3(256), 0, st, tmp, tmp_off, hw, lut, out, C, out_h, out_w, cpb);
+    return sc_check_launch(what);
 }
 
 extern "C" int scouter_resize_normalize_u8_f32(const unsigned char* const* srcs, const int* hw, unsigned char* tmp,
@@ -114,11 +134,21 @@ extern "C" int scouter_resize_normalize_u8_f32(const unsigned char* const* srcs,
     hipStream_t st = (hipStream_t)stream;
     ScProfScope prof("resize_normalize", st, 0,
                      (double)B * ((double)max_h * max_w * C + 2.0 * max_h * out_w * C + 4.0 * out_h * out_w * C));
-    const int rpb = 32;
-    hipLaunchKernelGGL(img_resize_h_kernel, dim3(sc_cdiv(out_w, IMG_TILE), sc_cdiv(max_h, rpb), B), dim3(256), 0, st, srcs,
-                       hw, tmp, tmp_off, C, out_w, rpb);
-    const int cpb = 64;
-    hipLaunchKernelGGL(img_resize_v_kernel, dim3(sc_cdiv(out_h, IMG_TILE), sc_cdiv(out_w, cpb), B), dim3(256), 0, st, tmp,
-                       tmp_off, hw, lut, out, C, out_h, out_w, cpb);
-    return sc_check_launch("resize_normalize");
+    return img_resize_launch("resize_normalize", srcs, hw, tmp, tmp_off, lut, out, B, C, max_h, max_w, out_h, out_w, st);
+}
+
+// the same resize with the bytes stored as they are: uint8 [B][C][out_h][out_w] (the input of the augmentation stages)
+extern "C" int scouter_resize_u8(const unsigned char* const* srcs, const int* hw, unsigned char* tmp, const long* tmp_off,
+                                 unsigned char* out, int B, int C, int max_h, int max_w, int out_h, int out_w, void* stream) {
+    SC_REQUIRE(srcs && hw && tmp && tmp_off && out, "resize_u8: null pointer");
+    SC_REQUIRE(B > 0 && (C == 1 || C == 3 || C == 4) && out_h > 0 && out_w > 0 && max_h > 0 && max_w > 0,
+               "resize_u8: bad shape B=%d C=%d out=%dx%d", B, C, out_h, out_w);
+    const int taps_w = 2 * (int)((max_w + out_w - 1) / out_w) + 1, taps_h = 2 * (int)((max_h + out_h - 1) / out_h) + 1;
+    SC_UNSUPPORTED(taps_w <= IMG_MAX_TAPS && taps_h <= IMG_MAX_TAPS,
+                   "resize_u8: down-scaling factor above %d is not supported (image %dx%d -> %dx%d)",
+                   (IMG_MAX_TAPS - 1) / 2, max_h, max_w, out_h, out_w);
+    hipStream_t st = (hipStream_t)stream;
+    ScProfScope prof("resize_u8", st, 0,
+                     (double)B * ((double)max_h * max_w * C + 2.0 * max_h * out_w * C + 1.0 * out_h * out_w * C));
+    return img_resize_launch("resize_u8", srcs, hw, tmp, tmp_off, nullptr, out, B, C, max_h, max_w, out_h, out_w, st);
 }

@@ -1637,15 +1637,15 @@ def linear_small_bwd(dy, x, w, dw=None, db=None, need_dx=True):
 
 
 # ---- input pipeline (dataset/transform_func.py:101-124 on the GPU)
-def resize_normalize(images_u8, out_size, lut, out=None):
-    """images_u8: list of B uint8 device tensors [h, w, C] (any sizes, same C) -> float32 [B, C, S, S]:
-    PIL-exact bilinear resize + ToTensor + Normalize (`lut` = [C, 256] float32 table).  Two launches per batch."""
+def _resize_args(what, images_u8, out_size):
+    """the metadata both resize entry points take: (B, C, device, meta [B ptrs | B offsets | B x (h, w)] int64 on the device,
+    (h, w) as int32, the scratch of the horizontal pass, largest height, largest width)"""
     B = len(images_u8)
     dev = images_u8[0].device
     C = images_u8[0].shape[2]
     for t in images_u8:
         assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == C and t.is_contiguous(), \
-            "resize_normalize: dense uint8 [h, w, C] device tensors expected"
+            what + ": dense uint8 [h, w, C] device tensors expected"
     hs, ws = [int(t.shape[0]) for t in images_u8], [int(t.shape[1]) for t in images_u8]
     offs, tot = [], 0
     for h in hs:
@@ -1655,13 +1655,109 @@ def resize_normalize(images_u8, out_size, lut, out=None):
                         dtype=torch.int64)
     meta = meta.to(dev, non_blocking=True)                    # [B ptrs | B offsets | B x (h, w)]
     hw32 = meta[2 * B:].to(torch.int32)
-    tmp = workspace(tot + 16, dev)
+    return B, C, dev, meta, hw32, workspace(tot + 16, dev), max(hs), max(ws)
+
+
+def resize_normalize(images_u8, out_size, lut, out=None):
+    """images_u8: list of B uint8 device tensors [h, w, C] (any sizes, same C) -> float32 [B, C, S, S]:
+    PIL-exact bilinear resize + ToTensor + Normalize (`lut` = [C, 256] float32 table).  Two launches per batch."""
+    B, C, dev, meta, hw32, tmp, max_h, max_w = _resize_args("resize_normalize", images_u8, out_size)
     if out is None:
         out = torch.empty((B, C, out_size, out_size), dtype=F32, device=dev)
     _native.check(_native.lib().scouter_resize_normalize_u8_f32(
-        _p(meta), _p(hw32), _p(tmp), _p(meta[B:]), _p(lut), _p(out), B, C, max(hs), max(ws), out_size, out_size,
+        _p(meta), _p(hw32), _p(tmp), _p(meta[B:]), _p(lut), _p(out), B, C, max_h, max_w, out_size, out_size,
         _stream()), "resize_normalize")
     return out
+
+
+def resize_u8(images_u8, out_size, out=None):
+    """images_u8 as for `resize_normalize` -> uint8 [B, C, S, S]: the PIL-exact resized bytes themselves, planar -- what the
+    augmentation stages below work on.  Two launches per batch."""
+    B, C, dev, meta, hw32, tmp, max_h, max_w = _resize_args("resize_u8", images_u8, out_size)
+    if out is None:
+        out = torch.empty((B, C, out_size, out_size), dtype=torch.uint8, device=dev)
+    _chk(out, "resize_u8: out", torch.uint8)
+    if tuple(out.shape) != (B, C, out_size, out_size):
+        raise RuntimeError("resize_u8: out must be uint8 %s, got shape %s" % ((B, C, out_size, out_size), tuple(out.shape)))
+    _native.check(_native.lib().scouter_resize_u8(
+        _p(meta), _p(hw32), _p(tmp), _p(meta[B:]), _p(out), B, C, max_h, max_w, out_size, out_size, _stream()),
+        "resize_u8")
+    return out
+
+
+# ---- training augmentation (csrc/augment.hip; the definition is the docstring of dataset/augment.py)
+def _aug_bytes(what, src, out):
+    _chk(src, what + ": src", torch.uint8)
+    if src.dim() != 4 or src.shape[2] != src.shape[3]:
+        raise RuntimeError("%s: src must be uint8 [B, C, S, S], got shape %s" % (what, tuple(src.shape)))
+    if out is None:
+        out = torch.empty_like(src)
+    _chk(out, what + ": out", torch.uint8)
+    if out.shape != src.shape or out.data_ptr() == src.data_ptr():
+        raise RuntimeError("%s: out must be another uint8 tensor of shape %s" % (what, tuple(src.shape)))
+    return out
+
+
+def _aug_table(what, t, dtype, B, width):
+    """a per-image table on the device, [B] or [B, width]: rows may be strided (a view into one packed parameter tensor),
+    the entries of a row are consecutive -> its row stride in elements"""
+    if t is None or not t.is_cuda or t.dtype != dtype:
+        raise RuntimeError("%s must be a %s device tensor" % (what, dtype))
+    if tuple(t.shape) != ((B,) if width == 1 else (B, width)) or (width > 1 and t.stride(1) != 1) or \
+            (B > 1 and t.stride(0) < width):
+        raise RuntimeError("%s must be [%d%s] with consecutive entries per image, got shape %s strides %s"
+                           % (what, B, "" if width == 1 else ", %d" % width, tuple(t.shape), t.stride()))
+    return int(t.stride(0)) if B > 1 else width
+
+
+def aug_blur(src, klen, taps, out=None):
+    """uint8 src [B, C, S, S] (S >= 5), int32 klen [B] (0: the image is copied; else 5, 7 or 9 -- odd, at most 9) and float32
+    taps [B, 9] (the first klen entries) on the device -> uint8 [B, C, S, S]: per image the Gaussian blur of
+    dataset/augment.py (reflect-101 border, row pass then column pass in float32, one rounding).  One launch."""
+    out = _aug_bytes("aug_blur", src, out)
+    B, C, S, _ = src.shape
+    ks, ts = _aug_table("aug_blur: klen", klen, torch.int32, B, 1), _aug_table("aug_blur: taps", taps, F32, B, 9)
+    _native.check(_native.lib().scouter_aug_blur_u8(_p(src), _p(out), _p(klen), ks, _p(taps), ts, B, C, S, _stream()),
+                  "aug_blur")
+    return out
+
+
+def aug_warp(src, minv, identity, out=None):
+    """uint8 src [B, C, S, S], float32 minv [B, 6] (top two rows of the inverse of the source -> destination matrix) and
+    int32 identity [B] (non-zero: the image is copied) on the device -> uint8 [B, C, S, S]: per image the bilinear warp of
+    dataset/augment.py with zeros outside the image.  One launch."""
+    out = _aug_bytes("aug_warp", src, out)
+    B, C, S, _ = src.shape
+    ms = _aug_table("aug_warp: minv", minv, F32, B, 6)
+    fs = _aug_table("aug_warp: identity", identity, torch.int32, B, 1)
+    _native.check(_native.lib().scouter_aug_warp_u8(_p(src), _p(out), _p(minv), ms, _p(identity), fs, B, C, S, _stream()),
+                  "aug_warp")
+    return out
+
+
+def aug_finish(src, lut, out=None):
+    """uint8 src [B, C, S, S] and the float32 [C, 256] normalisation table -> float32 [B, C, S, S] = lut[c][byte]: ToTensor +
+    Normalize, what `resize_normalize` ends with.  One launch."""
+    _chk(src, "aug_finish: src", torch.uint8); _chk(lut, "aug_finish: lut")
+    if src.dim() != 4 or src.shape[2] != src.shape[3] or tuple(lut.shape) != (src.shape[1], 256):
+        raise RuntimeError("aug_finish: src must be uint8 [B, C, S, S] and lut [C, 256] (got %s and %s)"
+                           % (tuple(src.shape), tuple(lut.shape)))
+    if out is None:
+        out = torch.empty(src.shape, dtype=F32, device=src.device)
+    _chk(out, "aug_finish: out")
+    if out.shape != src.shape:
+        raise RuntimeError("aug_finish: out must be float32 %s, got shape %s" % (tuple(src.shape), tuple(out.shape)))
+    B, C, S, _ = src.shape
+    _native.check(_native.lib().scouter_aug_finish_u8_f32(_p(src), _p(lut), _p(out), B, C, S, _stream()), "aug_finish")
+    return out
+
+
+def augment_bytes(src, params):
+    """The three stages on a batch: blur (klen_first), warp, blur (klen_last), with `params` the device views of the
+    packed table (dataset.augment.unpack_views).  Three launches; every image takes its own stages inside them."""
+    a = aug_blur(src, params["klen_first"], params["taps"])
+    b = aug_warp(a, params["minv"], params["identity"])
+    return aug_blur(b, params["klen_last"], params["taps"], out=a)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -8,8 +8,10 @@ run unchanged:
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m scouter_amd.train ...   # 8 GPUs
 
 One process per GPU; gradients are all-reduced over RCCL/xGMI by scouter_amd.parallel; the optimizer is the fused
-AdamW kernel.  The `--thop` FLOP-counting branch of the reference (train.py:91-137) is CPU-side tooling with
-third-party packages and is refused."""
+AdamW kernel.  `--aug true` (the reference's imgaug pipeline) runs on the device, in the train loader's transform, on
+the decoded bytes of real data (`--synthetic_data false`; `--aug_seed` seeds it; dataset/augment.py has the definition).
+The `--thop` FLOP-counting branch of the reference (train.py:91-137) is CPU-side tooling with third-party packages and
+is refused."""
 import argparse
 import datetime
 import time
@@ -49,7 +51,7 @@ _CLI = [
     ("pre_trained", True, _flag, "freeze `freeze_layers` stages (weights must be loaded from a checkpoint)"),
     ("use_slot", True, _flag, "xSlot head (false: global-pool + fc baseline)"),
     ("use_pre", False, _flag, "initialise the backbone from the FC-baseline checkpoint"),
-    ("aug", False, _flag, None),
+    ("aug", False, _flag, "training augmentation (mirrors, affine, blur) on the GPU; needs --synthetic_data false"),
     ("grad", False, _flag, "test.py: also write per-class gradient attribution maps grad_{c}.png (training ignores it)"),
     ("grad_min_level", 0.0, float, "test.py --grad: floor of the scaled attribution map, in [0, 1) (training ignores it)"),
     ("iterated_evaluation_num", 1, int, "repetitions per sweep value"),
@@ -69,6 +71,7 @@ _CLI = [
     ("precision", "fp32", str, "fp32 | bf16 (backbone convolutions on bf16 matrix inputs, fp32 accumulate; wide bottleneck tensors stored as bf16)"),
     ("synthetic_data", True, _flag, "seeded synthetic batches (the benchmark input)"),
     ("synthetic_len", 256, int, "images per synthetic epoch"),
+    ("aug_seed", 0, int, "seed of the --aug random stream (with the batch number and the rank)"),
     ("eval_fold", False, _flag, "eval-mode forwards run with every BatchNorm folded into its convolution (SlotModel.set_inference_fold)"),
 ]
 
@@ -94,12 +97,14 @@ def checkpoint_name(args, suffix="checkpoint.pth"):
 
 
 def _build_loaders(args):
+    raw = not getattr(args, "synthetic_data", True)     # real data: samples are decoded uint8 images of any size
+    if raw and getattr(args, "aug", False):
+        args.aug_on_device = True       # tells the host half (make_transform) that the train loader's device half augments
     train_set, val_set = select_dataset(args)
     if args.distributed:
         train_sampler, val_sampler = DistributedSampler(train_set), DistributedSampler(val_set, shuffle=False)
     else:
         train_sampler, val_sampler = RandomSampler(train_set), SequentialSampler(val_set)
-    raw = not getattr(args, "synthetic_data", True)     # real data: samples are decoded uint8 images of any size
     # raw frames travel packed in one buffer per batch, pinned by the DataLoader's pin thread (one async H2D per batch)
     extra = {"collate_fn": collate_raw, "pin_memory": torch.cuda.is_available()} if raw else {}
     train_loader = prt.DataLoaderX(train_set, batch_sampler=BatchSampler(train_sampler, args.batch_size, drop_last=True),
@@ -107,6 +112,8 @@ def _build_loaders(args):
     val_loader = prt.DataLoaderX(val_set, args.batch_size, sampler=val_sampler, num_workers=args.num_workers, **extra)
     if raw:
         train_loader.gpu_transform = val_loader.gpu_transform = make_gpu_transform(args)
+        if getattr(args, "aug", False):
+            train_loader.gpu_transform = make_gpu_transform(args, "train")
     return train_loader, val_loader, train_sampler
 
 
@@ -134,6 +141,9 @@ def _save(args, model, optimizer, scheduler, epoch):
 
 
 def main(args):
+    if getattr(args, "aug", False) and getattr(args, "synthetic_data", True):
+        raise ValueError("--aug true works on decoded image bytes (between the resize and the normalisation): it needs "
+                         "real data, --synthetic_data false; synthetic batches are floats and are not augmented")
     prt.init_distributed_mode(args)
     if args.thop:
         raise NotImplementedError("--thop (CPU FLOP counting with thop / tensorly) is outside the xSlot hot path")
