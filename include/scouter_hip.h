@@ -16,8 +16,8 @@
  *
  * Beyond the training path the library holds what an explanation is drawn and scored with, each in a section of its own below:
  * the input pipeline, Grad-CAM, RISE, insertion / deletion scores, Score-CAM, path and noise batches (Integrated Gradients,
- * SmoothGrad), Grad-CAM++, the infidelity / max-sensitivity scores and the mask sides of Extremal Perturbation and of
- * information-bottleneck attribution.  The reference
+ * SmoothGrad), Grad-CAM++, the infidelity / max-sensitivity scores, the mask sides of Extremal Perturbation and of
+ * information-bottleneck attribution, and the superpixel surrogates LIME and KernelSHAP.  The reference
  * computes none of the scores itself; where
  * no program exists to copy, the section's comment is the specification.
  */
@@ -732,6 +732,63 @@ int scouter_igos_trial_images_f32(const float* image, const float* base, const f
 int scouter_igos_step_f32(float* pmask, const float* dmask, const float* steps, const float* logp, const int* cols, const double* stats,
                           float* l1, double* curves, int R, int T1, int n_out, int hm, int wm, int it, int n_iters, double alpha,
                           float tv_coeff, float tv_beta, int adapt, void* stream);
+
+/* ---- LIME (Ribeiro et al., KDD 2016) and KernelSHAP (Lundberg & Lee, NeurIPS 2017): a linear surrogate over d superpixels,
+ * fitted to the class probabilities of N perturbed copies of an image (csrc/surrogate.hip, tools/attribution.py superpixels /
+ * lime / kernelshap).  No reference program runs either; this comment is the specification.  Images are fp32 [B][C][H][W],
+ * labels i32 [B][H][W] in [0, d), 1 <= d <= 128, C <= 30.  Every call has one fixed order per output element and no atomics:
+ * bit-identical run to run.  A null or misaligned pointer, a count below 1, d outside [1, 128], a grid larger than the image or
+ * K = 0 is SC_ERR_ARG, with a message that names the call; nothing is launched after an error.  Every label a kernel indexes
+ * with is clamped to [0, d - 1].
+ *
+ * SEGMENTATION: SLIC (Achanta et al. 2012) on the image as it is given (the normalised tensor, not Lab) and without the
+ * connectivity pass.  The grid: pixel (y, x) lies in cell (y * gy / H, x * gx / W) (integer division) and cell (i, j) has label
+ * i * gx + j, d = gy * gx.  labels_0 is the grid; for t = 1 .. iters: centres = update(x, labels_{t-1}), labels_t = assign(x,
+ * centres).
+ *
+ * UPDATE.  centres fp32 [B][d][C + 2] = (the C mean colours, mean y, mean x) and means fp32 [B][d][C] = the mean colours, of the
+ * pixels that carry the segment's label: float64 sums in a fixed order, one division, rounded once to fp32.  A segment without a
+ * pixel keeps the centre it had (centres is read and written) and gets means 0.  window = 1: a segment's pixels are looked for
+ * in the 3 x 3 cells around its own cell only, where `assign` puts them (gy <= H and gx <= W); window = 0: in the whole image,
+ * for labels of any origin (then only d = gy * gx counts).  One workgroup per (segment, image). */
+int scouter_slic_update_f32(const float* images, const int* labels, float* centres, float* means, int B, int C, int H, int W,
+                            int gy, int gx, int window, void* stream);
+/* ASSIGN.  Each pixel compares the centres of the 3 x 3 cells around its home cell, clipped to the grid, in ascending label
+ * order: D^2 = sum_c (x_c - mu_c)^2 (one fma per channel from 0) and then fma(lambda, fma(dy, dy, dx * dx), .), dy = y - c_y,
+ * dx = x - c_x, all fp32.  A strictly smaller D^2 wins, so a tie goes to the smallest label; when every D^2 is a NaN the pixel
+ * keeps its home cell.  lambda = (compactness / S)^2 with S = sqrt(H * W / d), formed by the caller in double. */
+int scouter_slic_assign_f32(const float* images, const float* centres, int* labels, int B, int C, int H, int W, int gy, int gx,
+                            float lambda, void* stream);
+/* THE PERTURBED BATCH of ONE image: image fp32 [C][H][W], labels i32 [H][W], z u8 [N][d] -> out fp32 [N][C][H][W],
+ * out[n][c][p] = z[n][labels[p]] != 0 ? image[c][p] : hide[c][p], with hide[c][p] = means[labels[p]][c] (means fp32 [d][C]) or,
+ * when means is null, the constant `fill`.  A select: every value is an exact copy.  16-byte accesses when W is a multiple of 4
+ * and image / labels / out are 16-byte aligned, one pixel per thread otherwise.  Any N >= 1. */
+int scouter_segment_images_f32(const float* image, const int* labels, const unsigned char* z, const float* means, float fill,
+                               float* out, int N, int d, int C, int H, int W, void* stream);
+/* THE MOMENTS of one image, a chunk of N sample rows at a time: z u8 [N][d], logp fp32 [N][n_classes], cols i32 [K] in
+ * [0, n_classes) (checked by the caller; clamped here).  With z^ = (1, z != 0) and y[n][k] = exp((double) logp[n][cols[k]]):
+ * S f64 [d + 1][d + 1] += sum_n pi_n z^ z^T and T f64 [d + 1][K] += sum_n pi_n z^ y^T.  mode 0 (LIME): pi_n = sqrt(exp(-D^2 /
+ * kernel_width^2)), D = 1 - sqrt(|z_n| / d) and D = 1 when |z_n| = 0, in double; mode 1 (KernelSHAP): pi_n = 1.  Every entry
+ * belongs to one thread, which starts from the stored value and adds the rows in ascending n: chunks of any length give the
+ * bits of one call.  `first` is the chunk's first row in the whole sample matrix: when the chunk holds rows 0 (all ones) and 1
+ * (all zeros) of it, their targets go to yref f64 [2][K] (yref may be null). */
+int scouter_surrogate_accumulate_f64(const float* logp, const int* cols, const unsigned char* z, double* S, double* T, double* yref,
+                                     long first, int N, int n_classes, int K, int d, int mode, double kernel_width, void* stream);
+/* THE FIT of B images in one launch, one workgroup each: S f64 [B][d + 1][d + 1], T f64 [B][d + 1][K], yref f64 [B][2][K] ->
+ * coef f64 [B][K][d], icpt f64 [B][K].  With S2 = S[1:, 1:], S1 = S[1:, 0], T1 = T[1:], T0 = T[0], S00 = S[0][0]:
+ *   mode 0, LIME (ridge alpha on the coefficients, free intercept):  G = S2 - S1 S1^T / S00 + alpha I,  R = T1 - S1 T0 / S00,
+ *     w = G^-1 R,  icpt = (T0 - S1^T w) / S00;
+ *   mode 1, KernelSHAP (intercept y_0 = yref[1], efficiency sum(phi) = Delta = yref[0] - yref[1] enforced by eliminating the last
+ *     feature e = d - 1):  G[a][c] = S2[a][c] - S2[a][e] - S2[e][c] + S2[e][e] + alpha delta_ac,  R[a][k] = T1[a][k] - T1[e][k] -
+ *     y_0[k] (S1[a] - S1[e]) - Delta_k (S2[a][e] - S2[e][e]) for a, c < e,  phi = G^-1 R,  phi_e = Delta - sum(phi); d = 1: phi_0 = Delta.
+ * G | R is written to ws (at least scouter_surrogate_solve_workspace_bytes(B, d, K) = 8 B d (d + K) bytes; less:
+ * SC_ERR_WORKSPACE), factored in place by a Cholesky factorisation and solved by substitution, all float64.  A pivot that is not
+ * positive (a NaN included) writes NaN coefficients for that image (and a NaN LIME intercept) and faults nothing. */
+size_t scouter_surrogate_solve_workspace_bytes(int B, int d, int K);
+int scouter_surrogate_solve_f64(const double* S, const double* T, const double* yref, double* coef, double* icpt, int B, int d,
+                                int K, int mode, double alpha, void* ws, size_t ws_bytes, void* stream);
+/* THE MAP: out fp32 [B][K][H][W], out[b][k][p] = (float) coef[b][k][labels[b][p]] -- a gather.  B * K <= 65535. */
+int scouter_segment_paint_f32(const double* coef, const int* labels, float* out, int B, int K, int d, int H, int W, void* stream);
 
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats

@@ -1958,6 +1958,138 @@ def heat_maps(maps, min_level=0.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# LIME and KernelSHAP (csrc/surrogate.hip; tools/attribution.py superpixels / lime / kernelshap)
+# ---------------------------------------------------------------------------------------------------------------
+SURROGATE_LIME, SURROGATE_SHAP = 0, 1            # the `mode` of surrogate_accumulate / surrogate_solve
+SURROGATE_MAX_D = 128
+
+
+def _slic_chk(what, images, labels, centres, gy, gx):
+    """images fp32 [B, C, H, W], labels int32 [B, H, W] and centres fp32 [B, gy * gx, C + 2] of one call -> (B, C, H, W)"""
+    _chk(images, what + ": images"); _chk(labels, what + ": labels", torch.int32); _chk(centres, what + ": centres")
+    if images.dim() != 4:
+        raise RuntimeError("%s: images must be [B, C, H, W], got shape %s" % (what, tuple(images.shape)))
+    B, C, H, W = images.shape
+    d = int(gy) * int(gx)
+    if tuple(labels.shape) != (B, H, W) or tuple(centres.shape) != (B, d, C + 2):
+        raise RuntimeError("%s: labels must be int32 [%d, %d, %d] and centres fp32 [%d, d = %d, C + 2 = %d] (got %s and %s)"
+                           % (what, B, H, W, B, d, C + 2, tuple(labels.shape), tuple(centres.shape)))
+    return B, C, H, W
+
+
+def slic_update(images, labels, centres, means, gy, gx, window=True):
+    """centres[b, l] = (mean colour [C], mean y, mean x) and means[b, l] = the mean colour of the pixels of images [B, C, H, W]
+    with labels[b] == l, l < d = gy * gx: float64 sums in a fixed order, rounded once to fp32.  A segment without a pixel keeps
+    its centre (centres fp32 [B, d, C + 2] is read and written) and gets means 0 (means fp32 [B, d, C]).  window: look for a
+    segment's pixels only in the 3 x 3 grid cells around its own, where `slic_assign` puts them; False: in the whole image.
+    One launch."""
+    B, C, H, W = _slic_chk("slic_update", images, labels, centres, gy, gx)
+    _chk(means, "slic_update: means")
+    if tuple(means.shape) != (B, int(gy) * int(gx), C):
+        raise RuntimeError("slic_update: means must be fp32 [%d, %d, %d], got shape %s"
+                           % (B, int(gy) * int(gx), C, tuple(means.shape)))
+    _native.check(_native.lib().scouter_slic_update_f32(_p(images), _p(labels), _p(centres), _p(means), B, C, H, W, int(gy),
+                                                        int(gx), int(bool(window)), _stream()), "slic_update")
+    return centres, means
+
+
+def slic_assign(images, centres, labels, gy, gx, lam):
+    """labels[b, y, x] = the nearest of the centres of the 3 x 3 grid cells around the pixel's home cell (y * gy // H, x * gx // W):
+    D^2 = sum_c (x_c - mu_c)^2 + lam * ((y - c_y)^2 + (x - c_x)^2) in fp32, the smallest label among equals.  One launch."""
+    B, C, H, W = _slic_chk("slic_assign", images, labels, centres, gy, gx)
+    _native.check(_native.lib().scouter_slic_assign_f32(_p(images), _p(centres), _p(labels), B, C, H, W, int(gy), int(gx),
+                                                        float(lam), _stream()), "slic_assign")
+    return labels
+
+
+def segment_images(image, labels, z, out, means=None, fill=0.0):
+    """out[n, c, p] = image[c, p] where z[n, labels[p]] is set, else the hidden value: means[labels[p], c] (means fp32 [d, C]) or,
+    without means, the constant `fill`.  image fp32 [C, H, W], labels int32 [H, W] in [0, d), z uint8 [N, d], out fp32
+    [N, C, H, W] (a dense leading slice of a longer buffer is fine).  A select: every value is an exact copy.  One launch."""
+    _chk(image, "segment_images: image"); _chk(labels, "segment_images: labels", torch.int32)
+    _chk(z, "segment_images: z", torch.uint8); _chk(out, "segment_images: out"); _chk(means, "segment_images: means")
+    if image.dim() != 3 or z.dim() != 2 or tuple(labels.shape) != tuple(image.shape[1:]):
+        raise RuntimeError("segment_images: image must be [C, H, W], labels [H, W] and z [N, d] (got %s, %s and %s)"
+                           % (tuple(image.shape), tuple(labels.shape), tuple(z.shape)))
+    C, H, W = image.shape
+    N, d = z.shape
+    if tuple(out.shape) != (N, C, H, W) or (means is not None and tuple(means.shape) != (d, C)):
+        raise RuntimeError("segment_images: out must be [N = %d, %d, %d, %d] and means [d = %d, C = %d] (got %s and %s)"
+                           % (N, C, H, W, d, C, tuple(out.shape), None if means is None else tuple(means.shape)))
+    _native.check(_native.lib().scouter_segment_images_f32(_p(image), _p(labels), _p(z), _p(means), float(fill), _p(out), N, d, C,
+                                                           H, W, _stream()), "segment_images")
+    return out
+
+
+def surrogate_accumulate(logp, cols, z, S, T, yref=None, first=0, mode=SURROGATE_LIME, kernel_width=0.25):
+    """S += sum_n pi_n zh zh^T and T += sum_n pi_n zh y_n^T for the rows of one chunk: zh = (1, z[n]), y_n[k] = exp(logp[n, cols[k]])
+    in float64.  logp fp32 [N, n_classes], cols int32 [K] on the device (the caller keeps them inside [0, n_classes)), z uint8
+    [N, d], S float64 [d + 1, d + 1], T float64 [d + 1, K].  mode SURROGATE_LIME: pi_n = sqrt(exp(-D^2 / kernel_width^2)),
+    D = 1 - sqrt(|z_n| / d) (1 for an empty row); SURROGATE_SHAP: pi_n = 1.  Every entry adds its rows in ascending n onto the
+    stored value: calls over consecutive chunks give the bits of one call.  `first` is the chunk's first row in the whole sample
+    matrix; the targets of its rows 0 and 1 go to yref float64 [2, K] when given.  One launch, nothing is read on the host."""
+    _chk(logp, "surrogate_accumulate: logp"); _chk(cols, "surrogate_accumulate: cols", torch.int32)
+    _chk(z, "surrogate_accumulate: z", torch.uint8)
+    for t, name in ((S, "S"), (T, "T"), (yref, "yref")):
+        _chk(t, "surrogate_accumulate: " + name, torch.float64)
+    if logp.dim() != 2 or cols.dim() != 1 or z.dim() != 2 or z.shape[0] != logp.shape[0]:
+        raise RuntimeError("surrogate_accumulate: logp must be [N, n_classes], cols [K] and z [N, d] (got %s, %s and %s)"
+                           % (tuple(logp.shape), tuple(cols.shape), tuple(z.shape)))
+    N, d = z.shape
+    Kc = int(cols.shape[0])
+    if tuple(S.shape) != (d + 1, d + 1) or tuple(T.shape) != (d + 1, Kc) or (yref is not None and tuple(yref.shape) != (2, Kc)):
+        raise RuntimeError("surrogate_accumulate: S must be [%d, %d], T [%d, %d] and yref [2, %d] (got %s, %s and %s)"
+                           % (d + 1, d + 1, d + 1, Kc, Kc, tuple(S.shape), tuple(T.shape),
+                              None if yref is None else tuple(yref.shape)))
+    _native.check(_native.lib().scouter_surrogate_accumulate_f64(_p(logp), _p(cols), _p(z), _p(S), _p(T), _p(yref), int(first), N,
+                                                                 int(logp.shape[1]), Kc, d, int(mode), float(kernel_width),
+                                                                 _stream()), "surrogate_accumulate")
+    return S, T
+
+
+def surrogate_solve(S, T, yref=None, mode=SURROGATE_LIME, ridge=1.0):
+    """The fit of B images from their moments S float64 [B, d + 1, d + 1] and T float64 [B, d + 1, K] -> (coefficients float64
+    [B, K, d], intercepts float64 [B, K]).  SURROGATE_LIME: ridge regression with a free intercept; SURROGATE_SHAP: the intercept
+    is yref[b, 1] and the coefficients sum to yref[b, 0] - yref[b, 1] (yref float64 [B, 2, K]), the last feature eliminated
+    (include/scouter_hip.h has the equations).  A float64 Cholesky factorisation per image; a pivot that is not positive gives
+    NaN coefficients for that image.  One launch."""
+    for t, name in ((S, "S"), (T, "T"), (yref, "yref")):
+        _chk(t, "surrogate_solve: " + name, torch.float64)
+    if S.dim() != 3 or T.dim() != 3 or S.shape[1] != S.shape[2] or S.shape[1] < 2 or tuple(T.shape[:2]) != tuple(S.shape[:2]):
+        raise RuntimeError("surrogate_solve: S must be [B, d + 1, d + 1] and T [B, d + 1, K] (got %s and %s)"
+                           % (tuple(S.shape), tuple(T.shape)))
+    B, d, Kc = int(S.shape[0]), int(S.shape[1]) - 1, int(T.shape[2])
+    if int(mode) == SURROGATE_SHAP and (yref is None or tuple(yref.shape) != (B, 2, Kc)):
+        raise RuntimeError("surrogate_solve: KernelSHAP needs yref float64 [%d, 2, %d], got %s"
+                           % (B, Kc, None if yref is None else tuple(yref.shape)))
+    coef = torch.empty((B, Kc, d), dtype=torch.float64, device=S.device)
+    icpt = torch.empty((B, Kc), dtype=torch.float64, device=S.device)
+    lib = _native.lib()
+    nbytes = lib.scouter_surrogate_solve_workspace_bytes(B, d, Kc)
+    ws = workspace(nbytes, S.device)
+    _native.check(lib.scouter_surrogate_solve_f64(_p(S), _p(T), _p(yref), _p(coef), _p(icpt), B, d, Kc, int(mode), float(ridge),
+                                                  _p(ws), nbytes, _stream()), "surrogate_solve")
+    return coef, icpt
+
+
+def segment_paint(coef, labels):
+    """out[b, k, y, x] = coef[b, k, labels[b, y, x]] as fp32 [B, K, H, W] for float64 coef [B, K, d] and int32 labels [B, H, W] in
+    [0, d): a gather.  One launch."""
+    _chk(coef, "segment_paint: coef", torch.float64); _chk(labels, "segment_paint: labels", torch.int32)
+    if coef.dim() != 3 or labels.dim() != 3 or labels.shape[0] != coef.shape[0]:
+        raise RuntimeError("segment_paint: coef must be [B, K, d] and labels [B, H, W] (got %s and %s)"
+                           % (tuple(coef.shape), tuple(labels.shape)))
+    B, Kc, d = coef.shape
+    H, W = labels.shape[1:]
+    out = torch.empty((B, Kc, H, W), dtype=torch.float32, device=coef.device)
+    if Kc == 0:
+        return out
+    _native.check(_native.lib().scouter_segment_paint_f32(_p(coef), _p(labels), _p(out), B, Kc, d, H, W, _stream()),
+                  "segment_paint")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Localisation scores of byte maps (csrc/localization.hip; tools/attribution.py localization / slot_maps)
 # ---------------------------------------------------------------------------------------------------------------
 def map_localization(maps, boxes=None, n_boxes=None):

@@ -234,13 +234,13 @@ def _call(args, model, x, family, function, **kwargs):
     return getattr(attribution, function)(model, x, **kwargs)
 
 
-def run_family(args, model, image, out_dir, name):
+def run_family(args, model, image, out_dir, name, rows=_ROWS):
     """`--<name> true`: the maps of every class of the family `name` for the one image -> `<out>/<name>_{c}.png`, uint8 maps at
     the input resolution, floored at --grad_min_level; returns them [C, H, W] (host).  run_grad, run_cam, ... below are this
-    function for one name each."""
+    function for one name each.  rows: the table the name is looked up in -- this tool's own, or one that extends it."""
     from PIL import Image
     from .tools import attribution
-    family = _row(name)
+    family = _row(name, rows)
     os.makedirs(out_dir, exist_ok=True)
     x, min_level = image.unsqueeze(0).to(args.device, dtype=torch.float32), float(args.grad_min_level)
     if family.reduce is None:
@@ -258,11 +258,11 @@ def run_family(args, model, image, out_dir, name):
 globals().update({"run_" + f.name: functools.partial(run_family, name=f.name) for f in FAMILIES if f.maps})
 
 
-def _family_attribution(args, model, x, pred, family, slot_map=None, full=False):
+def _family_attribution(args, model, x, pred, family, slot_map=None, full=False, rows=_ROWS):
     """the predicted class's FLOAT explanation of one family for the images x [n, C, H, W] on the device -> [n, 1, h, w]: the
     row's `explain`, brought to a map by its `reduce`; for the row without one (slot) the given `slot_map`, taken right after
     the forward that predicted.  full: the families with a `reduce` keep their attribution [n, 1, C, H, W] instead."""
-    row = _row(family)
+    row = _row(family, rows)
     if row.explain is None:
         return slot_map
     g = _call(args, model, x, row, row.explain, classes=[pred])
@@ -270,7 +270,7 @@ def _family_attribution(args, model, x, pred, family, slot_map=None, full=False)
 
 
 # ------------------------------------------------------------------------------------------------ the scores
-def run_causal(args, model, image, pred, families, slot_map=None):
+def run_causal(args, model, image, pred, families, slot_map=None, rows=_ROWS):
     """--causal true: the deletion / insertion scores (tools/attribution.py causal_metrics: --causal_step pixels per point, 0 =
     one image row) of the predicted class's FLOAT map (_family_attribution) of every family in `families`, one printed line
     each; returns {family: (deletion, insertion)}."""
@@ -280,14 +280,14 @@ def run_causal(args, model, image, pred, families, slot_map=None):
     kwargs = dict(option_kwargs(args, "causal"), batch=option_kwargs(args, "rise")["batch"])
     scores = {}
     for family in families:
-        maps = _family_attribution(args, model, x, pred, family, slot_map)
+        maps = _family_attribution(args, model, x, pred, family, slot_map, rows=rows)
         r = causal_metrics(model, x, maps, classes=[pred], **kwargs)
         scores[family] = (float(r.deletion[0, 0]), float(r.insertion[0, 0]))
         print("causal %s class %d: deletion %.6f insertion %.6f" % ((family, pred) + scores[family]))
     return scores
 
 
-def run_infidelity(args, model, image, pred, families, slot_map=None):
+def run_infidelity(args, model, image, pred, families, slot_map=None, rows=_ROWS):
     """--infidelity true: the infidelity (tools/attribution.py infidelity: --infidelity_samples noisy copies at --infidelity_sigma,
     --infidelity_batch rows per forward) of the predicted class's explanation of every family in `families` -- grad, ig and
     smoothgrad with their full [C, H, W] attribution, the other families with their map, which counts for every channel -- one
@@ -297,14 +297,14 @@ def run_infidelity(args, model, image, pred, families, slot_map=None):
     kwargs = option_kwargs(args, "infidelity")
     scores = {}
     for family in families:
-        attr = _family_attribution(args, model, x, pred, family, slot_map, full=True)
+        attr = _family_attribution(args, model, x, pred, family, slot_map, full=True, rows=rows)
         r = infidelity(model, x, attr, classes=[pred], **kwargs)
         scores[family] = (float(r.raw[0, 0]), float(r.normalized[0, 0]), float(r.beta[0, 0]))
         print("infidelity %s class %d: raw %.6e normalized %.6e beta %.6e" % ((family, pred) + scores[family]))
     return scores
 
 
-def run_sensitivity(args, model, image, pred, families):
+def run_sensitivity(args, model, image, pred, families, rows=_ROWS):
     """--sensitivity true: the max-sensitivity (tools/attribution.py sensitivity_max: --sensitivity_samples points of the box of
     half-width --sensitivity_radius, --sensitivity_batch rows per call) of the predicted class's FLOAT map of every family in
     `families`, each family explaining the perturbed images as it explained the image (slot: an eval forward, then
@@ -320,8 +320,8 @@ def run_sensitivity(args, model, image, pred, families):
 
     scores = {}
     for family in families:
-        explain = slot_maps if _row(family).explain is None else \
-            functools.partial(_family_attribution, args, model, pred=pred, family=family)
+        explain = slot_maps if _row(family, rows).explain is None else \
+            functools.partial(_family_attribution, args, model, pred=pred, family=family, rows=rows)
         r = sensitivity_max(explain, x, **kwargs)
         scores[family] = float(r.score[0, 0])
         print("sensitivity %s class %d: max %.6e" % (family, pred, scores[family]))
@@ -368,8 +368,9 @@ def build_model(args):
     return model, want_grad
 
 
-def main():
-    args = get_test_parser().parse_args()
+def single_image(args, families=FAMILIES, rows=_ROWS):
+    """what main() does with a parsed command line; families / rows: this tool's table, or one that extends it
+    (tools/surrogate.py)"""
     model, want_grad = build_model(args)
     channels, size = (1 if args.dataset == "MNIST" else 3), int(args.img_size)
     if args.image:
@@ -384,21 +385,25 @@ def main():
         from .tools.attribution import slot_saliency
         slot_map = slot_saliency(model)[:, pred:pred + 1].contiguous()       # (before another forward replaces last_attn)
     unflagged = {"slot": model.use_slot, "grad": want_grad}                  # the rows with `flag` False
-    drawn = [f for f in FAMILIES if (getattr(args, f.name) if f.flag else unflagged[f.name])]
+    drawn = [f for f in families if (getattr(args, f.name) if f.flag else unflagged[f.name])]
     for f in drawn:
         if f.maps:
-            run_family(args, model, image, args.vis_dir, f.name)
-    families = [f.name for f in drawn]
+            run_family(args, model, image, args.vis_dir, f.name, rows)
+    names = [f.name for f in drawn]
     if args.causal:
-        run_causal(args, model, image, pred, families, slot_map)
+        run_causal(args, model, image, pred, names, slot_map, rows)
     if args.infidelity:
-        run_infidelity(args, model, image, pred, families, slot_map)
+        run_infidelity(args, model, image, pred, names, slot_map, rows)
     if args.sensitivity:
-        run_sensitivity(args, model, image, pred, families)
+        run_sensitivity(args, model, image, pred, names, rows)
     print(out)
     print(pred)
     if ratio is not None and args.cal_area_size:
         print(f"attention_ratio: {ratio}")
+
+
+def main():
+    single_image(get_test_parser().parse_args())
 
 
 if __name__ == "__main__":

@@ -124,7 +124,18 @@ sums of a batch of maps (kernels.map_localization: the mass, the mass inside the
 position and whether a box holds it) and the ratios are float64 divisions of them on the device; `slot_maps` gives the byte
 slot maps of a whole batch, each image scaled as SlotAttention.vis_maps scales one on the host (kernels.group_maps), the maps
 the reference's attention_ratio is taken from.  tools/explanation_table.py puts these scores, `causal_metrics` and `infidelity`
-into the paper's table: one row per family, every cell a mean over a validation set."""
+into the paper's table: one row per family, every cell a mean over a validation set.
+
+Superpixel surrogates (`superpixels`, `lime_samples`, `kernelshap_samples`, `lime_fit`, `kernelshap_fit`, `lime`, `kernelshap`,
+`lime_maps`, `kernelshap_maps`): LIME (Ribeiro et al. 2016) and KernelSHAP (Lundberg & Lee 2017), the two explainers a comparison
+table is asked for first.  The image is cut into at most 128 superpixels (a SLIC loop of two HIP kernels, kernels.slic_update and
+kernels.slic_assign), a thousand copies with random subsets of them hidden go through the model, and a weighted linear model of
+the class probability over the subsets is fitted; its coefficients, painted back onto the segments, are the map.  Like `rise`
+both are black-box and cost eval forwards.  The perturbed batch, the float64 moments of the regression (summed in row order, so
+the chunking does not change a bit), the Cholesky fit and the painting are four more HIP kernels (kernels.segment_images,
+surrogate_accumulate, surrogate_solve, segment_paint) and nothing comes to the host in between.  No reference program runs
+either method here (lime, shap and skimage are not dependencies): the docstrings are the specification and say what departs
+from those packages.  tools/surrogate.py adds both as rows to the single-image tool and the explanation table."""
 import collections
 import contextlib
 import functools
@@ -489,6 +500,234 @@ def rise_maps(model, images, classes=None, min_level=0.0, **rise_kwargs):
     own size (kernels.heat_maps): negative values cut to 0, min-max scaled, raised to at least `min_level`, min-max scaled
     again, times 255.  A map that is constant at either scaling step is all zeros."""
     return K.heat_maps(rise(model, images, classes, **rise_kwargs), min_level)
+
+
+Superpixels = collections.namedtuple("Superpixels", "labels d means")
+Superpixels.__doc__ = """The segmentation of `superpixels`: labels int32 [B, H, W] in [0, d), the number of segments d and
+means fp32 [B, d, C], the mean colour of every segment (0 for a segment without a pixel)."""
+
+SurrogateFit = collections.namedtuple("SurrogateFit", "coef intercept labels")
+SurrogateFit.__doc__ = """What `lime_fit` / `kernelshap_fit` return: coefficients float64 [B, K, d], one per class and
+segment, intercepts float64 [B, K] and the segments' labels int32 [B, H, W]."""
+
+_MAX_SEGMENTS = K.SURROGATE_MAX_D
+
+
+def _check_segment_count(d):
+    if not 1 <= d <= _MAX_SEGMENTS:
+        raise ValueError("the number of segments must satisfy 1 <= d <= %d, got %d" % (_MAX_SEGMENTS, d))
+    return d
+
+
+def superpixels(images, segments=(8, 8), iters=10, compactness=1.0, d=None):
+    """Superpixels of `images` [B, C, H, W] -> Superpixels(labels int32 [B, H, W], d, means fp32 [B, d, C]) on the images' device.
+
+    segments = (gy, gx) (an int g: (g, g)), 1 <= gy <= H, 1 <= gx <= W, d = gy * gx <= 128.  labels_0 is the grid: pixel (y, x) lies
+    in cell (y * gy // H, x * gx // W) and cell (i, j) has label i * gx + j.  For t = 1 .. iters: centres = update(x, labels_{t-1})
+    (kernels.slic_update: per segment the mean colour and the mean (y, x), float64 sums rounded once to fp32; an empty segment
+    keeps its centre), labels_t = assign(x, centres) (kernels.slic_assign: among the centres of the 3 x 3 cells around the
+    pixel's home cell the smallest D^2 = sum_c (x_c - mu_c)^2 + lam ((y - c_y)^2 + (x - c_x)^2), lam = (compactness / S)^2,
+    S = sqrt(H W / d); the smallest label among equals).  iters = 0 gives the plain grid.  means are those of the final labels
+    (one more update).
+
+    This is SLIC (Achanta et al. 2012) WITHOUT its connectivity pass -- a segment may have stray pixels -- and on the image as
+    it is given, the normalised tensor, not Lab: what skimage.segmentation.slic would give differs.  The compactness default
+    of 1.0 is untuned.
+
+    segments may instead be an int32 tensor [B, H, W] of labels from elsewhere, passed with d= (every label in [0, d), checked
+    once on the host before any launch); then only the means are computed."""
+    B, C, H, W = _check_images(images).shape
+    if torch.is_tensor(segments):
+        if d is None:
+            raise ValueError("a tensor of labels needs d=, the number of segments")
+        d = _check_segment_count(int(d))
+        if segments.dtype != torch.int32 or tuple(segments.shape) != (B, H, W):
+            raise ValueError("a tensor of labels must be int32 [%d, %d, %d], got %s %s"
+                             % (B, H, W, segments.dtype, tuple(segments.shape)))
+        host = segments.detach().cpu()
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= d):
+            raise ValueError("a label lies outside [0, d = %d): the labels span [%d, %d]" % (d, int(host.min()), int(host.max())))
+        gy, gx, iters, given = 1, d, 0, segments.detach().to(images.device).contiguous()
+    else:
+        gy, gx = (int(segments),) * 2 if isinstance(segments, int) else (int(v) for v in segments)
+        if not (1 <= gy <= H and 1 <= gx <= W):
+            raise ValueError("the grid must satisfy 1 <= gy <= H = %d and 1 <= gx <= W = %d, got %d x %d" % (H, W, gy, gx))
+        d, given = _check_segment_count(gy * gx), None
+        iters = int(iters)
+        if iters < 0 or not float(compactness) >= 0.0:
+            raise ValueError("iters and compactness must be at least 0, got %r and %r" % (iters, compactness))
+    x = images.detach().contiguous()
+    x = x.float() if x.dtype != torch.float32 else x
+    dev = x.device
+    if given is None:
+        rows = (torch.arange(H, dtype=torch.int64) * gy) // H
+        cells = (torch.arange(W, dtype=torch.int64) * gx) // W
+        grid = (rows[:, None] * gx + cells[None, :]).to(torch.int32)
+        labels = grid.to(dev).unsqueeze(0).repeat(B, 1, 1)
+    else:
+        labels = given
+    lam = (float(compactness) / (H * W / float(d)) ** 0.5) ** 2
+    centres = torch.zeros((B, d, C + 2), dtype=torch.float32, device=dev)
+    means = torch.empty((B, d, C), dtype=torch.float32, device=dev)
+    for _ in range(iters):
+        K.slic_update(x, labels, centres, means, gy, gx)
+        K.slic_assign(x, centres, labels, gy, gx, lam)
+    K.slic_update(x, labels, centres, means, gy, gx, window=given is None)
+    return Superpixels(labels, d, means)
+
+
+def _check_samples_shape(N, d):
+    N, d = int(N), _check_segment_count(int(d))
+    if N < 1:
+        raise ValueError("the number of samples must be at least 1, got %d" % N)
+    return N, d
+
+
+def lime_samples(N, d, seed=0):
+    """The N x d sample matrix of a LIME run, uint8 on the host: from a CPU torch.Generator().manual_seed(seed),
+    torch.rand(N, d) < 0.5, then row 0 set to all ones (the image itself), as lime_image draws them."""
+    N, d = _check_samples_shape(N, d)
+    gen = torch.Generator().manual_seed(int(seed))
+    z = (torch.rand(N, d, generator=gen) < 0.5).to(torch.uint8)
+    z[0] = 1
+    return z
+
+
+def kernelshap_samples(N, d, seed=0):
+    """The N x d sample matrix of a KernelSHAP run, uint8 on the host.  Row 0 is all ones, row 1 all zeros.  From a CPU
+    torch.Generator().manual_seed(seed): first the sizes of rows 2 .. N - 1, m in [1, d - 1] with probability proportional to
+    (d - 1) / (m (d - m)) (one torch.multinomial with replacement), then torch.rand(N - 2, d), of which row n keeps its m
+    smallest entries (the first among equals).  Rows drawn under this size law carry weight 1 in the regression: the Shapley
+    kernel by importance sampling.  N >= d + 2; for d = 1 the matrix is rows 0 and 1 alone (N >= 2).  No paired (complement)
+    sampling."""
+    N, d = _check_samples_shape(N, d)
+    if N < (d + 2 if d > 1 else 2):
+        raise ValueError("KernelSHAP needs N >= d + 2 = %d samples (2 for d = 1), got %d" % (d + 2, N))
+    z = torch.zeros((N if d > 1 else 2, d), dtype=torch.uint8)
+    z[0] = 1
+    if d > 1 and N > 2:
+        gen = torch.Generator().manual_seed(int(seed))
+        m = torch.arange(1, d, dtype=torch.float64)
+        sizes = torch.multinomial((d - 1) / (m * (d - m)), N - 2, replacement=True, generator=gen) + 1
+        order = torch.rand(N - 2, d, generator=gen).argsort(dim=1, stable=True).argsort(dim=1, stable=True)
+        z[2:] = (order < sizes[:, None]).to(torch.uint8)
+    return z
+
+
+def _check_sample_matrix(z, d, shap):
+    """a caller's sample matrix against the segmentation of this call"""
+    if not torch.is_tensor(z) or z.dtype != torch.uint8 or z.dim() != 2 or z.shape[1] != d or z.shape[0] < 1:
+        raise ValueError("samples must be uint8 [N, d = %d], got %s" % (d, (z.dtype, tuple(z.shape)) if torch.is_tensor(z) else type(z)))
+    if shap:
+        head = z[:2].cpu()
+        if z.shape[0] < 2 or not bool(head[0].all()) or bool(head[1].any()):
+            raise ValueError("KernelSHAP samples: row 0 must be all ones and row 1 all zeros")
+    return z
+
+
+def _surrogate_fit(model, images, classes, seg, z, batch, hide, mode, kernel_width, ridge):
+    """the loop LIME and KernelSHAP share: image, then chunk of sample rows; then one fit for all images"""
+    B, C, H, W = images.shape
+    if isinstance(hide, str) and hide != "mean":
+        raise ValueError('hide must be "mean" or a number, got %r' % (hide,))
+    if not float(ridge) >= 0.0:
+        raise ValueError("ridge must be at least 0, got %r" % (ridge,))
+    per_image, cols = _class_columns(classes, B, _num_outputs(model, images))
+    x, batch = _check_images_batch(images, batch)
+    dev = x.device
+    z = z.to(dev).contiguous()
+    N, d = z.shape
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    if Kc == 0:
+        return SurrogateFit(torch.empty((B, 0, d), dtype=torch.float64, device=dev),
+                            torch.empty((B, 0), dtype=torch.float64, device=dev), seg.labels)
+    means = seg.means if hide == "mean" else None
+    fill = 0.0 if means is not None else float(hide)
+    S = torch.zeros((B, d + 1, d + 1), dtype=torch.float64, device=dev)
+    T = torch.zeros((B, d + 1, Kc), dtype=torch.float64, device=dev)
+    yref = torch.zeros((B, 2, Kc), dtype=torch.float64, device=dev)
+    buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            for n0 in range(0, N, batch):
+                zc = z[n0:n0 + batch]
+                chunk = K.segment_images(x[b], seg.labels[b], zc, buf[:zc.shape[0]], None if means is None else means[b], fill)
+                K.surrogate_accumulate(model(chunk), cb, zc, S[b], T[b], yref[b], n0, mode, kernel_width)
+        coef, icpt = K.surrogate_solve(S, T, yref, mode, ridge)
+    return SurrogateFit(coef, icpt, seg.labels)
+
+
+def _segmentation(images, segments, slic_iters, compactness, d):
+    return segments if isinstance(segments, Superpixels) else superpixels(images, segments, slic_iters, compactness, d)
+
+
+def lime_fit(model, images, classes=None, n_samples=1000, segments=(8, 8), batch=250, seed=0, hide="mean", kernel_width=0.25,
+             ridge=1.0, slic_iters=10, compactness=1.0, samples=None, d=None):
+    """LIME (Ribeiro et al. 2016, lime_image's arithmetic) for `images` [B, C, H, W] -> SurrogateFit(coef float64 [B, K, d],
+    intercept float64 [B, K], labels int32 [B, H, W]) on the images' device.
+
+    The segments are `superpixels(images, segments, slic_iters, compactness, d)` (or a Superpixels record given as `segments`),
+    the samples z uint8 [N, d] are `lime_samples(n_samples, d, seed)` (or `samples`), the same for every image.  Row n shows the
+    image where z[n, segment] is set and `hide` elsewhere: "mean", the segment's mean colour (lime_image's default), or a number,
+    a constant fill.  The targets are y[n, k] = exp(log_prob_n[classes[k]]) in float64, the weights pi_n = sqrt(exp(-D_n^2 /
+    kernel_width^2)) with D_n = 1 - sqrt(|z_n| / d) (1 for an empty row), and the fit minimises sum_n pi_n (y_n - b - w . z_n)^2 +
+    ridge |w|^2 with a free intercept b (sklearn's Ridge(alpha=1) at the default).  LIME's feature selection is left out: every
+    segment keeps its coefficient.
+
+    classes as in `gradcam` / `rise`; any module whose eval forward returns [n, n_outputs] works.  Per image the rows go through
+    the model in chunks of `batch`: kernels.segment_images into one reused buffer, the model under torch.no_grad() in eval mode
+    (folded when the model's inference fold is on; the caller's mode is restored), kernels.surrogate_accumulate onto the float64
+    moments in row order -- the same bits for any `batch` -- and one kernels.surrogate_solve at the end.  No BatchNorm buffer
+    moves, no `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop."""
+    seg = _segmentation(_check_images(images), segments, slic_iters, compactness, d)
+    z = lime_samples(n_samples, seg.d, seed) if samples is None else _check_sample_matrix(samples, seg.d, False)
+    if not float(kernel_width) > 0.0:
+        raise ValueError("kernel_width must be positive, got %r" % (kernel_width,))
+    return _surrogate_fit(model, images, classes, seg, z, batch, hide, K.SURROGATE_LIME, float(kernel_width), ridge)
+
+
+def kernelshap_fit(model, images, classes=None, n_samples=1000, segments=(8, 8), batch=250, seed=0, hide=0.0, ridge=0.0,
+                   slic_iters=10, compactness=1.0, samples=None, d=None):
+    """KernelSHAP (Lundberg & Lee 2017) for `images` [B, C, H, W] -> SurrogateFit(coef = phi float64 [B, K, d], intercept = y_0
+    float64 [B, K], labels int32 [B, H, W]) on the images' device.
+
+    Segments, perturbed rows, targets and the loop are those of `lime_fit`; the samples are `kernelshap_samples(n_samples, d,
+    seed)` (row 0 the image, row 1 everything hidden, the rest drawn under the Shapley kernel's size law, so every row weighs 1)
+    and `hide` defaults to the constant 0.0, the dataset mean of a normalised image.  The fit minimises sum_n (y_n - y_0 -
+    phi . z_n)^2 + ridge |phi|^2 with the intercept fixed at y_0, the target of row 1, and sum(phi) = y_full - y_0 enforced
+    exactly by eliminating the last segment.  n_samples >= d + 2.  No paired sampling and no exhaustive enumeration of small
+    coalitions (shap's KernelExplainer does both); a singular system (fewer distinct rows than segments) gives NaN."""
+    seg = _segmentation(_check_images(images), segments, slic_iters, compactness, d)
+    z = kernelshap_samples(n_samples, seg.d, seed) if samples is None else _check_sample_matrix(samples, seg.d, True)
+    return _surrogate_fit(model, images, classes, seg, z, batch, hide, K.SURROGATE_SHAP, 1.0, ridge)
+
+
+def lime(model, images, classes=None, **lime_kwargs):
+    """LIME saliency fp32 [B, K, H, W] on the device: `lime_fit`, every pixel painted with its segment's coefficient
+    (kernels.segment_paint)."""
+    fit = lime_fit(model, images, classes, **lime_kwargs)
+    return K.segment_paint(fit.coef, fit.labels)
+
+
+def kernelshap(model, images, classes=None, **shap_kwargs):
+    """KernelSHAP saliency fp32 [B, K, H, W] on the device: `kernelshap_fit`, every pixel painted with its segment's phi
+    (kernels.segment_paint)."""
+    fit = kernelshap_fit(model, images, classes, **shap_kwargs)
+    return K.segment_paint(fit.coef, fit.labels)
+
+
+def lime_maps(model, images, classes=None, min_level=0.0, **lime_kwargs):
+    """uint8 LIME heat maps [B, K, H, W] on the device: `lime`, then the drawing steps of `rise_maps` (kernels.heat_maps), which
+    cut negative coefficients to 0 -- lime_image's positive_only."""
+    return K.heat_maps(lime(model, images, classes, **lime_kwargs), min_level)
+
+
+def kernelshap_maps(model, images, classes=None, min_level=0.0, **shap_kwargs):
+    """uint8 KernelSHAP heat maps [B, K, H, W] on the device: `kernelshap`, then the drawing steps of `rise_maps`
+    (kernels.heat_maps); negative phi are cut to 0."""
+    return K.heat_maps(kernelshap(model, images, classes, **shap_kwargs), min_level)
 
 
 def scorecam(model, images, classes=None, batch=250):

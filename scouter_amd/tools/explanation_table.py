@@ -68,20 +68,20 @@ def get_table_parser():
     return parser
 
 
-def chosen_families(args):
+def chosen_families(args, families=FAMILIES):
     """the names of the families a parsed command line asks for, in table order: slot with --use_slot true, grad with --grad,
-    every other one by its own flag"""
+    every other one by its own flag.  families: this tool's table, or one that extends it (tools/surrogate.py)"""
     unflagged = {"slot": bool(args.use_slot), "grad": bool(args.grad)}
-    return [f.name for f in FAMILIES if (getattr(args, f.name, False) if f.flag else unflagged[f.name])]
+    return [f.name for f in families if (getattr(args, f.name, False) if f.flag else unflagged[f.name])]
 
 
-def check_request(families, use_slot, sensitivity=False):
-    """refuses, before any work, what the table cannot hold"""
+def check_request(families, use_slot, sensitivity=False, rows=_ROWS):
+    """refuses, before any work, what the table cannot hold (rows: the table the names are looked up in)"""
     if sensitivity:
         raise ValueError("--sensitivity is not a column of the table: sensitivity_max explains perturbed rows that carry no class "
                          "of their own; score one image with `python -m scouter_amd.test --sensitivity true`")
     for name in families:
-        T._row(name, _ROWS)
+        T._row(name, rows)
     if "fccam" in families and use_slot:
         raise ValueError("fccam: CAM reads the fc layer of the --use_slot false baseline; the slot model has none (use --cam, "
                          "Grad-CAM, for it)")
@@ -184,8 +184,9 @@ def _pick(maps, target):
     return maps[torch.arange(maps.shape[0], device=maps.device), target].unsqueeze(1).contiguous()
 
 
-def explanation_table(args, model, batches, families):
-    """Scores the families named in `families` (rows of FAMILIES, any order given is kept) over `batches` -> ExplanationTable.
+def explanation_table(args, model, batches, families, rows=_ROWS):
+    """Scores the families named in `families` (rows of FAMILIES -- or of `rows`, a table that extends this tool's -- any order
+    given is kept) over `batches` -> ExplanationTable.
 
     batches: an iterable of {"image": fp32 [B, C, H, W] on the device, "label": int64 [B], and optionally "boxes" int32
     [B, nb, 4] / "n_boxes" int32 [B] on the device, pixel boxes of the image's own grid}.  `args` is a namespace of the table
@@ -195,7 +196,7 @@ def explanation_table(args, model, batches, families):
     the loop (the families bring the class tensor over, as everywhere); one transfer at the end."""
     from . import attribution as A
     families = list(families)
-    check_request(families, bool(model.use_slot), bool(getattr(args, "sensitivity", False)))
+    check_request(families, bool(model.use_slot), bool(getattr(args, "sensitivity", False)), rows)
     want_loc, want_causal = bool(getattr(args, "localization", False)), bool(getattr(args, "causal", False))
     want_inf, by_label = bool(getattr(args, "infidelity", False)), getattr(args, "table_target", "pred") == "label"
     min_level = float(getattr(args, "grad_min_level", 0.0))
@@ -219,7 +220,7 @@ def explanation_table(args, model, batches, families):
             if want_loc:
                 values[("slot", "ratio")] = _pick(A.localization(A.slot_maps(model)).area, target)[:, 0]
         for name in families:
-            row = T._row(name, _ROWS)
+            row = T._row(name, rows)
             if row.explain is None:
                 attr = fmap = slot_map
             else:
@@ -283,11 +284,12 @@ def format_row(family, columns, images=None):
     return " ".join(words)
 
 
-def main():
-    args = get_table_parser().parse_args()
+def run_table(args, table=FAMILIES, rows=_ROWS):
+    """what main() does with a parsed command line; table / rows: this tool's families, or a table that extends them
+    (tools/surrogate.py)"""
     # (BEFORE build_model: it clears args.grad, the flag of the grad row, so that the model is built as for training)
-    families = chosen_families(args)
-    check_request(families, bool(args.use_slot), bool(args.sensitivity))
+    families = chosen_families(args, table)
+    check_request(families, bool(args.use_slot), bool(args.sensitivity), rows)
     if args.table_images < 1:
         raise ValueError("--table_images must be at least 1, got %d" % args.table_images)
     boxes_table = read_boxes_file(args.boxes_file) if args.boxes_file else None
@@ -295,11 +297,15 @@ def main():
     from ..train import _build_loaders
     args.distributed = bool(getattr(args, "distributed", False))
     _, loader, _ = _build_loaders(args)
-    result = explanation_table(args, model, table_batches(args, loader, boxes_table), families)
+    result = explanation_table(args, model, table_batches(args, loader, boxes_table), families, rows)
     for name in families:
         print(format_row(name, result.rows[name], len(result.correct)))
     print("table accuracy %.6f images %d" % (float(result.correct.mean()), len(result.correct)))
     return result
+
+
+def main():
+    return run_table(get_table_parser().parse_args())
 
 
 if __name__ == "__main__":
