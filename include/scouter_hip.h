@@ -790,6 +790,41 @@ int scouter_surrogate_solve_f64(const double* S, const double* T, const double* 
 /* THE MAP: out fp32 [B][K][H][W], out[b][k][p] = (float) coef[b][k][labels[b][p]] -- a gather.  B * K <= 65535. */
 int scouter_segment_paint_f32(const double* coef, const int* labels, float* out, int B, int K, int d, int H, int W, void* stream);
 
+/* ---- Occlusion sensitivity (Zeiler & Fergus, ECCV 2014; captum's Occlusion) and Ablation-CAM (Desai & Ramaswamy, WACV 2020): take
+ * a part away -- a window of the image, a channel of the backbone's output -- and see what the class loses (csrc/occlusion.hip,
+ * csrc/ablation.hip, tools/attribution.py occlusion / ablationcam).  No reference program runs either; this comment is the
+ * specification.  Both loops put the untouched input in row 0 of every batch and read the loss with scouter_output_deltas_f64.  Every
+ * call has one fixed order per output element and no atomics: bit-identical run to run.  A null or misaligned pointer, a count
+ * below 1, rows outside the stream or a geometry outside the rule below is SC_ERR_ARG, with a message that names the call; nothing
+ * is launched after an error.
+ *
+ * THE WINDOWS, per axis of `size` pixels with window `win` and stride `str`, 1 <= str <= win <= size: n = 1 + ceil((size - win) / str)
+ * windows; window i covers [i * str, min(i * str + win, size)) -- the last one may be partial; the windows that cover pixel y are
+ * exactly i in [max(0, ceil((y - win + 1) / str)), min(n - 1, floor(y / str))], a range that is never empty.  With (wh, sy) for the
+ * rows and (ww, sx) for the columns there are ny and nx of them, window n = iy * nx + ix, N = ny * nx.
+ *
+ * THE OCCLUDED BATCH: image fp32 [C][H][W] -> out fp32 [1 + n][C][H][W].  Row 0 is the image; row 1 + j is the image with window
+ * first + j set to `fill` (not a NaN) in every channel and a bit-exact copy elsewhere; first >= 0, first + n <= N.  16-byte accesses
+ * when W is a multiple of 4 and image / out are 16-byte aligned, one pixel per thread otherwise: the same bits. */
+int scouter_occlude_images_f32(const float* image, float* out, int first, int n, int C, int H, int W, int wh, int ww, int sy, int sx,
+                               float fill, void* stream);
+/* THE MAP: deltas fp64 [K][N] (what scouter_output_deltas_f64 wrote for the N windows) -> out fp32 [K][H][W], overwritten:
+ * out[k][y][x] = (float)((sum_iy sum_ix deltas[k][iy * nx + ix]) / count) over the windows that cover (y, x), iy ascending, then ix
+ * ascending, in fp64; count is their number.  One thread per output element: no atomics and no partial sums. */
+int scouter_occlusion_finish_f32(const double* deltas, float* out, int K, int H, int W, int wh, int ww, int sy, int sx, void* stream);
+/* THE ABLATED BATCH: feat fp32 NHWC [P = h * w][C] -> out fp32 [1 + n][P][C].  Row 0 is feat; row 1 + j is feat with channel first + j
+ * set to 0.0f at every position and a bit-exact copy elsewhere; first >= 0, first + n <= C.  16-byte accesses when C is a multiple
+ * of 4 and feat / out are 16-byte aligned, one element per thread otherwise: the same bits. */
+int scouter_ablate_channels_f32(const float* feat, float* out, int first, int n, int P, int C, void* stream);
+/* THE CLASS MAP: deltas fp64 [K][C] (the drop of the class probability per ablated channel), clean fp32 [n_classes] (the clean
+ * log-probabilities), cols i32 [K] in [0, n_classes) (checked by the caller; clamped here), feat as above -> out fp32 [K][P],
+ * overwritten.  w[k][c] = (float)(deltas[k][c] / exp((double)clean[cols[k]])), rounded from fp64 once (a clean probability of 0
+ * gives the infinity or NaN the division gives); out[k][p] starts from 0 and adds fmaf(w[k][c], feat[p][c], .) for c ascending,
+ * then is clamped at 0 (fmaxf: a NaN becomes 0) when relu != 0.  One thread per output element, the weights staged through LDS in
+ * pieces.  Any C >= 1, any K >= 1. */
+int scouter_ablation_contract_f32(const double* deltas, const float* clean, const int* cols, const float* feat, float* out, int K,
+                                  int n_classes, int P, int C, int relu, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

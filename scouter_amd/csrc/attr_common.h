@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip), each defined ONCE: where two kernels promise the same bits --
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip, occlusion.hip, ablation.hip), each defined ONCE: where two kernels promise the same bits --
 // heat_maps and cam_maps at the map's own size, resize_bilinear and the resize inside cam_maps and scorecam_ranges -- they call
 // the same inlined function here on the same operands.  (The mask and the fma chain of the Score-CAM family have one file,
 // scorecam.hip, and are defined there.)  Inlined functions and templates only: no kernel, no entry point, no state.
@@ -258,13 +258,21 @@ static inline AtPixelGrid at_pixel_grid(int H, int W, int threads, uintptr_t poi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The end the class-tiled kernels share (rise_accumulate_kernel, sscam_contract_kernel): acc[k0 + k][p] = a[k] for the kt
-// classes a thread holds in registers for element p of the plane
+// The end the class-tiled kernels share (rise_accumulate_kernel, sscam_contract_kernel, ablation_contract_kernel):
+// acc[k0 + k][p] = a[k] for the kt classes a thread holds in registers for element p of the plane
 template <int KT>
 __device__ __forceinline__ void at_store_acc(float* __restrict__ acc, long plane, long p, int k0, int kt, const float (&a)[KT]) {
 #pragma unroll
     for (int k = 0; k < KT; ++k)
         if (k < kt) acc[(long)(k0 + k) * plane + p] = a[k];
+}
+
+// The step the class-tiled kernels share (rise_accumulate_kernel, sscam_contract_kernel, ablation_contract_kernel): one value v
+// of the plane's element times the KT staged weights w [KT] of a term, one fma per class onto the accumulators
+template <int KT>
+__device__ __forceinline__ void at_fma_tile(const float* __restrict__ w, float v, float (&a)[KT]) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k) a[k] = fmaf(w[k], v, a[k]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

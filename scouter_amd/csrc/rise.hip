@@ -169,8 +169,7 @@ __global__ __launch_bounds__(RS_THREADS) void rise_accumulate_kernel(const float
                 at_source(y + s_shift[j][0], sy, s, y0, y1, ty);
                 at_source(x + s_shift[j][1], sx, s, x0, x1, tx);
                 const float m = rs_mask(s_g[j], s, y0, y1, ty, x0, x1, tx);
-#pragma unroll
-                for (int k = 0; k < RS_KT; ++k) a[k] = fmaf(s_w[j][k], m, a[k]);
+                at_fma_tile<RS_KT>(s_w[j], m, a);
             }
         }
     }

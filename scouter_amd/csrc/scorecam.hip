@@ -67,9 +67,7 @@ __device__ __forceinline__ void sc_add_live(const float* __restrict__ f, const f
                                             float (&a)[SC_KT]) {
     for (int j = 0; j < np; ++j) {
         if (!s_live[j]) continue;
-        const float v = f[j];
-#pragma unroll
-        for (int k = 0; k < SC_KT; ++k) a[k] = fmaf(s_w[j][k], v, a[k]);
+        at_fma_tile<SC_KT>(s_w[j], f[j], a);
     }
 }
 

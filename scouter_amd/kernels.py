@@ -2090,6 +2090,115 @@ def segment_paint(coef, labels):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Occlusion sensitivity and Ablation-CAM (csrc/occlusion.hip, csrc/ablation.hip; tools/attribution.py occlusion / ablationcam)
+# ---------------------------------------------------------------------------------------------------------------
+def _pair(v, name, what):
+    """an int, or a pair of them (rows, columns) -> two ints"""
+    try:
+        a, b = v if isinstance(v, (tuple, list, torch.Size)) else (v, v)
+        return int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s must be an int or a pair of ints, got %r" % (what, name, v)) from None
+
+
+def occlusion_windows(size, window, stride, what="occlusion_windows"):
+    """(ny, nx): the windows per axis of an occlusion run over maps of `size` = (H, W); `window` and `stride` are an int or a
+    pair (rows, columns).  Per axis with 1 <= stride <= window <= size (anything else is a ValueError that names `what`):
+    n = 1 + ceil((size - window) / stride) windows, window i covers [i * stride, min(i * stride + window, size)) -- the last one may
+    be partial -- and the windows that cover pixel y are i in [max(0, ceil((y - window + 1) / stride)), min(n - 1, y // stride)].
+    Window n = iy * nx + ix.  Host arithmetic only; the definition of include/scouter_hip.h."""
+    (H, W), (wh, ww), (sy, sx) = _pair(size, "size", what), _pair(window, "window", what), _pair(stride, "stride", what)
+    for axis, n, w, s in (("rows", H, wh, sy), ("columns", W, ww, sx)):
+        if not 1 <= s <= w <= n:
+            raise ValueError("%s: %s: stride %d, window %d, size %d (1 <= stride <= window <= size)" % (what, axis, s, w, n))
+    return 1 + -(-(H - wh) // sy), 1 + -(-(W - ww) // sx)
+
+
+def occlude_images(image, out, first, window, stride, fill=0.0):
+    """out[0] = image and out[1 + j] = image with window first + j of `occlusion_windows(image.shape[1:], window, stride)` set to
+    `fill` in every channel, a bit-exact copy elsewhere, for fp32 image [C, H, W] and fp32 out [1 + n, C, H, W] (a dense leading
+    slice of a longer buffer is fine), n >= 1 and first + n <= ny * nx.  A select: no value is computed.  One launch."""
+    what = "occlude_images"
+    _chk(image, what + ": image"); _chk(out, what + ": out")
+    if image.dim() != 3:
+        raise RuntimeError("%s: image must be [C, H, W], got shape %s" % (what, tuple(image.shape)))
+    C, H, W = image.shape
+    if out.dim() != 4 or tuple(out.shape[1:]) != (C, H, W) or out.shape[0] < 2:
+        raise RuntimeError("%s: out must be [1 + n, %d, %d, %d] with n >= 1, got shape %s" % (what, C, H, W, tuple(out.shape)))
+    (wh, ww), (sy, sx) = _pair(window, "window", what), _pair(stride, "stride", what)
+    ny, nx = occlusion_windows((H, W), (wh, ww), (sy, sx), what)
+    first, n = int(first), int(out.shape[0]) - 1
+    if first < 0 or first + n > ny * nx:
+        raise ValueError("%s: windows [%d, %d) lie outside [0, %d x %d = %d)" % (what, first, first + n, ny, nx, ny * nx))
+    _native.check(_native.lib().scouter_occlude_images_f32(_p(image), _p(out), first, n, C, H, W, wh, ww, sy, sx, float(fill),
+                                                           _stream()), what)
+    return out
+
+
+def occlusion_finish(deltas, out, window, stride):
+    """out[k, y, x] = float32(the mean of deltas[k, n] over the windows n that cover (y, x)) for fp64 deltas [K, ny * nx] (what
+    `output_deltas` wrote for the windows of `occlude_images`) and fp32 out [K, H, W], which is overwritten: one thread per
+    element adds the covering windows in float64, rows of windows ascending, then columns, and divides by their number.  One launch."""
+    what = "occlusion_finish"
+    _chk(deltas, what + ": deltas", torch.float64); _chk(out, what + ": out")
+    if out.dim() != 3 or deltas.dim() != 2 or deltas.shape[0] != out.shape[0] or out.shape[0] < 1:
+        raise RuntimeError("%s: deltas must be fp64 [K, N] and out fp32 [K, H, W] with K >= 1 (got %s and %s)"
+                           % (what, tuple(deltas.shape), tuple(out.shape)))
+    K_, H, W = out.shape
+    (wh, ww), (sy, sx) = _pair(window, "window", what), _pair(stride, "stride", what)
+    ny, nx = occlusion_windows((H, W), (wh, ww), (sy, sx), what)
+    if deltas.shape[1] != ny * nx:
+        raise RuntimeError("%s: deltas has %d columns for %d x %d = %d windows" % (what, deltas.shape[1], ny, nx, ny * nx))
+    _native.check(_native.lib().scouter_occlusion_finish_f32(_p(deltas), _p(out), K_, H, W, wh, ww, sy, sx, _stream()), what)
+    return out
+
+
+def _ablation_feat_chk(what, feat):
+    """feat fp32 [h, w, C], one image's NHWC features -> (h, w, C)"""
+    _chk(feat, what + ": feat")
+    if feat.dim() != 3 or feat.numel() < 1:
+        raise RuntimeError("%s: feat must be one image's NHWC features [h, w, C], got shape %s" % (what, tuple(feat.shape)))
+    return tuple(int(v) for v in feat.shape)
+
+
+def ablate_channels(feat, out, first):
+    """out[0] = feat and out[1 + j] = feat with channel first + j set to 0.0 at every position, a bit-exact copy elsewhere, for fp32
+    feat [h, w, C] (one image's NHWC features) and fp32 out [1 + n, h, w, C] (a dense leading slice of a longer buffer is fine),
+    n >= 1 and first + n <= C.  A select: no value is computed.  One launch."""
+    what = "ablate_channels"
+    h, w, C = _ablation_feat_chk(what, feat)
+    _chk(out, what + ": out")
+    if out.dim() != 4 or tuple(out.shape[1:]) != (h, w, C) or out.shape[0] < 2:
+        raise RuntimeError("%s: out must be [1 + n, %d, %d, %d] with n >= 1, got shape %s" % (what, h, w, C, tuple(out.shape)))
+    first, n = int(first), int(out.shape[0]) - 1
+    if first < 0 or first + n > C:
+        raise ValueError("%s: channels [%d, %d) lie outside [0, C = %d)" % (what, first, first + n, C))
+    _native.check(_native.lib().scouter_ablate_channels_f32(_p(feat), _p(out), first, n, h * w, C, _stream()), what)
+    return out
+
+
+def ablation_contract(deltas, clean, cols, feat, out, relu=True):
+    """out[k, p] = sum_c float32(deltas[k, c] / exp(float64(clean[cols[k]]))) * feat[p, c] for fp64 deltas [K, C] (what
+    `output_deltas(of="prob")` wrote for the channels of `ablate_channels`), fp32 clean [n_classes] (the clean log-probabilities),
+    cols int32 [K] on the device (the caller keeps them inside [0, n_classes)), feat [h, w, C] and fp32 out [K, h, w], which is
+    overwritten: the weight is rounded from float64 once, then one thread per element adds the channels one fma at a time in
+    ascending order from 0; relu: the sum is clamped at 0.  One launch; nothing is read on the host."""
+    what = "ablation_contract"
+    _chk(deltas, what + ": deltas", torch.float64); _chk(clean, what + ": clean"); _chk(cols, what + ": cols", torch.int32)
+    _chk(out, what + ": out")
+    h, w, C = _ablation_feat_chk(what, feat)
+    if deltas.dim() != 2 or cols.dim() != 1 or clean.dim() != 1 or clean.shape[0] < 1 or cols.shape[0] < 1 or \
+            tuple(deltas.shape) != (cols.shape[0], C) or tuple(out.shape) != (cols.shape[0], h, w):
+        raise RuntimeError("%s: deltas must be fp64 [K, C = %d], clean [n_classes], cols [K] with K >= 1 and out [K, %d, %d] (got %s, "
+                           "%s, %s and %s)" % (what, C, h, w, tuple(deltas.shape), tuple(clean.shape), tuple(cols.shape),
+                                               tuple(out.shape)))
+    _native.check(_native.lib().scouter_ablation_contract_f32(_p(deltas), _p(clean), _p(cols), _p(feat), _p(out),
+                                                              int(cols.shape[0]), int(clean.shape[0]), h * w, C, 1 if relu else 0,
+                                                              _stream()), what)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Localisation scores of byte maps (csrc/localization.hip; tools/attribution.py localization / slot_maps)
 # ---------------------------------------------------------------------------------------------------------------
 def map_localization(maps, boxes=None, n_boxes=None):

@@ -135,7 +135,24 @@ both are black-box and cost eval forwards.  The perturbed batch, the float64 mom
 the chunking does not change a bit), the Cholesky fit and the painting are four more HIP kernels (kernels.segment_images,
 surrogate_accumulate, surrogate_solve, segment_paint) and nothing comes to the host in between.  No reference program runs
 either method here (lime, shap and skimage are not dependencies): the docstrings are the specification and say what departs
-from those packages.  tools/surrogate.py adds both as rows to the single-image tool and the explanation table."""
+from those packages.  tools/surrogate.py adds both as rows to the single-image tool and the explanation table.
+
+Occlusion maps (`occlusion_windows`, `occlusion`, `occlusion_maps`): occlusion sensitivity (Zeiler & Fergus 2014; captum's Occlusion,
+from the package the reference's captum_vis.py draws its methods from), the first baseline a perturbation method is compared
+with.  A window slides over the image, every occluded copy goes through the model, and a pixel's score is the mean drop of the
+class probability over the windows that covered it: the deterministic counterpart of `rise`, with no random stream and no
+surrogate.  The occluded batch is written straight into one reused buffer with the clean image in row 0 (kernels.occlude_images),
+the drops are float64 differences inside one forward (kernels.output_deltas) and the map is their mean over the covering windows
+in one fixed order (kernels.occlusion_finish); nothing comes to the host in between.  Like `rise` it is black-box and costs eval
+forwards: 729 for a 224 x 224 image at the default window 16 and stride 8.
+
+The gradient-free class activation map (`ablationcam`, `ablationcam_maps`): Ablation-CAM (Desai & Ramaswamy, WACV 2020).  Every
+channel of the layer `gradcam` reads is zeroed in turn and weighted by the relative drop of the class probability.  The ablated
+copies are rows of one reused feature buffer (kernels.ablate_channels) and go through SlotModel.head_pass alone -- the backbone
+runs once per batch, where `scorecam` runs it once per channel -- the drops come from kernels.output_deltas and the weighted sum
+from kernels.ablation_contract (the weight rounded from float64 once, one fma per channel in ascending order).  No backward, and
+nothing comes to the host in between.  tools/ablation.py adds both methods as rows to the single-image tool and the explanation
+table."""
 import collections
 import contextlib
 import functools
@@ -1946,3 +1963,137 @@ def igos_maps(model, images, classes=None, min_level=0.0, **kwargs):
     """uint8 I-GOS heat maps [B, K, H, W] on the device: `igos_saliency`, then the drawing steps of `rise_maps` at the maps' own
     size (kernels.heat_maps)."""
     return K.heat_maps(igos_saliency(model, images, classes, **kwargs), min_level)
+
+
+def occlusion_windows(size, window, stride):
+    """(ny, nx): the number of windows per axis of an `occlusion` run over images of `size` = (H, W); `window` and `stride` are an
+    int or a pair (rows, columns).  Per axis, with 1 <= stride <= window <= size (anything else is a ValueError):
+    n = 1 + ceil((size - window) / stride); window i covers [i * stride, min(i * stride + window, size)), so the last one may be
+    partial and every pixel is covered; the windows that cover pixel y are i in [max(0, ceil((y - window + 1) / stride)),
+    min(n - 1, y // stride)].  Window n = iy * nx + ix.  Host arithmetic only."""
+    return K.occlusion_windows(size, window, stride)
+
+
+def _rows_per_forward(batch):
+    if batch < 2:
+        raise ValueError("batch must be at least 2 (the clean row and one changed row), got %d" % batch)
+    return batch
+
+
+def occlusion(model, images, classes=None, window=16, stride=8, fill=0.0, batch=250, of="prob"):
+    """Occlusion sensitivity (Zeiler & Fergus 2014; captum's Occlusion) of `images` [B, C, H, W] -> fp32 [B, K, H, W] on the images'
+    device:  S[b, k, y, x] = the mean, over the windows n that cover (y, x), of F(out_clean[classes[k]]) - F(out_n[classes[k]]),
+    out_n the eval-mode output for images[b] with window n set to `fill` in every channel.  of="prob": F = exp, the drop of the
+    class probability; of="log_prob": F is the identity (the two modes of kernels.output_deltas, in float64).
+
+    The windows are those of `occlusion_windows((H, W), window, stride)` -- `window` and `stride` an int or a pair (rows, columns),
+    1 <= stride <= window <= size per axis; the last window of an axis may be partial; the order is rows of windows, then columns.
+    `fill` is one number for every channel: 0.0 is the dataset mean of a normalised image.  classes as in `gradcam` / `rise`: None
+    (every class), a list of ints (K = len), or a LongTensor [B] (each image its own class, K = 1).  Any module whose eval forward
+    returns log-probabilities [n, n_outputs] will do.
+
+    Per image the N = ny * nx windows go through the model in chunks of batch - 1 occluded rows behind the clean image in row 0
+    (batch >= 2; the last chunk may be shorter): kernels.occlude_images into one reused buffer, the model under torch.no_grad() in
+    eval mode (folded when the model's inference fold is on; the caller's mode is restored), kernels.output_deltas -- both sides of
+    a difference come from the same forward.  kernels.occlusion_finish once per image: the covering windows are added in float64
+    in one fixed order, divided by their number and rounded to fp32 once.  The same bits for any two runs.  No BatchNorm buffer
+    moves, no `.grad` appears, nothing is copied to the host and nothing synchronises inside the loop.
+
+    What departs from captum's Occlusion: one window for all channels (captum slides over the channel axis too; this is its
+    window shape (C, wh, ww)); a scalar baseline; every class is read from the ONE stream of forwards, where captum takes one
+    target per call; the clean output is recomputed in every forward, so that both sides of a difference see the same kernels;
+    the mean is formed in float64; and the default F is the probability, where captum differences whatever the forward returns
+    (of="log_prob" is that).  The window rule -- a stride no larger than the window, a partial last window -- is captum's as far
+    as it is remembered here; captum is no dependency and nothing was checked against it."""
+    if of not in ("log_prob", "prob"):
+        raise ValueError("of must be 'log_prob' or 'prob', got %r" % (of,))
+    B, C, H, W = _check_images(images).shape
+    ny, nx = occlusion_windows((H, W), window, stride)
+    fill = float(fill)
+    if fill != fill:
+        raise ValueError("fill must be a number, got %r" % (fill,))
+    x, batch = _check_images_batch(images, batch)
+    batch = _rows_per_forward(batch)
+    per_image, cols = _class_columns(classes, B, _num_outputs(model, images))
+    dev = images.device
+    N = ny * nx
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    out = torch.empty((B, Kc, H, W), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    deltas = torch.empty((Kc, N), dtype=torch.float64, device=dev)
+    buf = torch.empty((min(batch, N + 1), C, H, W), dtype=torch.float32, device=dev)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            for first in range(0, N, batch - 1):
+                chunk = K.occlude_images(x[b], buf[:1 + min(batch - 1, N - first)], first, window, stride, fill)
+                logp = model(chunk)
+                logp = logp if logp.dtype == torch.float32 and logp.is_contiguous() else logp.float().contiguous()
+                K.output_deltas(logp, cb, deltas, first, of)
+            K.occlusion_finish(deltas, out[b], window, stride)
+    return out
+
+
+def occlusion_maps(model, images, classes=None, min_level=0.0, **kwargs):
+    """uint8 occlusion heat maps [B, K, H, W] on the device: `occlusion` (its other keyword arguments pass through), then the
+    drawing steps of `rise_maps` at the maps' own size (kernels.heat_maps), which cut the pixels whose occlusion RAISED the class
+    to 0."""
+    return K.heat_maps(occlusion(model, images, classes, **kwargs), min_level)
+
+
+def ablationcam(model, images, classes=None, batch=256, relu=True):
+    """Ablation-CAM (Desai & Ramaswamy, WACV 2020) of `images` [B, Cin, H, W] at the backbone's output -> fp32 [B, K, h, w] on the
+    images' device:  S[b, k, p] = sum_c w[b, k, c] * A[b, p, c], clamped at 0 when `relu`, with A = model.feature_pass(images)
+    .features (NHWC [B, h, w, C], the layer `gradcam` reads) and
+    w[b, k, c] = float32((P(A[b]) - P(A[b] with channel c zeroed)) / P_clean),  P = exp(log_prob[classes[k]])
+    in float64: the relative drop of the class probability when channel c is taken away.  The two P of the numerator come from ONE
+    head forward (the clean features ride in row 0 of every chunk); the denominator P_clean is the feature pass's own
+    log-probability.  The channels are added in ascending order, one fma each, the weight rounded from float64 once.
+
+    One `feature_pass` for the batch; then per image the C channels go in chunks of batch - 1 ablated rows behind the clean
+    features in row 0 (batch >= 2; the last chunk may be shorter): kernels.ablate_channels into one reused buffer,
+    model.head_pass(buf).log_probs -- the head alone: the 2048 ablated copies of resnest26d never enter the backbone, where
+    `scorecam` pays 2048 whole forwards -- and kernels.output_deltas(of="prob"); kernels.ablation_contract once per image.  No
+    backward runs.  The same bits for any two runs.  No BatchNorm buffer moves, no `.grad` appears, nothing is copied to the host
+    and nothing synchronises inside the loop.  classes as in `gradcam`; it needs a SlotModel (slot head or FC baseline).
+
+    What departs from the paper: the weights are relative drops of the class PROBABILITY, the quantity `scorecam` weights by,
+    where the paper uses the raw class score before the softmax; ablation is to 0, the minimum of post-ReLU features (the paper's
+    choice for such layers); a clean probability that underflows to 0 gives the infinity or NaN the division gives."""
+    B = _check_images(images).shape[0]
+    per_image, cols = _class_columns(classes, B, _num_classes(model, images))
+    x, batch = _check_images_batch(images, batch)
+    batch = _rows_per_forward(batch)
+    dev = images.device
+    fp = model.feature_pass(x)
+    feat, clean = fp.features.detach(), fp.log_probs.detach()   # (the FeaturePass and its head state are dropped here)
+    del fp
+    feat = (feat.float() if feat.dtype != torch.float32 else feat).contiguous()
+    clean = (clean.float() if clean.dtype != torch.float32 else clean).contiguous()
+    _, h, w, C = feat.shape
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(dev)
+    Kc = 1 if per_image else len(cols)
+    out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+    if Kc == 0:
+        return out
+    deltas = torch.empty((Kc, C), dtype=torch.float64, device=dev)
+    buf = torch.empty((min(batch, C + 1), h, w, C), dtype=torch.float32, device=dev)
+    with _eval_mode(model), torch.no_grad():
+        for b in range(B):
+            cb = cols_dev[b:b + 1] if per_image else cols_dev
+            for first in range(0, C, batch - 1):
+                chunk = K.ablate_channels(feat[b], buf[:1 + min(batch - 1, C - first)], first)
+                logp = model.head_pass(chunk).log_probs
+                logp = logp if logp.dtype == torch.float32 and logp.is_contiguous() else logp.float().contiguous()
+                K.output_deltas(logp, cb, deltas, first, "prob")
+            K.ablation_contract(deltas, clean[b], cb, feat[b], out[b], relu)
+    return out
+
+
+def ablationcam_maps(model, images, classes=None, size=None, min_level=0.0, **kwargs):
+    """uint8 Ablation-CAM heat maps [B, K, H, W] on the device: `ablationcam` (its other keyword arguments pass through), then the
+    drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(ablationcam(model, images, classes, **kwargs), H, W, min_level)
