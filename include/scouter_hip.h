@@ -825,6 +825,43 @@ int scouter_ablate_channels_f32(const float* feat, float* out, int first, int n,
 int scouter_ablation_contract_f32(const double* deltas, const float* clean, const int* cols, const float* feat, float* out, int K,
                                   int n_classes, int P, int C, int relu, void* stream);
 
+/* ---- Layer attributions that keep the gradient per position of the backbone's output (the reference's captum_vis.py attributes
+ * to model.layer4 with captum's layer methods): Layer Integrated Gradients, Layer Conductance (Dhamdhere et al. 2018), HiResCAM
+ * (Draelos & Carin 2020) and LayerCAM (Jiang et al. 2021) (csrc/layerattr.hip, tools/attribution.py layer_integrated_gradients /
+ * layer_conductance / layer_gradxact).  No reference program runs them; this comment is the specification.  Features and
+ * gradients are fp32 NHWC, one image [P = h * w][C]; every product and sum is formed in fp64.  Every call has one fixed order per
+ * output element and no atomics: bit-identical run to run.  A null or misaligned pointer (fp32: 4 bytes, fp64: 8), a count below
+ * 1, r below 2 or an unknown mode is SC_ERR_ARG; a tensor past the 32-bit offsets is SC_ERR_UNSUPPORTED; each with a message that
+ * names the call, and nothing is launched after an error.  16-byte accesses when C is a multiple of 4 and the pointers are
+ * 16-byte aligned, one element at a time otherwise.
+ *
+ * A POSITION'S CHANNEL SUM, shared by the map of scouter_layer_attr_finish_f32 and by scouter_layer_gxa_f32: one wave per
+ * position; lane l adds the terms of the channel groups q = l, l + 64, ... (V = 4 channels on the 16-byte path, else 1; within a
+ * group and from group to group in ascending c) onto 0.0, then the 64 partial sums meet in a butterfly.  The order depends on C
+ * and V alone; the error is inside the (C + 2) * 2^-53 * sum|terms| of any summation order, and a sum of zeros is exactly 0.
+ *
+ * CONDUCTANCE STEPS: feats, grads fp32 [r][P][C] (r >= 2 consecutive points of a path and the gradients there), acc fp64 [P][C]:
+ * acc[e] = fma((double)grads[j][e], (double)feats[j + 1][e] - (double)feats[j][e], acc[e]) for j = 0 .. r - 2 ascending, onto what
+ * acc holds.  grads[r - 1] is not read.  Calls over the rows [0 .. m] and [m .. n], which share row m, give the bits of one call
+ * over [0 .. n]. */
+int scouter_conductance_accumulate_f64(const float* feats, const float* grads, double* acc, int r, int P, int C, void* stream);
+/* THE MAPS: acc fp64 [K][P][C] -> map fp32 [K][P], overwritten.  mode SCOUTER_LAYER_PATH: term[k][p][c] = ((double)feat[p][c] -
+ * (double)base[p][c]) * acc[k][p][c] with feat, base fp32 [P][C] (base null: zeros); SCOUTER_LAYER_SUM: term = acc, feat and base
+ * are ignored and may be null.  map[k][p] = (float)(the channel sum of the terms, above).  attr (may be null) fp32 [K][P][C]
+ * receives (float)term.  total (may be null) fp64 [K] receives the sum over p of the UNROUNDED fp64 channel sums: one workgroup
+ * of 16 waves per class, wave v adds its positions v, v + 16, ... in ascending order, then the 16 sums are added in wave order. */
+int scouter_layer_attr_finish_f32(const float* feat, const float* base, const double* acc, float* map, float* attr, double* total,
+                                  int K, int P, int C, int mode, void* stream);
+#define SCOUTER_LAYER_PATH 0
+#define SCOUTER_LAYER_SUM 1
+/* GRADIENT TIMES ACTIVATION: feat, dfeat fp32 [B][P][C] -> out[b * out_stride + p] = (float)(the channel sum of
+ * (double)(rectify != 0 ? fmaxf(dfeat, 0) : dfeat) * (double)feat), clamped at 0 in fp64 when relu != 0 (a NaN becomes 0).  out is
+ * fp32 [B][P] written through a batch stride in elements, as in scouter_gradcam_f32: one column of a [B][K][P] tensor; a stride
+ * below P with B > 1 is SC_ERR_ARG.  rectify = relu = 0 is HiResCAM (captum's LayerGradientXActivation summed over the
+ * channels), rectify = relu = 1 LayerCAM. */
+int scouter_layer_gxa_f32(const float* feat, const float* dfeat, float* out, int B, int P, int C, long out_stride, int rectify,
+                          int relu, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

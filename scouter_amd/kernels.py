@@ -2199,6 +2199,68 @@ def ablation_contract(deltas, clean, cols, feat, out, relu=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Layer IG, layer conductance, HiResCAM and LayerCAM (csrc/layerattr.hip; tools/attribution.py layer_integrated_gradients /
+# layer_conductance / layer_gradxact)
+# ---------------------------------------------------------------------------------------------------------------
+LAYER_PATH, LAYER_SUM = 0, 1                                    # (include/scouter_hip.h SCOUTER_LAYER_*)
+
+
+def conductance_accumulate(feats, grads, acc):
+    """acc += sum_{j < r - 1} grads[j] * (feats[j + 1] - feats[j]) for fp32 feats / grads [r, h, w, C] (r >= 2 consecutive points
+    of a path at the backbone's output and the gradients there; a dense leading slice of a longer buffer is fine) and fp64 acc
+    [h, w, C]: float64 differences, one fma per step in ascending j onto the values in acc.  grads[r - 1] is not read, so calls over
+    the rows [0 .. m] and [m .. n], which share row m, give the bits of one call over [0 .. n].  One launch."""
+    what = "conductance_accumulate"
+    _chk(feats, what + ": feats"); _chk(grads, what + ": grads"); _chk(acc, what + ": acc", torch.float64)
+    if feats.dim() != 4 or feats.shape[0] < 2 or feats.numel() < 1 or grads.shape != feats.shape or \
+            tuple(acc.shape) != tuple(feats.shape[1:]):
+        raise RuntimeError("%s: feats and grads must be the same [r, h, w, C] shape with r >= 2 and acc fp64 [h, w, C] (got %s, %s "
+                           "and %s)" % (what, tuple(feats.shape), tuple(grads.shape), tuple(acc.shape)))
+    r, h, w, C = (int(v) for v in feats.shape)
+    _native.check(_native.lib().scouter_conductance_accumulate_f64(_p(feats), _p(grads), _p(acc), r, h * w, C, _stream()), what)
+    return acc
+
+
+def layer_attr_finish(mode, acc, out, feat=None, base=None, attr=None, total=None):
+    """The fp32 maps of a layer path method from its fp64 sums acc [K, h, w, C] -> out fp32 [K, h, w], which is overwritten.  mode
+    LAYER_PATH: term = (feat - base) * acc, the float64 difference of fp32 feat / base [h, w, C] (base None: zeros); LAYER_SUM:
+    term = acc (feat and base are ignored).  out[k, p] = float32(sum_c term[k, p, c]) in float64 -- one wave per position, one
+    fixed order that depends on C alone.  attr: fp32 [K, h, w, C] that receives float32(term); total: fp64 [K] that receives
+    sum_p of the unrounded position sums, in one fixed order.  One launch; two calls give the same bits."""
+    what = "layer_attr_finish"
+    if mode not in (LAYER_PATH, LAYER_SUM):
+        raise ValueError("%s: mode must be LAYER_PATH (%d) or LAYER_SUM (%d), got %r" % (what, LAYER_PATH, LAYER_SUM, mode))
+    _chk(acc, what + ": acc", torch.float64); _chk(out, what + ": out"); _chk(feat, what + ": feat"); _chk(base, what + ": base")
+    _chk(attr, what + ": attr"); _chk(total, what + ": total", torch.float64)
+    if acc.dim() != 4 or acc.numel() < 1 or tuple(out.shape) != tuple(acc.shape[:3]):
+        raise RuntimeError("%s: acc must be fp64 [K, h, w, C] with no empty dimension and out fp32 [K, h, w] (got %s and %s)"
+                           % (what, tuple(acc.shape), tuple(out.shape)))
+    Kc, h, w, C = (int(v) for v in acc.shape)
+    if mode == LAYER_PATH and feat is None:
+        raise RuntimeError("%s: mode LAYER_PATH needs feat" % what)
+    for name, t, shape in (("feat", feat, (h, w, C)), ("base", base, (h, w, C)), ("attr", attr, (Kc, h, w, C)), ("total", total, (Kc,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s must be %s, got shape %s" % (what, name, shape, tuple(t.shape)))
+    _native.check(_native.lib().scouter_layer_attr_finish_f32(_p(feat), _p(base), _p(acc), _p(out), _p(attr), _p(total), Kc, h * w,
+                                                              C, int(mode), _stream()), what)
+    return out
+
+
+def layer_gxa(feat, dfeat, out, rectify=False, relu=False):
+    """out[b, p] = float32(sum_c (max(dfeat[b, p, c], 0) if rectify else dfeat[b, p, c]) * feat[b, p, c]) in float64 (relu: clamped at
+    0) for NHWC fp32 feat / dfeat [B, h, w, C]: gradient times activation summed over the channels -- HiResCAM with rectify = relu
+    = False, LayerCAM with both True.  `out` as in `gradcam`: fp32 [B, h, w] or [B, h * w], dense within an image, ANY batch stride,
+    so a column `t[:, k]` of a [B, K, h, w] tensor is filled in place.  One launch, one wave per position, one fixed summation
+    order per element (two calls give the same bits)."""
+    if feat.dim() == 4 and feat.numel() < 1:
+        raise RuntimeError("layer_gxa: feat must be NHWC [B, h, w, C] with no empty dimension, got shape %s" % (tuple(feat.shape),))
+    B, N, C = _cam_pair_chk("layer_gxa", feat, dfeat, out)
+    _native.check(_native.lib().scouter_layer_gxa_f32(_p(feat), _p(dfeat), _p(out), B, N, C, out.stride(0), int(bool(rectify)),
+                                                      int(bool(relu)), _stream()), "layer_gxa")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Localisation scores of byte maps (csrc/localization.hip; tools/attribution.py localization / slot_maps)
 # ---------------------------------------------------------------------------------------------------------------
 def map_localization(maps, boxes=None, n_boxes=None):

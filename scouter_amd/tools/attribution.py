@@ -152,7 +152,26 @@ copies are rows of one reused feature buffer (kernels.ablate_channels) and go th
 runs once per batch, where `scorecam` runs it once per channel -- the drops come from kernels.output_deltas and the weighted sum
 from kernels.ablation_contract (the weight rounded from float64 once, one fma per channel in ascending order).  No backward, and
 nothing comes to the host in between.  tools/ablation.py adds both methods as rows to the single-image tool and the explanation
-table."""
+table.
+
+Layer Integrated Gradients (`layer_integrated_gradients`, `layerig_maps`): captum's LayerIntegratedGradients at the layer `gradcam`
+reads, the layer the reference's captum_vis.py attributes to.  The straight line runs IN FEATURE SPACE from the baseline image's
+features to the image's, so a step is a head forward and a head backward and nothing enters the backbone: for a head that is
+linear in the features (the FC baseline's logits) it equals the DeepLIFT the reference draws, and for the slot head it is the
+quantity DeepLIFT's Rescale rule approximates (Ancona et al. 2018).  The path rows are written by kernels.path_images into one
+reused feature buffer, one SlotModel.head_pass per chunk serves every class (one `.grad` each), kernels.grad_accumulate keeps
+float64 sums in step order and kernels.layer_attr_finish forms all maps, the attributions and the completeness sums in one launch.
+
+Layer Conductance (`layer_conductance`, `conductance_maps`): Dhamdhere et al. 2018, captum's LayerConductance.  The path runs IN
+IMAGE SPACE, n + 1 equidistant images, and the attribution is sum_i g(A(x_i)) * (A(x_{i+1}) - A(x_i)): what flows through every
+element of the backbone's output along the way.  One SlotModel.feature_pass per chunk, one `.grad` per class, and
+kernels.conductance_accumulate adds the steps in float64; consecutive chunks share a row, so no step is lost between them.  The
+sum over positions and channels telescopes to out(x) - out(x') as the steps shrink.
+
+The class maps that keep the gradient per position (`layer_gradxact`, `hirescam`, `layercam` and their `*_maps`): HiResCAM (Draelos
+& Carin 2020; captum's LayerGradientXActivation summed over the channels), sum_c g[p, c] A[p, c], and LayerCAM (Jiang et al. 2021),
+relu(sum_c relu(g[p, c]) A[p, c]), where `gradcam` pools the gradient over the positions first.  They run on `gradcam`'s loop with
+kernels.layer_gxa as its fill.  tools/layer.py adds the four methods as rows to the single-image tool and the explanation table."""
 import collections
 import contextlib
 import functools
@@ -2097,3 +2116,244 @@ def ablationcam_maps(model, images, classes=None, size=None, min_level=0.0, **kw
     drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images' H x W)."""
     H, W = _out_size(size, images)
     return K.cam_maps(ablationcam(model, images, classes, **kwargs), H, W, min_level)
+
+
+def _image_baseline(baseline, x):
+    """the `baseline` argument of the path methods, an IMAGE: None (zeros), [C, H, W] (one for the batch) or [B, C, H, W] -> None or
+    the tensor on x's device, fp32 and contiguous"""
+    B, C, H, W = x.shape
+    if baseline is None:
+        return None
+    if not torch.is_tensor(baseline) or tuple(baseline.shape) not in ((C, H, W), (B, C, H, W)):
+        raise ValueError("baseline must be None, [%d, %d, %d] or [%d, %d, %d, %d], got %s"
+                         % (C, H, W, B, C, H, W, tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__))
+    return baseline.detach().to(x.device, dtype=torch.float32).contiguous()
+
+
+def _fp32_dense(t):
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def _one_hot_rows(cols_dev, n):
+    """cols int64 [M] on the device -> fp32 [M, n], row j the one-hot seed of class cols[j]"""
+    rows = torch.zeros((cols_dev.shape[0], n), dtype=torch.float32, device=cols_dev.device)
+    return rows.scatter_(1, cols_dev[:, None], 1.0) if cols_dev.shape[0] else rows
+
+
+def _layer_results(out, attr, totals, ends, return_attr, return_delta):
+    """(maps[, attr][, delta]) of the two layer path methods; delta = the float64 completeness sums minus `ends` [B, K], the
+    float64 differences out(x)[c] - out(x')[c]"""
+    res = [out]
+    if return_attr:
+        res.append(attr)
+    if return_delta:
+        res.append((totals - ends).float())
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def layer_integrated_gradients(model, images, classes=None, baseline=None, n_steps=50, method="gausslegendre", batch=256,
+                               return_attr=False, return_delta=False):
+    """Layer Integrated Gradients (captum's LayerIntegratedGradients) of `images` [B, Cin, H, W] at the backbone's output -> fp32
+    [B, K, h, w] on the images' device.  With A = the features of images[b] (NHWC [h, w, C], the layer `gradcam` reads), A' = the
+    features of the baseline IMAGE x' and g(F) = d out[:, c_k] / dF, the gradient of the head alone at the features F:
+    attr[b, k] = (A - A') * sum_i w_i g(A' + alpha_i (A - A')),   map[b, k, p] = sum_c attr[b, k, p, c],
+    a straight line IN FEATURE SPACE, (alpha_i, w_i) = ig_quadrature(n_steps, method).  The sum of a map over its positions satisfies
+    completeness: it approaches out(x)[c_k] - out(x')[c_k] as n_steps grows.  For a head that is linear in the features (the FC
+    baseline's logits) this is DeepLIFT; for the slot head it is what DeepLIFT's Rescale rule approximates.
+
+    `baseline` is an image: None (zeros), [Cin, H, W] (one for the batch) or [B, Cin, H, W], as in `integrated_gradients`.  classes
+    as in `gradcam`: None (every class), a list of ints (K = len), or a LongTensor [B] (each image its own class, K = 1); a class
+    outside the outputs is an IndexError.  return_attr: also attr fp32 [B, K, h, w, C]; return_delta: also fp32 [B, K], the
+    completeness gap sum_p map - (out(x) - out(x')), formed in float64.  The results come in that order.
+
+    One SlotModel.feature_pass of the baseline and image rows gives A' and A (BatchNorm-folded when the model's inference fold is
+    on).  Per image the n_steps path rows go through the head in chunks of `batch` (the last may be shorter): kernels.path_images
+    into one reused feature buffer, ONE SlotModel.head_pass, and per class one `.grad` with a one-hot column and one
+    kernels.grad_accumulate onto that class's float64 sums in step order -- one head forward per chunk, not one per class.  Then
+    kernels.layer_attr_finish once for all K classes: maps, attributions and the float64 sum of each map.  The gap compares that sum
+    with the two rows of one head_pass([A', A]).  Nothing is copied to the host and nothing synchronises inside the loop; no
+    BatchNorm buffer moves and the caller's mode is restored; head parameters that require grad get their `.grad` overwritten by
+    each backward, as in `gradcam`, and nothing enters the backbone.  It needs a SlotModel (slot head or FC baseline).
+
+    What departs from captum's LayerIntegratedGradients: `out` is the eval-mode model output, the LOG-PROBABILITIES, as in every
+    method here (the reference's captum script targets logits); the float map is the channel SUM, so that completeness holds map by
+    map (the reference draws the channel mean; the factor 1 / C disappears in the min-max of the drawing); the quadrature table is
+    `ig_quadrature`'s, rounded to fp32; the difference A - A' the path walks is formed in fp32 (kernels.path_images), the one
+    that multiplies the sums in float64.  captum is no dependency and nothing was checked against it."""
+    x, batch = _check_images_batch(images, batch)
+    B = x.shape[0]
+    alphas, weights = ig_quadrature(n_steps, method)
+    baseline = _image_baseline(baseline, x)
+    n = _num_classes(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    dev = x.device
+    # (every upload comes before the first pass: a copy from the host waits for the work queued ahead of it)
+    alphas, weights = alphas.to(dev), weights.to(dev)
+    cols_dev = torch.tensor(cols, dtype=torch.int64).to(dev)
+    onehots = _one_hot_rows(cols_dev, n)
+    base_rows = torch.zeros_like(x[:1]) if baseline is None else baseline if baseline.dim() == 4 else baseline[None]
+    nb = int(base_rows.shape[0])
+    feats = _fp32_dense(model.feature_pass(torch.cat([base_rows, x])).features)
+    _, h, w, C = feats.shape
+    Kc = 1 if per_image else len(cols)
+    out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+    attr = torch.empty((B, Kc, h, w, C), dtype=torch.float32, device=dev) if return_attr else None
+    totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    ends = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    if Kc == 0 or B == 0:
+        return _layer_results(out, attr, totals, ends, return_attr, return_delta)
+    N = int(alphas.shape[0])
+    buf = torch.empty((min(batch, N), h, w, C), dtype=torch.float32, device=dev)
+    seed = torch.empty((min(batch, N), n), dtype=torch.float32, device=dev)
+    acc = torch.empty((Kc, h, w, C), dtype=torch.float64, device=dev)
+    with _eval_mode(model):
+        for b in range(B):
+            A0, A1 = feats[b if nb > 1 else 0], feats[nb + b]
+            acc.zero_()
+            for first in range(0, N, batch):
+                m = min(batch, N - first)
+                fp = model.head_pass(K.path_images(A1, A0, alphas, buf[:m], first))
+                for k in range(Kc):
+                    seed.copy_(onehots[b if per_image else k])  # (one launch: the row of the class, for every path row)
+                    K.grad_accumulate(_fp32_dense(fp.grad(seed[:m])), weights, acc[k], None, first)
+                del fp
+            K.layer_attr_finish(K.LAYER_PATH, acc, out[b], feat=A1, base=A0, attr=None if attr is None else attr[b],
+                                total=None if totals is None else totals[b])
+            if return_delta:
+                logp = model.head_pass(torch.stack([A0, A1])).log_probs.double()
+                ends[b] = (logp[1] - logp[0]).index_select(0, cols_dev[b:b + 1] if per_image else cols_dev)
+    return _layer_results(out, attr, totals, ends, return_attr, return_delta)
+
+
+def layer_conductance(model, images, classes=None, baseline=None, n_steps=50, batch=50, return_attr=False, return_delta=False):
+    """Layer Conductance (Dhamdhere et al. 2018; captum's LayerConductance) of `images` [B, Cin, H, W] at the backbone's output ->
+    fp32 [B, K, h, w] on the images' device.  The path runs IN IMAGE SPACE: x_i = x' + (i / n) (x - x') for i = 0 .. n = n_steps,
+    A(x_i) the backbone's output there (NHWC [h, w, C]) and g_i = d out[:, c_k] / dA at A(x_i):
+    attr[b, k] = sum_{i < n} g_i * (A(x_{i+1}) - A(x_i)),   map[b, k, p] = sum_c attr[b, k, p, c],
+    what flows through every element of the layer along the path.  The sum of a map over its positions approaches
+    out(x)[c_k] - out(x')[c_k] as n_steps grows (completeness).
+
+    `baseline`, `classes`, return_attr (fp32 [B, K, h, w, C]) and return_delta (fp32 [B, K]) as in `layer_integrated_gradients`.
+    The table alpha_i = i / n is built in float64, rounded to fp32 and uploaded once.  Per image the n + 1 path images go through
+    the model in chunks of the steps first .. first + m, at most `batch` rows (batch >= 2), and the next chunk starts at the row
+    the last one ended at: kernels.path_images into one reused image buffer, ONE SlotModel.feature_pass per chunk
+    (BatchNorm-folded when the model's inference fold is on), and per class one `.grad` with a one-hot column and one
+    kernels.conductance_accumulate onto that class's float64 sums -- float64 differences of neighbouring rows, one fma per step in
+    step order.  Then kernels.layer_attr_finish (mode LAYER_SUM) once for all K classes.  The gap compares the float64 sum of each
+    map with the two ends of the path, out(x_n) and out(x_0), as the feature passes of the first and the last chunk gave them.
+    The guarantees are those of `layer_integrated_gradients`: nothing is copied to the host or synchronises inside the loop, no
+    BatchNorm buffer moves, the caller's mode is restored, only head parameters get a `.grad`, nothing is differentiated inside
+    the backbone.
+
+    What departs from captum's LayerConductance: the LOG-PROBABILITIES are the output, not the logits; the float map is the channel
+    SUM, not the mean; the path has n + 1 equidistant points and n forward differences (captum differences the same rows), and
+    the differences and sums are float64.  captum is no dependency and nothing was checked against it."""
+    x, batch = _check_images_batch(images, batch)
+    batch = _rows_per_forward(batch)
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError("n_steps must be at least 1, got %d" % n_steps)
+    B = x.shape[0]
+    baseline = _image_baseline(baseline, x)
+    n = _num_classes(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    dev = x.device
+    Kc = 1 if per_image else len(cols)
+    cols_dev = torch.tensor(cols, dtype=torch.int64).to(dev)
+    onehots = _one_hot_rows(cols_dev, n)
+    alphas = torch.from_numpy((np.arange(n_steps + 1, dtype=np.float64) / n_steps).astype(np.float32)).to(dev)
+    rows = min(batch, n_steps + 1)
+    buf = torch.empty((rows,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+    seed = torch.empty((rows, n), dtype=torch.float32, device=dev)
+    out = attr = acc = None
+    totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    ends = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    with _eval_mode(model):
+        for b in range(B if Kc else 0):
+            base = None if baseline is None else baseline if baseline.dim() == 3 else baseline[b]
+            for first in range(0, n_steps, batch - 1):
+                m = min(batch - 1, n_steps - first)             # (steps of the chunk: rows first .. first + m)
+                fp = model.feature_pass(K.path_images(x[b], base, alphas, buf[:m + 1], first))
+                feats = _fp32_dense(fp.features)
+                if acc is None:                                 # (the first pass tells the layer's shape)
+                    _, h, w, C = feats.shape
+                    out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+                    attr = torch.empty((B, Kc, h, w, C), dtype=torch.float32, device=dev) if return_attr else None
+                    acc = torch.empty((Kc, h, w, C), dtype=torch.float64, device=dev)
+                if first == 0:
+                    acc.zero_()
+                    if return_delta:
+                        ends[b] = -fp.log_probs[0].double().index_select(0, cols_dev[b:b + 1] if per_image else cols_dev)
+                for k in range(Kc):
+                    seed.copy_(onehots[b if per_image else k])
+                    K.conductance_accumulate(feats, _fp32_dense(fp.grad(seed[:m + 1])), acc[k])
+                if return_delta and first + m == n_steps:
+                    ends[b] += fp.log_probs[m].double().index_select(0, cols_dev[b:b + 1] if per_image else cols_dev)
+                del fp
+            K.layer_attr_finish(K.LAYER_SUM, acc, out[b], attr=None if attr is None else attr[b],
+                                total=None if totals is None else totals[b])
+    if out is None:                                             # (no class or no image: the shape comes from one feature pass)
+        _, h, w, C = model.feature_pass(x[:1]).features.shape if B else (0, 0, 0, 0)
+        out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+        attr = torch.empty((B, Kc, h, w, C), dtype=torch.float32, device=dev) if return_attr else None
+    return _layer_results(out, attr, totals, ends, return_attr, return_delta)
+
+
+def layer_gradxact(model, images, classes=None, rectify=False, relu=False):
+    """Gradient times activation at the backbone's output, summed over the channels, of `images` [B, Cin, H, W] -> fp32 [B, K, h, w]
+    on the images' device.  With A = features[b] (NHWC, the layer `gradcam` reads) and g = d out_k / dA:
+    map[b, k, p] = sum_c r(g[p, c]) A[p, c],  r = max(., 0) when `rectify` and the identity otherwise, clamped at 0 when `relu`;
+    the products and the sum in float64, rounded to fp32 once (kernels.layer_gxa, which fills cam[:, k] in place).  Where
+    `gradcam` pools the gradient over the positions before it weights the channels, this keeps the gradient per position.
+    rectify = relu = False is HiResCAM (`hirescam`), rectify = relu = True LayerCAM (`layercam`).
+
+    classes, the feature pass, the head backwards and their side effects as in `gradcam`: None, a list of ints or a LongTensor
+    [B]; one SlotModel.feature_pass, one head backward per class, one feature gradient alive at a time.  out_k is the
+    LOG-PROBABILITY of class k, the model's output, not the raw score the papers and captum's scripts differentiate, and the map
+    is the channel SUM."""
+    return _gradient_cam(model, images, classes,
+                         lambda feat, dfeat, out: K.layer_gxa(feat, dfeat, out, rectify=rectify, relu=relu))
+
+
+def hirescam(model, images, classes=None):
+    """HiResCAM (Draelos & Carin 2020; captum's LayerGradientXActivation at the backbone's output, summed over the channels) ->
+    fp32 [B, K, h, w]: map[b, k, p] = sum_c g[p, c] A[p, c], signed.  `layer_gradxact` with rectify = relu = False, which see for
+    what departs from captum (log-probabilities, the channel sum)."""
+    return layer_gradxact(model, images, classes, rectify=False, relu=False)
+
+
+def layercam(model, images, classes=None):
+    """LayerCAM (Jiang et al. 2021) at the backbone's output -> fp32 [B, K, h, w]:
+    map[b, k, p] = max(0, sum_c max(g[p, c], 0) A[p, c]), never negative.  `layer_gradxact` with rectify = relu = True, which see
+    for what departs from the paper (log-probabilities)."""
+    return layer_gradxact(model, images, classes, rectify=True, relu=True)
+
+
+def layerig_maps(model, images, classes=None, size=None, min_level=0.0, **kwargs):
+    """uint8 Layer Integrated Gradients heat maps [B, K, H, W] on the device: `layer_integrated_gradients` (its other keyword
+    arguments pass through), then the drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None:
+    the images' H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(layer_integrated_gradients(model, images, classes, **kwargs), H, W, min_level)
+
+
+def conductance_maps(model, images, classes=None, size=None, min_level=0.0, **kwargs):
+    """uint8 Layer Conductance heat maps [B, K, H, W] on the device: `layer_conductance` (its other keyword arguments pass
+    through), then the drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images'
+    H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(layer_conductance(model, images, classes, **kwargs), H, W, min_level)
+
+
+def hirescam_maps(model, images, classes=None, size=None, min_level=0.0):
+    """uint8 HiResCAM heat maps [B, K, H, W] on the device: `hirescam`, then the drawing steps of `gradcam_maps` (kernels.cam_maps),
+    which cut the negative evidence to 0."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(hirescam(model, images, classes), H, W, min_level)
+
+
+def layercam_maps(model, images, classes=None, size=None, min_level=0.0):
+    """uint8 LayerCAM heat maps [B, K, H, W] on the device: `layercam`, then the drawing steps of `gradcam_maps` (kernels.cam_maps)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(layercam(model, images, classes), H, W, min_level)
