@@ -862,6 +862,42 @@ int scouter_layer_attr_finish_f32(const float* feat, const float* base, const do
 int scouter_layer_gxa_f32(const float* feat, const float* dfeat, float* out, int B, int P, int C, long out_stride, int rectify,
                           int relu, void* stream);
 
+/* ---- GradientSHAP / expected gradients (Lundberg & Lee 2017; Erion et al. 2019; captum's GradientShap and LayerGradientShap of
+ * the reference's captum_vis.py) (csrc/gradshap.hip, tools/attribution.py gradient_shap / layer_gradient_shap): a path method
+ * whose every row walks from its own randomly drawn baseline of a BANK by its own random fraction.  No reference program runs it
+ * with this stream; this comment is the specification.  E is the flat element count of one image (or of one image's features),
+ * e the flat index, image fp32 [E], bank fp32 [R][E], every tensor dense.
+ *
+ * THE DRAWS of sample s: (r0, r1, ., .) = Philox4x32-10 (as in scouter_noise_images_f32) of the counter (0, s, 2, 0) under the
+ * key (seed_lo, seed_hi); pick_s = ((uint64) r0 * R) >> 32 in [0, R), alpha_s = (float)(2 * (r1 >> 9) + 1) * 2^-24, exact and
+ * inside (0, 1).  They depend on (seed, s, R) alone.  The third counter word names the stream: 0 is the normal stream of
+ * scouter_noise_images_f32, 1 the uniform stream of scouter_uniform_images_f32, 2 this one; nothing else uses 2.
+ * THE NOISY IMAGE: sigma == 0: x~_s = image exactly (no Philox call; a -0.0 stays -0.0); sigma > 0: x~_s[e] is the value
+ * scouter_noise_images_f32 writes for (seed, sample s, element e): fmaf(sigma, z(seed, s, e), image[e]), counter (e / 4, s, 0, 0).
+ * THE ROW: d_s[e] = x~_s[e] - bank[pick_s][e], one fp32 subtraction; row_s[e] = fmaf(alpha_s, d_s[e], bank[pick_s][e]), the
+ * expression of scouter_path_images_f32.
+ *
+ * One thread owns four consecutive elements (one Philox call serves them), one fixed order per output element, no atomics:
+ * bit-identical run to run.  Each call has a 16-byte form (E a multiple of 4 and every pointer 16-byte aligned) and a one-element
+ * form that give the same bits.  R < 1, n < 0, first < 0, first + n above 2^31 - 1, E < 0, a sigma that is negative or not finite,
+ * an inv_n that is not finite, a null pointer where one is required or a misaligned one (fp32 / int32: 4 bytes, fp64: 8) is
+ * SC_ERR_ARG; n * E or R * E of 2^31 or more is SC_ERR_UNSUPPORTED; each with a message that names the call, and nothing is
+ * launched after an error.  n == 0 or E == 0 is SC_OK without a launch, after the scalar arguments have been checked all the same
+ * (an empty tensor's pointer may be null).
+ *
+ * picks int32 [n], alphas fp32 [n]: the draws of the samples first .. first + n - 1.  Either may be null (both: no launch). */
+int scouter_gradshap_draws(int* picks, float* alphas, int seed_lo, int seed_hi, int first, int n, int R, void* stream);
+/* out fp32 [n][E], out[j] = row_{first + j}.  A row's value depends on (seed, first + j, e) alone, so chunks written by separate
+ * calls equal one call.  A dense leading slice of a longer out is fine.  At most 65535 * 8 rows per call (SC_ERR_UNSUPPORTED). */
+int scouter_gradshap_images_f32(const float* image, const float* bank, float* out, float sigma, int seed_lo, int seed_hi, int first,
+                                int n, int R, long E, void* stream);
+/* grads fp32 [n][E] (the gradients at the rows first .. first + n - 1), acc fp64 [E]: for j ascending t = (double)grads[j][e] *
+ * (double)d_{first + j}[e], exact in fp64, then acc[e] = fma(t, inv_n, acc[e]), onto what acc holds.  d is formed again from the
+ * draws, the noise included, as scouter_perturb_dots_f64 forms its noise again; it is never stored.  The accumulator stays in
+ * registers over the j loop: calls over consecutive pieces give the bits of one call. */
+int scouter_gradshap_accumulate_f64(const float* grads, const float* image, const float* bank, double* acc, float sigma,
+                                    double inv_n, int seed_lo, int seed_hi, int first, int n, int R, long E, void* stream);
+
 /* ---- BatchNorm2d (+ReLU, +residual add): timm/models/resnet.py:383 (norm_layer), BasicBlock :172-199,
  * ResNestBottleneck resnest.py:111-143.  Training mode: batch statistics (fp64 accumulation), running stats
  * updated with `momentum` and the unbiased variance; eval mode: running stats.

@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip, occlusion.hip, ablation.hip, layerattr.hip), each defined ONCE: where two kernels promise the same bits --
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip, occlusion.hip, ablation.hip, layerattr.hip, gradshap.hip), each defined ONCE: where two kernels promise the same bits --
 // heat_maps and cam_maps at the map's own size, resize_bilinear and the resize inside cam_maps and scorecam_ranges -- they call
 // the same inlined function here on the same operands.  (The mask and the fma chain of the Score-CAM family have one file,
 // scorecam.hip, and are defined there.)  Inlined functions and templates only: no kernel, no entry point, no state.
@@ -90,7 +90,9 @@ struct AtHeatScale {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The random streams of pathgrad.hip (noise_images) and fidelity.hip (perturb_dots, uniform_images), one copy for both.
+// The random streams of pathgrad.hip (noise_images), fidelity.hip (perturb_dots, uniform_images) and gradshap.hip, one copy for
+// all.  The third counter word names the stream: 0 the normal stream, 1 the uniform stream of fidelity.hip, 2 the draws of
+// gradshap.hip (gs_draw).
 // Philox4x32-10 (Salmon et al., SC 2011): ten rounds, the key bumped between them
 __device__ __forceinline__ void pg_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                           unsigned (&r)[4]) {
@@ -143,6 +145,11 @@ __device__ __forceinline__ void at_load(const double* __restrict__ p, double (&v
             v[k] = t[0]; v[k + 1] = t[1];
         }
     }
+}
+template <int V>
+__device__ __forceinline__ void at_store(float* __restrict__ p, const float (&v)[V]) {
+    if constexpr (V == 4) *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
+    else *p = v[0];
 }
 template <int V>
 __device__ __forceinline__ void at_store(double* __restrict__ p, const double (&v)[V]) {

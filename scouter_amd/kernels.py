@@ -2613,6 +2613,79 @@ def channel_mean(x, absolute=False, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# GradientSHAP / expected gradients (csrc/gradshap.hip; tools/attribution.py gradient_shap / layer_gradient_shap)
+# ---------------------------------------------------------------------------------------------------------------
+def _bank_of(what, image, bank):
+    """bank must be [R, *image.shape] with R >= 1 -> R"""
+    if bank.dim() != image.dim() + 1 or tuple(bank.shape[1:]) != tuple(image.shape) or bank.shape[0] < 1:
+        raise RuntimeError("%s: bank must be [R, %s] with R >= 1, got shape %s"
+                           % (what, ", ".join(str(v) for v in image.shape), tuple(bank.shape)))
+    return int(bank.shape[0])
+
+
+def gradshap_draws(n, R, seed, first=0, picks=None, alphas=None):
+    """The draws of GradientSHAP's samples first .. first + n - 1 against a bank of R baselines -> (picks int32 [n], alphas fp32
+    [n]) on the current device (given tensors are filled): (r0, r1, ., .) = Philox4x32-10 of the counter (0, s, 2, 0) keyed by the
+    64-bit `seed`, picks[j] = (r0 * R) >> 32, alphas[j] = (2 (r1 >> 9) + 1) 2^-24, inside (0, 1).  They depend on (seed, s, R)
+    alone.  One launch; nothing is read on the host."""
+    n, R = int(n), int(R)
+    if n < 0:
+        raise RuntimeError("gradshap_draws: n = %d must not be negative" % n)
+    given = picks if picks is not None else alphas
+    dev = given.device if given is not None else torch.device("cuda", torch.cuda.current_device())
+    if picks is None:
+        picks = torch.empty((n,), dtype=torch.int32, device=dev)
+    if alphas is None:
+        alphas = torch.empty((n,), dtype=F32, device=dev)
+    _chk(picks, "gradshap_draws: picks", torch.int32); _chk(alphas, "gradshap_draws: alphas")
+    if tuple(picks.shape) != (n,) or tuple(alphas.shape) != (n,):
+        raise RuntimeError("gradshap_draws: picks and alphas must be [n = %d], got shapes %s and %s"
+                           % (n, tuple(picks.shape), tuple(alphas.shape)))
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_gradshap_draws(_p(picks) if n else None, _p(alphas) if n else None, lo, hi, int(first), n,
+                                                       R, _stream()), "gradshap_draws")
+    return picks, alphas
+
+
+def gradshap_images(image, bank, out, sigma, seed, first):
+    """out[j] = b + alpha_s * (x~_s - b) for the samples s = first + j of GradientSHAP: fp32 image [...], fp32 bank [R, *image.shape]
+    and fp32 out [n, *image.shape] (a dense leading slice of a longer buffer is fine).  b = bank[pick_s] and alpha_s are the draws
+    of `gradshap_draws` for (seed, s, R); x~_s = image when sigma == 0 (exactly: no noise is drawn), else the row `noise_images`
+    writes for (image, sigma, seed, s).  One fp32 subtraction and one fma, the expressions of `path_images`.  A row's value depends
+    on (seed, s, element) alone, so chunks written by separate calls equal one call.  sigma >= 0.  One launch."""
+    _chk(image, "gradshap_images: image"); _chk(bank, "gradshap_images: bank"); _chk(out, "gradshap_images: out")
+    n, E = _batch_of("gradshap_images", image, out)
+    R = _bank_of("gradshap_images", image, bank)
+    lo, hi = _seed_words(seed)
+    # (an empty chunk goes through too: the library checks sigma and first for it and launches nothing)
+    _native.check(_native.lib().scouter_gradshap_images_f32(_p(image), _p(bank), _p(out), float(sigma), lo, hi, int(first), n, R, E,
+                                                            _stream()), "gradshap_images")
+    return out
+
+
+def gradshap_accumulate(grads, image, bank, acc, sigma, seed, first, inv_n=1.0):
+    """acc += inv_n * sum_j grads[j] * d_s for the samples s = first + j of GradientSHAP: fp32 grads [n, *image.shape] (the
+    gradients at the rows of `gradshap_images`), fp32 image, fp32 bank [R, *image.shape] and fp64 acc of the image's shape.
+    d_s = x~_s - bank[pick_s], the fp32 difference `gradshap_images` walks, is formed again from (seed, s) -- the noise included --
+    and never stored.  float64: the product is exact, one fma per sample in ascending j onto the values in acc, so calls over
+    consecutive pieces give the bits of one call.  One launch."""
+    _chk(grads, "gradshap_accumulate: grads"); _chk(image, "gradshap_accumulate: image"); _chk(bank, "gradshap_accumulate: bank")
+    _chk(acc, "gradshap_accumulate: acc", torch.float64)
+    if grads.dim() != image.dim() + 1 or tuple(grads.shape[1:]) != tuple(image.shape):
+        raise RuntimeError("gradshap_accumulate: grads must be [n, *image.shape] (got %s for an image of %s)"
+                           % (tuple(grads.shape), tuple(image.shape)))
+    n, E = int(grads.shape[0]), int(image.numel())
+    R = _bank_of("gradshap_accumulate", image, bank)
+    if tuple(acc.shape) != tuple(image.shape):
+        raise RuntimeError("gradshap_accumulate: acc must be fp64 of the image's shape %s, got %s"
+                           % (tuple(image.shape), tuple(acc.shape)))
+    lo, hi = _seed_words(seed)
+    _native.check(_native.lib().scouter_gradshap_accumulate_f64(_p(grads), _p(image), _p(bank), _p(acc), float(sigma), float(inv_n),
+                                                                lo, hi, int(first), n, R, E, _stream()), "gradshap_accumulate")
+    return acc
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # infidelity and max-sensitivity (csrc/fidelity.hip; tools/attribution.py infidelity / sensitivity_max)
 # ---------------------------------------------------------------------------------------------------------------
 DELTA_LOG_PROB, DELTA_PROB = 0, 1                               # (include/scouter_hip.h SCOUTER_DELTA_*)

@@ -171,7 +171,17 @@ sum over positions and channels telescopes to out(x) - out(x') as the steps shri
 The class maps that keep the gradient per position (`layer_gradxact`, `hirescam`, `layercam` and their `*_maps`): HiResCAM (Draelos
 & Carin 2020; captum's LayerGradientXActivation summed over the channels), sum_c g[p, c] A[p, c], and LayerCAM (Jiang et al. 2021),
 relu(sum_c relu(g[p, c]) A[p, c]), where `gradcam` pools the gradient over the positions first.  They run on `gradcam`'s loop with
-kernels.layer_gxa as its fill.  tools/layer.py adds the four methods as rows to the single-image tool and the explanation table."""
+kernels.layer_gxa as its fill.  tools/layer.py adds the four methods as rows to the single-image tool and the explanation table.
+
+GradientSHAP (`gradient_shap`, drawn by `gradient_maps`; `layer_gradient_shap`, `layergradshap_maps`): expected gradients (Lundberg
+& Lee 2017; Erion et al. 2019), captum's GradientShap and LayerGradientShap, the first name the reference's captum_vis.py imports.
+The one gradient method here that explains against a DISTRIBUTION of baselines: every sample walks from its own randomly drawn
+baseline of a bank by its own random fraction, optionally from a noisy copy of the image, and the attribution is the mean of
+gradient times that sample's own difference.  The draws are a Philox stream of their own (kernels.gradshap_draws), the rows are
+written by kernels.gradshap_images into the reused buffer of `integrated_gradients` (or, for the layer variant, the feature buffer
+of `layer_integrated_gradients`, with one SlotModel.head_pass per chunk), and kernels.gradshap_accumulate forms every sample's
+difference again from the draws and adds gradient times difference in float64 in sample order: the differences are never
+stored.  tools/gradshap.py adds both methods as rows to the single-image tool and the explanation table."""
 import collections
 import contextlib
 import functools
@@ -1131,10 +1141,11 @@ def _chunk_gradient(model, chunk, seed):
     return g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()
 
 
-def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, want_sq, finish, totals=None):
-    """the loop shared by integrated_gradients and smoothgrad: image, then class, then chunk.  (per_image, cols) come from
-    _class_columns for a model of n outputs; fill(b, buf, first) writes the images first .. first + len(buf) - 1 of image b's
-    batch of N into buf; finish(b, acc, acc_sq, out, total) forms out[b, k]."""
+def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, want_sq, finish, totals=None, accumulate=None):
+    """the loop shared by integrated_gradients, smoothgrad and gradient_shap: image, then class, then chunk.  (per_image, cols)
+    come from _class_columns for a model of n outputs; fill(b, buf, first) writes the images first .. first + len(buf) - 1 of
+    image b's batch of N into buf; finish(b, acc, acc_sq, out, total) forms out[b, k].  accumulate(b, grads, acc, first), when
+    given, adds a chunk's gradients in place of kernels.grad_accumulate with `weights`."""
     B, C, H, W = images.shape
     dev = images.device
     Kc = 1 if per_image else len(cols)
@@ -1155,7 +1166,11 @@ def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, wan
                 seed[:, c] = 1.0
                 for first in range(0, N, batch):
                     chunk = fill(b, buf[:min(batch, N - first)], first)
-                    K.grad_accumulate(_chunk_gradient(model, chunk, seed), weights, acc, acc_sq, first)
+                    grads = _chunk_gradient(model, chunk, seed)
+                    if accumulate is None:
+                        K.grad_accumulate(grads, weights, acc, acc_sq, first)
+                    else:
+                        accumulate(b, grads, acc, first)
                 finish(b, acc, acc_sq, out[b, k], None if totals is None else totals[b, k:k + 1])
     return out
 
@@ -2357,3 +2372,189 @@ def layercam_maps(model, images, classes=None, size=None, min_level=0.0):
     """uint8 LayerCAM heat maps [B, K, H, W] on the device: `layercam`, then the drawing steps of `gradcam_maps` (kernels.cam_maps)."""
     H, W = _out_size(size, images)
     return K.cam_maps(layercam(model, images, classes), H, W, min_level)
+
+
+def _check_gradshap(n_samples, bank_sigma, sigma=0.0):
+    n_samples, bank_sigma, sigma = int(n_samples), float(bank_sigma), float(sigma)
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+    for name, v in (("sigma", sigma), ("bank_sigma", bank_sigma)):
+        if not 0.0 <= v < float("inf"):
+            raise ValueError("%s must be finite and not negative, got %r" % (name, v))
+    return n_samples, bank_sigma, sigma
+
+
+def _gradshap_bank(baselines, bank_sigma, n_samples, seed, x):
+    """the `baselines` argument of the GradientSHAP methods -> the bank of baseline IMAGES, fp32 [R, C, H, W] on x's device: a
+    tensor of that shape, or an int R >= 1 for the Gaussian bank, rows n_samples .. n_samples + R - 1 of
+    kernels.noise_images(zeros, bank_sigma, seed) -- samples the noise of the image never reads"""
+    C, H, W = x.shape[1:]
+    if torch.is_tensor(baselines):
+        if baselines.dim() != 4 or tuple(baselines.shape[1:]) != (C, H, W) or baselines.shape[0] < 1:
+            raise ValueError("a tensor of baselines must be [R >= 1, %d, %d, %d], got %s" % (C, H, W, tuple(baselines.shape)))
+        return baselines.detach().to(x.device, dtype=torch.float32).contiguous()
+    if isinstance(baselines, bool) or not isinstance(baselines, (int, np.integer)):
+        raise ValueError("baselines must be a tensor [R, %d, %d, %d] or an int R >= 1, got %s" % (C, H, W, type(baselines).__name__))
+    if baselines < 1:
+        raise ValueError("baselines must be at least 1, got %d" % baselines)
+    bank = torch.empty((int(baselines), C, H, W), dtype=torch.float32, device=x.device)
+    if bank.numel():
+        K.noise_images(torch.zeros((C, H, W), dtype=torch.float32, device=x.device), bank, bank_sigma, seed, n_samples)
+    return bank
+
+
+def _gradshap_shares(n_samples, R, seed, dev):
+    """n_r / n_samples, float64 [R] on the device: the share of the samples that drew baseline r (kernels.gradshap_draws; the
+    counts are added on the device, nothing is read on the host)"""
+    picks, _ = K.gradshap_draws(n_samples, R, seed, picks=torch.empty((n_samples,), dtype=torch.int32, device=dev))
+    counts = torch.zeros((R,), dtype=torch.float64, device=dev)
+    counts.index_add_(0, picks.long(), torch.ones((n_samples,), dtype=torch.float64, device=dev))
+    return counts / n_samples
+
+
+def gradient_shap(model, images, classes=None, baselines=10, bank_sigma=1.0, n_samples=50, sigma=0.0, batch=50, seed=0,
+                  return_delta=False):
+    """GradientSHAP / expected gradients (Lundberg & Lee 2017; Erion et al. 2019; captum's GradientShap: NoiseTunnel over
+    InputBaselineXGradient with multiply_by_inputs) of `images` [B, C, H, W] -> fp32 [B, K, C, H, W] on the images' device.  With
+    a bank of R baselines b_r, per sample s < n_samples a baseline pick_s and a fraction alpha_s in (0, 1) drawn from `seed`:
+    x~_s = x_b + sigma * z_s (sigma == 0: x_b itself), d_s = x~_s - b_pick_s, row_s = b_pick_s + alpha_s * d_s,
+    attr[b, k] = (1 / n_samples) sum_s (d out[:, c_k] / d row at row_s) * d_s,
+    out the eval-mode model output as in input_gradients(of="log_prob").  classes as in `gradcam` / `rise`: None (every output),
+    a list of ints (K = len), or a LongTensor [B] (each image its own class, K = 1).
+
+    `baselines` is the bank: a tensor [R, C, H, W], or an int R >= 1 for a Gaussian bank built on the device, rows n_samples ..
+    n_samples + R - 1 of kernels.noise_images(zeros, bank_sigma, seed) (the noise of the image reads the samples below
+    n_samples only).  In normalised image space that is the per-pixel Gaussian with the dataset's own mean and deviation;
+    bank_sigma = 0 with R = 1 is the black image.  Anything else is a ValueError.
+
+    The loop is that of `integrated_gradients`: per image and class the samples go through the model in chunks of `batch`
+    (the last may be shorter) -- kernels.gradshap_images into one reused buffer, an eval-mode forward and one backward with a
+    one-hot column, kernels.gradshap_accumulate (which forms d_s again from the draws; it is never stored) onto float64 sums in
+    sample order, kernels.attr_finish at the end of the class -- with the same guarantees: the chunking does not change a bit, no
+    BatchNorm buffer moves, the caller's mode is restored, nothing is copied to the host or synchronises inside the loop, `.grad`
+    of parameters that require grad is overwritten, and any module whose eval forward returns [n, n_outputs] will do.  The same
+    seed repeats bit for bit.
+
+    return_delta=True: also `delta` fp32 [B, K] = sum(attr[b, k]) - (out(x_b)[c_k] - sum_r (n_r / n_samples) out(b_r)[c_k]),
+    n_r the number of samples that drew r, formed in float64 from the sum of attr_finish; it costs one extra no_grad forward of
+    the bank and the images.  The gap is a MONTE-CARLO quantity: one random point per sample stands for the integral along that
+    sample's line, so it shrinks like 1 / sqrt(n_samples), not like a quadrature error; with sigma > 0 it also holds the noise,
+    since the lines end at x~_s and the comparison is made at x_b.
+
+    What departs from captum's GradientShap: the random stream is ours (Philox, kernels.gradshap_draws; captum draws from
+    torch's generator); `out` is the LOG-PROBABILITIES, as in every method here; ONE draw sequence serves all images and
+    classes (sample s of every image and class has the same pick, fraction and noise); sigma is absolute, not relative to the
+    image's range.  captum is no dependency and nothing was checked against it."""
+    x, batch = _check_images_batch(images, batch)
+    n_samples, bank_sigma, sigma = _check_gradshap(n_samples, bank_sigma, sigma)
+    bank = _gradshap_bank(baselines, bank_sigma, n_samples, seed, x)
+    B = x.shape[0]
+    dev = x.device
+    inv_n = 1.0 / n_samples
+
+    def fill(b, buf, first):
+        return K.gradshap_images(x[b], bank, buf, sigma, seed, first)
+
+    def accumulate(b, grads, acc, first):
+        K.gradshap_accumulate(grads, x[b], bank, acc, sigma, seed, first, inv_n)
+
+    def finish(b, acc, acc_sq, out, total):
+        K.attr_finish(K.ATTR_MEAN, acc, inv_n=1.0, out=out, total=total)
+
+    n = _num_outputs(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    Kc = 1 if per_image else len(cols)
+    totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    attr = _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, False, finish, totals, accumulate)
+    if not return_delta:
+        return attr
+    delta = torch.zeros((B, Kc), dtype=torch.float32, device=dev)
+    if Kc and B:
+        R = int(bank.shape[0])
+        cols_dev = torch.tensor(cols, dtype=torch.int64).to(dev)
+        shares = _gradshap_shares(n_samples, R, seed, dev)
+        with _eval_mode(model), torch.no_grad():
+            logp = model(torch.cat([bank, x])).double()
+        expected = shares @ logp[:R]                            # [n_outputs]: the bank's expected output under the draws
+        gaps = logp[R:] - expected[None]
+        ends = gaps.gather(1, cols_dev[:, None]) if per_image else gaps.index_select(1, cols_dev)
+        delta = (totals - ends).float()
+    return attr, delta
+
+
+def layer_gradient_shap(model, images, classes=None, baselines=10, bank_sigma=1.0, n_samples=200, batch=256, seed=0,
+                        return_attr=False, return_delta=False):
+    """Layer GradientSHAP (captum's LayerGradientShap) of `images` [B, Cin, H, W] at the backbone's output, the layer `gradcam`
+    reads -> fp32 [B, K, h, w] on the images' device.  With A = the features of images[b] (NHWC [h, w, C]), A_r the features of the
+    bank's baseline IMAGE b_r, g(F) = d out[:, c_k] / dF the gradient of the head alone, and per sample s < n_samples a pick_s and
+    a fraction alpha_s drawn from `seed` as in `gradient_shap`:
+    d_s = A - A_pick_s,  attr[b, k] = (1 / n_samples) sum_s g(A_pick_s + alpha_s d_s) * d_s,  map[b, k, p] = sum_c attr[b, k, p, c],
+    lines IN FEATURE SPACE.  There is NO noise option: noise on the image would move the end of every line through the backbone,
+    one feature pass per sample, and the method would no longer live in the head.
+
+    `baselines` and `bank_sigma` as in `gradient_shap` (a tensor [R, Cin, H, W] of baseline images, or an int R for the Gaussian
+    bank); classes as in `gradcam`: None, a list of ints (K = len) or a LongTensor [B] (K = 1).  return_attr: also attr fp32
+    [B, K, h, w, C]; return_delta: also fp32 [B, K], sum_p map - (out(A)[c] - sum_r (n_r / n_samples) out(A_r)[c]) in float64, a
+    Monte-Carlo gap as in `gradient_shap`.  The results come in that order.
+
+    The loop is that of `layer_integrated_gradients` with the new kernels: ONE SlotModel.feature_pass of the bank and the images
+    gives A_r and A; per image the samples go through the head in chunks of `batch` -- kernels.gradshap_images (sigma = 0) into one
+    reused feature buffer, ONE SlotModel.head_pass per chunk, per class one `.grad` with a one-hot column and one
+    kernels.gradshap_accumulate onto that class's float64 sums in sample order -- then kernels.layer_attr_finish (mode LAYER_SUM)
+    once per image for all K classes.  The gap comes from one head_pass of [A_0 .. A_{R-1}, A].  Nothing enters the backbone after
+    the feature pass; nothing is copied to the host or synchronises inside the loop; no BatchNorm buffer moves and the caller's
+    mode is restored; only head parameters get a `.grad`.  It needs a SlotModel (slot head or FC baseline).
+
+    What departs from captum's LayerGradientShap: our random stream, the LOG-PROBABILITIES as output, one draw sequence for all
+    images and classes, the channel SUM as the float map (as in `layer_integrated_gradients`), and no stdevs."""
+    x, batch = _check_images_batch(images, batch)
+    n_samples, bank_sigma, _ = _check_gradshap(n_samples, bank_sigma)
+    bank = _gradshap_bank(baselines, bank_sigma, n_samples, seed, x)
+    B, R = x.shape[0], int(bank.shape[0])
+    n = _num_classes(model, x)
+    per_image, cols = _class_columns(classes, B, n)
+    dev = x.device
+    inv_n = 1.0 / n_samples
+    # (every upload comes before the first pass: a copy from the host waits for the work queued ahead of it)
+    cols_dev = torch.tensor(cols, dtype=torch.int64).to(dev)
+    onehots = _one_hot_rows(cols_dev, n)
+    feats = _fp32_dense(model.feature_pass(torch.cat([bank, x])).features)
+    _, h, w, C = feats.shape
+    bank_feats = feats[:R]
+    Kc = 1 if per_image else len(cols)
+    out = torch.empty((B, Kc, h, w), dtype=torch.float32, device=dev)
+    attr = torch.empty((B, Kc, h, w, C), dtype=torch.float32, device=dev) if return_attr else None
+    totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    ends = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
+    if Kc == 0 or B == 0:
+        return _layer_results(out, attr, totals, ends, return_attr, return_delta)
+    shares = _gradshap_shares(n_samples, R, seed, dev) if return_delta else None
+    rows = min(batch, n_samples)
+    buf = torch.empty((rows, h, w, C), dtype=torch.float32, device=dev)
+    onehot = torch.empty((rows, n), dtype=torch.float32, device=dev)
+    acc = torch.empty((Kc, h, w, C), dtype=torch.float64, device=dev)
+    with _eval_mode(model):
+        for b in range(B):
+            A = feats[R + b]
+            acc.zero_()
+            for first in range(0, n_samples, batch):
+                m = min(batch, n_samples - first)
+                fp = model.head_pass(K.gradshap_images(A, bank_feats, buf[:m], 0.0, seed, first))
+                for k in range(Kc):
+                    onehot.copy_(onehots[b if per_image else k])  # (one launch: the row of the class, for every sample)
+                    K.gradshap_accumulate(_fp32_dense(fp.grad(onehot[:m])), A, bank_feats, acc[k], 0.0, seed, first, inv_n)
+                del fp
+            K.layer_attr_finish(K.LAYER_SUM, acc, out[b], attr=None if attr is None else attr[b],
+                                total=None if totals is None else totals[b])
+            if return_delta:
+                logp = model.head_pass(torch.cat([bank_feats, A[None]])).log_probs.double()
+                ends[b] = (logp[R] - shares @ logp[:R]).index_select(0, cols_dev[b:b + 1] if per_image else cols_dev)
+    return _layer_results(out, attr, totals, ends, return_attr, return_delta)
+
+
+def layergradshap_maps(model, images, classes=None, size=None, min_level=0.0, **kwargs):
+    """uint8 Layer GradientSHAP heat maps [B, K, H, W] on the device: `layer_gradient_shap` (its other keyword arguments pass
+    through), then the drawing steps of `gradcam_maps` in one launch (kernels.cam_maps) at `size` = (H, W) (None: the images'
+    H x W)."""
+    H, W = _out_size(size, images)
+    return K.cam_maps(layer_gradient_shap(model, images, classes, **kwargs), H, W, min_level)
