@@ -1166,6 +1166,26 @@ int scouter_bn_fold_multi(const void* table, int nrows, long total, void* stream
 int scouter_sa_gate_fwd_f32(const float* gap, const float* w1, const float* b1, const float* w2, const float* b2, float* a,
                             int B, int Cp, int A, void* stream);
 
+/* ---- Backward of the folded path: what a gradient with respect to the IMAGE needs next to the convolution input gradients
+ * (SlotModel.image_pass).  Deterministic, no atomics; bad arguments are refused before any launch.
+ * scouter_sa_gate_bwd_f32: the backward of scouter_sa_gate_fwd_f32 in one launch, one workgroup per image.  With a [B][2Cp] the
+ * forward's output and da [B][2Cp] its gradient: dz = radix softmax backward (the expression of scouter_radix_softmax_bwd_f32),
+ * h = relu(gap . w1 + b1) re-formed by the forward's own device function (the same bits), dh = (dz . w2^T) * [h > 0],
+ * dgap [B][Cp] = dh . w1^T.  h_out [B][A] (may be NULL) receives h.  fc2's bias is not needed.  One summation order per output
+ * element, a function of (Cp, A) alone: a row does not depend on B.  w1 and w2 are read as 16-byte vectors (16-byte aligned).
+ * Covers the shapes of scouter_sa_gate_fwd_f32; anything else is SC_ERR_UNSUPPORTED. */
+int scouter_sa_gate_bwd_f32(const float* gap, const float* w1, const float* b1, const float* w2, const float* a,
+                            const float* da, float* dgap, float* h_out, int B, int Cp, int A, void* stream);
+/* dx[b][p][r Cp + c] = x0[b][p][r Cp + c] > 0 ? dout[b][p][c] * a[b][r Cp + c] + dgap[b][c] * (1 / HW) : +0, r = 0, 1:
+ * scouter_sa_apply_bwd_f32 and the ReLU backward of the folded radix convolution (whose output x0 [B][HW][2Cp] is stored after its
+ * ReLU) in one pass.  Cp a multiple of 4. */
+int scouter_sa_apply_relu_bwd_f32(const float* dout, const float* a, const float* dgap, const float* x0, float* dx, int B,
+                                  int HW, int Cp, void* stream);
+/* scouter_maxpool_bwd_f32 followed by scouter_relu_bwd_f32 with y = h [B][H][W][C], the pool's input, in one pass -- the same
+ * windows added in the same order, so the same bits. */
+int scouter_maxpool_relu_bwd_f32(const float* dy, const unsigned char* argmax, const float* h, float* dx, int B, int H, int W,
+                                 int C, int k, int stride, int pad, void* stream);
+
 /* p[i] += v for n 64-bit counters (the num_batches_tracked buffers of a model as views of one flat buffer: one launch per
  * training forward instead of one ATen launch; torch.nn.BatchNorm2d increments them one by one) */
 int scouter_iadd_i64(long* p, long n, long v, void* stream);

@@ -3,6 +3,7 @@
 //   scouter_sa_gate_fwd_f32   the split-attention gate fc1' -> ReLU -> fc2 -> radix softmax of one image per workgroup
 // Plain C++, vector stores only.
 #include "common.h"
+#include "sa_gate.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // fold: s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ conv_bias * s); products in fp64, rounded once
@@ -62,19 +63,6 @@ extern "C" int scouter_bn_fold_multi(const void* table, int nrows, long total, v
 // ---------------------------------------------------------------------------------------------------------------
 // split-attention gate (timm/models/layers/split_attn.py:68-75 with bn1 folded into fc1)
 // ---------------------------------------------------------------------------------------------------------------
-#define GATE_MAX_CP 512
-#define GATE_THREADS 256
-
-// sum_k x[k] * w[k * ld] over k0 <= k < k1, k1 - k0 a multiple of 8: eight interleaved fmaf chains combined as a fixed tree
-__device__ __forceinline__ float gate_dot(const float* __restrict__ x, const float* __restrict__ w, int ld, int k0, int k1) {
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = k0; k < k1; k += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] = __builtin_fmaf(x[k + u], w[(long)(k + u) * ld], acc[u]);
-    }
-    return ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-}
-
 // one workgroup per image: the result of an image depends on its own row of `gap` only, in one fixed summation order
 __global__ __launch_bounds__(GATE_THREADS) void sa_gate_fwd_kernel(const float* __restrict__ gap, const float* __restrict__ w1,
                                                                    const float* __restrict__ b1, const float* __restrict__ w2,
@@ -87,16 +75,8 @@ __global__ __launch_bounds__(GATE_THREADS) void sa_gate_fwd_kernel(const float* 
     const int tid = threadIdx.x, b = blockIdx.x;
     for (int c = tid; c < Cp; c += GATE_THREADS) s_gap[c] = gap[(long)b * Cp + c];
     __syncthreads();
-    // fc1' + ReLU: GATE_THREADS / A slices of the Cp input channels per output column, added in slice order
-    const int parts = GATE_THREADS / A, j = tid % A, p = tid / A, chunk = Cp / parts;
-    s_part[tid] = gate_dot(s_gap, w1 + j, A, p * chunk, (p + 1) * chunk);
-    __syncthreads();
-    if (tid < A) {
-        float h = s_part[tid];
-        for (int q = 1; q < parts; ++q) h += s_part[q * A + tid];
-        s_h[tid] = fmaxf(h + b1[tid], 0.f);
-    }
-    __syncthreads();
+    // fc1' + ReLU (sa_gate.h: the function the backward re-forms the hidden activation with)
+    gate_hidden(s_gap, w1, b1, s_part, s_h, Cp, A, tid);
     // fc2
     for (int n = tid; n < 2 * Cp; n += GATE_THREADS) s_z[n] = gate_dot(s_h, w2 + n, 2 * Cp, 0, A) + b2[n];
     __syncthreads();
@@ -112,8 +92,7 @@ __global__ __launch_bounds__(GATE_THREADS) void sa_gate_fwd_kernel(const float* 
 extern "C" int scouter_sa_gate_fwd_f32(const float* gap, const float* w1, const float* b1, const float* w2, const float* b2,
                                        float* a, int B, int Cp, int A, void* stream) {
     SC_REQUIRE(gap && w1 && b1 && w2 && b2 && a && B > 0 && Cp > 0 && A > 0, "sa_gate_fwd: null pointer or empty shape");
-    // (every slice of fc1's K and fc2's K = A are walked eight channels at a time)
-    SC_UNSUPPORTED((A == 32 || A == 64 || A == 128 || A == 256) && Cp <= GATE_MAX_CP && Cp % (8 * (GATE_THREADS / A)) == 0,
+    SC_UNSUPPORTED(gate_shape_ok(Cp, A),
                    "sa_gate_fwd: covers attention widths 32 / 64 / 128 / 256 and up to %d channels in multiples of 8 per slice "
                    "(got Cp %d, width %d)", GATE_MAX_CP, Cp, A);
     ScProfScope prof("sa_gate_fwd", (hipStream_t)stream, 6.0 * B * Cp * A, 4.0 * (3.0 * B * Cp + 3.0 * Cp * A));

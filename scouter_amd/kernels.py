@@ -1528,6 +1528,50 @@ def sa_apply_bwd(dout, a, dgap):
     return dx
 
 
+# ---- the gradient-only backward of the folded eval path (csrc/fold_bwd.hip; SlotModel.image_pass)
+def sa_gate_bwd(gap, w1, b1, w2, a, da, want_h=False):
+    """The backward of sa_gate_fwd in one launch: da [B, 2C'] (the gradient of its output a) -> dgap [B, C'], through the radix
+    softmax, fc2, the ReLU of the hidden activation h = relu(gap . w1 + b1) -- re-formed with the forward's own device function,
+    the same bits -- and the folded fc1.  want_h: returns (dgap, h [B, A]).  One workgroup per image: a row does not depend on
+    the batch it is computed in.  The shapes of sa_gate_eligible."""
+    for n, t in (("gap", gap), ("w1", w1), ("b1", b1), ("w2", w2), ("a", a), ("da", da)):
+        _chk(t, n)
+    B, Cp = gap.shape
+    A = w1.shape[-1]
+    assert tuple(w1.shape[-2:]) == (Cp, A) and tuple(w2.shape[-2:]) == (A, 2 * Cp) and b1.numel() == A
+    assert tuple(a.shape) == (B, 2 * Cp) and tuple(da.shape) == (B, 2 * Cp)
+    dgap = torch.empty((B, Cp), dtype=F32, device=gap.device)
+    h = torch.empty((B, A), dtype=F32, device=gap.device) if want_h else None
+    _native.check(_native.lib().scouter_sa_gate_bwd_f32(_p(gap), _p(w1), _p(b1), _p(w2), _p(a), _p(da), _p(dgap), _p(h), B, Cp, A,
+                                                        _stream()), "sa_gate_bwd")
+    return (dgap, h) if want_h else dgap
+
+
+def sa_apply_relu_bwd(dout, a, dgap, x0):
+    """sa_apply_bwd and relu_bwd(., x0) in one pass: dx [B, H, W, 2C'] = [x0 > 0] * (dout * a_r + dgap / HW), x0 the folded radix
+    convolution's output (stored after its ReLU)."""
+    for n, t in (("dout", dout), ("a", a), ("dgap", dgap), ("x0", x0)):
+        _chk(t, n)
+    B, H, W, Cp = dout.shape
+    assert tuple(x0.shape) == (B, H, W, 2 * Cp) and a.numel() == B * 2 * Cp and dgap.numel() == B * Cp
+    dx = torch.empty((B, H, W, 2 * Cp), dtype=F32, device=dout.device)
+    _native.check(_native.lib().scouter_sa_apply_relu_bwd_f32(_p(dout), _p(a), _p(dgap), _p(x0), _p(dx), B, H * W, Cp, _stream()),
+                  "sa_apply_relu_bwd")
+    return dx
+
+
+def maxpool_relu_bwd(dy, arg, h, k=3, stride=2, pad=1):
+    """maxpool_bwd followed by relu_bwd(., h) in one pass (the same bits): h [B, H, W, C] the pool's input, a ReLU's output."""
+    _chk(dy, "dy"); _chk(h, "h")
+    B, H, W, C = h.shape
+    assert arg.dtype == torch.uint8 and arg.is_contiguous() and tuple(arg.shape) == tuple(dy.shape)
+    assert tuple(dy.shape) == (B, pool_out(H, k, stride, pad), pool_out(W, k, stride, pad), C)
+    dx = torch.empty_like(h)
+    _native.check(_native.lib().scouter_maxpool_relu_bwd_f32(_p(dy), _p(arg), _p(h), _p(dx), B, H, W, C, k, stride, pad,
+                                                             _stream()), "maxpool_relu_bwd")
+    return dx
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # xSlot head
 # ---------------------------------------------------------------------------------------------------------------

@@ -168,6 +168,25 @@ class Conv2d(nn.Module):
         return K.conv2d_fwd(x, f.w, f.b, addend, self.stride, self.padding, self.groups, relu, precision=self.precision,
                             wt=f.wt)
 
+    def dgrad_folded(self, dy, xshape, addend=None, wd=None):
+        """conv'^T(dy) [+ addend]: the input gradient of fwd_folded's convolution (SlotModel.image_pass), on the FOLDED weight,
+        fp32 in and out.  wd: the input-gradient planes of the folded weight from the model's one-launch split -- with them the
+        call runs on the bf16x3 family the layer's route offers for a plain fp32 gradient ("xhalo" / "x3") where that admits the
+        shape; without them, and for every other layer, on the igemm kernels."""
+        f = self._fold
+        if f is None:
+            raise RuntimeError("Conv2d.dgrad_folded: the model has not folded this layer (SlotModel.image_pass)")
+        if self.precision != "fp32":
+            raise NotImplementedError("Conv2d.dgrad_folded: precision %r has no folded input gradient" % (self.precision,))
+        k = self.kernel_size
+        xshape = tuple(xshape)
+        fam = next((fm for fm in self.route().dgrad
+                    if fm in ("xhalo", "x3") and self._dgrad_fits(fm, dy, None, wd, None, None, xshape)), "igemm")
+        if fam != "igemm":
+            return K.conv2d_dgrad_x3(dy, wd, xshape, addend, tile=7 if fam == "xhalo" else None, kh=k, pad=self.padding,
+                                     groups=self.groups)
+        return K.conv2d_dgrad(dy, f.w, xshape, addend, self.stride, self.padding, self.groups)
+
     def x3_mode(self):
         """True if a pass of this layer runs on a register-split kernel (SlotModel._x3_convs)."""
         r = self.route()
@@ -371,6 +390,18 @@ class StemConv2d(Conv2d):
                                % (self.in_channels, tuple(x_nchw.shape)))
         col = K.im2col_nchw(x_nchw, self.kernel_size, self.stride, self.padding, self.kpad)
         return K.conv2d_fwd(col, f.w, f.b, addend, 1, 0, 1, relu, precision=self.precision, wt=f.wt)
+
+    def dgrad_folded(self, dy, xshape, addend=None, wd=None):
+        """The image gradient (NCHW fp32) of fwd_folded's convolution: kernels.stem_dgrad on the folded weight, whose first
+        `kdim` rows are the HWIO weight (the rest is the GEMM's zero padding)."""
+        f = self._fold
+        if f is None:
+            raise RuntimeError("StemConv2d.dgrad_folded: the model has not folded this layer (SlotModel.image_pass)")
+        if addend is not None:
+            raise RuntimeError("StemConv2d.dgrad_folded: the image gradient takes no addend")
+        k = self.kernel_size
+        w = f.w.view(self.kpad, self.out_channels)[:self.kdim].view(k, k, self.in_channels, self.out_channels)
+        return K.stem_dgrad(dy, w, xshape, k, self.stride, self.padding)
 
     def fwd(self, x_nchw, save, relu=False, addend=None, bn_stats=False):
         if x_nchw.dim() != 4 or x_nchw.shape[1] != self.in_channels:

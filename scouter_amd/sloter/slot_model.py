@@ -71,6 +71,22 @@ class _FusedStep(torch.autograd.Function):
         return None, None, dx, None
 
 
+def _seeded_head_backward(m, logp, hstate, seed):
+    """d(sum seed * log_probs) / d features by one head backward (SlotModel._head_backward), nothing of the backbone; the head
+    parameters that require grad get their `.grad` overwritten.  What FeaturePass.grad and ImagePass.grad share, refusals
+    included."""
+    if not torch.is_tensor(seed) or seed.shape != logp.shape or seed.dtype != torch.float32 or seed.device != logp.device:
+        raise ValueError("seed must be an fp32 tensor of shape %s on %s" % (tuple(logp.shape), logp.device))
+    arena = m.grad_arena()
+    dfeat = m._head_backward(hstate, seed.contiguous(), None, None, None, need_dfeat=True, post=None)
+    K.join_side_stream(dfeat.device)                     # (the head's parameter gradients ran on the side stream)
+    head = "backbone.fc." if not m.use_slot else None
+    for name, p, _, _ in arena.entries:
+        if name.startswith(head) if head else not name.startswith("backbone."):
+            p.grad = arena.views[name]
+    return dfeat
+
+
 class FeaturePass:
     """What SlotModel.feature_pass returns: the backbone's output, the model's output and the head's backward from one to
     the other."""
@@ -84,17 +100,42 @@ class FeaturePass:
         """seed: fp32 [B, classes] on the device -> d(sum seed * log_probs) / d features, NHWC fp32 [B, h, w, channel]: one
         head backward (SlotModel._head_backward), nothing of the backbone.  Head parameters that require grad get their
         `.grad` overwritten, as in any backward of the model; the backbone's parameter gradients are not touched."""
-        m, logp = self._model, self.log_probs
-        if not torch.is_tensor(seed) or seed.shape != logp.shape or seed.dtype != torch.float32 or seed.device != logp.device:
-            raise ValueError("seed must be an fp32 tensor of shape %s on %s" % (tuple(logp.shape), logp.device))
-        arena = m.grad_arena()
-        dfeat = m._head_backward(self._hstate, seed.contiguous(), None, None, None, need_dfeat=True, post=None)
-        K.join_side_stream(dfeat.device)                     # (the head's parameter gradients ran on the side stream)
-        head = "backbone.fc." if not m.use_slot else None
-        for name, p, _, _ in arena.entries:
-            if name.startswith(head) if head else not name.startswith("backbone."):
-                p.grad = arena.views[name]
-        return dfeat
+        return _seeded_head_backward(self._model, self.log_probs, self._hstate, seed)
+
+
+class ImagePass:
+    """What SlotModel.image_pass returns: the model's output, the backbone's output, and the backward from the output to the
+    IMAGE on the folded weights -- one forward, any number of gradients."""
+
+    def __init__(self, model, features, log_probs, bstate, hstate, wds, gen):
+        self.features, self.log_probs = features, log_probs
+        self._model, self._bstate, self._hstate, self._wds, self._gen = model, bstate, hstate, wds, gen
+
+    @torch.no_grad()
+    def grad(self, seed):
+        """seed: fp32 [B, n_outputs] on the device -> d(sum seed * log_probs) / d x, NCHW fp32 in the shape of the pass's images:
+        one head backward (as FeaturePass.grad, with its refusals and its effect on the head's `.grad`), then the backbone's
+        input gradients on the folded weights (ResNet.image_bwd) -- no BatchNorm kernel, no backbone parameter gradient.  May be
+        called any number of times; a pass whose model has folded again since (new weights in the same buffers) refuses."""
+        m = self._model
+        if m._fold_gen != self._gen:
+            raise RuntimeError("ImagePass.grad: the model has folded its weights again since this pass; run image_pass again")
+        dfeat = _seeded_head_backward(m, self.log_probs, self._hstate, seed)
+        return m.backbone.image_bwd(dfeat, self._bstate, self._wds)
+
+    def relu_outputs(self):
+        """{name: activation} whose signs the backward used, in the keys of the training path's capture: the name of the
+        BatchNorm each ReLU follows (the split-attention gate's hidden activation under its `bn1`), `conv1x1` for the head's,
+        and `maxpool` for the max-pool's window indices (uint8 NHWC).  For tests that pin an oracle to this pass's pattern."""
+        m = self._model
+        names = {mod: n for n, mod in m.named_modules()}
+        with torch.no_grad():
+            pairs, arg = m.backbone.image_relus(self._bstate)
+        out = {names[bn]: t for bn, t in pairs}
+        if m.use_slot:
+            out["conv1x1"] = self._hstate[1]
+        out["maxpool"] = arg
+        return out
 
 
 class SlotModel(nn.Module):
@@ -116,7 +157,8 @@ class SlotModel(nn.Module):
         self.inference_fold = False          # set_inference_fold
         self._folder = None                  # K.BnFolder: table + the flat buffer of every folded weight / bias
         self._fold_splitter = K.PlaneWeightSplitter()
-        self._fold_stale = True
+        self._fold_gen = 0                   # folds so far (ImagePass.grad: the folded buffers are rewritten in place)
+        self._fold_stale = True              # (a property: going stale drops the folded weights' input-gradient planes)
         self._flatten_tracked()              # BatchNorm counters: views of one flat buffer, from construction on
         self._post_backward_hooks = []       # called with the GradArena after every backward (data-parallel reduce)
         self._grad_ready_hooks = []          # called (arena, lo, hi) as soon as arena.flat[lo:hi] is final
@@ -153,10 +195,23 @@ class SlotModel(nn.Module):
         (whose convolutions still round their matrix inputs to bf16).  Measured: +1.3 % at batch 70 and
         1.8 x on single images in fp32; under precision "bf16" at batch 256 it is 17 % SLOWER than the unfolded path with its
         bf16 storage -- leave it off there.
-        The folded path has no backward: an input that requires grad (d output / d image, tools/attribution.py) runs the
-        unfolded eval forward, fold or no fold, and gets the same gradient."""
+        Autograd does not see the folded path: an input that requires grad (d output / d image, tools/attribution.py
+        route="autograd") runs the unfolded eval forward, fold or no fold, and gets the same gradient.  The folded path's own
+        backward is explicit -- image_pass(x).grad(seed), a gradient with respect to the image only -- and runs whether this
+        switch is on or off."""
         self.inference_fold = bool(enabled)
         self._fold_stale = True
+
+    @property
+    def _fold_stale(self):
+        return self.__dict__.get("_fold_is_stale", True)
+
+    @_fold_stale.setter
+    def _fold_stale(self, stale):
+        self.__dict__["_fold_is_stale"] = bool(stale)
+        if stale:                            # the planes image_pass split from the folded weights go with the fold
+            self.__dict__["_fold_wd"] = None
+            self.__dict__["_fold_dsplitter"] = None
 
     def refold(self):
         """The next folded forward folds the current parameters and running statistics again."""
@@ -189,7 +244,24 @@ class SlotModel(nn.Module):
             # (precision "bf16": the transposed bf16 weight the bf16-input forward reads, once per fold instead of per call)
             wt = K.weight_bf16t(w, c.groups) if c.precision == "bf16" else None
             c._fold = FoldedConv(w, b, wf.get(c), wt)
+        self._fold_gen += 1
         self._fold_stale = False
+
+    def _fold_dgrad_planes(self):
+        """{layer: input-gradient planes of its FOLDED weight} for the layers whose route offers a bf16x3 input gradient for a
+        plain fp32 gradient ("xhalo" / "x3"): one launch of a splitter of their own on the first image_pass after a fold --
+        an inference-only user never pays for them -- and dropped with the fold (the _fold_stale setter)."""
+        wds = self.__dict__.get("_fold_wd")
+        if wds is None:
+            convs = [c for c, _ in self.backbone.fold_pairs()
+                     if not isinstance(c, StemConv2d) and any(f in ("xhalo", "x3") for f in c.route().dgrad)]
+            wds = {}
+            if convs:
+                splitter = self.__dict__["_fold_dsplitter"] = K.PlaneWeightSplitter()
+                outs = splitter.run([(c._fold.w, c.groups, False, True) for c in convs], 3)
+                wds = {c: o[1] for c, o in zip(convs, outs)}
+            self.__dict__["_fold_wd"] = wds
+        return wds
 
     def _forward_folded(self, x, target):
         if not x.is_cuda:
@@ -415,6 +487,41 @@ class SlotModel(nn.Module):
             if was_training:
                 self.train(True)
         return FeaturePass(self, feat, logp, hstate)
+
+    def image_pass(self, x):
+        """One eval-mode forward on the BatchNorm-FOLDED weights that keeps what a gradient with respect to the image needs:
+        every ReLU output, the max-pool's window indices, the split-attention vectors and the head's state -- no BatchNorm
+        statistics, masks or convolution inputs of the training backward.  Returns an ImagePass: `.log_probs` [B, n_outputs],
+        `.features` (NHWC fp32), `.grad(seed)` = d(sum seed * log_probs) / d x (NCHW fp32, any number of times) and
+        `.relu_outputs()`.  The weights are folded again when stale, as in feature_pass, and the pass runs whether or not
+        set_inference_fold is on: it has no unfolded form.  No BatchNorm buffer or counter moves, no backbone parameter gradient
+        is computed or touched, the caller's mode is restored.  resnet18 / resnest26d / resnest50d, use_slot on and off, fp32:
+        precision "bf16" is refused (DESIGN.md advises against the folded path there)."""
+        if self.precision == "bf16":
+            raise NotImplementedError('image_pass: precision "bf16" has no folded backward (fp32 only)')
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError("scouter_amd.SlotModel runs on a HIP device (got %s); there is no CPU fallback"
+                               % (x.device if torch.is_tensor(x) else type(x).__name__,))
+        if x.dim() != 4:
+            raise ValueError("images must be [B, C, H, W], got shape %s" % (tuple(x.shape),))
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad():
+                x = x.detach().contiguous()
+                if x.dtype != torch.float32:
+                    x = x.float()
+                if self._fold_stale or self._folder is None:
+                    self._refold()
+                wds = self._fold_dgrad_planes()
+                feat, bstate = self.backbone.image_fwd(x)
+                logp, _, hstate = self._head_forward(feat, None, True)
+                gen = self._fold_gen
+        finally:
+            if was_training:
+                self.train(True)
+        return ImagePass(self, feat, logp, bstate, hstate, wds, gen)
 
     def head_pass(self, features):
         """`feature_pass` without the backbone: NHWC fp32 `features` [n, h, w, channel] on the device -- the backbone's output, or

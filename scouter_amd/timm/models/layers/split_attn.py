@@ -63,6 +63,50 @@ class SplitAttnConv2d(nn.Module):
             a = K.radix_softmax_fwd(z2.view(B, -1))
         return K.sa_apply_fwd(x0, a, None)
 
+    def fwd_image(self, x):
+        """fwd_folded that keeps what a gradient with respect to its input needs (SlotModel.image_pass): the radix convolution's
+        output x0 (after its ReLU), the pooled vector, the attention -- and, where the gate runs unfused, its hidden
+        activation.  -> (out, ctx)"""
+        x0 = self.conv.fwd_folded(x, relu=True)
+        B = x0.shape[0]
+        gap = K.sa_gap(x0, None)
+        g1 = None
+        if K.sa_gate_eligible(gap.shape[1], self.fc1.out_channels):
+            f = self.fc1._fold
+            a = K.sa_gate_fwd(gap, f.w, f.b, K.hwio(self.fc2.weight), self.fc2.bias)
+        else:
+            g1 = self.fc1.fwd_folded(gap.view(B, 1, 1, -1), relu=True)
+            z2, _ = self.fc2.fwd(g1, False)
+            a = K.radix_softmax_fwd(z2.view(B, -1))
+        return K.sa_apply_fwd(x0, a, None), (tuple(x.shape), x0, gap, a, g1)
+
+    def bwd_image(self, dout, ctx, wds):
+        """The gradient of fwd_image's input from that of its output: d(attention) as in training, the gate's backward in one
+        launch (K.sa_gate_bwd; the unfused chain where fwd_image ran unfused), the weighted sum's + GAP's backward with x0's ReLU
+        mask in one pass (K.sa_apply_relu_bwd), the radix convolution's input gradient on the folded weight.  wds: the model's
+        {layer: input-gradient planes of its folded weight}."""
+        xshape, x0, gap, a, g1 = ctx
+        B = x0.shape[0]
+        da = K.sa_dattn(x0, dout, None)
+        if g1 is None:
+            f = self.fc1._fold
+            dgap = K.sa_gate_bwd(gap, f.w, f.b, K.hwio(self.fc2.weight), a, da)
+        else:
+            dz2 = K.radix_softmax_bwd(a, da)
+            dg1 = K.conv2d_dgrad(dz2.view(B, 1, 1, -1), K.hwio(self.fc2.weight), tuple(g1.shape))
+            dgap = self.fc1.dgrad_folded(K.relu_bwd(dg1, g1), (B, 1, 1, gap.shape[1]), wd=wds.get(self.fc1)).view(B, -1)
+        return self.conv.dgrad_folded(K.sa_apply_relu_bwd(dout, a, dgap, x0), xshape, wd=wds.get(self.conv))
+
+    def image_relus(self, ctx):
+        """[(BatchNorm, the ReLU output that followed it in fwd_image)]: x0 and the gate's hidden activation [B, 1, 1, A] --
+        where the gate ran fused, re-formed by the backward kernel (a zero gradient in, h out)."""
+        xshape, x0, gap, a, g1 = ctx
+        if g1 is None:
+            f = self.fc1._fold
+            _, h = K.sa_gate_bwd(gap, f.w, f.b, K.hwio(self.fc2.weight), a, a.new_zeros(a.shape), want_h=True)
+            g1 = h.view(h.shape[0], 1, 1, -1)
+        return [(self.bn0, x0), (self.bn1, g1)]
+
     def bwd(self, dout, ctx, post=None):
         """post: K.BnBwdFuse of the BatchNorm in front of this layer (finished in the input-gradient epilogue)."""
         c_conv, x0, saved0, training0, c_fc1, c_bn1, c_fc2, a = ctx

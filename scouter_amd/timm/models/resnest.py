@@ -95,6 +95,29 @@ class ResNestBottleneck(nn.Module):
         p = self.avd_last.fwd(sa) if self.avd_last is not None else sa
         return self.conv3.fwd_folded(p, relu=True, addend=res)
 
+    def fwd_image(self, x):
+        """fwd_folded that keeps what a gradient with respect to x needs (SlotModel.image_pass) -> (out, ctx)"""
+        res, kd = self.downsample.fwd_image(x) if self.downsample is not None else (x, None)
+        h1 = self.conv1.fwd_folded(x, relu=True)
+        sa, ksa = self.conv2.fwd_image(h1)
+        p = self.avd_last.fwd(sa) if self.avd_last is not None else sa
+        out = self.conv3.fwd_folded(p, relu=True, addend=res)
+        return out, (tuple(x.shape), kd, h1, ksa, tuple(sa.shape), tuple(p.shape), out)
+
+    def bwd_image(self, dout, ctx, wds):
+        """d x from d out: ReLU mask, conv3, the avd pool, the split attention, ReLU mask, conv1 with the shortcut's gradient
+        as its addend -- input gradients on the folded weights only (wds: SplitAttnConv2d.bwd_image)."""
+        xshape, kd, h1, ksa, sa_shape, p_shape, out = ctx
+        d = K.relu_bwd(dout, out)
+        dxres = self.downsample.bwd_image(d, kd, wds) if self.downsample is not None else d
+        dp = self.conv3.dgrad_folded(d, p_shape, wd=wds.get(self.conv3))
+        dsa = self.avd_last.bwd(dp, sa_shape) if self.avd_last is not None else dp
+        dh1 = K.relu_bwd(self.conv2.bwd_image(dsa, ksa, wds), h1)
+        return self.conv1.dgrad_folded(dh1, xshape, addend=dxres, wd=wds.get(self.conv1))
+
+    def image_relus(self, ctx):
+        return [(self.bn1, ctx[2])] + self.conv2.image_relus(ctx[3]) + [(self.bn3, ctx[6])]
+
     def out_fuse(self, ctx):
         """What the kernel producing this block's OUTPUT gradient needs to finish the backward reductions of bn3 (and
         of the downsample BatchNorm, fed by the same masked gradient) in its epilogue."""

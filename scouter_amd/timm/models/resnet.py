@@ -68,6 +68,22 @@ class Downsample(nn.Sequential):
         pool = mods[0] if len(mods) == 3 and isinstance(mods[0], AvgPool2dSpec) else None
         return mods[-2].fwd_folded(pool.fwd(x) if pool is not None else x)
 
+    def fwd_image(self, x):
+        """fwd_folded -> (the normalised shortcut, ctx for bwd_image)"""
+        mods = list(self)
+        pool = mods[0] if len(mods) == 3 and isinstance(mods[0], AvgPool2dSpec) else None
+        xin = pool.fwd(x) if pool is not None else x
+        return mods[-2].fwd_folded(xin), (tuple(x.shape), tuple(xin.shape))
+
+    def bwd_image(self, dy, ctx, wds):
+        """the shortcut's gradient with respect to the block input: the convolution's input gradient on the folded weight, then
+        the pool's backward"""
+        x_shape, xin_shape = ctx
+        mods = list(self)
+        pool = mods[0] if len(mods) == 3 and isinstance(mods[0], AvgPool2dSpec) else None
+        dx = mods[-2].dgrad_folded(dy, xin_shape, wd=wds.get(mods[-2]))
+        return pool.bwd(dx, x_shape) if pool is not None else dx
+
     # ---- the branch on its own stream ("branch": never behind the backlog of weight gradients), next to the block's
     # main branch whose many small launches leave the GPU idle in between.  Measured on the benchmark step (3 x 120 steps,
     # interleaved, one box): forward +0.5 % (3 970 -> 3 991), backward +1.6 % (3 947 -> 4 011).
@@ -149,6 +165,25 @@ class BasicBlock(nn.Module):
     def fwd_folded(self, x):
         res = self.downsample.fwd_folded(x) if self.downsample is not None else x
         return self.conv2.fwd_folded(self.conv1.fwd_folded(x, relu=True), relu=True, addend=res)
+
+    def fwd_image(self, x):
+        """fwd_folded that keeps what a gradient with respect to x needs (SlotModel.image_pass) -> (out, ctx)"""
+        res, kd = self.downsample.fwd_image(x) if self.downsample is not None else (x, None)
+        h1 = self.conv1.fwd_folded(x, relu=True)
+        out = self.conv2.fwd_folded(h1, relu=True, addend=res)
+        return out, (tuple(x.shape), kd, h1, out)
+
+    def bwd_image(self, dout, ctx, wds):
+        """d x from d out: ReLU mask, conv2, ReLU mask, conv1 with the shortcut's gradient as its addend (wds:
+        SplitAttnConv2d.bwd_image)"""
+        xshape, kd, h1, out = ctx
+        d = K.relu_bwd(dout, out)
+        dxres = self.downsample.bwd_image(d, kd, wds) if self.downsample is not None else d
+        dh1 = K.relu_bwd(self.conv2.dgrad_folded(d, tuple(h1.shape), wd=wds.get(self.conv2)), h1)
+        return self.conv1.dgrad_folded(dh1, xshape, addend=dxres, wd=wds.get(self.conv1))
+
+    def image_relus(self, ctx):
+        return [(self.bn1, ctx[2]), (self.bn2, ctx[3])]
 
     def out_fuse(self, ctx):
         """see ResNestBottleneck.out_fuse: bn2 (+ the downsample BatchNorm)"""
@@ -302,6 +337,50 @@ class ResNet(nn.Module):
             for blk in getattr(self, "layer%d" % li):
                 x = blk.fwd_folded(x)
         return x
+
+    # ---- the folded forward that keeps what a gradient with respect to the IMAGE needs, and that gradient (SlotModel.image_pass)
+    def _stem_convs(self):
+        return [self.conv1[i] for i in (0, 3, 6)] if isinstance(self.conv1, nn.Sequential) else [self.conv1]
+
+    def image_fwd(self, x_nchw):
+        """features_fwd_folded -> (NHWC features, ctx): every ReLU output (the masks of the backward), the max-pool's window
+        indices and the shapes -- no convolution input is kept for its own sake, no BatchNorm kernel runs."""
+        hs, h = [], x_nchw
+        for conv in self._stem_convs():
+            h = conv.fwd_folded(h, relu=True)
+            hs.append(h)
+        x, arg = K.maxpool_fwd(h, 3, 2, 1, want_argmax=True)
+        blocks = []
+        for li in range(1, 5):
+            for blk in getattr(self, "layer%d" % li):
+                x, c_blk = blk.fwd_image(x)
+                blocks.append(c_blk)
+        return x, (tuple(x_nchw.shape), hs, arg, blocks)
+
+    def image_bwd(self, dfeat, ctx, wds):
+        """d image (NCHW fp32) from d features: the blocks in reverse, the max-pool gather with the stem ReLU's mask in one pass
+        (K.maxpool_relu_bwd), the deep stem's input gradients and ReLU masks, the stem convolution's image gradient -- on the
+        folded weights; no parameter gradient, no BatchNorm kernel.  wds: {layer: input-gradient planes of its folded weight}."""
+        x_shape, hs, arg, blocks = ctx
+        mods = [blk for li in range(1, 5) for blk in getattr(self, "layer%d" % li)]
+        d = dfeat
+        for blk, c_blk in zip(reversed(mods), reversed(blocks)):
+            d = blk.bwd_image(d, c_blk, wds)
+        d = K.maxpool_relu_bwd(d, arg, hs[-1], 3, 2, 1)
+        convs = self._stem_convs()
+        for i in range(len(convs) - 1, 0, -1):
+            d = K.relu_bwd(convs[i].dgrad_folded(d, tuple(hs[i - 1].shape), wd=wds.get(convs[i])), hs[i - 1])
+        return convs[0].dgrad_folded(d, x_shape)
+
+    def image_relus(self, ctx):
+        """[(BatchNorm, the ReLU output that followed it)] of image_fwd in forward order, and the max-pool's window indices"""
+        x_shape, hs, arg, blocks = ctx
+        bns = [self.conv1[1], self.conv1[4], self.bn1] if isinstance(self.conv1, nn.Sequential) else [self.bn1]
+        pairs = list(zip(bns, hs))
+        mods = [blk for li in range(1, 5) for blk in getattr(self, "layer%d" % li)]
+        for blk, c_blk in zip(mods, blocks):
+            pairs += blk.image_relus(c_blk)
+        return pairs, arg
 
     def _first_trainable_stage(self):
         """Index of the earliest stage (0 = stem, 1..4 = layer1..4) holding a trainable parameter; 5 if none."""

@@ -192,7 +192,61 @@ import torch
 from .. import kernels as K
 
 
-def input_gradients(model, images, classes=None, of="log_prob", target=None):
+_ROUTES = ("autograd", "folded")
+
+
+def _check_route(route, of="log_prob"):
+    """the `route` argument of the image-space gradient methods, checked before any launch"""
+    if route not in _ROUTES:
+        raise ValueError("route must be 'autograd' or 'folded', got %r" % (route,))
+    if route == "folded" and of == "loss":
+        raise ValueError("route='folded' differentiates the model output; of='loss' needs route='autograd'")
+    return route
+
+
+def _check_device_images(images):
+    """route="folded" has no host form: refused before any launch"""
+    if not torch.is_tensor(images) or not images.is_cuda:
+        raise RuntimeError("route='folded' runs on a HIP device (got %s); there is no CPU fallback"
+                           % (images.device if torch.is_tensor(images) else type(images).__name__,))
+
+
+@contextlib.contextmanager
+def _eval_mode_once(model):
+    """_eval_mode for the folded route: a model that is in eval mode already is left alone -- SlotModel.eval() / train() mark the
+    folded weights stale (the model would fold them again for every call, and an ImagePass taken before would refuse)"""
+    if not getattr(model, "training", False):
+        yield
+    else:
+        with _eval_mode(model):
+            yield
+
+
+def _folded_input_gradients(model, images, classes):
+    """input_gradients(route="folded"): ONE model.image_pass and one .grad per class column (a LongTensor: one .grad)"""
+    _check_device_images(images)
+    B = images.shape[0]
+    n = _num_classes(model, images)
+    per_image, cols = _class_list(classes, B, n)
+    _check_class_range(cols, n)
+    with _eval_mode_once(model):
+        ip = model.image_pass(images)
+        seed = torch.zeros_like(ip.log_probs)
+        grads = []
+        if per_image:
+            seed[torch.arange(B, device=seed.device), classes.to(seed.device)] = 1.0
+            grads.append(ip.grad(seed))
+        else:
+            for c in cols:
+                seed.zero_()
+                seed[:, c] = 1.0
+                grads.append(ip.grad(seed))
+    if not grads:
+        return torch.empty((B, 0) + tuple(images.shape[1:]), dtype=torch.float32, device=images.device)
+    return torch.stack(grads, dim=1)
+
+
+def input_gradients(model, images, classes=None, of="log_prob", target=None, route="autograd"):
     """Gradient of the model output with respect to `images` [B, C, H, W] -> fp32 [B, K, C, H, W] on the images' device.
 
     of="log_prob": K = len(classes) (None: every class); slice [:, k] is d(sum_b output[b, classes[k]]) / d images -- one
@@ -204,12 +258,21 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None):
     of="loss": K = 1, the gradient of the training loss (losses[0]) for the labels `target`.
 
     The model is put in eval mode (BatchNorm uses its running statistics and no buffer moves) and the caller's mode is
-    restored.  Parameters that require grad get their `.grad` overwritten by each backward, as in any backward of the model."""
+    restored.  Parameters that require grad get their `.grad` overwritten by each backward, as in any backward of the model.
+
+    route="autograd" (the default) is the path above: the unfolded layer-by-layer forward and the training backward walked on to
+    the image, once per class.  route="folded": ONE forward on the BatchNorm-folded weights (model.image_pass) and one
+    gradient-only backward per class column -- no BatchNorm kernel, no parameter gradient of the backbone; of="log_prob" only
+    (of="loss" is a ValueError), fp32 models only.  The two routes agree to rounding, not bit for bit: the folded weights are
+    rounded once more and the ReLU signs are those of the folded forward.  Any other value is a ValueError before any launch."""
     if of not in ("log_prob", "loss"):
         raise ValueError("of must be 'log_prob' or 'loss', got %r" % (of,))
+    _check_route(route, of)
     _check_images(images)
     if of == "loss" and target is None:
         raise ValueError("of='loss' needs target= labels")
+    if route == "folded":
+        return _folded_input_gradients(model, images, classes)
     with _eval_mode(model):
         grads = []
         with torch.enable_grad():
@@ -1141,16 +1204,48 @@ def _chunk_gradient(model, chunk, seed):
     return g if g.dtype == torch.float32 and g.is_contiguous() else g.float().contiguous()
 
 
-def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, want_sq, finish, totals=None, accumulate=None):
+def _path_method(model, images, n, per_image, cols, batch, N, fill, weights, want_sq, finish, totals=None, accumulate=None,
+                 route="autograd"):
     """the loop shared by integrated_gradients, smoothgrad and gradient_shap: image, then class, then chunk.  (per_image, cols)
     come from _class_columns for a model of n outputs; fill(b, buf, first) writes the images first .. first + len(buf) - 1 of
     image b's batch of N into buf; finish(b, acc, acc_sq, out, total) forms out[b, k].  accumulate(b, grads, acc, first), when
-    given, adds a chunk's gradients in place of kernels.grad_accumulate with `weights`."""
+    given, adds a chunk's gradients in place of kernels.grad_accumulate with `weights`.
+    route="folded": the second loop order, image, then chunk, then class -- the rows of a chunk do not depend on the class, so ONE
+    fill and ONE model.image_pass serve every class of the chunk; per class one .grad and one accumulate onto that class's own
+    float64 sums (acc / acc_sq [K, C, H, W]), `finish` per class at the end.  Per class the chunks still arrive in ascending
+    order, so the chunking changes no bit."""
     B, C, H, W = images.shape
     dev = images.device
     Kc = 1 if per_image else len(cols)
     out = torch.empty((B, Kc, C, H, W), dtype=torch.float32, device=dev)
     if Kc == 0:
+        return out
+    if route == "folded":
+        buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
+        seed = torch.zeros((min(batch, N), n), dtype=torch.float32, device=dev)
+        acc = torch.empty((Kc, C, H, W), dtype=torch.float64, device=dev)
+        acc_sq = torch.empty_like(acc) if want_sq else None
+        with _eval_mode_once(model), torch.no_grad():
+            for b in range(B):
+                cb = cols[b:b + 1] if per_image else cols
+                acc.zero_()
+                if want_sq:
+                    acc_sq.zero_()
+                for first in range(0, N, batch):
+                    chunk = fill(b, buf[:min(batch, N - first)], first)
+                    ip = model.image_pass(chunk)
+                    rows = seed[:chunk.shape[0]]
+                    for k, c in enumerate(cb):
+                        rows.zero_()
+                        rows[:, c] = 1.0
+                        grads = ip.grad(rows)
+                        if accumulate is None:
+                            K.grad_accumulate(grads, weights, acc[k], None if acc_sq is None else acc_sq[k], first)
+                        else:
+                            accumulate(b, grads, acc[k], first)
+                for k in range(len(cb)):
+                    finish(b, acc[k], None if acc_sq is None else acc_sq[k], out[b, k],
+                           None if totals is None else totals[b, k:k + 1])
         return out
     buf = torch.empty((min(batch, N), C, H, W), dtype=torch.float32, device=dev)
     seed = torch.zeros((min(batch, N), n), dtype=torch.float32, device=dev)
@@ -1214,8 +1309,23 @@ def integrated_gradients(model, images, classes=None, baseline=None, n_steps=50,
     sum(attr[b, k]) - (out(x_b)[c_k] - out(x'_b)[c_k]), the completeness gap, from the float64 sum of attr_finish and one extra
     no_grad forward of [x'_b, x_b] per image.  No BatchNorm buffer moves, nothing is copied to the host and nothing synchronises
     inside the loop; parameters that require grad get their `.grad` overwritten by each backward, as in `input_gradients`.  Any
-    module whose eval forward returns [n, n_outputs] will do."""
+    module whose eval forward returns [n, n_outputs] will do.  `integrated_gradients_by_route` is this method with one more
+    option, the route its gradients take."""
+    return integrated_gradients_by_route(model, images, classes=classes, baseline=baseline, n_steps=n_steps, method=method,
+                                         batch=batch, return_delta=return_delta, route="autograd")
+
+
+def integrated_gradients_by_route(model, images, classes=None, baseline=None, n_steps=50, method="gausslegendre", batch=50,
+                                  return_delta=False, route="autograd"):
+    """`integrated_gradients` with the option `route` (that function keeps the parameter list its callers know):
+    route="autograd" is `integrated_gradients`, the same code and the same bits.  route="folded" (a SlotModel in fp32): the chunks
+    go through model.image_pass -- ONE forward of a chunk on the BatchNorm-folded weights serves every class, each class one
+    gradient-only backward (the loop order image, chunk, class of _path_method); the chunking still changes no bit, return_delta
+    and everything downstream are the same.  Any other value is a ValueError before any launch."""
+    _check_route(route)
     x, batch = _check_images_batch(images, batch)
+    if route == "folded":
+        _check_device_images(x)
     B, C, H, W = x.shape
     alphas, weights = ig_quadrature(n_steps, method)
     dev = x.device
@@ -1239,7 +1349,8 @@ def integrated_gradients(model, images, classes=None, baseline=None, n_steps=50,
     per_image, cols = _class_columns(classes, B, n)
     Kc = 1 if per_image else len(cols)
     totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
-    attr = _path_method(model, x, n, per_image, cols, batch, int(alphas.shape[0]), fill, weights, False, finish, totals)
+    attr = _path_method(model, x, n, per_image, cols, batch, int(alphas.shape[0]), fill, weights, False, finish, totals,
+                        route=route)
     if not return_delta:
         return attr
     delta = torch.zeros((B, Kc), dtype=torch.float32, device=dev)
@@ -1268,8 +1379,19 @@ def smoothgrad(model, images, classes=None, n_samples=50, sigma=1.0, kind="smoot
     forward and one backward with a one-hot column, kernels.grad_accumulate onto float64 sums in sample order,
     kernels.attr_finish at the end of the class, with the same guarantees -- no BatchNorm buffer moves, the caller's mode is
     restored, nothing is copied to the host or synchronises inside the loop, `.grad` of parameters that require grad is
-    overwritten."""
+    overwritten.  `smoothgrad_by_route` is this method with one more option, the route its gradients take."""
+    return smoothgrad_by_route(model, images, classes=classes, n_samples=n_samples, sigma=sigma, kind=kind, batch=batch, seed=seed,
+                               route="autograd")
+
+
+def smoothgrad_by_route(model, images, classes=None, n_samples=50, sigma=1.0, kind="smoothgrad", batch=50, seed=0, route="autograd"):
+    """`smoothgrad` with the option `route` (that function keeps the parameter list its callers know): route="autograd" is
+    `smoothgrad`, the same code and the same bits; route="folded": as in `integrated_gradients_by_route` -- one folded forward of
+    a chunk for every class.  Any other value is a ValueError before any launch."""
+    _check_route(route)
     x, batch = _check_images_batch(images, batch)
+    if route == "folded":
+        _check_device_images(x)
     n_samples, sigma = int(n_samples), float(sigma)
     if n_samples < 1:
         raise ValueError("n_samples must be at least 1, got %d" % n_samples)
@@ -1287,7 +1409,7 @@ def smoothgrad(model, images, classes=None, n_samples=50, sigma=1.0, kind="smoot
 
     n = _num_outputs(model, x)
     per_image, cols = _class_columns(classes, x.shape[0], n)
-    return _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, mode != K.ATTR_MEAN, finish)
+    return _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, mode != K.ATTR_MEAN, finish, route=route)
 
 
 def gradient_maps(attr, min_level=0.0, absolute=False):
@@ -2413,7 +2535,7 @@ def _gradshap_shares(n_samples, R, seed, dev):
 
 
 def gradient_shap(model, images, classes=None, baselines=10, bank_sigma=1.0, n_samples=50, sigma=0.0, batch=50, seed=0,
-                  return_delta=False):
+                  return_delta=False, route="autograd"):
     """GradientSHAP / expected gradients (Lundberg & Lee 2017; Erion et al. 2019; captum's GradientShap: NoiseTunnel over
     InputBaselineXGradient with multiply_by_inputs) of `images` [B, C, H, W] -> fp32 [B, K, C, H, W] on the images' device.  With
     a bank of R baselines b_r, per sample s < n_samples a baseline pick_s and a fraction alpha_s in (0, 1) drawn from `seed`:
@@ -2444,8 +2566,13 @@ def gradient_shap(model, images, classes=None, baselines=10, bank_sigma=1.0, n_s
     What departs from captum's GradientShap: the random stream is ours (Philox, kernels.gradshap_draws; captum draws from
     torch's generator); `out` is the LOG-PROBABILITIES, as in every method here; ONE draw sequence serves all images and
     classes (sample s of every image and class has the same pick, fraction and noise); sigma is absolute, not relative to the
-    image's range.  captum is no dependency and nothing was checked against it."""
+    image's range.  captum is no dependency and nothing was checked against it.
+
+    route="folded": as in `integrated_gradients_by_route` -- one folded forward of a chunk for every class."""
+    _check_route(route)
     x, batch = _check_images_batch(images, batch)
+    if route == "folded":
+        _check_device_images(x)
     n_samples, bank_sigma, sigma = _check_gradshap(n_samples, bank_sigma, sigma)
     bank = _gradshap_bank(baselines, bank_sigma, n_samples, seed, x)
     B = x.shape[0]
@@ -2465,7 +2592,8 @@ def gradient_shap(model, images, classes=None, baselines=10, bank_sigma=1.0, n_s
     per_image, cols = _class_columns(classes, B, n)
     Kc = 1 if per_image else len(cols)
     totals = torch.zeros((B, Kc), dtype=torch.float64, device=dev) if return_delta else None
-    attr = _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, False, finish, totals, accumulate)
+    attr = _path_method(model, x, n, per_image, cols, batch, n_samples, fill, None, False, finish, totals, accumulate,
+                        route=route)
     if not return_delta:
         return attr
     delta = torch.zeros((B, Kc), dtype=torch.float32, device=dev)
