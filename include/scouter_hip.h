@@ -218,6 +218,13 @@ int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int B, 
  * the call returns SC_ERR_UNSUPPORTED: fp32 tile 4 on a covered shape with an epilogue that is not its own (forward: bias /
  * addend / ReLU), fp32 tile 5, tile 4 of the typed kernels, tile 7 of the register-split family, plane tile 6.  Arguments no
  * tensor reaches (2^36 pixels, 2^20 channels) answer 0.  Shape arguments are those of the entry point (B, H, W: the INPUT map).
+ * TWO LIMITS every pixel-walking kernel shares (csrc/conv_common.h sc_tap_mask_ok / sc_pixel_walk_ok), answered 0 here and
+ * refused with SC_ERR_UNSUPPORTED by the entry points: a filter of more than 32 taps (kh * kw; the tap validity of a GEMM row
+ * is one 32-bit word: fp32 / bf16-input / register-split / plane forward and input gradient), and more than 2^22 - 256 pixels
+ * in one image of the GEMM-row map (the forward's OUTPUT map, the input gradient's and weight gradient's INPUT map; the fp32
+ * pixel unflattening is exact below 2^22: all of the above and the weight-gradient kernels).  Pointwise layers on the kernels that
+ * walk no pixels there (fp32 tiles 0-5, the register-split pointwise kernel, the pointwise weight gradients) have neither limit.
+ * tests/test_conv_tiles_cpu.py proves the domain and asks every family's query on both sides of it.
  * epilogue: SCOUTER_EPI_* bits of the call; io: SCOUTER_IO_* (forward) / SCOUTER_DGRAD_IO_* (typed input gradient). */
 #define SCOUTER_EPI_BIAS 1      /* bias != NULL */
 #define SCOUTER_EPI_ADDEND 2    /* addend != NULL */

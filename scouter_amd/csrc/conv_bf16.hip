@@ -290,15 +290,22 @@ static void launch_bhalo_fwd(const void* src, const void* w, const float* bias, 
                        (const unsigned short*)w, bias, addend, dst, bn_part, g, relu, mtiles, (io & SC_IO_Y_BF16) ? 1 : 0);
 }
 // what both entry points ask of every shape
-static bool bf16_entry_ok(const ConvGeom& g) {
+static bool bf16_size_ok(const ConvGeom& g) {
     return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28);
+}
+// (igemm_bf16_kernel has no pointwise instantiation: every shape walks its pixels and keeps a tap mask)
+static bool bf16_entry_ok(const ConvGeom& g) { return bf16_size_ok(g) && sc_tap_mask_ok(g) && sc_pixel_walk_ok(g); }
+// the entry points' refusal by bf16_entry_ok, before the profile row of the launch is opened
+static int bf16_entry_check(const ConvGeom& g) {
+    SC_UNSUPPORTED(bf16_size_ok(g), "conv2d_bf16: more than 2^31 output pixels or an image above 2^28 elements is not supported");
+    SC_UNSUPPORTED(sc_tap_mask_ok(g), "conv2d_bf16: " SC_TAP_MASK_MSG);
+    SC_UNSUPPORTED(bf16_entry_ok(g), "conv2d_bf16: " SC_PIXEL_WALK_MSG);
+    return 0;
 }
 template <bool DGRAD>
 static int dispatch_bf16(const void* src, const void* w, const float* bias, const float* addend, float* dst,
                          double* bn_part, const ConvGeom& g, int relu, int tile, hipStream_t st,
                          const BnBwdFuse& fz, int io, bool bhalo) {   // bhalo: the caller's resident-rows decision
-    SC_UNSUPPORTED(bf16_entry_ok(g),
-                   "conv2d_bf16: more than 2^31 output pixels or an image above 2^28 elements is not supported");
     if (!DGRAD && bhalo) {
         // resident x rows for all nine taps (conv_halo_dgrad_bf16.h): bit-identical to tiles 1 / 3, same partial rows
         if (g.Ng == 64) launch_bhalo_fwd<2>(src, w, bias, addend, dst, bn_part, g, relu, st, io);
@@ -501,6 +508,7 @@ extern "C" int scouter_conv2d_fwd_bf16_io(const void* x, const void* wt_bf16, co
                    "conv2d_fwd_bf16: tile 4 (persistent) covers 1x1 / stride 1 / groups 1 layers with 64 / 128 / 256 / 512 input "
                    "channels stored as bf16, 128-multiples of output channels, no bias / addend / ReLU");
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
+    if (tile != 4) { if (const int rc = bf16_entry_check(g)) return rc; }       // (tile 4 has its own rule above)
     // tiles 1 (128 x 64) / 3 (128 x 32): the same 128-pixel partial rows (SCOUTER_BHALO=0: the tile kernel)
     const bool bhalo = sc_switch(SC_SW_BHALO) && bhalo_fwd_runs(g, tile, io);
     ScProfScope prof(bhalo ? "bhalo_fwd<bf16>" : names[tile], (hipStream_t)stream, 2.0 * g.M * Cout * g.Cg * kh * kw,
@@ -557,6 +565,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_bf16_io(const void* dy, const float* w
                    "BatchNorm-backward epilogue: Cout of 64 / 128 / 256 / 512, 128-multiples of Cin, every tensor stored as bf16; "
                    "without: Cout of 64 ... 1024, 64-multiples of Cin, dy stored as bf16, dx fp32");
     const int tile = tile_hint == 4 ? 4 : bf16_tile(g, tile_hint);
+    if (tile != 4) { if (const int rc = bf16_entry_check(g)) return rc; }       // (tile 4 has its own rule above)
     // algorithmic bytes: dy, dx and -- the fused launch -- the shortcut gradient, the BatchNorm input(s) and the ReLU bits
     const double out_elems = (double)g.M * Cin;
     const bool bhalo = sc_switch(SC_SW_BHALO) && bhalo_dgrad_runs(g, tile, epi, io);      // (SCOUTER_BHALO=0: the tile kernel)

@@ -67,6 +67,22 @@ inline bool sc_igemm_tile_ok(int Ng, int tile) {
     return (tile == 0 && Ng % 128 == 0) || ((tile == 1 || tile == 2) && Ng % 64 == 0) || tile == 3;
 }
 
+// ---- two limits of the block prologues every pixel-walking kernel shares (conv_igemm.hip, conv_bf16.hip, conv_x3.hip,
+// conv_planes.hip, conv_planes_persist.h, conv_xhalo.hip and the weight-gradient kernels); each family's rule calls them.
+// The tap validity of an A row is ONE 32-bit word (bit r*S + q): a filter with more taps would alias shifts of 32 and more onto
+// the low bits -- border pixels would take taps outside the image and drop taps inside it.
+#define SC_MASK_TAPS 32
+inline bool sc_tap_mask_ok(const ConvGeom& g) { return (long)g.R * g.S <= SC_MASK_TAPS; }
+// The pixel (y, x) of a GEMM row comes from fast_div (below), exact for arguments below SC_WALK_MAX.  What the prologues hand it:
+// blk_rem < Ho*Wo, blk_x + rowoff < Wo + SC_WALK_ROWS and blk_y + qx < Ho + SC_WALK_ROWS, rowoff (and so the row carry qx) below
+// the tallest block tile of any family (256 rows: the plane and resident-rows kernels; 128 here, 32 / 64 in the weight gradients).
+// Wo, Ho <= Ho*Wo, so one bound on the pixels of an image covers all three.
+#define SC_WALK_MAX (1 << 22)
+#define SC_WALK_ROWS 256
+inline bool sc_pixel_walk_ok(const ConvGeom& g) { return (long)g.Ho * g.Wo + SC_WALK_ROWS <= SC_WALK_MAX; }
+#define SC_TAP_MASK_MSG "filters of more than 32 taps are not supported (one 32-bit tap mask per row)"
+#define SC_PIXEL_WALK_MSG "more than 2^22 - 256 pixels per image are not supported (the fp32 pixel unflattening is exact below 2^22)"
+
 // epilogue of a call as the rules read it (include/scouter_hip.h SCOUTER_EPI_*)
 #define SC_EPI_BIAS 1
 #define SC_EPI_ADDEND 2
@@ -80,8 +96,12 @@ inline int sc_epi_bits(const void* bias, const void* addend, int relu, const voi
            (part1 ? SC_EPI_BN_BWD : 0) | (part2 ? SC_EPI_BN_BWD2 : 0);
 }
 
-// floor(n / d) for 0 <= n < 2^20 with inv = 1/d: (n + 0.5) / d is at least 0.5/d away from every integer, far more
-// than the float rounding error at these magnitudes, so truncation is exact (3 VALU instead of ~40 for a division)
+// floor(n / d) for 0 <= n < 2^22 (SC_WALK_MAX) and every d >= 1, with inv = 1.0f / (float)d: (n + 0.5) / d is at least 0.5/d away
+// from every integer; n + 0.5 is exact in fp32 below 2^23 and the two roundings (of inv, of the product) move the quotient by
+// less than that up to 2^22 -- proved by enumeration of n = k*d - 1 and n = k*d for every d (tests/test_conv_tiles_cpu.py; the
+// expression is monotone in n).  Beyond it the truncation IS wrong: n = 4 201 469, d = 4095 is the first failure, and n =
+// 4 275 584, d = 255 (a block start) gives 16 767 for 16 766.  sc_pixel_walk_ok below keeps every caller inside the domain
+// (3 VALU instead of ~40 for a division)
 __device__ __forceinline__ int fast_div(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
 
 

@@ -796,8 +796,16 @@ static void launch_xpw_fwd(const float* src, const float* w, float* dst, double*
 }
 
 // what both entry points ask of every shape
-static bool igemm_entry_ok(const ConvGeom& g) {
+static bool igemm_size_ok(const ConvGeom& g) {
     return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28);
+}
+// (the pointwise instantiation walks no pixels and has no taps: launch_igemm's `pw` -- which also asks 4 * BM * C < 2^31; a
+// pointwise shape past that has C >= 2^22, so by the size rule at most 64 pixels per image)
+static bool igemm_pointwise(const ConvGeom& g) {
+    return g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.H == g.Ho && g.W == g.Wo;
+}
+static bool igemm_entry_ok(const ConvGeom& g) {
+    return igemm_size_ok(g) && sc_tap_mask_ok(g) && (igemm_pointwise(g) || sc_pixel_walk_ok(g));
 }
 // naming `tile` runs that tile's kernel for this shape and epilogue (SC_EPI_*).  Tiles 0-3 are hints: where one does not divide
 // Ng the heuristic below picks another; the persistent tiles 4 / 5 are refused where the epilogue is not theirs
@@ -822,11 +830,18 @@ static int igemm_tile(const ConvGeom& g, int hint = -1) {     // 0: 128x128  1: 
     return 3;
 }
 
+// the entry points' refusal by igemm_entry_ok, before the profile row of the launch is opened
+static int igemm_entry_check(const ConvGeom& g) {
+    SC_UNSUPPORTED(igemm_size_ok(g), "conv2d: more than 2^31 output pixels or an image above 2^28 elements is not supported");
+    SC_UNSUPPORTED(sc_tap_mask_ok(g), "conv2d: " SC_TAP_MASK_MSG);
+    SC_UNSUPPORTED(igemm_entry_ok(g), "conv2d: " SC_PIXEL_WALK_MSG);
+    return 0;
+}
+
 template <bool DGRAD>
 static int dispatch_igemm(const float* src, const float* w, const float* bias, const float* addend, float* dst,
                           double* bn_part, const ConvGeom& g, int relu, int tile, hipStream_t st,
                           const BnBwdFuse& fz = BnBwdFuse{}) {
-    SC_UNSUPPORTED(igemm_entry_ok(g), "conv2d: more than 2^31 output pixels or an image above 2^28 elements is not supported");
     const int epi = sc_epi_bits(bias, addend, relu, bn_part, fz.part1, fz.part2);
     if (tile == 4) {
         // (the caller named the persistent kernel: its partial-row layout differs, so an unsupported request is an error,
@@ -894,6 +909,7 @@ extern "C" int scouter_conv2d_fwd_f32(const float* x, const float* w, const floa
                                    "igemm_fwd<persistent>", "xpw_fwd<bf16x3>"};
     SC_UNSUPPORTED(tile_hint != 5 || xpw_geom_ok(g), "conv2d_fwd: tile 5 (persistent bf16x3 kernel) covers 1x1 / stride 1 / groups 1 "
                    "layers with 64 / 128 / 256 input channels and 64-multiples of output channels");
+    if (const int rc = igemm_entry_check(g)) return rc;
     const int tile = igemm_tile(g, tile_hint);
     ScProfScope prof(names[tile], (hipStream_t)stream, 2.0 * g.M * Cout * g.Cg * kh * kw,
                      4.0 * ((double)B * H * W * Cin + (double)g.M * Cout));
@@ -933,6 +949,7 @@ extern "C" int scouter_conv2d_dgrad_bnbwd_f32(const float* dy, const float* w, c
     SC_UNSUPPORTED(tile_hint != 5 || (part1 && xpw_geom_ok(g)),
                    "conv2d_dgrad: tile 5 (persistent bf16x3 kernel) covers 1x1 / stride 1 / groups 1 input gradients with the fused "
                    "BatchNorm-backward epilogue, Cout of 64 / 128 / 256, 64-multiples of Cin");
+    if (const int rc = igemm_entry_check(g)) return rc;
     const int tile = igemm_tile(g, tile_hint);
     const double out_elems = (double)g.M * Cin;
     ScProfScope prof(part1 ? names_bn[tile] : names[tile], (hipStream_t)stream,
@@ -991,10 +1008,17 @@ static ConvGeom wgrad_geom(int B, int H, int W, int Cin, int Cout, int kh, int k
 // have tap-fused kernels: fp32 (conv_wgrad_taps.h), behind switch xwt the register-split bf16x3 one on maps up to 112 wide
 // (conv_wgrad_taps_x3.h), and -- the bf16-input entry point, both operands STORED as bf16, switch bwt -- the one-plane kernel
 // (conv_wgrad_taps_bf16.h).  Everything else: one workgroup per tap (wgrad_plan).
-static bool wgrad_entry_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0; }
+// "same" stride-1 convolutions: 2 = pointwise, 1 = at most one row wrap and one image wrap per `chunk` pixels, 0 = neither
+static int wgrad_same_mode(const ConvGeom& g, int chunk) {
+    const bool same = g.stride == 1 && g.Ho == g.H && g.Wo == g.W;
+    return !same ? 0 : (g.R == 1 && g.S == 1 && g.pad == 0) ? 2 : (chunk / g.Wo + 1 < g.Ho ? 1 : 0);
+}
+// (mode 2, the pointwise layers, needs no pixel coordinates; every other mode unflattens its chunk's first pixel)
+static bool wgrad_walk_ok(const ConvGeom& g, int chunk) { return wgrad_same_mode(g, chunk) == 2 || sc_pixel_walk_ok(g); }
+static bool wgrad_entry_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0 && wgrad_walk_ok(g, BK); }
 static bool wgrad_taps_geom_ok(const ConvGeom& g) {
     return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Cg == 32 && BK / g.Wo + 1 < g.Ho && g.M < (1L << 31) &&
-           (long)(2 * g.W + 2) * g.C * 4 < (1L << 31);
+           (long)(2 * g.W + 2) * g.C * 4 < (1L << 31) && sc_pixel_walk_ok(g);
 }
 // the layers whose plan the wrappers leave to the library (the deep stem, layer1's radix convolutions): 3x3 / stride 1 / pad 1 with
 // 32 input channels per group on a map at most 112 pixels wide -- the shape the register-split and the one-plane kernel share
@@ -1002,13 +1026,8 @@ static bool wgrad_rows32_ok(const ConvGeom& g) {
     return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Cg == 32 && g.W <= 112 && g.H >= 2;
 }
 static bool xwt_geom_ok(const ConvGeom& g) { return wgrad_rows32_ok(g) && wgrad_taps_geom_ok(g) && BK == 32; }
-// "same" stride-1 convolutions: 2 = pointwise, 1 = at most one row wrap and one image wrap per `chunk` pixels, 0 = neither
-static int wgrad_same_mode(const ConvGeom& g, int chunk) {
-    const bool same = g.stride == 1 && g.Ho == g.H && g.Wo == g.W;
-    return !same ? 0 : (g.R == 1 && g.S == 1 && g.pad == 0) ? 2 : (chunk / g.Wo + 1 < g.Ho ? 1 : 0);
-}
 static bool wgrad_bf16_geom_ok(const ConvGeom& g) {
-    return wgrad_same_mode(g, 64) != 0 && g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31);
+    return wgrad_same_mode(g, 64) != 0 && g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.M < (1L << 31) && wgrad_walk_ok(g, 64);
 }
 static bool bwt_geom_ok(const ConvGeom& g, int io) {
     return wgrad_bf16_geom_ok(g) && (io & SC_IO_X_BF16) && (io & SC_IO_R_BF16) && wgrad_rows32_ok(g) && BWT_CH / g.Wo + 1 < g.Ho &&
@@ -1080,7 +1099,7 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     SC_REQUIRE(x && dy && dw && B > 0, "conv2d_wgrad: null pointer or empty shape");
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad: channels not divisible by groups");
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    SC_UNSUPPORTED(wgrad_entry_ok(g), "conv2d_wgrad: per-group channels must be multiples of 32");
+    SC_UNSUPPORTED(wgrad_entry_ok(g), "conv2d_wgrad: per-group channels must be multiples of 32; " SC_PIXEL_WALK_MSG);
     // 3x3 / stride 1 / pad 1 with 32 input channels per group: tap-fused kernel (conv_wgrad_taps.h)
     if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {
         const int bn = g.Ng % 64 == 0 ? 64 : 32;
@@ -1203,7 +1222,7 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad_bf16: channels not divisible by groups");
     ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     const int mode = wgrad_same_mode(g, 64);
-    SC_UNSUPPORTED(wgrad_bf16_geom_ok(g), "conv2d_wgrad_bf16: shape not covered by the bf16 kernel");
+    SC_UNSUPPORTED(wgrad_bf16_geom_ok(g), "conv2d_wgrad_bf16: shape not covered by the bf16 kernel; " SC_PIXEL_WALK_MSG);
     // 3x3 / stride 1 / pad 1 with 32 input channels per group, both operands stored as bf16: tap-fused kernel (conv_wgrad_taps_bf16.h;
     // the library's own plan, SCOUTER_BWT=0: off) -- every X row fetched once per workgroup instead of once per tap
     if (plan_hint < 0 && bwt_geom_ok(g, io)) {

@@ -784,7 +784,7 @@ static bool ppersist_stores(int io) { return !(io & SC_IO_Y_BF16); }
 static bool pconv_channels_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 64 == 0; }
 static bool pconv_size_ok(const ConvGeom& g, int nplanes) {
     const long img = (long)g.H * g.W * g.C, a_pe = g.B * img;
-    return g.M < (1L << 31) && (long)nplanes * a_pe * 2 < (1L << 31) + img * 2 && img < (1L << 28);
+    return g.M < (1L << 31) && (long)nplanes * a_pe * 2 < (1L << 31) + img * 2 && img < (1L << 28) && sc_tap_mask_ok(g) && sc_pixel_walk_ok(g);
 }
 // naming `tile` runs that tile's kernel (dispatch_pconv below, which maps every other request to the 128 x (128 | 64) kernel):
 // 0 = 128x128, 1 = 128x64 with three LDS stages, three planes only 2 = 128x64 with two, 3 = 64x64, 4 = 256x128; 5 = resident
@@ -876,7 +876,7 @@ extern "C" int scouter_conv2d_fwd_planes_io(const void* x_planes, const void* w_
     const int Cg = g.Cg;
     SC_UNSUPPORTED(pconv_channels_ok(g), "conv2d_fwd_planes: needs Cin/groups %% 32 == 0 and Cout/groups %% 64 == 0");
     const long a_pe = (long)B * H * W * Cin, w_pe = (long)kh * kw * Cg * Cout;
-    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_fwd_planes: tensor too large for 32-bit plane offsets");
+    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_fwd_planes: tensor too large for 32-bit plane offsets; " SC_TAP_MASK_MSG "; " SC_PIXEL_WALK_MSG);
     ScProfScope prof(nplanes == 3 ? "pconv_fwd<bf16x3>" : "pconv_fwd<bf16>", (hipStream_t)stream,
                      2.0 * g.M * Cout * Cg * kh * kw,
                      2.0 * nplanes * ((double)a_pe) + ((io & SC_IO_Y_BF16) ? 2.0 : 4.0) * (double)g.M * Cout);
@@ -909,7 +909,7 @@ extern "C" int scouter_conv2d_dgrad_planes_bnbwd(const void* dy_planes, const vo
     const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
     SC_UNSUPPORTED(pconv_channels_ok(g), "conv2d_dgrad_planes: needs Cout/groups %% 32 == 0 and Cin/groups %% 64 == 0");
     const long a_pe = (long)B * g.H * g.W * Cout, w_pe = (long)kh * kw * Cig * Cout;
-    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_dgrad_planes: tensor too large for 32-bit plane offsets");
+    SC_UNSUPPORTED(pconv_size_ok(g, nplanes), "conv2d_dgrad_planes: tensor too large for 32-bit plane offsets; " SC_TAP_MASK_MSG "; " SC_PIXEL_WALK_MSG);
     ScProfScope prof(nplanes == 3 ? "pconv_dgrad<bf16x3>" : "pconv_dgrad<bf16>", (hipStream_t)stream,
                      2.0 * g.M * Cin * Cog * kh * kw, 2.0 * nplanes * ((double)a_pe) + 4.0 * (double)g.M * Cin);
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2};
@@ -1220,7 +1220,7 @@ static PwgPlan pwg_plan(long M, int Cg, int Ng, int groups, int taps, int plan_h
 
 // same-size convolutions with 64-multiples of channels per group, at most one row wrap and one image wrap per 32-pixel chunk
 static bool pwgrad_shape_ok(const ConvGeom& g) {
-    return g.R == g.S && 2 * g.pad == g.R - 1 && g.Cg % 64 == 0 && g.Ng % 64 == 0 && 32 / g.W + 1 < g.H;
+    return g.R == g.S && 2 * g.pad == g.R - 1 && g.Cg % 64 == 0 && g.Ng % 64 == 0 && 32 / g.W + 1 < g.H && sc_pixel_walk_ok(g);
 }
 static bool pwgrad_size_ok(const ConvGeom& g, int nplanes) {
     return g.M < (1L << 31) && (long)nplanes * g.M * g.C * 2 < (1L << 32) && (long)nplanes * g.M * g.N * 2 < (1L << 32);
@@ -1256,7 +1256,7 @@ extern "C" int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_
     SC_REQUIRE(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_wgrad_planes: channels not divisible by groups");
     const int Cg = Cin / groups, Ng = Cout / groups;
     const ConvGeom g = sc_with_reciprocals(sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups));
-    SC_UNSUPPORTED(pwgrad_shape_ok(g), "conv2d_wgrad_planes: same-size convolutions with 64-multiples of channels per group only");
+    SC_UNSUPPORTED(pwgrad_shape_ok(g), "conv2d_wgrad_planes: same-size convolutions with 64-multiples of channels per group only; " SC_PIXEL_WALK_MSG);
     const long x_pe = g.M * Cin, dy_pe = g.M * Cout;
     SC_UNSUPPORTED(pwgrad_size_ok(g, nplanes), "conv2d_wgrad_planes: tensor too large for 32-bit plane offsets");
     const PwgPlan plan = pwg_plan(g.M, Cg, Ng, groups, kh * kw, plan_hint);

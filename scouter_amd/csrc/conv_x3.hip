@@ -390,8 +390,9 @@ static int dispatch_x3(const float* a, const void* w, long w_pe, const float* bi
 static bool x3_filter_ok(const ConvGeom& g) { return g.R == g.S && (g.R & 1) && 2 * g.pad == g.R - 1 && g.R <= 5 && g.stride == 1; }
 static bool x3_channels_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.R * g.S * (g.Cg / 32) >= 2; }
 static bool x3_size_ok(const ConvGeom& g) {
+    // (the pointwise groups-1 instantiation walks no pixels; x3_filter_ok keeps the taps at 25)
     return g.M < (1L << 31) && (long)g.R * g.S * g.wtap * 2 * 3 < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28) &&
-           256L * g.C * 4 < (1L << 31);
+           256L * g.C * 4 < (1L << 31) && sc_tap_mask_ok(g) && ((g.R == 1 && g.S == 1 && g.groups == 1) || sc_pixel_walk_ok(g));
 }
 // naming `tile` runs that tile's kernel; tile 7 = the resident-rows kernel of conv_xhalo.hip (the forward: no bias / addend).
 // tile < 0: the library's choice
@@ -431,7 +432,7 @@ extern "C" int scouter_conv2d_fwd_x3(const float* x, const void* w_planes_fwd, c
     const int Cg = g.Cg, Ng = g.Ng;
     SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_fwd_x3: 1x1 or odd same-size filters only");
     SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_fwd_x3: needs 32-multiples of channels per group and two K-tiles");
-    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_fwd_x3: tensor too large for 32-bit offsets");
+    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_fwd_x3: tensor too large for 32-bit offsets, or " SC_PIXEL_WALK_MSG);
     const long w_pe = (long)kh * kw * Cg * Cout;
     if (tile_hint == 7) {           // resident rows, split once per element, persistent (conv_xhalo.hip): 32 columns per group
         SC_UNSUPPORTED(x3_named_tile_ok<false>(g, 7, sc_epi_bits(bias, addend, relu, bn_partial)), "conv2d_fwd_x3: tile 7 covers 3x3 / pad 1 layers with 32 output channels per "
@@ -461,7 +462,7 @@ extern "C" int scouter_conv2d_dgrad_x3_bnbwd(const float* dy, const void* w_plan
     const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
     SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_dgrad_x3: 1x1 or odd same-size filters only");
     SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_dgrad_x3: needs 32-multiples of channels per group and two K-tiles");
-    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_dgrad_x3: tensor too large for 32-bit offsets");
+    SC_UNSUPPORTED(x3_size_ok(g), "conv2d_dgrad_x3: tensor too large for 32-bit offsets, or " SC_PIXEL_WALK_MSG);
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2, 0};
     const long w_pe = (long)kh * kw * Cig * Cout;
     if (tile_hint == 7) {           // (conv_xhalo.hip: 32 input channels per group = 32 GEMM columns)

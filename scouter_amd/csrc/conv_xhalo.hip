@@ -392,7 +392,7 @@ static int xh_grid(int groups) {
 bool sc_xhalo_ok(const ConvGeom& g) {
     return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.H == g.Ho && g.W == g.Wo && g.W <= 126 && g.Ng == 32 &&
            g.Cg % 16 == 0 && g.Cg >= 16 && g.M * g.C * 4 < (1L << 31) && g.M * g.N * 4 < (1L << 31) &&
-           (long)9 * g.N * g.Cg * 2 * 3 < (1L << 31);
+           (long)9 * g.N * g.Cg * 2 * 3 < (1L << 31) && sc_pixel_walk_ok(g);
 }
 int sc_xhalo_partial_rows(int groups) { return xh_grid(groups) / groups; }
 
