@@ -1193,6 +1193,39 @@ int scouter_sa_apply_relu_bwd_f32(const float* dout, const float* a, const float
 int scouter_maxpool_relu_bwd_f32(const float* dy, const unsigned char* argmax, const float* h, float* dx, int B, int H, int W,
                                  int C, int k, int stride, int pad, void* stream);
 
+/* ---- The rule a ReLU's backward applies in that backward (ImagePass.grad_from `rule`): with g the gradient arriving at the
+ * ReLU's output and y that output,
+ *   0 gradient    y > 0 ? g : +0                 the derivative: what the four entry points without `rule` compute
+ *   1 guided      (y > 0 && g > 0) ? g : +0      guided backpropagation (Springenberg et al. 2015)
+ *   2 deconvnet   g > 0 ? g : +0                 the deconvnet rule (Zeiler & Fergus 2014)
+ * in plain fp32 comparisons: a NaN or a -0 in g gives +0 under rules 1 and 2.  g is the value the kernel forms in front of its
+ * mask: dy (relu_bwd), the row dot sum_n dz[n] w2[j][n] (sa_gate_bwd; h is re-formed and h_out written under every rule),
+ * dout * a_r + dgap / HW with the roundings of rule 0 (sa_apply_relu_bwd), the gathered sum of the windows that chose the pixel in
+ * the order of rule 0 (maxpool_relu_bwd; the gather itself is the ordinary one).  The rule is a compile-time argument of the
+ * kernels: rule 0 runs the code and gives the bits of the entry point without `rule`; rule 2 issues no load of the activation
+ * (y / x0 / h; 12 instead of 20 bytes per dout element in sa_apply_relu_bwd), whose pointer is still checked like the others.
+ * Any other rule is SC_ERR_ARG before any launch; every other argument and refusal is that of the entry point without `rule`. */
+#define SCOUTER_RULE_GRADIENT 0
+#define SCOUTER_RULE_GUIDED 1
+#define SCOUTER_RULE_DECONVNET 2
+int scouter_relu_bwd_rule_f32(const float* dy, const float* y, float* dx, long n, int rule, void* stream);
+int scouter_sa_gate_bwd_rule_f32(const float* gap, const float* w1, const float* b1, const float* w2, const float* a,
+                                 const float* da, float* dgap, float* h_out, int B, int Cp, int A, int rule, void* stream);
+int scouter_sa_apply_relu_bwd_rule_f32(const float* dout, const float* a, const float* dgap, const float* x0, float* dx, int B,
+                                       int HW, int Cp, int rule, void* stream);
+int scouter_maxpool_relu_bwd_rule_f32(const float* dy, const unsigned char* argmax, const float* h, float* dx, int B, int H,
+                                      int W, int C, int k, int stride, int pad, int rule, void* stream);
+
+/* Guided Grad-CAM's product: out[b][c][y][x] = grad[b][c][y][x] * up(cam[b])[y][x], one fp32 multiplication per element.  grad /
+ * out dense NCHW fp32 [B][C][H][W] (out == grad allowed; any other overlap is refused), cam [h][w] dense per image, image b at
+ * cam + b * cam_stride_b (any stride >= h * w: a column of a [B][K][h][w] tensor).  mode 0: nearest, source index (y h) / H and
+ * (x w) / W in integer arithmetic (F.interpolate(mode = "nearest") whenever H % h == 0 and W % w == 0); mode 1: bilinear,
+ * align_corners = False, the expressions and the bits of scouter_resize_bilinear_f32.  16-byte accesses when W % 4 == 0 and grad
+ * and out are 16-byte aligned, one element at a time otherwise.  Deterministic, no atomics.  Pointers 4-byte aligned; C * H * W and
+ * h * w below 2^31. */
+int scouter_guided_cam_f32(const float* grad, const float* cam, float* out, int B, int C, int H, int W, int h, int w,
+                           long cam_stride_b, int mode, void* stream);
+
 /* p[i] += v for n 64-bit counters (the num_batches_tracked buffers of a model as views of one flat buffer: one launch per
  * training forward instead of one ATen launch; torch.nn.BatchNorm2d increments them one by one) */
 int scouter_iadd_i64(long* p, long n, long v, void* stream);

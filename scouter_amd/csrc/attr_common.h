@@ -1,5 +1,5 @@
 // The device expressions the attribution kernels share (gradcam.hip, gradcampp.hip, rise.hip, scorecam.hip, causal.hip,
-// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip, occlusion.hip, ablation.hip, layerattr.hip, gradshap.hip), each defined ONCE: where two kernels promise the same bits --
+// pathgrad.hip, fidelity.hip, extremal.hip, iba.hip, igos.hip, surrogate.hip, occlusion.hip, ablation.hip, layerattr.hip, gradshap.hip, guided.hip), each defined ONCE: where two kernels promise the same bits --
 // heat_maps and cam_maps at the map's own size, resize_bilinear and the resize inside cam_maps and scorecam_ranges -- they call
 // the same inlined function here on the same operands.  (The mask and the fma chain of the Score-CAM family have one file,
 // scorecam.hip, and are defined there.)  Inlined functions and templates only: no kernel, no entry point, no state.

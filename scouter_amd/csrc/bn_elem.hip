@@ -5,6 +5,7 @@
 // Replaces nn.BatchNorm2d / ReLU / MaxPool2d / AvgPool2d of the reference backbone (timm/models/resnet.py:383,
 // 404-412, 292-306; resnest.py:93,128-129) and their autograd backward.
 #include "common.h"
+#include "relu_rule.h"
 
 #include <string>
 #include <vector>
@@ -485,13 +486,17 @@ __global__ __launch_bounds__(256) void colsum_finalize_kernel(const double* __re
 }
 
 // g = dy * (y > 0)   (ReLU backward where no BN follows, e.g. the head's conv1x1+ReLU)
+// RULE (relu_rule.h): 0 is that; 1 / 2 the guided-backpropagation / deconvnet rules of the folded path's backward.  Rule 2 does
+// not read y.
+template <int RULE>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                        float* __restrict__ dx, long n4) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         f32x4 g = *(const f32x4*)(dy + i * 4);
-        const f32x4 v = *(const f32x4*)(y + i * 4);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (rule_reads_activation<RULE>) v = *(const f32x4*)(y + i * 4);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] = v[k] > 0.f ? g[k] : 0.f;
+        for (int k = 0; k < 4; ++k) g[k] = relu_rule<RULE>(g[k], v[k]);
         *(f32x4*)(dx + i * 4) = g;
     }
 }
@@ -1330,7 +1335,17 @@ extern "C" int scouter_colsum_f32(const float* a, const float* b, float* out, lo
 
 extern "C" int scouter_relu_bwd_f32(const float* dy, const float* y, float* dx, long n, void* stream) {
     SC_REQUIRE(dy && y && dx && n % 4 == 0, "relu_bwd: null pointer or n %% 4 != 0");
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n / 4);
+    hipLaunchKernelGGL(relu_bwd_kernel<RULE_GRADIENT>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n / 4);
+    return sc_check_launch("relu_bwd");
+}
+
+extern "C" int scouter_relu_bwd_rule_f32(const float* dy, const float* y, float* dx, long n, int rule, void* stream) {
+    SC_REQUIRE(dy && y && dx && n % 4 == 0, "relu_bwd: null pointer or n %% 4 != 0");
+    SC_REQUIRE_RULE(rule, "relu_bwd");
+    rule_dispatch(rule, [&](auto r) {
+        hipLaunchKernelGGL(relu_bwd_kernel<decltype(r)::value>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, y, dx,
+                           n / 4);
+    });
     return sc_check_launch("relu_bwd");
 }
 

@@ -1264,9 +1264,29 @@ def iadd_i64(t, v=1):
     return t
 
 
-def relu_bwd(dy, y):
+# the rule a ReLU's backward applies in the gradient-only backward of the folded path (include/scouter_hip.h SCOUTER_RULE_*):
+# the derivative, guided backpropagation, the deconvnet rule
+RULE_GRADIENT, RULE_GUIDED, RULE_DECONVNET = 0, 1, 2
+
+
+def _chk_rule(rule, what):
+    """refused on the host, before any launch; a bool is no rule"""
+    if isinstance(rule, bool) or not isinstance(rule, int) or rule not in (RULE_GRADIENT, RULE_GUIDED, RULE_DECONVNET):
+        raise ValueError("%s: rule must be RULE_GRADIENT (0), RULE_GUIDED (1) or RULE_DECONVNET (2), got %r" % (what, rule))
+    return rule
+
+
+def relu_bwd(dy, y, rule=RULE_GRADIENT):
+    """dx = [y > 0] dy; rule: RULE_GUIDED keeps the positive part of that, RULE_DECONVNET the positive part of dy (y is not read)"""
+    if _chk_rule(rule, "relu_bwd") == RULE_GRADIENT:
+        dx = torch.empty_like(dy)
+        _native.check(_native.lib().scouter_relu_bwd_f32(_p(dy), _p(y), _p(dx), dy.numel(), _stream()), "relu_bwd")
+        return dx
+    _chk(dy, "dy"); _chk(y, "y")
+    if y.shape != dy.shape:
+        raise RuntimeError("relu_bwd: dy %s and y %s must have the same shape" % (tuple(dy.shape), tuple(y.shape)))
     dx = torch.empty_like(dy)
-    _native.check(_native.lib().scouter_relu_bwd_f32(_p(dy), _p(y), _p(dx), dy.numel(), _stream()), "relu_bwd")
+    _native.check(_native.lib().scouter_relu_bwd_rule_f32(_p(dy), _p(y), _p(dx), dy.numel(), rule, _stream()), "relu_bwd")
     return dx
 
 
@@ -1529,11 +1549,13 @@ def sa_apply_bwd(dout, a, dgap):
 
 
 # ---- the gradient-only backward of the folded eval path (csrc/fold_bwd.hip; SlotModel.image_pass)
-def sa_gate_bwd(gap, w1, b1, w2, a, da, want_h=False):
+def sa_gate_bwd(gap, w1, b1, w2, a, da, want_h=False, rule=RULE_GRADIENT):
     """The backward of sa_gate_fwd in one launch: da [B, 2C'] (the gradient of its output a) -> dgap [B, C'], through the radix
     softmax, fc2, the ReLU of the hidden activation h = relu(gap . w1 + b1) -- re-formed with the forward's own device function,
     the same bits -- and the folded fc1.  want_h: returns (dgap, h [B, A]).  One workgroup per image: a row does not depend on
-    the batch it is computed in.  The shapes of sa_gate_eligible."""
+    the batch it is computed in.  The shapes of sa_gate_eligible.  rule: what the hidden ReLU's backward does to the row dot
+    dz . w2^T (RULE_*); h is re-formed and returned under every rule."""
+    _chk_rule(rule, "sa_gate_bwd")
     for n, t in (("gap", gap), ("w1", w1), ("b1", b1), ("w2", w2), ("a", a), ("da", da)):
         _chk(t, n)
     B, Cp = gap.shape
@@ -1542,33 +1564,37 @@ def sa_gate_bwd(gap, w1, b1, w2, a, da, want_h=False):
     assert tuple(a.shape) == (B, 2 * Cp) and tuple(da.shape) == (B, 2 * Cp)
     dgap = torch.empty((B, Cp), dtype=F32, device=gap.device)
     h = torch.empty((B, A), dtype=F32, device=gap.device) if want_h else None
-    _native.check(_native.lib().scouter_sa_gate_bwd_f32(_p(gap), _p(w1), _p(b1), _p(w2), _p(a), _p(da), _p(dgap), _p(h), B, Cp, A,
-                                                        _stream()), "sa_gate_bwd")
+    _native.check(_native.lib().scouter_sa_gate_bwd_rule_f32(_p(gap), _p(w1), _p(b1), _p(w2), _p(a), _p(da), _p(dgap), _p(h), B, Cp,
+                                                             A, rule, _stream()), "sa_gate_bwd")
     return (dgap, h) if want_h else dgap
 
 
-def sa_apply_relu_bwd(dout, a, dgap, x0):
+def sa_apply_relu_bwd(dout, a, dgap, x0, rule=RULE_GRADIENT):
     """sa_apply_bwd and relu_bwd(., x0) in one pass: dx [B, H, W, 2C'] = [x0 > 0] * (dout * a_r + dgap / HW), x0 the folded radix
-    convolution's output (stored after its ReLU)."""
+    convolution's output (stored after its ReLU).  rule: what that ReLU's backward does to dout * a_r + dgap / HW (RULE_*);
+    RULE_DECONVNET does not read x0."""
+    _chk_rule(rule, "sa_apply_relu_bwd")
     for n, t in (("dout", dout), ("a", a), ("dgap", dgap), ("x0", x0)):
         _chk(t, n)
     B, H, W, Cp = dout.shape
     assert tuple(x0.shape) == (B, H, W, 2 * Cp) and a.numel() == B * 2 * Cp and dgap.numel() == B * Cp
     dx = torch.empty((B, H, W, 2 * Cp), dtype=F32, device=dout.device)
-    _native.check(_native.lib().scouter_sa_apply_relu_bwd_f32(_p(dout), _p(a), _p(dgap), _p(x0), _p(dx), B, H * W, Cp, _stream()),
-                  "sa_apply_relu_bwd")
+    _native.check(_native.lib().scouter_sa_apply_relu_bwd_rule_f32(_p(dout), _p(a), _p(dgap), _p(x0), _p(dx), B, H * W, Cp, rule,
+                                                                   _stream()), "sa_apply_relu_bwd")
     return dx
 
 
-def maxpool_relu_bwd(dy, arg, h, k=3, stride=2, pad=1):
-    """maxpool_bwd followed by relu_bwd(., h) in one pass (the same bits): h [B, H, W, C] the pool's input, a ReLU's output."""
+def maxpool_relu_bwd(dy, arg, h, k=3, stride=2, pad=1, rule=RULE_GRADIENT):
+    """maxpool_bwd followed by relu_bwd(., h) in one pass (the same bits): h [B, H, W, C] the pool's input, a ReLU's output.
+    rule: what that ReLU's backward does to the gathered sum (RULE_*); the gather is the same, RULE_DECONVNET does not read h."""
+    _chk_rule(rule, "maxpool_relu_bwd")
     _chk(dy, "dy"); _chk(h, "h")
     B, H, W, C = h.shape
     assert arg.dtype == torch.uint8 and arg.is_contiguous() and tuple(arg.shape) == tuple(dy.shape)
     assert tuple(dy.shape) == (B, pool_out(H, k, stride, pad), pool_out(W, k, stride, pad), C)
     dx = torch.empty_like(h)
-    _native.check(_native.lib().scouter_maxpool_relu_bwd_f32(_p(dy), _p(arg), _p(h), _p(dx), B, H, W, C, k, stride, pad,
-                                                             _stream()), "maxpool_relu_bwd")
+    _native.check(_native.lib().scouter_maxpool_relu_bwd_rule_f32(_p(dy), _p(arg), _p(h), _p(dx), B, H, W, C, k, stride, pad, rule,
+                                                                  _stream()), "maxpool_relu_bwd")
     return dx
 
 
@@ -1859,6 +1885,41 @@ def cam_maps(cam, H, W, min_level=0.0):
     out = torch.empty(lead + (int(H), int(W)), dtype=torch.uint8, device=cam.device)
     _native.check(_native.lib().scouter_cam_maps_u8(_p(cam), _p(out), M, h, w, int(H), int(W), float(min_level), _stream()),
                   "cam_maps")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Guided Grad-CAM's product (csrc/guided.hip; tools/attribution.py guided_gradcam)
+# ---------------------------------------------------------------------------------------------------------------
+GUIDED_CAM_MODES = {"nearest": 0, "bilinear": 1}
+
+
+def guided_cam(grad, cam, out=None, mode="nearest"):
+    """out[b, c, y, x] = grad[b, c, y, x] * up(cam[b])[y, x], one fp32 multiplication per element: grad fp32 NCHW [B, C, H, W],
+    cam fp32 [B, h, w] dense within an image with ANY batch stride (a column `t[:, k]` of a [B, K, h, w] tensor, as `gradcam`
+    fills it), out fp32 [B, C, H, W] dense (None: a new tensor; `grad` itself: in place; a column of a [B, K, C, H, W] tensor is
+    NOT dense and is refused).  mode "nearest": the source index (y h) // H, (x w) // W in integer arithmetic, F.interpolate's
+    nearest whenever H % h == 0 and W % w == 0; "bilinear": the resize of `resize_bilinear`, the same bits.  One launch in which
+    the upsampled value is formed once for the C channels of a pixel."""
+    if mode not in GUIDED_CAM_MODES:
+        raise ValueError("guided_cam: mode must be 'nearest' or 'bilinear', got %r" % (mode,))
+    _chk(grad, "guided_cam: grad")
+    if grad.dim() != 4:
+        raise RuntimeError("guided_cam: grad must be NCHW [B, C, H, W], got shape %s" % (tuple(grad.shape),))
+    B, C, H, W = grad.shape
+    if not torch.is_tensor(cam) or not cam.is_cuda or cam.dtype != F32 or cam.dim() != 3 or cam.shape[0] != B or \
+            (cam[0].numel() > 0 and not cam[0].is_contiguous()) or (B > 1 and cam.stride(0) < cam[0].numel()):
+        raise RuntimeError("guided_cam: cam must be fp32 [B = %d, h, w] on the device, dense within an image (got %s %s, strides %s)"
+                           % (B, getattr(cam, "dtype", None), tuple(getattr(cam, "shape", ())),
+                              cam.stride() if torch.is_tensor(cam) else None))
+    h, w = cam.shape[1:]
+    if out is None:
+        out = torch.empty_like(grad)
+    _chk(out, "guided_cam: out")
+    if out.shape != grad.shape:
+        raise RuntimeError("guided_cam: out must be fp32 %s, got shape %s" % (tuple(grad.shape), tuple(out.shape)))
+    _native.check(_native.lib().scouter_guided_cam_f32(_p(grad), _p(cam), _p(out), B, C, H, W, h, w, cam.stride(0),
+                                                       GUIDED_CAM_MODES[mode], _stream()), "guided_cam")
     return out
 
 

@@ -111,17 +111,49 @@ class ImagePass:
         self.features, self.log_probs = features, log_probs
         self._model, self._bstate, self._hstate, self._wds, self._gen = model, bstate, hstate, wds, gen
 
+    RULES = {"gradient": K.RULE_GRADIENT, "guided": K.RULE_GUIDED, "deconvnet": K.RULE_DECONVNET}
+
+    def _check(self, rule):
+        """the refusals of grad / grad_from that come before any launch -> the kernels' rule"""
+        if not isinstance(rule, str) or rule not in self.RULES:
+            raise ValueError("rule must be 'gradient', 'guided' or 'deconvnet', got %r" % (rule,))
+        if self._model._fold_gen != self._gen:
+            raise RuntimeError("ImagePass.grad: the model has folded its weights again since this pass; run image_pass again")
+        return self.RULES[rule]
+
     @torch.no_grad()
     def grad(self, seed):
         """seed: fp32 [B, n_outputs] on the device -> d(sum seed * log_probs) / d x, NCHW fp32 in the shape of the pass's images:
         one head backward (as FeaturePass.grad, with its refusals and its effect on the head's `.grad`), then the backbone's
         input gradients on the folded weights (ResNet.image_bwd) -- no BatchNorm kernel, no backbone parameter gradient.  May be
-        called any number of times; a pass whose model has folded again since (new weights in the same buffers) refuses."""
+        called any number of times; a pass whose model has folded again since (new weights in the same buffers) refuses.
+        It is grad_from(feature_grad(seed)): its parameter list is pinned (tests/test_foldgrad_cpu.py), so the gradient under
+        another ReLU rule is grad_from(feature_grad(seed), rule)."""
+        self._check("gradient")
+        return self.grad_from(self.feature_grad(seed))
+
+    @torch.no_grad()
+    def feature_grad(self, seed):
+        """d(sum seed * log_probs) / d features, NHWC fp32 in the shape of `.features`: the head backward `grad` runs, with its
+        refusals and its effect on the head's `.grad`.  The head keeps the plain rule under every `rule` of grad_from."""
+        return _seeded_head_backward(self._model, self.log_probs, self._hstate, seed)
+
+    @torch.no_grad()
+    def grad_from(self, dfeat, rule="gradient"):
+        """The backbone's backward alone: dfeat (NHWC fp32 in the shape of `.features`, not written) -> the gradient of the image,
+        NCHW fp32.  rule is what the backward does where it meets a ReLU OF THE BACKBONE (the entries of relu_outputs() other
+        than "conv1x1" and "maxpool"), with g the gradient arriving at the ReLU's output y:
+            "gradient"    y > 0 ? g : 0               the derivative
+            "guided"      (y > 0 and g > 0) ? g : 0   guided backpropagation (Springenberg et al. 2015)
+            "deconvnet"   g > 0 ? g : 0               the deconvnet rule (Zeiler & Fergus 2014)
+        The pool's gather, the radix softmax, the average pools and every convolution keep their ordinary backward.  Anything else
+        is a ValueError, a stale pass a RuntimeError, both before any launch."""
+        r = self._check(rule)
+        if not torch.is_tensor(dfeat) or dfeat.shape != self.features.shape or dfeat.dtype != torch.float32 or \
+                dfeat.device != self.features.device:
+            raise ValueError("dfeat must be an fp32 tensor of shape %s on %s" % (tuple(self.features.shape), self.features.device))
         m = self._model
-        if m._fold_gen != self._gen:
-            raise RuntimeError("ImagePass.grad: the model has folded its weights again since this pass; run image_pass again")
-        dfeat = _seeded_head_backward(m, self.log_probs, self._hstate, seed)
-        return m.backbone.image_bwd(dfeat, self._bstate, self._wds)
+        return m.backbone.image_bwd(dfeat.contiguous(), self._bstate, self._wds, r)
 
     def relu_outputs(self):
         """{name: activation} whose signs the backward used, in the keys of the training path's capture: the name of the

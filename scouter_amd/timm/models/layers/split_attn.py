@@ -80,22 +80,24 @@ class SplitAttnConv2d(nn.Module):
             a = K.radix_softmax_fwd(z2.view(B, -1))
         return K.sa_apply_fwd(x0, a, None), (tuple(x.shape), x0, gap, a, g1)
 
-    def bwd_image(self, dout, ctx, wds):
+    def bwd_image(self, dout, ctx, wds, rule=K.RULE_GRADIENT):
         """The gradient of fwd_image's input from that of its output: d(attention) as in training, the gate's backward in one
         launch (K.sa_gate_bwd; the unfused chain where fwd_image ran unfused), the weighted sum's + GAP's backward with x0's ReLU
         mask in one pass (K.sa_apply_relu_bwd), the radix convolution's input gradient on the folded weight.  wds: the model's
-        {layer: input-gradient planes of its folded weight}."""
+        {layer: input-gradient planes of its folded weight}.  rule (K.RULE_*): what the backward of the two ReLUs here does -- the
+        gate's hidden one (in K.sa_gate_bwd, or the unfused chain's K.relu_bwd) and the radix convolution's (in
+        K.sa_apply_relu_bwd); the radix softmax keeps its ordinary backward."""
         xshape, x0, gap, a, g1 = ctx
         B = x0.shape[0]
         da = K.sa_dattn(x0, dout, None)
         if g1 is None:
             f = self.fc1._fold
-            dgap = K.sa_gate_bwd(gap, f.w, f.b, K.hwio(self.fc2.weight), a, da)
+            dgap = K.sa_gate_bwd(gap, f.w, f.b, K.hwio(self.fc2.weight), a, da, rule=rule)
         else:
             dz2 = K.radix_softmax_bwd(a, da)
             dg1 = K.conv2d_dgrad(dz2.view(B, 1, 1, -1), K.hwio(self.fc2.weight), tuple(g1.shape))
-            dgap = self.fc1.dgrad_folded(K.relu_bwd(dg1, g1), (B, 1, 1, gap.shape[1]), wd=wds.get(self.fc1)).view(B, -1)
-        return self.conv.dgrad_folded(K.sa_apply_relu_bwd(dout, a, dgap, x0), xshape, wd=wds.get(self.conv))
+            dgap = self.fc1.dgrad_folded(K.relu_bwd(dg1, g1, rule), (B, 1, 1, gap.shape[1]), wd=wds.get(self.fc1)).view(B, -1)
+        return self.conv.dgrad_folded(K.sa_apply_relu_bwd(dout, a, dgap, x0, rule), xshape, wd=wds.get(self.conv))
 
     def image_relus(self, ctx):
         """[(BatchNorm, the ReLU output that followed it in fwd_image)]: x0 and the gate's hidden activation [B, 1, 1, A] --

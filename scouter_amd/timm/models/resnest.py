@@ -104,15 +104,15 @@ class ResNestBottleneck(nn.Module):
         out = self.conv3.fwd_folded(p, relu=True, addend=res)
         return out, (tuple(x.shape), kd, h1, ksa, tuple(sa.shape), tuple(p.shape), out)
 
-    def bwd_image(self, dout, ctx, wds):
+    def bwd_image(self, dout, ctx, wds, rule=K.RULE_GRADIENT):
         """d x from d out: ReLU mask, conv3, the avd pool, the split attention, ReLU mask, conv1 with the shortcut's gradient
-        as its addend -- input gradients on the folded weights only (wds: SplitAttnConv2d.bwd_image)."""
+        as its addend -- input gradients on the folded weights only (wds, rule: SplitAttnConv2d.bwd_image)."""
         xshape, kd, h1, ksa, sa_shape, p_shape, out = ctx
-        d = K.relu_bwd(dout, out)
+        d = K.relu_bwd(dout, out, rule)
         dxres = self.downsample.bwd_image(d, kd, wds) if self.downsample is not None else d
         dp = self.conv3.dgrad_folded(d, p_shape, wd=wds.get(self.conv3))
         dsa = self.avd_last.bwd(dp, sa_shape) if self.avd_last is not None else dp
-        dh1 = K.relu_bwd(self.conv2.bwd_image(dsa, ksa, wds), h1)
+        dh1 = K.relu_bwd(self.conv2.bwd_image(dsa, ksa, wds, rule), h1, rule)
         return self.conv1.dgrad_folded(dh1, xshape, addend=dxres, wd=wds.get(self.conv1))
 
     def image_relus(self, ctx):

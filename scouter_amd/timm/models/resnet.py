@@ -173,13 +173,13 @@ class BasicBlock(nn.Module):
         out = self.conv2.fwd_folded(h1, relu=True, addend=res)
         return out, (tuple(x.shape), kd, h1, out)
 
-    def bwd_image(self, dout, ctx, wds):
-        """d x from d out: ReLU mask, conv2, ReLU mask, conv1 with the shortcut's gradient as its addend (wds:
+    def bwd_image(self, dout, ctx, wds, rule=K.RULE_GRADIENT):
+        """d x from d out: ReLU mask, conv2, ReLU mask, conv1 with the shortcut's gradient as its addend (wds, rule:
         SplitAttnConv2d.bwd_image)"""
         xshape, kd, h1, out = ctx
-        d = K.relu_bwd(dout, out)
+        d = K.relu_bwd(dout, out, rule)
         dxres = self.downsample.bwd_image(d, kd, wds) if self.downsample is not None else d
-        dh1 = K.relu_bwd(self.conv2.dgrad_folded(d, tuple(h1.shape), wd=wds.get(self.conv2)), h1)
+        dh1 = K.relu_bwd(self.conv2.dgrad_folded(d, tuple(h1.shape), wd=wds.get(self.conv2)), h1, rule)
         return self.conv1.dgrad_folded(dh1, xshape, addend=dxres, wd=wds.get(self.conv1))
 
     def image_relus(self, ctx):
@@ -357,19 +357,22 @@ class ResNet(nn.Module):
                 blocks.append(c_blk)
         return x, (tuple(x_nchw.shape), hs, arg, blocks)
 
-    def image_bwd(self, dfeat, ctx, wds):
+    def image_bwd(self, dfeat, ctx, wds, rule=K.RULE_GRADIENT):
         """d image (NCHW fp32) from d features: the blocks in reverse, the max-pool gather with the stem ReLU's mask in one pass
         (K.maxpool_relu_bwd), the deep stem's input gradients and ReLU masks, the stem convolution's image gradient -- on the
-        folded weights; no parameter gradient, no BatchNorm kernel.  wds: {layer: input-gradient planes of its folded weight}."""
+        folded weights; no parameter gradient, no BatchNorm kernel.  wds: {layer: input-gradient planes of its folded weight}.
+        rule: what the backward of every ReLU of the backbone does (K.RULE_GRADIENT the derivative, K.RULE_GUIDED guided
+        backpropagation, K.RULE_DECONVNET the deconvnet rule); the pool's gather, the average pools, the radix softmax and the
+        convolutions keep their ordinary backward."""
         x_shape, hs, arg, blocks = ctx
         mods = [blk for li in range(1, 5) for blk in getattr(self, "layer%d" % li)]
         d = dfeat
         for blk, c_blk in zip(reversed(mods), reversed(blocks)):
-            d = blk.bwd_image(d, c_blk, wds)
-        d = K.maxpool_relu_bwd(d, arg, hs[-1], 3, 2, 1)
+            d = blk.bwd_image(d, c_blk, wds, rule)
+        d = K.maxpool_relu_bwd(d, arg, hs[-1], 3, 2, 1, rule=rule)
         convs = self._stem_convs()
         for i in range(len(convs) - 1, 0, -1):
-            d = K.relu_bwd(convs[i].dgrad_folded(d, tuple(hs[i - 1].shape), wd=wds.get(convs[i])), hs[i - 1])
+            d = K.relu_bwd(convs[i].dgrad_folded(d, tuple(hs[i - 1].shape), wd=wds.get(convs[i])), hs[i - 1], rule)
         return convs[0].dgrad_folded(d, x_shape)
 
     def image_relus(self, ctx):

@@ -181,7 +181,19 @@ gradient times that sample's own difference.  The draws are a Philox stream of t
 written by kernels.gradshap_images into the reused buffer of `integrated_gradients` (or, for the layer variant, the feature buffer
 of `layer_integrated_gradients`, with one SlotModel.head_pass per chunk), and kernels.gradshap_accumulate forms every sample's
 difference again from the draws and adds gradient times difference in float64 in sample order: the differences are never
-stored.  tools/gradshap.py adds both methods as rows to the single-image tool and the explanation table."""
+stored.  tools/gradshap.py adds both methods as rows to the single-image tool and the explanation table.
+
+Guided backpropagation, deconvnet and Guided Grad-CAM (`guided_backprop`, `deconvnet`, `guided_gradcam`, drawn by `gradient_maps`):
+Springenberg et al. 2015, Zeiler & Fergus 2014 and Selvaraju et al. 2017; captum's GuidedBackprop, Deconvolution and the
+GuidedGradCam the reference's captum_vis.py imports.  The backward to the image with another rule at every ReLU of the backbone:
+what is positive in the arriving gradient and lies where the output was positive (guided), or the positive part of the arriving
+gradient alone (deconvnet).  They run on SlotModel.image_pass only -- the gradient-only backward of the folded path applies every
+ReLU mask in four kernels (kernels.relu_bwd, sa_gate_bwd, sa_apply_relu_bwd, maxpool_relu_bwd), whose `rule` is a compile-time
+argument -- so one forward serves every class and there is no autograd form.  Guided Grad-CAM multiplies the guided gradient by
+the rectified class map of the backbone's output, brought to the image's size inside kernels.guided_cam; one head backward per
+class (ImagePass.feature_grad) serves both factors.  The head's own ReLU keeps the plain rule (captum's hooks do not see it in the
+reference) and the log-probabilities are differentiated.  tools/guided.py adds the three methods as rows to the single-image tool
+and the explanation table."""
 import collections
 import contextlib
 import functools
@@ -301,6 +313,87 @@ def input_gradients(model, images, classes=None, of="log_prob", target=None, rou
                     seed[:, int(c)] = 1.0
                     grads.append(torch.autograd.grad(out, x, seed)[0])
         return torch.stack(grads, dim=1)
+
+
+_RULES = ("gradient", "guided", "deconvnet")
+_INTERPOLATE = ("nearest", "bilinear")
+
+
+def _rule_columns(model, images, classes, rule, column):
+    """the loop guided_backprop, deconvnet and guided_gradcam share: the refusals that come before any launch, ONE
+    model.image_pass, then column(ip, seed, k) -> fp32 [B, C, H, W] per class column (a LongTensor: one column); stacked to
+    [B, K, C, H, W]"""
+    if rule not in _RULES:
+        raise ValueError("rule must be 'gradient', 'guided' or 'deconvnet', got %r" % (rule,))
+    _check_images(images)
+    _check_device_images(images)
+    if getattr(model, "precision", "fp32") == "bf16":
+        raise NotImplementedError('the folded pass has no backward under precision "bf16" (fp32 only)')
+    B = images.shape[0]
+    n = _num_classes(model, images)
+    per_image, cols = _class_columns(classes, B, n)
+    with _eval_mode_once(model):
+        ip = model.image_pass(images)
+        seed = torch.zeros_like(ip.log_probs)
+        outs = []
+        if per_image:
+            seed[torch.arange(B, device=seed.device), classes.to(seed.device)] = 1.0
+            outs.append(column(ip, seed, 0, 1))
+        else:
+            for k, c in enumerate(cols):
+                seed.zero_()
+                seed[:, c] = 1.0
+                outs.append(column(ip, seed, k, len(cols)))
+    if not outs:
+        return torch.empty((B, 0) + tuple(images.shape[1:]), dtype=torch.float32, device=images.device)
+    return torch.stack(outs, dim=1)
+
+
+def guided_backprop(model, images, classes=None, rule="guided"):
+    """Guided backpropagation (Springenberg et al. 2015; captum's GuidedBackprop) of `images` [B, C, H, W] on the device -> fp32
+    [B, K, C, H, W]: the backward of the class output to the image in which every ReLU OF THE BACKBONE passes only what is
+    positive in the gradient arriving at it AND lies where its output was positive.  `classes` as in `input_gradients`: None
+    (every class), a list of ints, or a LongTensor [B] (every image its own class, K = 1).
+
+    ONE forward on the BatchNorm-folded weights (model.image_pass) and one gradient-only backward under the rule per class
+    column (ImagePass.grad_from(feature_grad(seed), rule)): the rule is a compile-time switch in the four kernels that apply a ReLU mask there, there is no autograd form.  rule="deconvnet" is
+    `deconvnet`, rule="gradient" the plain gradient of input_gradients(route="folded"); anything else is a ValueError before
+    any launch.  Departures from captum: the output differentiated is the log-probability (as everywhere here), and the head's
+    own ReLU behind conv1x1 keeps the plain rule -- it is `torch.relu` in the reference, not a module captum's hooks see.
+    fp32 models only (precision "bf16" is a NotImplementedError); the caller's mode is restored, no BatchNorm buffer moves."""
+    return _rule_columns(model, images, classes, rule, lambda ip, seed, k, K_: ip.grad_from(ip.feature_grad(seed), rule))
+
+
+def deconvnet(model, images, classes=None):
+    """The deconvnet rule (Zeiler & Fergus 2014; captum's Deconvolution) -> fp32 [B, K, C, H, W]: `guided_backprop` with every
+    ReLU of the backbone passing the positive part of the gradient arriving at it, whatever its output was -- the backward
+    kernels do not read the activations at all."""
+    return guided_backprop(model, images, classes, rule="deconvnet")
+
+
+def guided_gradcam(model, images, classes=None, interpolate="nearest"):
+    """Guided Grad-CAM (Selvaraju et al. 2017; captum's GuidedGradCam) -> fp32 [B, K, C, H, W]:
+    guided_backprop(x)[c] * up(relu(gradcam(x)[c])), the class map of the backbone's output (kernels.gradcam with relu=True)
+    brought to the image's size.  interpolate="nearest" (captum's default): source index (y h) // H, (x w) // W;
+    "bilinear": the resize of kernels.resize_bilinear.  Anything else is a ValueError before any launch.
+
+    ONE model.image_pass; per class column ONE head backward (ImagePass.feature_grad) that serves both factors -- the class map
+    and the guided gradient (ImagePass.grad_from) -- and one launch for the product (kernels.guided_cam).  Nothing is read on the
+    host.  `classes`, the departures from captum and the refusals are those of `guided_backprop`."""
+    if interpolate not in _INTERPOLATE:
+        raise ValueError("interpolate must be 'nearest' or 'bilinear', got %r" % (interpolate,))
+    state = {}
+
+    def column(ip, seed, k, K_):
+        if "cam" not in state:
+            B, h, w, _ = ip.features.shape
+            state["cam"] = torch.empty((B, K_, h, w), dtype=torch.float32, device=ip.features.device)
+        cam = state["cam"]
+        dfeat = ip.feature_grad(seed)
+        K.gradcam(ip.features, dfeat, cam[:, k], relu=True)
+        g = ip.grad_from(dfeat, "guided")
+        return K.guided_cam(g, cam[:, k], out=g, mode=interpolate)
+    return _rule_columns(model, images, classes, "guided", column)
 
 
 @contextlib.contextmanager
