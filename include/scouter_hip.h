@@ -1127,7 +1127,8 @@ int scouter_conv2d_wgrad_planes(const void* x_planes, const void* dy_planes, flo
  * tile_hint 7 (round 6, csrc/conv_xhalo.hip; only on request, never the library's choice): the 3x3 / pad 1 layers whose GEMM
  * is 32 columns wide per group -- forward with Cout / groups == 32, input gradient with Cin / groups == 32 (the deep stem's
  * 32 -> 32 and 32 -> 64 convolutions, resnet.py:471-489; the input gradient of layer1's radix convolution,
- * layers/split_attn.py:54-60), maps up to 126 pixels wide, no bias / forward addend -- on a PERSISTENT kernel that splits
+ * layers/split_attn.py:54-60), 16-multiples of GEMM-K channels per group (its own channel rule: 16 and 48 run, which tiles 0-6
+ * refuse), maps up to 126 pixels wide, no bias / forward addend -- on a PERSISTENT kernel that splits
  * every input element once and keeps the split rows resident in LDS for all nine taps.  Same error bound as the other
  * tiles, another summation order (16-channel chunk outer, tap inner): equal to fp32 rounding, not bit for bit.  Its
  * bn_partial / part1 / part2 have scouter_conv2d_x3_halo_partial_rows(groups) rows (one per workgroup of a group). */

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void split_weight_multi_kernel(const SplitWeig
 // ---------------------------------------------------------------------------------------------------------------
 // g describes the GEMM exactly as in conv_igemm.hip (for DGRAD the A tensor is dY and the columns are Cin).
 // NWM waves along M x 2 along N (4 or 8 waves: 256 or 512 threads); every wave owns a 64 x (BN/2) or (BM/NWM) x (BN/2) tile.
-template <int BM, int BN, int NP, int NSTAGE, bool DGRAD, int NWM = 2>
+template <int BM, int BN, int NP, int NSTAGE, bool DGRAD, int NWM = 2, bool Y16 = false>
 __global__ __launch_bounds__(NWM * 128, 1) void pconv_kernel(const unsigned short* __restrict__ a_planes, long a_plane_elems,
                                                        const unsigned short* __restrict__ w_planes, long w_plane_elems,
                                                        const float* __restrict__ bias, const float* __restrict__ addend,
@@ -355,8 +355,10 @@ __global__ __launch_bounds__(NWM * 128, 1) void pconv_kernel(const unsigned shor
             for (int j = 0; j < NT; ++j) acc[i][j] += accl[i][j];
     }
     // epilogue shared with the fp32 kernels (LDS-staged 16-byte stores, bias / addend / ReLU, BatchNorm statistics); the
-    // one-plane instantiations (bf16 mode) are the TYPED ones: their forward may store bf16 (fz.io bit 3)
-    if constexpr (NP == 1)
+    // one-plane instantiations (bf16 mode) are the TYPED ones: their forward may store bf16 (fz.io bit 3).  A three-plane forward
+    // asked for a bf16 output is an instantiation of its own with the typed epilogue (Y16; the plain epilogue writes fp32 whatever
+    // fz.io says -- over a bf16 buffer of half the size); the fp32-storing ones compile as before
+    if constexpr (NP == 1 || Y16)
         igemm_epilogue_typed<BM, BN, WM, WN, DGRAD>(acc, (float*)lds_raw, g, bias, addend, dst, bn_part, relu, m0, n0, grp, mt_id,
                                                     &fz, false);
     else
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(NWM * 128, 1) void pconv_kernel(const unsigned shor
 #define PHALO_ABLATE 0      // dev builds only (tools_dev/phalo_ablate.sh): 1 = no DMA, 2 = no DMA wait / barrier, 4 = no LDS reads,
                             // 8 = cycle stamps (start, prologue done, K loop done, stores retired) instead of BatchNorm partials
 #endif
-template <int BN, int NP, bool DGRAD>
+template <int BN, int NP, bool DGRAD, bool Y16 = false>
 __global__ __launch_bounds__(512, 1) void phalo_kernel(const unsigned short* __restrict__ a_planes, long a_plane_elems,
                                                        const unsigned short* __restrict__ w_planes, long w_plane_elems,
                                                        const float* __restrict__ bias, const float* __restrict__ addend,
@@ -653,7 +655,7 @@ __global__ __launch_bounds__(512, 1) void phalo_kernel(const unsigned short* __r
         o[0] = stamp[0]; o[1] = stamp[1]; o[2] = stamp[2]; o[3] = stamp[3];
     }
 #else
-    if constexpr (NP == 1)
+    if constexpr (NP == 1 || Y16)           // (Y16: a bf16 output at three planes, as in pconv_kernel)
         igemm_epilogue_typed<BM, BN, WM, WN, DGRAD>(acc, (float*)lds_raw, g, bias, addend, dst, bn_part, relu, m0, n0, grp, mt_id,
                                                     &fz, false);
     else
@@ -724,6 +726,9 @@ static void launch_pconv(const void* a, long a_pe, const void* w, long w_pe, con
     constexpr int EPI_BYTES = 2 * NWM * (BM / NWM) * (BN / 2 + 4) * 4;
     const size_t lds = (size_t)(NSTAGE * STAGE_BYTES > EPI_BYTES ? NSTAGE * STAGE_BYTES : EPI_BYTES);
     auto kern = pconv_kernel<BM, BN, NP, NSTAGE, DGRAD, NWM>;
+    if constexpr (NP == 3 && !DGRAD) {
+        if (fz.io & 8) kern = pconv_kernel<BM, BN, NP, NSTAGE, DGRAD, NWM, true>;      // (y stored as bf16)
+    }
     sc_dyn_lds((const void*)kern, lds);
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles * g.groups), dim3(NWM * 128), lds, st, (const unsigned short*)a, a_pe,
                        (const unsigned short*)w, w_pe, bias, addend, dst, bn_part, gg, relu, mtiles, ntiles, fz);
@@ -763,6 +768,9 @@ static void launch_phalo(const void* a, long a_pe, const void* w, long w_pe, con
     constexpr int IMG = 2 * NP * 13 * 1024, WST = 2 * 3 * NP * BN * 32, EPI = 8 * 64 * (BN / 2 + 4) * 4;
     constexpr int LDS = IMG + WST > EPI ? IMG + WST : EPI;
     auto kern = phalo_kernel<BN, NP, DGRAD>;
+    if constexpr (NP == 3 && !DGRAD) {
+        if (fz.io & 8) kern = phalo_kernel<BN, NP, DGRAD, true>;
+    }
     sc_dyn_lds((const void*)kern, LDS);
     const int agroups = (BM + 2 * g.W + 2 + 31) / 32;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles * g.groups), dim3(512), LDS, st, (const unsigned short*)a, a_pe,

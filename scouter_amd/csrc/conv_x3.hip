@@ -388,7 +388,10 @@ static int dispatch_x3(const float* a, const void* w, long w_pe, const float* bi
 
 // what the two entry points take at all (g as for the GEMM: C / Cg the K-side channels, wtap the elements of one weight tap)
 static bool x3_filter_ok(const ConvGeom& g) { return g.R == g.S && (g.R & 1) && 2 * g.pad == g.R - 1 && g.R <= 5 && g.stride == 1; }
-static bool x3_channels_ok(const ConvGeom& g) { return g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.R * g.S * (g.Cg / 32) >= 2; }
+// (tile 7 has its own channel rule in sc_xhalo_ok: 32 columns and 16-multiples of K per group, one 16-channel chunk at least)
+static bool x3_channels_ok(const ConvGeom& g, int tile) {
+    return tile == 7 || (g.Cg % 32 == 0 && g.Ng % 32 == 0 && g.R * g.S * (g.Cg / 32) >= 2);
+}
 static bool x3_size_ok(const ConvGeom& g) {
     // (the pointwise groups-1 instantiation walks no pixels; x3_filter_ok keeps the taps at 25)
     return g.M < (1L << 31) && (long)g.R * g.S * g.wtap * 2 * 3 < (1L << 31) && (long)g.H * g.W * g.C < (1L << 28) &&
@@ -405,13 +408,13 @@ extern "C" int scouter_conv2d_fwd_x3_tile_ok(int B, int H, int W, int Cin, int C
                                              int groups, int tile, int epilogue) {
     if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
     const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    return x3_filter_ok(g) && x3_channels_ok(g) && x3_size_ok(g) && x3_named_tile_ok<false>(g, tile, epilogue);
+    return x3_filter_ok(g) && x3_channels_ok(g, tile) && x3_size_ok(g) && x3_named_tile_ok<false>(g, tile, epilogue);
 }
 extern "C" int scouter_conv2d_dgrad_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
                                                int groups, int tile, int epilogue) {
     if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
     const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    return x3_filter_ok(g) && x3_channels_ok(g) && x3_size_ok(g) && x3_named_tile_ok<true>(g, tile, epilogue);
+    return x3_filter_ok(g) && x3_channels_ok(g, tile) && x3_size_ok(g) && x3_named_tile_ok<true>(g, tile, epilogue);
 }
 
 extern "C" int scouter_conv2d_x3_tile(long M, int N, int tile_hint) { return tile_hint == 7 && N == 32 ? 7 : x3_tile(M, N, tile_hint); }
@@ -431,7 +434,7 @@ extern "C" int scouter_conv2d_fwd_x3(const float* x, const void* w_planes_fwd, c
     const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
     const int Cg = g.Cg, Ng = g.Ng;
     SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_fwd_x3: 1x1 or odd same-size filters only");
-    SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_fwd_x3: needs 32-multiples of channels per group and two K-tiles");
+    SC_UNSUPPORTED(x3_channels_ok(g, tile_hint), "conv2d_fwd_x3: needs 32-multiples of channels per group and two K-tiles");
     SC_UNSUPPORTED(x3_size_ok(g), "conv2d_fwd_x3: tensor too large for 32-bit offsets, or " SC_PIXEL_WALK_MSG);
     const long w_pe = (long)kh * kw * Cg * Cout;
     if (tile_hint == 7) {           // resident rows, split once per element, persistent (conv_xhalo.hip): 32 columns per group
@@ -461,7 +464,7 @@ extern "C" int scouter_conv2d_dgrad_x3_bnbwd(const float* dy, const void* w_plan
     const int Cig = Cin / groups, Cog = Cout / groups;
     const ConvGeom g = sc_dgrad_geom(B, H, W, Cin, Cout, kh, kw, 1, pad, groups);
     SC_UNSUPPORTED(x3_filter_ok(g), "conv2d_dgrad_x3: 1x1 or odd same-size filters only");
-    SC_UNSUPPORTED(x3_channels_ok(g), "conv2d_dgrad_x3: needs 32-multiples of channels per group and two K-tiles");
+    SC_UNSUPPORTED(x3_channels_ok(g, tile_hint), "conv2d_dgrad_x3: needs 32-multiples of channels per group and two K-tiles");
     SC_UNSUPPORTED(x3_size_ok(g), "conv2d_dgrad_x3: tensor too large for 32-bit offsets, or " SC_PIXEL_WALK_MSG);
     const BnBwdFuse fz{part1 ? (const unsigned long long*)relu_mask : nullptr, x1, saved1, part1, x2, saved2, part2, 0};
     const long w_pe = (long)kh * kw * Cig * Cout;
