@@ -1039,6 +1039,27 @@ int scouter_xslot_bwd_f32(const float* X, const float* PE, const float* const* t
                           const float* Hsave, const float* states, const float* dlogits, const float* g_area_sum,
                           int B, int N, int d, int S, int spc, int T, int L, float loss_status, float* dX, float* dgi,
                           float* dgh, float* Usave, float* ds0, float* dZ, void* ws, size_t ws_bytes, void* stream);
+/* ---- HEAD INSTANCES: which kernel instantiation scouter_xslot_fwd_f32 / scouter_xslot_bwd_f32 take for a head of N tokens,
+ * S slots, T iterations and L to_k layers under the CURRENT switches xslot_small / xslot_bwd_halves / xslot_bwd_scratch, asked
+ * without calling them: no HIP call, so it answers before a device exists and on a machine without one.  Returns 1 and fills
+ * inst[SCOUTER_XSLOT_INST_WORDS], or 0 when the entry points refuse the shape (N > 96, S > 512, T > 8, L > 8, a size < 1).  Both
+ * entry points select their kernel through the same rule (csrc/xslot_common.h, xs_instance), and the tile backward derives
+ * its walk from the inline that fills words 6 and 7.  attn_align16: whether the `attn` pointer is 16-byte aligned.
+ *   [0] small      1: the 16-slot kernels (S <= 16 with xslot_small on), else the 32-slot tile kernels
+ *   [1] NJT        token tiles of 32, 1..3 (small: the token-width parameter, 1 for N <= 64, else 2)
+ *   [2] GX         forward: live 8-token groups of the token contraction -- 4 NJT, or 11 for 65 <= N <= 88 (small: 0)
+ *   [3] TPW        forward: slot tiles per wave, ceil(ceil(S / 32) / 4) = 1..4 (small: 0)
+ *   [4] attn form  forward: 1 = 16-byte stores of the attention map (S * N % 4 == 0 and the pointer aligned), 0 = scalar
+ *   [5] backward   SCOUTER_XSLOT_BWD_* family
+ *   [6] nfull, [7] nhalf   backward walk: slot tiles walked 32 wide, then live 16-slot half tiles (small: 0, 0)
+ *   [8] backward dynamic-LDS bytes
+ *   [9] ceil(S / 32),  [10] forward: the leftover tiles (ceil(S / 32) % 4 = 1, 2) are shared by wave pairs */
+#define SCOUTER_XSLOT_BWD_TILE 0     /* xslot_bwd_kernel<1 | 2> */
+#define SCOUTER_XSLOT_BWD_TILE_WG 1  /* xslot_bwd_kernel<3, true>: 64 < N <= 96, W_ih read from global memory */
+#define SCOUTER_XSLOT_BWD_SCRATCH 2  /* xslot_bwd_scratch_kernel<3>: 64 < N <= 96 with xslot_bwd_scratch on */
+#define SCOUTER_XSLOT_BWD_SMALL 3    /* xslot_small_bwd_kernel<1 | 2> */
+#define SCOUTER_XSLOT_INST_WORDS 11
+int scouter_xslot_instance(int N, int S, int T, int L, int attn_align16, int* inst);
 /* stats[0..4] = loss, nll, area**power, top-1 accuracy, area.  labels: int64 (may be NULL -> log_softmax only). */
 int scouter_slot_loss_fwd_f32(const float* logits, const long* labels, const float* area_part, int n_area_part, int B,
                               int C, double area_count, float lambda, float power, float* logp, float* stats,

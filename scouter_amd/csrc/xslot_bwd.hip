@@ -558,11 +558,9 @@ __global__ __launch_bounds__(256) void xslot_bwd_kernel(XsBwdArgs a) {
     // (slot-per-lane-16 layout of xslot_small_common.h, every operand from the same LDS images): half the time of a tile,
     // no exchange between waves -- 2.5 tiles per wave.  Their slot contractions feed the SAME 32 x 32 accumulators (eight
     // k-steps instead of sixteen), so parks and the final reduction do not change.
-    const int rem4 = ntiles & 3;
-    const bool halves = !WG && NJT <= 2 && a.halves && (rem4 == 1 || rem4 == 2);
-    const int nfull = halves ? (ntiles & ~3) : ntiles;              // tiles walked 32 slots wide
+    int nfull, nhalf;               // tiles walked 32 slots wide | live half tiles (<= 4): wave w walks half w
+    xs_bwd_walk(S, NJT, WG, a.halves != 0, nfull, nhalf);           // (xslot_common.h: the rule the host query answers with)
     const int TPW = (nfull + 3) >> 2;
-    const int nhalf = halves ? (S - 32 * nfull + 15) >> 4 : 0;      // live half tiles (<= 4): wave w walks half w
     const int nent = nfull + nhalf;                                 // entries of the tau / c0 partial tables
     const bool my_half = wave < nhalf;
     const int hslot0 = 32 * nfull + 16 * wave, m16 = lane & 15, g4 = lane >> 4;
@@ -1296,6 +1294,23 @@ static size_t xs_bwd_lds_bytes(int NJT, bool scratch) {
                     4 * 32 * XS_LDB) * sizeof(float);
 }
 
+static size_t xs_bwd_instance_lds_bytes(const XsInstance& in) {
+    return in.bwd == XS_BWD_SMALL ? xs_small_bwd_lds_bytes(in.njt) : xs_bwd_lds_bytes(in.njt, in.bwd == XS_BWD_SCRATCH);
+}
+
+// host only: no device call (include/scouter_hip.h, HEAD INSTANCES)
+extern "C" int scouter_xslot_instance(int N, int S, int T, int L, int attn_align16, int* inst) {
+    XsInstance in;
+    if (!inst || !xs_instance(N, S, T, L, sc_switch(SC_SW_XSLOT_SMALL) != 0, sc_switch(SC_SW_XSLOT_BWD_HALVES) != 0,
+                              sc_switch(SC_SW_XSLOT_BWD_SCRATCH) != 0, &in))
+        return 0;
+    const int words[XS_INST_WORDS] = {
+        in.small, in.njt, in.gx, in.tpw, !in.small && xs_attn_vec4(S, N, attn_align16 ? 0 : 4), in.bwd, in.nfull, in.nhalf,
+        (int)xs_bwd_instance_lds_bytes(in), in.ntiles, in.share};
+    for (int k = 0; k < XS_INST_WORDS; ++k) inst[k] = words[k];
+    return 1;
+}
+
 extern "C" size_t scouter_xslot_bwd_workspace_bytes(int B, int N, int d, int S, int T) {
     (void)d;
     const long Sp = (S + 31) / 32 * 32, NP = (N + 31) / 32 * 32;
@@ -1316,13 +1331,16 @@ extern "C" int scouter_xslot_bwd_f32(const float* X, const float* PE, const floa
     SC_REQUIRE((T <= 1) || (states && dgi && dgh && Usave), "xslot_bwd: missing GRU buffers");
     SC_REQUIRE(Hsave, "xslot_bwd: missing to_k activations");
     SC_REQUIRE(B > 0 && N > 0 && S > 0 && spc > 0 && S % spc == 0 && T >= 1 && L >= 1, "xslot_bwd: bad dims");
-    SC_UNSUPPORTED(d == XS_D && N <= XS_MAX_N && S <= 512 && T <= 8, "xslot_bwd: unsupported dims d=%d N=%d S=%d T=%d",
-                   d, N, S, T);
+    SC_UNSUPPORTED(d == XS_D, "xslot_bwd: hidden_dim must be 64 (got %d)", d);
+    XsInstance in;          // the instance rule of xslot_common.h -- its limits too: the answer scouter_xslot_instance gives
+    SC_UNSUPPORTED(xs_instance(N, S, T, L, sc_switch(SC_SW_XSLOT_SMALL) != 0, sc_switch(SC_SW_XSLOT_BWD_HALVES) != 0,
+                               sc_switch(SC_SW_XSLOT_BWD_SCRATCH) != 0, &in),
+                   "xslot_bwd: at most %d tokens, 512 slots, 8 iterations and 8 to_k layers (got N=%d S=%d T=%d L=%d)", XS_MAX_N,
+                   N, S, T, L);
     if (ws_bytes < scouter_xslot_bwd_workspace_bytes(B, N, d, S, T)) {
         sc_set_error("xslot_bwd: workspace too small");
         return SC_ERR_WORKSPACE;
     }
-    SC_UNSUPPORTED(L <= 8, "xslot_bwd: at most 8 to_k layers (got %d)", L);
     XsBwdArgs a{X, PE, {}, slots0, w_ih, w_hh, b_ih, b_hh, Ksave, Hsave, states, dlogits, g_area_sum,
                 dX, dgi, dgh, Usave, ds0, dZ, (float*)ws, B, N, S, S / spc, spc, T, L, loss_status,
                 sc_switch(SC_SW_XSLOT_BWD_HALVES) != 0};
@@ -1330,16 +1348,14 @@ extern "C" int scouter_xslot_bwd_f32(const float* X, const float* PE, const floa
         SC_REQUIRE(tok_w[l], "xslot_bwd: null to_k layer %d", l);
         a.tok_w[l] = tok_w[l];
     }
-    const int NJT = (N + 31) / 32;
-    const bool scratch = NJT > 2 && sc_switch(SC_SW_XSLOT_BWD_SCRATCH);
-    const size_t lds = xs_bwd_lds_bytes(NJT, scratch);
+    const size_t lds = xs_bwd_instance_lds_bytes(in);
     hipStream_t st = (hipStream_t)stream;
     const double flops = 2.0 * (double)B * (2.0 * L * N * d * d + (double)T * 4.0 * S * N * d + (T - 1) * 12.0 * S * d * d);
     ScProfScope prof("xslot_bwd", st, flops, 4.0 * B * (3.0 * N * d + (double)S * d));
     // (SCOUTER_XSLOT_SMALL=0: heads with <= 16 slots stay on the 32-slot-tile kernels: A/B, tests)
-    if (S <= 16 && sc_switch(SC_SW_XSLOT_SMALL)) {        // the metric's own head: xslot_small_bwd.h
-        const int NTW = N <= 64 ? 1 : 2;
-        const int slds = (int)xs_small_bwd_lds_bytes(NTW);
+    if (in.bwd == XS_BWD_SMALL) {                         // the metric's own head: xslot_small_bwd.h
+        const int NTW = in.njt;
+        const int slds = (int)lds;
         if (ws_bytes < xs_small_bwd_park_bytes(B, NTW)) {
             sc_set_error("xslot_bwd: workspace too small");
             return SC_ERR_WORKSPACE;
@@ -1349,8 +1365,8 @@ extern "C" int scouter_xslot_bwd_f32(const float* X, const float* PE, const floa
         hipLaunchKernelGGL(kern, dim3(B), dim3(256), slds, st, a);
         return sc_check_launch("xslot_small_bwd");
     }
-    auto kern = NJT == 1 ? xslot_bwd_kernel<1> : NJT == 2 ? xslot_bwd_kernel<2>
-              : scratch ? xslot_bwd_scratch_kernel<3> : xslot_bwd_kernel<3, true>;
+    auto kern = in.bwd == XS_BWD_TILE ? (in.njt == 1 ? xslot_bwd_kernel<1> : xslot_bwd_kernel<2>)
+              : in.bwd == XS_BWD_SCRATCH ? xslot_bwd_scratch_kernel<3> : xslot_bwd_kernel<3, true>;
     sc_dyn_lds((const void*)kern, lds);
     hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, st, a);
     return sc_check_launch("xslot_bwd");

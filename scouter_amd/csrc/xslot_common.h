@@ -18,6 +18,60 @@
 #define XS_LD 68         // LDS row stride (floats): 16B-aligned rows, conflict-free ds_read_b128 over 16 rows
 #define XS_MAX_N 96      // tokens per image: N <= 96 (7x7 and the reference's 9x9 grid); NJT = ceil(N/32) token tiles
 
+// ---- HEAD INSTANCES: which kernel instantiation a head of N tokens, S slots takes, stated ONCE.  scouter_xslot_fwd_f32 and
+// scouter_xslot_bwd_f32 launch what xs_instance() names, scouter_xslot_instance (include/scouter_hip.h) answers with it, and the
+// tile backward derives its walk from xs_bwd_walk() -- the same inline the host calls.
+#define XS_BWD_TILE 0        // xslot_bwd_kernel<1 | 2>
+#define XS_BWD_TILE_WG 1     // xslot_bwd_kernel<3, true>: W_ih read from global memory
+#define XS_BWD_SCRATCH 2     // xslot_bwd_scratch_kernel<3> (switch xslot_bwd_scratch)
+#define XS_BWD_SMALL 3       // xslot_small_bwd_kernel<1 | 2>
+#define XS_INST_WORDS 11     // = SCOUTER_XSLOT_INST_WORDS, like the XS_BWD_* above mirror SCOUTER_XSLOT_BWD_*
+struct XsInstance {
+    int small;      // S <= 16 and switch xslot_small: the 16-slot kernels (njt = their NTW, 1 | 2)
+    int njt;        // token tiles of 32 (tile kernels) / token-width parameter NTW (small kernels)
+    int gx;         // forward: live 8-token groups of the token contraction (4 njt, or 11 for 65 <= N <= 88); small: 0
+    int tpw;        // forward: slot tiles per wave, 1..4; small: 0
+    int bwd;        // XS_BWD_*
+    int nfull;      // backward walk: slot tiles walked 32 slots wide ...
+    int nhalf;      // ... and live 16-slot half tiles behind them (tile kernels with switch xslot_bwd_halves only)
+    int ntiles;     // ceil(S / 32)
+    int share;      // forward: the ntiles % 4 = 1, 2 leftover tiles are shared by wave pairs
+};
+// the tile backward's walk over ceil(S / 32) slot tiles: leftovers of one or two tiles go as 16-slot halves, one per wave
+__host__ __device__ inline void xs_bwd_walk(int S, int NJT, bool WG, bool halves_on, int& nfull, int& nhalf) {
+    const int ntiles = (S + 31) >> 5, rem4 = ntiles & 3;
+    const bool halves = !WG && NJT <= 2 && halves_on && (rem4 == 1 || rem4 == 2);
+    nfull = halves ? (ntiles & ~3) : ntiles;
+    nhalf = halves ? (S - 32 * nfull + 15) >> 4 : 0;
+}
+// the forward's ntiles % 4 = 1, 2 leftover tiles are each SHARED by a wave pair (three token tiles exchange the halves through the
+// `states` rows, which a single iteration does not store)
+__host__ __device__ inline bool xs_fwd_share(int S, int NJT, int T) {
+    const int rem = ((S + 31) >> 5) & 3;
+    return (rem == 1 || rem == 2) && (NJT <= 2 || T > 1);
+}
+// the forward's 16-byte store form of the attention map: every image's [S][N] block starts on a 16-byte boundary
+__host__ __device__ inline bool xs_attn_vec4(int S, int N, size_t attn) { return ((S * N) & 3) == 0 && (attn & 15) == 0; }
+// false: the head kernels refuse the shape
+inline bool xs_instance(int N, int S, int T, int L, bool sw_small, bool sw_halves, bool sw_scratch, XsInstance* o) {
+    if (N < 1 || S < 1 || T < 1 || L < 1 || N > 96 || S > 512 || T > 8 || L > 8) return false;
+    o->ntiles = (S + 31) / 32;
+    o->small = S <= 16 && sw_small;
+    if (o->small) {
+        o->njt = N <= 64 ? 1 : 2;
+        o->gx = o->tpw = o->share = o->nfull = o->nhalf = 0;
+        o->bwd = XS_BWD_SMALL;
+        return true;
+    }
+    o->njt = (N + 31) / 32;
+    o->gx = o->njt == 3 && N <= 88 ? 11 : 4 * o->njt;     // (the reference's 9x9 grid: the last 8-token group is skipped)
+    o->tpw = (o->ntiles + 3) / 4;
+    o->share = xs_fwd_share(S, o->njt, T);
+    o->bwd = o->njt <= 2 ? XS_BWD_TILE : sw_scratch ? XS_BWD_SCRATCH : XS_BWD_TILE_WG;
+    xs_bwd_walk(S, o->njt, o->bwd != XS_BWD_TILE, sw_halves, o->nfull, o->nhalf);
+    return true;
+}
+
 // Ends a scheduling region: without it the compiler hoists the LDS operand loads of many MFMA blocks ahead
 // (everything is unrolled) and runs out of the 512-entry register file.
 #define XS_REGION_END() __builtin_amdgcn_sched_barrier(0)

@@ -399,7 +399,7 @@ __global__ __launch_bounds__(64 * XS_FWD_WAVES) void xslot_fwd_kernel(XsFwdArgs 
     // state rows in L2, NJT = 3)
     const int ntiles = (S + 31) >> 5, nfull4 = ntiles >> 2, rem = ntiles & 3;
     constexpr bool GX = NJT > 2;                // no LDS for the exchange buffer: through the `states` rows (xs_tile_shared_a)
-    const bool share = (rem == 1 || rem == 2) && (!GX || a.T > 1);
+    const bool share = xs_fwd_share(S, NJT, a.T);
     int tile_id[TPW];
     f32x16 h[TPW][2];
     // initial slots: each wave fetches its tiles as whole 256-byte rows (coalesced; a register-layout gather straight
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(64 * XS_FWD_WAVES) void xslot_fwd_kernel(XsFwdArgs 
     const XsLds m{Xs, Ks, Wih, Whh, bias};
     float* exch = usum + 512;                                   // [4 waves][4][64][4] (only when NJT <= 2)
     const XsOut o{a.states, a.attn + (long)b * S * N, usum, area_s, Wih + wave * (32 * XS_MAX_N), exch,
-                  S, N, lane, l31, hh, wave, ((S * N) & 3) == 0 && ((size_t)a.attn & 15) == 0
+                  S, N, lane, l31, hh, wave, xs_attn_vec4(S, N, (size_t)a.attn)
 #ifdef XS_TIMING
                   , a.stamps, &nstamp
 #endif
@@ -593,9 +593,11 @@ extern "C" int scouter_xslot_fwd_f32(const float* X, const float* PE, const floa
                Ksave && (states || T <= 1) && Hsave, "xslot_fwd: null pointer");
     SC_REQUIRE(B > 0 && N > 0 && S > 0 && spc > 0 && S % spc == 0 && T >= 1 && L >= 1, "xslot_fwd: bad dims");
     SC_UNSUPPORTED(d == XS_D, "xslot_fwd: hidden_dim must be 64 (got %d)", d);
-    SC_UNSUPPORTED(N <= XS_MAX_N, "xslot_fwd: at most %d tokens per image (got %d)", XS_MAX_N, N);
-    SC_UNSUPPORTED(S <= 512 && T <= 8, "xslot_fwd: at most 512 slots and 8 iterations (got S=%d T=%d)", S, T);
-    SC_UNSUPPORTED(L <= 8, "xslot_fwd: at most 8 to_k layers (got %d)", L);
+    XsInstance in;          // the instance rule of xslot_common.h -- its limits too: the answer scouter_xslot_instance gives
+    SC_UNSUPPORTED(xs_instance(N, S, T, L, sc_switch(SC_SW_XSLOT_SMALL) != 0, sc_switch(SC_SW_XSLOT_BWD_HALVES) != 0,
+                               sc_switch(SC_SW_XSLOT_BWD_SCRATCH) != 0, &in),
+                   "xslot_fwd: at most %d tokens, 512 slots, 8 iterations and 8 to_k layers (got N=%d S=%d T=%d L=%d)", XS_MAX_N,
+                   N, S, T, L);
     XsFwdArgs a{X, PE, {}, {}, slots0, w_ih, w_hh, b_ih, b_hh, logits, attn, area_part, Ksave, Hsave, states,
                 B, N, S, S / spc, spc, T, L, loss_status};
     for (int l = 0; l < L; ++l) {
@@ -603,15 +605,14 @@ extern "C" int scouter_xslot_fwd_f32(const float* X, const float* PE, const floa
         a.tok_w[l] = tok_w[l];
         a.tok_b[l] = tok_b[l];
     }
-    const int ntiles = (S + 31) / 32, NJT = (N + 31) / 32;
-    const int NW = XS_FWD_WAVES, TPW = (ntiles + NW - 1) / NW;
+    const int NJT = in.njt, NW = XS_FWD_WAVES, TPW = in.tpw;
     const size_t lds = xs_fwd_lds_bytes(NJT);
     hipStream_t st = (hipStream_t)stream;
     const double flops = (double)B * (2.0 * L * N * d * d + (double)T * 4.0 * S * N * d + (T - 1) * 12.0 * S * d * d);
     ScProfScope prof("xslot_fwd", st, flops, 4.0 * B * (2.0 * N * d + (double)S * N));
     // (SCOUTER_XSLOT_SMALL=0 keeps heads with <= 16 slots on the 32-slot-tile kernels: A/B runs, tests of those paths)
-    if (S <= 16 && sc_switch(SC_SW_XSLOT_SMALL)) {          // the metric's own head (10 slots): xslot_small_fwd.h
-        if (N <= 64) hipLaunchKernelGGL(xslot_small_fwd_kernel<1>, dim3(B), dim3(256), 0, st, a);
+    if (in.small) {                                         // the metric's own head (10 slots): xslot_small_fwd.h
+        if (in.njt == 1) hipLaunchKernelGGL(xslot_small_fwd_kernel<1>, dim3(B), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(xslot_small_fwd_kernel<2>, dim3(B), dim3(256), 0, st, a);
         return sc_check_launch("xslot_small_fwd");
     }
@@ -633,7 +634,7 @@ extern "C" int scouter_xslot_fwd_f32(const float* X, const float* PE, const floa
 #else
     if (NJT == 1) XS_TPW(1);
     else if (NJT == 2) XS_TPW(2);
-    else if (N <= 88) XS_TPW(3, 11);      // (the reference's 9x9 grid: the token contraction skips the last 8-token group)
+    else if (in.gx == 11) XS_TPW(3, 11);      // (the reference's 9x9 grid: the token contraction skips the last 8-token group)
     else XS_TPW(3);
 #endif
 #undef XS_TPW

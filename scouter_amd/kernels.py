@@ -1620,6 +1620,22 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+XSLOT_BWD_FAMILIES = ("tile", "tile_wg", "scratch", "small")          # SCOUTER_XSLOT_BWD_*
+_XSLOT_INST_FIELDS = ("small", "NJT", "GX", "TPW", "attn_vec4", "bwd", "nfull", "nhalf", "bwd_lds_bytes", "ntiles", "share")
+
+
+def xslot_instance(N, S, T=3, L=1, attn_aligned=True):
+    """The kernel instantiation scouter_xslot_fwd_f32 / scouter_xslot_bwd_f32 take for this head under the current switches
+    (include/scouter_hip.h, HEAD INSTANCES), or None where they refuse the shape.  Host arithmetic only: needs no device."""
+    import ctypes
+    words = (ctypes.c_int * len(_XSLOT_INST_FIELDS))()
+    if not _native.lib().scouter_xslot_instance(int(N), int(S), int(T), int(L), int(bool(attn_aligned)), words):
+        return None
+    inst = dict(zip(_XSLOT_INST_FIELDS, words))
+    inst["bwd"] = XSLOT_BWD_FAMILIES[inst["bwd"]]
+    return inst
+
+
 def xslot_fwd(X, PE, tok_w, tok_b, slots0, w_ih, w_hh, b_ih, b_hh, spc, T, loss_status):
     """tok_w / tok_b: lists of the L to_k Linear weights [d,d] (out,in) / biases [d]."""
     for n, t in (("X", X), ("PE", PE), ("slots0", slots0), ("w_ih", w_ih), ("w_hh", w_hh), ("b_ih", b_ih),

@@ -133,7 +133,7 @@ def test_xslot_large_batch_properties():
 
 
 @pytest.mark.parametrize("B,S,N,T,L,spc", [(2, 512, 64, 8, 2, 1),      # S, T at the kernel limits, 16 slot tiles
-                                            (2, 512, 96, 3, 8, 2),      # N, L at the limits (scratch variant)
+                                            (2, 512, 96, 3, 8, 2),      # N, L at the limits (xslot_bwd_kernel<3, true>)
                                             (3, 33, 20, 1, 1, 3),       # a single iteration (no GRU), ragged tiles
                                             (1, 96, 32, 2, 1, 1),       # one image, N = one token tile exactly
                                             # leftover slot tiles walked as 16-slot half tiles by the backward (round 6):
