@@ -248,6 +248,9 @@ int scouter_conv2d_fwd_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh
 int scouter_conv2d_dgrad_x3_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                     int tile, int epilogue);
 int scouter_conv2d_wgrad_x3_ok(int B, int H, int W, int Cin, int Cout);
+/* the launch of scouter_conv2d_wgrad_x3 for plan_hint, by its own plan function.  field 0: CI_TILES, 1: CO_TILES (128-channel
+ * tiles), 2: SPLITS (above 1: the slab sum runs), 3: PIX_PER_SPLIT.  -1 where scouter_conv2d_wgrad_x3_ok answers 0 */
+long scouter_conv2d_wgrad_x3_plan(int B, int H, int W, int Cin, int Cout, int plan_hint, int field);
 int scouter_conv2d_fwd_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                       int nplanes, int tile, int epilogue, int io);
 int scouter_conv2d_dgrad_planes_tile_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
@@ -255,6 +258,11 @@ int scouter_conv2d_dgrad_planes_tile_ok(int B, int H, int W, int Cin, int Cout, 
 /* the plane weight gradient takes this shape with this plan (bit 6: the tap-fused plans) */
 int scouter_conv2d_wgrad_planes_plan_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int pad, int groups,
                                         int nplanes, int plan);
+/* the launch of scouter_conv2d_wgrad_planes for plan_hint, by its own plan function.  field 0: BM, 1: BN (channel edges of the
+ * block tile, 64 or 128), 2: SPLITS, 3: PIX_PER_SPLIT, 4: FUSED (1: the tap-fused kernel, 64 x 64 tiles that carry all nine taps).
+ * -1 where scouter_conv2d_wgrad_planes_plan_ok answers 0 */
+long scouter_conv2d_wgrad_planes_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int pad, int groups,
+                                      int nplanes, int plan_hint, int field);
 /* rows of fused BatchNorm partials plane tile 0..6 writes for M GEMM rows */
 int scouter_conv2d_planes_partial_rows(long M, int tile);
 /* which weight-gradient kernels take this shape: F32 / BF16 -- the entry point does; TAPS / XWT -- scouter_conv2d_wgrad_f32's
@@ -270,17 +278,23 @@ int scouter_conv2d_planes_partial_rows(long M, int tile);
 #define SCOUTER_WGRAD_ROWS32 5
 int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                    int kernel);
-/* the launch of the per-tap kernel (one workgroup per tap: kernel = SCOUTER_WGRAD_F32 / SCOUTER_WGRAD_BF16) for this shape and
- * plan_hint, one integer per call: BM / BN -- the input / output channel edge of the block tile; SPLITS -- split-K slabs (above 1:
- * the slab sum runs); PIX_PER_SPLIT -- pixels of one split (the last split holds the rest); MODE -- the addressing mode, 0 =
- * general, 1 = same-size padded taps, 2 = pointwise.  Evaluated by the launchers' own plan and mode functions.  -1: the entry
- * point refuses the shape (or an unknown kernel / field).  With plan_hint < 0 the entry points run a tap-fused kernel instead
- * where scouter_conv2d_wgrad_kernel_ok says TAPS / XWT / BWT; this query describes the per-tap launch they fall back to. */
+/* the launch of a weight-gradient kernel of scouter_conv2d_wgrad_f32 / _bf16_io for this shape, one integer per call.
+ * kernel = SCOUTER_WGRAD_F32 / SCOUTER_WGRAD_BF16: the per-tap kernel (one workgroup per tap) under plan_hint.  BM / BN -- the input /
+ * output channel edge of the block tile; SPLITS -- split-K slabs (above 1: the slab sum runs); PIX_PER_SPLIT -- pixels of one
+ * split (the last split holds the rest); MODE -- the addressing mode, 0 = general, 1 = same-size padded taps, 2 = pointwise.
+ * With plan_hint < 0 the entry points run a tap-fused kernel instead where scouter_conv2d_wgrad_kernel_ok says TAPS / XWT / BWT;
+ * kernel 0 / 1 describe the per-tap launch they fall back to.
+ * kernel = SCOUTER_WGRAD_TAPS / SCOUTER_WGRAD_XWT / SCOUTER_WGRAD_BWT: that tap-fused launch (plan_hint is not read).  BM -- 32; BN --
+ * the column tile, 32 or 64; SPLITS, PIX_PER_SPLIT as above; field 4 (CHUNK) -- the pixels a workgroup stages per turn, 32 for TAPS,
+ * 64 for XWT and BWT.
+ * Evaluated by the launchers' own plan and mode functions.  -1: scouter_conv2d_wgrad_kernel_ok answers 0 for this kernel (or an
+ * unknown kernel / field). */
 #define SCOUTER_WGRAD_PLAN_BM 0
 #define SCOUTER_WGRAD_PLAN_BN 1
 #define SCOUTER_WGRAD_PLAN_SPLITS 2
 #define SCOUTER_WGRAD_PLAN_PIX_PER_SPLIT 3
 #define SCOUTER_WGRAD_PLAN_MODE 4
+#define SCOUTER_WGRAD_PLAN_CHUNK 4
 long scouter_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                int kernel, int plan_hint, int field);
 /* stem (Cin < 32): im2col of the NCHW image into [M][Kpad] rows so the stem runs as a 1x1 conv on the same path */

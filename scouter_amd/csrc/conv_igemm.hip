@@ -1034,10 +1034,7 @@ static bool bwt_geom_ok(const ConvGeom& g, int io) {
            (g.M + 512) * (long)(g.C > g.N ? g.C : g.N) * 2 < (1L << 31);
 }
 // kernel: SCOUTER_WGRAD_* (include/scouter_hip.h); the switches xwt / bwt are the caller's to read
-extern "C" int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
-                                              int groups, int kernel) {
-    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
-    const ConvGeom g = sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
+static bool wgrad_kernel_takes(const ConvGeom& g, int kernel) {
     switch (kernel) {
         case 0: return wgrad_entry_ok(g);
         case 1: return wgrad_bf16_geom_ok(g);
@@ -1045,17 +1042,62 @@ extern "C" int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int 
         case 3: return wgrad_entry_ok(g) && xwt_geom_ok(g);
         case 4: return bwt_geom_ok(g, SC_IO_X_BF16 | SC_IO_R_BF16);
         case 5: return wgrad_entry_ok(g) && wgrad_rows32_ok(g);
-        default: return 0;
+        default: return false;
     }
 }
+extern "C" int scouter_conv2d_wgrad_kernel_ok(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
+                                              int groups, int kernel) {
+    if (!sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return 0;
+    return wgrad_kernel_takes(sc_fwd_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups), kernel);
+}
 
-// what the per-tap launch of scouter_conv2d_wgrad_f32 / _bf16_io is for this shape and plan_hint: the wgrad_plan() and
-// wgrad_same_mode() calls of the two launchers below, nothing of its own
+// (column tile, split-K) plan of the TAP-FUSED kernels, the library's own plan (plan_hint < 0) on 3x3 / stride 1 / pad 1 layers with
+// 32 input channels per group.  kind = SCOUTER_WGRAD_TAPS: wgrad_taps_kernel, 32-pixel chunks, ~1024 workgroups; SCOUTER_WGRAD_XWT:
+// xwgrad_taps_kernel -- one workgroup per CU (147 KB of LDS) and a five-unit prologue per workgroup: ONE round of long pixel
+// ranges, not four of short ones -- whole 64-pixel chunks; SCOUTER_WGRAD_BWT: bwgrad_taps_kernel, 64-pixel chunks, two
+// workgroups per CU.  The two launchers, the workspace query and scouter_conv2d_wgrad_plan all take it from here.
+struct WgradTapsPlan { int bn, co_tiles, splits, chunk; long tiles, pix_per_split; };
+static inline WgradTapsPlan wgrad_taps_plan(const ConvGeom& g, int kind) {
+    WgradTapsPlan p;
+    p.bn = g.Ng % 64 == 0 ? 64 : 32;
+    p.co_tiles = g.Ng / p.bn;
+    p.tiles = (long)p.co_tiles * g.groups;
+    p.chunk = kind == 4 ? BWT_CH : BK;
+    long want = (kind == 4 ? 512 : kind == 3 ? 256 : 1024) / p.tiles;
+    if (want < 1) want = 1;
+    const long chunks = (g.M + p.chunk - 1) / p.chunk;
+    long cps = (chunks + want - 1) / want;
+    const long floor_cps = 256 / p.chunk;                 // at least 256 pixels per workgroup
+    if (cps < floor_cps) cps = floor_cps;
+    if (kind == 3) cps += cps & 1;
+    p.pix_per_split = cps * p.chunk;
+    p.splits = (int)((g.M + p.pix_per_split - 1) / p.pix_per_split);
+    if (kind == 3) p.chunk = XWT_CH;
+    return p;
+}
+static size_t wgrad_taps_ws_bytes(const ConvGeom& g, const WgradTapsPlan& p) {
+    return p.splits > 1 ? (size_t)p.splits * 9 * g.Cg * g.N * sizeof(float) : 0;
+}
+
+// what the launch of scouter_conv2d_wgrad_f32 / _bf16_io is for this shape: kernel 0 / 1 -- the per-tap launch for plan_hint, the
+// wgrad_plan() and wgrad_same_mode() calls of the two launchers below; kernel 2 / 3 / 4 -- their tap-fused launch,
+// wgrad_taps_plan() (plan_hint is not read: the tap-fused kernels are the library's own plan).  Nothing of its own
 extern "C" long scouter_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int groups,
                                           int kernel, int plan_hint, int field) {
-    if ((kernel != 0 && kernel != 1) || !sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return -1;
+    if (kernel < 0 || kernel > 4 || !sc_conv_args_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, groups)) return -1;
     const ConvGeom g = wgrad_geom(B, H, W, Cin, Cout, kh, kw, stride, pad, groups);
-    if (kernel == 0 ? !wgrad_entry_ok(g) : !wgrad_bf16_geom_ok(g)) return -1;
+    if (!wgrad_kernel_takes(g, kernel)) return -1;
+    if (kernel >= 2) {
+        const WgradTapsPlan t = wgrad_taps_plan(g, kernel);
+        switch (field) {
+            case 0: return 32;
+            case 1: return t.bn;
+            case 2: return t.splits;
+            case 3: return t.pix_per_split;
+            case 4: return t.chunk;
+            default: return -1;
+        }
+    }
     const WgradPlan p = kernel == 0 ? wgrad_plan(g, plan_hint) : wgrad_plan(g, plan_hint, true, 64);
     switch (field) {
         case 0: return p.bm;
@@ -1080,15 +1122,13 @@ extern "C" size_t scouter_conv2d_wgrad_workspace_bytes(int B, int H, int W, int 
         const size_t nb = pb.splits <= 1 ? 0 : (size_t)pb.splits * kh * kw * g.Cg * Cout * sizeof(float);
         if (nb > need) need = nb;
     }
-    if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {                                           // tap-fused plan (see wgrad_f32)
-        const long tiles = (long)(g.Ng / (g.Ng % 64 == 0 ? 64 : 32)) * groups;
-        long want = 1024 / tiles;
-        if (want < 1) want = 1;
-        long chunks = (g.M + BK - 1) / BK, cps = (chunks + want - 1) / want;
-        if (cps < 8) cps = 8;
-        const long splits = (g.M + cps * BK - 1) / (cps * BK);
-        const size_t nt = splits > 1 ? (size_t)splits * 9 * g.Cg * Cout * sizeof(float) : 0;
-        if (nt > need) need = nt;
+    if (plan_hint < 0) {
+        // the tap-fused plans the shape admits (the launchers fall back to the per-tap kernel on a workspace that is too small)
+        for (int kind = 2; kind <= 4; ++kind)
+            if (wgrad_kernel_takes(g, kind)) {
+                const size_t nt = wgrad_taps_ws_bytes(g, wgrad_taps_plan(g, kind));
+                if (nt > need) need = nt;
+            }
     }
     return need;
 }
@@ -1102,21 +1142,13 @@ extern "C" int scouter_conv2d_wgrad_f32(const float* x, const float* dy, float* 
     SC_UNSUPPORTED(wgrad_entry_ok(g), "conv2d_wgrad: per-group channels must be multiples of 32; " SC_PIXEL_WALK_MSG);
     // 3x3 / stride 1 / pad 1 with 32 input channels per group: tap-fused kernel (conv_wgrad_taps.h)
     if (plan_hint < 0 && wgrad_taps_geom_ok(g)) {
-        const int bn = g.Ng % 64 == 0 ? 64 : 32;
-        const int co_tiles = g.Ng / bn;
-        const long tiles = (long)co_tiles * groups;
-        // default (SCOUTER_XWT=0: off): the register-split bf16x3 kernel (64-pixel chunks, rows up to 112 pixels wide).  One workgroup per CU
-        // (147 KB of LDS) and a five-unit prologue per workgroup: ONE round of long pixel ranges, not four of short ones
+        // default (SCOUTER_XWT=0: off): the register-split bf16x3 kernel (64-pixel chunks, rows up to 112 pixels wide)
         const bool xwt = sc_switch(SC_SW_XWT) && xwt_geom_ok(g);
-        long want = (xwt ? 256 : 1024) / tiles;
-        if (want < 1) want = 1;
-        long chunks = (g.M + BK - 1) / BK, cps = (chunks + want - 1) / want;
-        if (cps < 8) cps = 8;
-        if (xwt) cps += cps & 1;
-        const long pps = cps * BK;
-        const int splits = (int)((g.M + pps - 1) / pps);
+        const WgradTapsPlan tp = wgrad_taps_plan(g, xwt ? 3 : 2);
+        const int bn = tp.bn, co_tiles = tp.co_tiles, splits = tp.splits;
+        const long tiles = tp.tiles, pps = tp.pix_per_split;
         const long slab_t = (long)9 * g.Cg * Cout;
-        const size_t need_t = splits > 1 ? (size_t)splits * slab_t * sizeof(float) : 0;
+        const size_t need_t = wgrad_taps_ws_bytes(g, tp);
         if (need_t <= ws_bytes && (!need_t || ws)) {
             hipStream_t st = (hipStream_t)stream;
             float* out = splits > 1 ? (float*)ws : dw;
@@ -1226,17 +1258,11 @@ extern "C" int scouter_conv2d_wgrad_bf16_io(const void* x, const void* dy, float
     // 3x3 / stride 1 / pad 1 with 32 input channels per group, both operands stored as bf16: tap-fused kernel (conv_wgrad_taps_bf16.h;
     // the library's own plan, SCOUTER_BWT=0: off) -- every X row fetched once per workgroup instead of once per tap
     if (plan_hint < 0 && bwt_geom_ok(g, io)) {
-        const int bn = g.Ng % 64 == 0 ? 64 : 32;
-        const int co_tiles = g.Ng / bn;
-        const long tiles = (long)co_tiles * groups;
-        long want = 512 / tiles;                                   // two workgroups per CU
-        if (want < 1) want = 1;
-        long chunks = (g.M + BWT_CH - 1) / BWT_CH, cps = (chunks + want - 1) / want;
-        if (cps < 4) cps = 4;
-        const long pps = cps * BWT_CH;
-        const int splits = (int)((g.M + pps - 1) / pps);
+        const WgradTapsPlan tp = wgrad_taps_plan(g, 4);           // (two workgroups per CU)
+        const int bn = tp.bn, co_tiles = tp.co_tiles, splits = tp.splits;
+        const long tiles = tp.tiles, pps = tp.pix_per_split;
         const long slab_t = (long)9 * g.Cg * Cout;
-        const size_t need_t = splits > 1 ? (size_t)splits * slab_t * sizeof(float) : 0;
+        const size_t need_t = wgrad_taps_ws_bytes(g, tp);
         if (sc_switch(SC_SW_BWT) && need_t <= ws_bytes && (!need_t || ws)) {
             hipStream_t st = (hipStream_t)stream;
             float* out = splits > 1 ? (float*)ws : dw;

@@ -1244,6 +1244,22 @@ extern "C" int scouter_conv2d_wgrad_planes_plan_ok(int B, int H, int W, int Cin,
     return pwgrad_shape_ok(g) && pwgrad_size_ok(g, nplanes) && (plan < 64 || pwgrad_fused_ok(g));
 }
 
+// the launch of scouter_conv2d_wgrad_planes for this shape and plan_hint, one integer per call, from pwg_plan(); -1: refused
+// (or an unknown field)
+extern "C" long scouter_conv2d_wgrad_planes_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int pad, int groups,
+                                                 int nplanes, int plan_hint, int field) {
+    if (!scouter_conv2d_wgrad_planes_plan_ok(B, H, W, Cin, Cout, kh, kw, pad, groups, nplanes, plan_hint)) return -1;
+    const PwgPlan p = pwg_plan((long)B * H * W, Cin / groups, Cout / groups, groups, kh * kw, plan_hint);
+    switch (field) {
+        case 0: return p.bm;
+        case 1: return p.bn;
+        case 2: return p.splits;
+        case 3: return p.pps;
+        case 4: return p.fused;
+        default: return -1;
+    }
+}
+
 extern "C" size_t scouter_conv2d_wgrad_planes_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw,
                                                               int groups, int plan_hint) {
     if (groups <= 0 || Cin % groups || Cout % groups) return 0;

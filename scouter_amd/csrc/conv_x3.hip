@@ -702,6 +702,19 @@ static bool x3_wgrad_channels_ok(int Cin, int Cout) { return Cin % 128 == 0 && C
 extern "C" int scouter_conv2d_wgrad_x3_ok(int B, int H, int W, int Cin, int Cout) {
     return sc_pixels_ok(B, H, W) && Cin > 0 && Cout > 0 && x3_wgrad_channels_ok(Cin, Cout) && (long)B * H * W < (1L << 31);
 }
+// the launch of scouter_conv2d_wgrad_x3 for this shape and plan_hint, one integer per call, from xw_plan(); -1: refused (or an
+// unknown field)
+extern "C" long scouter_conv2d_wgrad_x3_plan(int B, int H, int W, int Cin, int Cout, int plan_hint, int field) {
+    if (!scouter_conv2d_wgrad_x3_ok(B, H, W, Cin, Cout)) return -1;
+    const XwPlan p = xw_plan((long)B * H * W, Cin, Cout, plan_hint);
+    switch (field) {
+        case 0: return p.ci_tiles;
+        case 1: return p.co_tiles;
+        case 2: return p.splits;
+        case 3: return p.pix_per_split;
+        default: return -1;
+    }
+}
 extern "C" size_t scouter_conv2d_wgrad_x3_workspace_bytes(int B, int H, int W, int Cin, int Cout, int plan_hint) {
     if (Cin % 128 || Cout % 128 || B <= 0) return 0;
     const XwPlan p = xw_plan((long)B * H * W, Cin, Cout, plan_hint);

@@ -328,6 +328,12 @@ def _fuse_wanted(post, kh, plane_kernel=False):
 EPI_BIAS, EPI_ADDEND, EPI_RELU, EPI_BN_STATS, EPI_BN_BWD, EPI_BN_BWD2 = 1, 2, 4, 8, 16, 32          # (SCOUTER_EPI_*)
 WGRAD_F32, WGRAD_BF16, WGRAD_TAPS, WGRAD_XWT, WGRAD_BWT, WGRAD_ROWS32 = 0, 1, 2, 3, 4, 5             # (SCOUTER_WGRAD_*)
 WGRAD_PLAN_FIELDS = ("bm", "bn", "splits", "pix_per_split", "mode")                                  # (SCOUTER_WGRAD_PLAN_*)
+# ask("wgrad_plan", *shape, WGRAD_TAPS | WGRAD_XWT | WGRAD_BWT, -1, field): the tap-fused launch, field 4 = the chunk in pixels;
+# ask("wgrad_x3_plan", B, H, W, Cin, Cout, plan, field) / ask("wgrad_planes_plan", B, H, W, Cin, Cout, kh, kw, pad, groups,
+# nplanes, plan, field): the register-split pointwise / the plane weight gradient's launch
+WGRAD_TAPS_PLAN_FIELDS = ("bm", "bn", "splits", "pix_per_split", "chunk")
+WGRAD_X3_PLAN_FIELDS = ("ci_tiles", "co_tiles", "splits", "pix_per_split")
+WGRAD_PLANES_PLAN_FIELDS = ("bm", "bn", "splits", "pix_per_split", "fused")
 _asked = {}
 
 
